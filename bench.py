@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the detect + track hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: set-up, W warm-up steps and the pre-warm, the K timed
+steps, the result line.  --full adds everything else the line can carry (cold pipeline, long
+window with clock and power, the self-check against the oracle, the per-kernel eager profile,
+the host-frame leg, fewer frames per launch set, the tracker stress sequences, single-stream
+latency, the CPU baseline); the --no-* options skip single legs of a --full run.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 
 One "step" = one pass of the hot path over one batch of synthetic video: for each of the
 rank's S streams (default 8 = BASELINE config 4's per-GPU shard of 64 streams over 8 GPUs)
@@ -88,6 +95,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 MFMA_F16_DENSE_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PFLOP/s dense fp16/bf16
+# the tuner's decisions for every detector shape the default and --full runs build (RTMODT_TUNE_CACHE format; written by
+# `RTMODT_TUNE_CACHE=<file> python bench.py --full` on an MI355X, regenerated whenever the tile table changes)
+TUNE_SEED = os.path.join(ROOT, "profiles", "bench_tune_cache.txt")
 
 
 def parse():
@@ -125,7 +135,12 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0: min(os.cpu_count(), 16))")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendez-vous only: every rank joins the process group, rank 0 prints {n_gpus, ranks}, nobody touches a GPU (CPU test of the launcher path)")
-    ap.add_argument("--long", type=float, default=1.0, help="seconds of the additional long steady-state window reported beside the K timed steps (0: off)")
+    ap.add_argument("--long", type=float, default=1.0, help="seconds of the additional long steady-state window reported beside the K timed steps (0: off; --full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every measurement and check beside the headline (cold pipeline, long window, self-check, eager per-kernel profile, host-frame leg, "
+                         "F = 1 / 2 comparison, tracker stress, single-stream latency, CPU baseline); without it only the K timed steps are measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's detections and tracker state) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -300,6 +315,42 @@ def verify_outputs(pkg, det, frame_ptrs, size, max_det, weights, scale):
             "worst_layer_behind_a_fused_pair": {"name": worst_fused[0], "err_over_tol": round(worst_fused[1], 3)}, "launches_by_kernel_family": fam}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(dets, trk, n_streams, max_det, max_tracks) -> dict:
+    """What one step hands its caller, as float arrays: the fetched detections of every image of the retired batch (row
+    f * S + s, padded with zeros to max_det) and every stream's track list after the step's tracker update (padded to
+    max_tracks); *_count says how many rows of each are real.  Fixed shapes for fixed arguments, so that two runs compare
+    element for element.  Integers are stored exactly (float32 below 2^24, float64 for the 64-bit track ids)."""
+    def pad(rows, n, tail, dt):
+        a = np.zeros((len(rows), n) + tail, dt)
+        for i, r in enumerate(rows):
+            a[i, :len(r)] = r
+        return a
+    out = {"det_count": np.asarray([len(d) for d in dets], np.float32),
+           "det_xyxy": pad([d.xyxy for d in dets], max_det, (4,), np.float32),
+           "det_confidence": pad([d.confidence for d in dets], max_det, (), np.float32),
+           "det_class_id": pad([d.class_id for d in dets], max_det, (), np.float32)}
+    snaps = [trk.snapshot(s) for s in range(n_streams)]
+    out["trk_count"] = np.asarray([len(s["ids"]) for s in snaps], np.float32)
+    out["trk_next_id"] = np.asarray([s["next_id"] for s in snaps], np.float64)
+    out["trk_id"] = pad([s["ids"] for s in snaps], max_tracks, (), np.float64)
+    out["trk_xyxy"] = pad([s["xyxy"] for s in snaps], max_tracks, (4,), np.float32)
+    for key, name in (("conf", "trk_confidence"), ("cls", "trk_class_id"), ("age", "trk_age"), ("tsu", "trk_time_since_update")):
+        out[name] = pad([s[key] for s in snaps], max_tracks, (), np.float32)
+    return out
+
+
+def write_outputs(dir_, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: the step's outputs take {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed for --dump-outputs")
+    os.makedirs(dir_, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dir_, name + ".npy"), a)
+
+
 def launch_ranks(args) -> int:
     """`bench.py --gpus N` started WITHOUT a launcher (WORLD_SIZE unset): start the N ranks ourselves, as a CHILD
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>`,
@@ -398,8 +449,17 @@ def main():
         os.replace(tmp, wpath)
     sync.barrier()
     # the tuner's decisions are shared by every detector this process builds for one shape (main run, host-frame leg,
-    # self-check): one file per rank
-    os.environ.setdefault("RTMODT_TUNE_CACHE", os.path.join(tempfile.gettempdir(), f"rtmodt_bench_tune_{os.getpid()}.txt"))
+    # self-check): one file per rank.  Unless the caller names a cache, that file starts as a copy of TUNE_SEED: every run
+    # then launches the same tiles and computes the same outputs (tiles differ in fp16 rounding, and a choice made by timing
+    # differs from run to run).  A launch the seed does not cover -- other arguments, or a build whose tile table changed,
+    # which makes the engine ignore the seed -- is tuned in this process, and the line says so (config.tiles)
+    tune_seed = None
+    if "RTMODT_TUNE_CACHE" not in os.environ:
+        os.environ["RTMODT_TUNE_CACHE"] = os.path.join(tempfile.gettempdir(), f"rtmodt_bench_tune_{os.getpid()}.txt")
+        with open(TUNE_SEED) as f:
+            tune_seed = f.read()
+        with open(os.environ["RTMODT_TUNE_CACHE"], "w") as f:
+            f.write(tune_seed)
 
     # ---- frames resident in HBM: this rank owns the global streams {id : id % world == rank}, seed 1234 + id ----
     per = size * size * 3
@@ -436,15 +496,18 @@ def main():
         det.synchronize()                           # hipDeviceSynchronize through the C ABI
         sync.device_synchronize()                   # + torch.cuda.synchronize() when torch.distributed is up
 
-    def measure(F, steps, warmup, collective=True, prewarm_s=None, long_s=0.0, host=False):
+    def measure(F, steps, warmup, collective=True, prewarm_s=None, long_s=0.0, host=False, cold=True, keep_outputs=False):
         """K timed steps; a step = one launch set over S streams x F consecutive frames (image f * S + s).
 
         Protocol: W warm-up steps, then an untimed time-based pre-warm of the full pipeline (>= 1 s:
         clocks and caches as in a long-running service, whatever W is), barrier + device sync, then
-          * cold:   K batches submitted into the EMPTY pipeline and retired, device sync at the end (fill + drain inside);
-          * steady: the pipeline is refilled (S + 1 batches in flight), the clock starts right after a fetch() and stops
-                    right after the K-th next fetch(): exactly K batches retired, S + 1 in flight throughout -- `value`.
-        Both brackets are closed by a barrier + device sync of every rank."""
+          * cold (with `cold`): K batches submitted into the EMPTY pipeline and retired, device sync at the end (fill + drain inside);
+          * steady: the tracker is reset and the frame sequence restarts at frame 0 (the number of pre-warm steps depends on
+                    the clock, so this is what makes the steady phase's inputs the same in every run), the pipeline is refilled
+                    (S + 1 batches in flight), the clock starts right after a fetch() and stops right after the K-th next
+                    fetch(): exactly K batches retired, S + 1 in flight throughout -- `value`.
+        Both brackets are closed by a barrier + device sync of every rank.  `keep_outputs`: the last timed step's
+        detections and the tracker's state after it are returned as m["outputs"] (step_outputs)."""
         if host:
             make_host_ring()
         mapped = host and args.host_mode == "mapped" and not args.pageable
@@ -505,16 +568,20 @@ def main():
             sync.barrier()
             sync_all(det)
         # ---- cold: K batches through an empty pipeline, sync-bracketed ----
-        t0 = pc()
-        fill()
-        for _ in range(max(steps - (depth - 1), 0)):
-            step(t); t += 1
-        drain()
-        sync_all(det)
-        cold = pc() - t0
-        if collective:
-            sync.barrier()
+        cold_s = None
+        if cold:
+            t0 = pc()
+            fill()
+            for _ in range(max(steps - (depth - 1), 0)):
+                step(t); t += 1
+            drain()
+            sync_all(det)
+            cold_s = pc() - t0
+            if collective:
+                sync.barrier()
         # ---- steady: exactly K batches retired with the pipeline full on both sides of the clock ----
+        trk.reset()                                     # synchronous; nothing is in flight after the drain
+        t = 0
         fill()
         for _ in range(depth):
             step(t); t += 1
@@ -529,6 +596,7 @@ def main():
             fwd_ms += b
             n_det += sum(len(d) for d in out)
         elapsed = stamps[-1] - stamps[0]
+        outputs = step_outputs(out, trk, S, args.max_det, trk.max_tracks) if keep_outputs else None    # after the clock stopped
         # ---- the same steady state over a longer window (>= long_s seconds), for the record ----
         long_run = None
         if long_s > 0:
@@ -562,17 +630,27 @@ def main():
             sync_all(det)
         gc.enable()
         per = np.diff(np.asarray(stamps)) * 1e3
-        return {"elapsed": elapsed, "cold": cold, "fwd_ms": fwd_ms, "tot_ms": tot_ms, "n_det": n_det, "det": det, "trk": trk,
-                "step_ms": per, "long": long_run, "stages": n_st, "depth": depth}
+        return {"elapsed": elapsed, "cold": cold_s, "fwd_ms": fwd_ms, "tot_ms": tot_ms, "n_det": n_det, "det": det, "trk": trk,
+                "step_ms": per, "long": long_run, "stages": n_st, "depth": depth, "outputs": outputs}
 
     if args.steps < 4:
         raise SystemExit("--steps must be at least 4 (the staged engine keeps 4 batches in flight)")
-    m = measure(F, args.steps, args.warmup, long_s=args.long, host=args.host_frames)
+    m = measure(F, args.steps, args.warmup, long_s=args.long if args.full else 0.0, host=args.host_frames, cold=args.full,
+                keep_outputs=args.dump_outputs is not None and rank == 0)
     det, trk, elapsed, fwd_ms, tot_ms, n_det = m["det"], m["trk"], m["elapsed"], m["fwd_ms"], m["tot_ms"], m["n_det"]
+    if tune_seed is None:
+        tiles = "replayed from or tuned into the cache the caller named (RTMODT_TUNE_CACHE)"
+    else:
+        with open(os.environ["RTMODT_TUNE_CACHE"]) as f:      # the engine rewrites the file only when it tuned a launch
+            replayed = f.read() == tune_seed
+        tiles = ("replayed from profiles/bench_tune_cache.txt" if replayed else
+                 "tuned in this process: profiles/bench_tune_cache.txt does not cover this configuration or tile table, outputs may differ from run to run")
+        if not replayed:
+            print(f"bench.py: {tiles}", file=sys.stderr)
     flops_step = det.model.conv_flops_per_frame * S * F
     per_rank_fps = sync.gather_floats(S * F * args.steps / elapsed)      # every rank's own frames/s (stragglers show in a SCALE run)
     elapsed = sync.max_time(elapsed)                # MAX over ranks
-    cold = sync.max_time(m["cold"])
+    cold = sync.max_time(m["cold"]) if args.full else None
     n_tracks = sum(len(trk.snapshot(s)["ids"]) for s in range(S))
     # optional stats reduce: ~24 bytes over RCCL, once per run
     n_det, n_tracks_node = sync.sum_stats([n_det, n_tracks])
@@ -581,6 +659,8 @@ def main():
         sync.barrier()                               # wait for rank 0's extra (untimed) measurements, then leave together
         sync.close()
         return
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, m["outputs"])
 
     frames_total = world * S * F * args.steps
     fps = frames_total / elapsed
@@ -603,12 +683,11 @@ def main():
                                f"frames from: {src}, detections copied to host every step",
                    "baseline_config": workload_label(args.model, size, S),
                    "streams_per_gpu": S, "frames_per_stream_per_step": F, "frames_per_step": S * F * world,
-                   "weights": "synthetic seed 0, LSUV-calibrated on noise frames",
-                   "parallelism": f"streams sharded {world} ways, no data-path collective"},
-        "timing": {"protocol": f"{args.warmup} warm-up steps + {args.prewarm:g} s untimed pre-warm, barrier + device sync, then exactly {args.steps} batches "
-                               f"retired with {m['depth']} in flight on both sides of the clock (host clock stamped after fetch()); max over ranks",
-                   "cold_ms_per_step": round(cold / args.steps * 1e3, 4),
-                   "cold_note": "the same K batches through an EMPTY pipeline, device-sync bracketed (pipeline fill and drain inside the bracket)",
+                   "weights": "synthetic seed 0, LSUV-calibrated on noise frames", "weights_sha16": pkg.weights.digest(weights) if weights is not None else None,
+                   "parallelism": f"streams sharded {world} ways, no data-path collective", "tiles": tiles},
+        "timing": {"protocol": f"{args.warmup} warm-up steps + {args.prewarm:g} s untimed pre-warm, barrier + device sync, tracker reset and frame sequence "
+                               f"restarted, then exactly {args.steps} batches retired with {m['depth']} in flight on both sides of the clock "
+                               f"(host clock stamped after fetch()); max over ranks",
                    "step_ms_p50": round(float(np.median(m["step_ms"])), 4), "step_ms_max": round(float(m["step_ms"].max()), 4),
                    "step_ms_min": round(float(m["step_ms"].min()), 4)},
         "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_F16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -622,8 +701,11 @@ def main():
                      "batch_latency_note": "HIP events, first launch of a batch -> its NMS done (pipeline latency of one batch, not a per-step time)"},
         "per_rank_frames_s": [round(v, 1) for v in per_rank_fps],
         "detections_per_frame": round(n_det / frames_total, 2), "live_tracks_node": n_tracks_node,
-        "frames_source": src,
+        "frames_source": src, "full": args.full,
     }
+    if cold is not None:
+        res["timing"]["cold_ms_per_step"] = round(cold / args.steps * 1e3, 4)
+        res["timing"]["cold_note"] = "the same K batches through an EMPTY pipeline, device-sync bracketed (pipeline fill and drain inside the bracket)"
     if m["long"]:
         lr = m["long"]
         res["timing"]["long_window"] = {"value": round(world * S * F * lr["steps"] / lr["seconds"], 1), "unit": "frames/s (rank 0's own clock)",
@@ -661,27 +743,28 @@ def main():
 
     # ---- untimed self-check on one more batch of the SAME detector: NMS survivors, boxes, scores and classes of every image
     # must equal the oracle's non_max_suppression + scale_boxes on the engine's own pre-NMS tensor (the oracle is the checker) ----
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         res["verified"] = verify_outputs(pkg, det, [pt for f in range(F) for pt in ptrs[f % R]], size, args.max_det,
                                          weights if weights is not None else pkg.weights.load(wpath)[0], args.model)
 
     # ---- per-kernel view (eager, HIP events around every launch) ----
-    prof = det.profile(3)
-    conv_ms = sum(ms for name, ms, fl in prof if fl > 0)
-    res["roofline"]["conv_launches_per_step"] = sum(1 for _, _, fl in prof if fl > 0)
-    res["roofline"]["conv_kernels_ms_eager"] = round(conv_ms, 4)
-    res["roofline"]["conv_kernels_frames_eager"] = S * F // chains      # the profiler times one chain's launches alone on the device
-    res["roofline"]["conv_kernels_tflops_eager"] = round(sum(fl for _, _, fl in prof) / (conv_ms * 1e-3) / 1e12, 2)
-    top = sorted(prof, key=lambda r: -r[1])[:6]
-    res["roofline"]["slowest_launches"] = [{"op": n, "ms": round(ms, 4), "tflops": round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 else 0} for n, ms, fl in top]
-    # every launch of the forward pass alone on the device (eager, HIP events): [op, microseconds, TFLOP/s]
-    res["roofline"]["launches_eager"] = [[n, round(ms * 1e3, 1), round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 and fl > 0 else 0] for n, ms, fl in prof]
+    if args.full:
+        prof = det.profile(3)
+        conv_ms = sum(ms for name, ms, fl in prof if fl > 0)
+        res["roofline"]["conv_launches_per_step"] = sum(1 for _, _, fl in prof if fl > 0)
+        res["roofline"]["conv_kernels_ms_eager"] = round(conv_ms, 4)
+        res["roofline"]["conv_kernels_frames_eager"] = S * F // chains      # the profiler times one chain's launches alone on the device
+        res["roofline"]["conv_kernels_tflops_eager"] = round(sum(fl for _, _, fl in prof) / (conv_ms * 1e-3) / 1e12, 2)
+        top = sorted(prof, key=lambda r: -r[1])[:6]
+        res["roofline"]["slowest_launches"] = [{"op": n, "ms": round(ms, 4), "tflops": round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 else 0} for n, ms, fl in top]
+        # every launch of the forward pass alone on the device (eager, HIP events): [op, microseconds, TFLOP/s]
+        res["roofline"]["launches_eager"] = [[n, round(ms * 1e3, 1), round(fl / (ms * 1e-3) / 1e12, 1) if ms > 0 and fl > 0 else 0] for n, ms, fl in prof]
     det.close()
     trk.close()
 
     # ---- the same workload with the frames arriving from page-locked HOST memory every step (PCIe-inclusive; the reference's
     # detect() takes a host ndarray, detector.py:98-111).  Reported beside `value`, never as `value` ----
-    if world == 1 and not args.host_frames and not args.no_host_leg:
+    if args.full and world == 1 and not args.host_frames and not args.no_host_leg:
         mh = measure(F, args.steps, args.warmup, collective=False, host=True)
         res["host_frames"] = {"value": round(S * F * args.steps / mh["elapsed"], 1), "unit": "frames/s",
                               "ms_per_step": round(mh["elapsed"] / args.steps * 1e3, 4),
@@ -693,7 +776,7 @@ def main():
 
     # ---- the same workload with fewer frames of every stream per launch set (2: the configuration of rounds 1-2's records;
     # 1: no batching over time), for comparison ----
-    if F > 1 and world == 1 and not args.host_frames and not args.no_compare:
+    if F > 1 and args.full and world == 1 and not args.host_frames and not args.no_compare:
         for Fc in sorted({1, 2} - {F}, reverse=True):
             m1 = measure(Fc, args.steps, args.warmup, collective=False, prewarm_s=0.3)
             f1 = m1["fwd_ms"] / args.steps
@@ -713,11 +796,11 @@ def main():
         res["frac_no_temporal_batching"] = res["roofline"]["frac"]
 
     # ---- BASELINE configs 3 / 5: the 200- and 500-box association sequences, bit-checked against the reference-generated fixtures ----
-    if world == 1 and not args.no_tracker_stress:
+    if args.full and world == 1 and not args.no_tracker_stress:
         res["tracker_stress"] = tracker_stress(pkg, dev)
 
     # ---- single-stream latency (BASELINE config 1/2 shape: batch 1, sync per frame) ----
-    if not args.no_latency:
+    if args.full and not args.no_latency:
         det1 = pkg.Detector(wpath, input_size=(size, size), max_det=args.max_det, device=f"cuda:{dev}", batch=1, warmup=False)
         trk1 = core_cls(device=dev, n_streams=1, max_dets=max(128, args.max_det), max_tracks=2048)
         lat = []
@@ -736,7 +819,7 @@ def main():
         det1.close()
         trk1.close()
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         if weights is None:
             weights = pkg.weights.load(wpath)[0]
         res["cpu_baseline"] = cpu_baseline(pkg, weights, args)

@@ -37,7 +37,7 @@ def main():
                 os.sched_setaffinity(0, cpus)
             except (AttributeError, OSError):
                 pass
-        children.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-baseline-only", "--cpu-threads", str(args.threads)],
+        children.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-baseline-only", "--cpu-threads", str(args.threads)],
                                          stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, env=env, preexec_fn=pin))
     per = []
     for c in children:

@@ -57,3 +57,37 @@ def test_workload_label_follows_the_arguments():
     for other in (("s", 640, 16), ("m", 640, 8), ("n", 640, 8), ("s", 1280, 1)):
         assert b.workload_label(*other) == "not a BASELINE configuration"
     assert "120 ms" in b.live_stream_cost(4) and "no batching" in b.live_stream_cost(1)
+
+
+def test_dump_outputs_have_fixed_shapes_and_float_dtypes(tmp_path):
+    """--dump-outputs: what the last timed step returned, padded to max_det / max_tracks rows so that two runs with the same
+    arguments compare element for element; float32 / float64 only, integers stored exactly."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+
+    class Det:
+        def __init__(self, k):
+            self.xyxy = np.arange(4 * k, dtype=np.float32).reshape(k, 4)
+            self.confidence = np.full(k, 0.5, np.float32)
+            self.class_id = np.arange(k, dtype=np.int32)
+
+        def __len__(self):
+            return len(self.confidence)
+
+    class Trk:
+        def snapshot(self, s):
+            k = 2 * s
+            return {"ids": np.arange(k, dtype=np.int64) + (1 << 40), "xyxy": np.ones((k, 4), np.float32), "conf": np.ones(k, np.float32),
+                    "cls": np.full(k, 3, np.int32), "age": np.full(k, 7, np.int32), "tsu": np.zeros(k, np.int32), "next_id": k + 1}
+
+    out = b.step_outputs([Det(3), Det(0), Det(5)], Trk(), 3, max_det=6, max_tracks=8)
+    b.write_outputs(str(tmp_path), out)
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert set(got) == set(out) and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["det_count"].tolist() == [3, 0, 5] and got["det_xyxy"].shape == (3, 6, 4) and got["det_confidence"].shape == (3, 6)
+    assert np.array_equal(got["det_xyxy"][2, :5], Det(5).xyxy) and not got["det_xyxy"][2, 5:].any()
+    assert got["trk_count"].tolist() == [0, 2, 4] and got["trk_xyxy"].shape == (3, 8, 4) and got["trk_next_id"].tolist() == [1, 3, 5]
+    assert got["trk_id"].dtype == np.float64 and got["trk_id"][2, 3] == (1 << 40) + 3

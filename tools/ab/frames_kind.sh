@@ -1,7 +1,7 @@
 #!/bin/bash
 # how much of the staged bench's rate is the chip's power limit answering the DATA: white-noise frames against smooth ones
 mkdir -p gpurun_out/fk; rm -f gpurun_out/fk/*.smi
-Q="--no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20 --long 10"
+Q="--full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20 --long 10"
 for rep in 1 2; do
 for k in noise structured; do
   python bench.py $Q --frames-kind $k > gpurun_out/fk/${k}_$rep.json 2>/dev/null &

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/y; rm -f gpurun_out/y/*.smi
 L="real-time-multi-object-detection---tracking-system_amd/lib"
 cp $L/librtmodt_hip.so $L/new.so.keep
-Q="--no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20 --long 10"
+Q="--full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20 --long 10"
 for rep in 1 2; do
 for v in prev new; do
   if [ $v = prev ]; then cp $L/librtmodt_hip_prev.so $L/librtmodt_hip.so; else cp $L/new.so.keep $L/librtmodt_hip.so; fi

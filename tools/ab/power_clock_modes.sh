@@ -1,7 +1,7 @@
 #!/bin/bash
 # clocks and package power while the bench runs: staged default, plain engine, 1 frame per stream
 mkdir -p gpurun_out/x
-Q="--no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20"
+Q="--full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 300 --warmup 20"
 sample() {  # $1 = tag, rest = env + command
   tag=$1; shift
   env "$@" > gpurun_out/x/$tag.json 2>/dev/null &

@@ -5,7 +5,7 @@
 # Rebuilds the library inside the GPU box's scratch copy only.
 set -e
 O=gpurun_out/ablate; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 200 --warmup 20"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 200 --warmup 20"
 C=real-time-multi-object-detection---tracking-system_amd/csrc
 export RTMODT_TUNE_CACHE=/tmp/tune_abl.txt
 $B > $O/warm.json 2>/dev/null

@@ -2,7 +2,7 @@
 # r03: wave issue priority around the conv epilogues (RTMODT_EPI_PRIO: 0 = none, 1 = epilogue raised, 2 = main loops raised), staged bench, alternating
 set -e
 O=gpurun_out/epi_prio; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20"
 export RTMODT_TUNE_CACHE=/tmp/tune_prio.txt
 $B > $O/warm.json 2>/dev/null
 for i in 1 2 3; do

@@ -16,7 +16,7 @@ for r in csv.DictReader(open(sys.argv[1])):
 PY
   rm -rf $O/x
 done
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20"
 export RTMODT_TUNE_CACHE=/tmp/tk.txt
 for i in 1 2; do
   $B > $O/noise_$i.json 2>/dev/null && $B --frames-kind structured > $O/struct_$i.json 2>/dev/null

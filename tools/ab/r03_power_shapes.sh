@@ -2,7 +2,7 @@
 # r03: in-kernel clock and package power (hwmon, where readable) for the engine shapes: three stages (default), two, plain engine, one frame per stream
 set -e
 O=gpurun_out/power_shapes; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20 --long 2"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20 --long 2"
 export RTMODT_TUNE_CACHE=/tmp/tune_ps.txt
 $B > $O/warm.json 2>/dev/null
 $B > $O/stages3.json 2>/dev/null

@@ -8,7 +8,7 @@ RTMODT_TUNE_LOG=1 RTMODT_CHAINS=1 timeout -k 10 300 python3 tools/profile_layers
 grep -E "pt:256x128s3/16w" $O/tune.log | head -40
 grep -E "16w|^total" $O/layers.txt
 # same-box A/B of the one-workgroup-per-CU tile families in the STAGED bench (the tuner times launches alone; 144-KiB workgroups keep the other stages off their CU)
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 200 --warmup 20"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --steps 200 --warmup 20"
 for i in 1 2; do
   RTMODT_TUNE_SKIP="48,49,53,54" RTMODT_TUNE_CACHE=/tmp/tune_small.txt $B > $O/bench_small_$i.json 2>/dev/null
   RTMODT_TUNE_SKIP="48,49,54" RTMODT_TUNE_CACHE=/tmp/tune_w16.txt $B > $O/bench_w16_$i.json 2>/dev/null

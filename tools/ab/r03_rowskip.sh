@@ -6,6 +6,6 @@ timeout -k 10 500 python3 -m pytest tests/test_gpu_detector.py -m gpu -x -q -k "
 tail -n 3 $O/tests.txt
 RTMODT_CHAINS=1 timeout -k 10 300 python3 tools/profile_layers.py > $O/layers.txt 2> /dev/null
 grep -E "rows|^total" $O/layers.txt
-python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20 > $O/bench.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --steps 200 --warmup 20 > $O/bench.json 2>/dev/null
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['frac'], d['verified']['layers_ok'])"

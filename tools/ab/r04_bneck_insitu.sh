@@ -2,7 +2,7 @@
 # r04: the tuner times a Bottleneck's two forms ALONE (fused kernel vs two ping-pong launches: 59.7 vs 50.2 us at c = 64).  In the staged bench the launches
 # share the device with two other stages: does forcing the fused form (fewer bytes, smaller LDS footprint) change the step?  Same box, alternating.
 O=gpurun_out/r04/bneck_insitu; mkdir -p $O
-Q="--steps 100 --warmup 10 --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --long 0"
+Q="--full --steps 100 --warmup 10 --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --long 0"
 for i in 1 2; do
   for m in tuner 1 0; do
     if [ $m = tuner ]; then unset RTMODT_BNECK; else export RTMODT_BNECK=$m; fi

@@ -12,10 +12,10 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # the first run tunes and records its choices; every later process (profilers included) replays exactly that configuration
 export RTMODT_TUNE_CACHE=/tmp/rtmodt_tune_$R.txt
 rm -f $RTMODT_TUNE_CACHE
-python bench.py > $O/bench_default.json 2> $O/bench_default.log || exit 1
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.log || exit 1
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> /dev/null || exit 1
 echo "[collect] bench done"
-B="python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --long 0 --prewarm 0.2"
+B="python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --no-verify --long 0 --prewarm 0.2"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 100 --warmup 10 > $O/stats_bench.json 2> $O/stats.log || exit 1
 python tools/trace_gaps.py $O/stats/*/*_kernel_trace.csv 50 > $O/step_gaps.txt 2>&1
 rm -f $O/stats/*/*_kernel_trace.csv
@@ -56,5 +56,5 @@ python tests/perf/tracker_modes.py > $O/tracker_modes.json 2> /dev/null
 python tools/bw_probe.py > $O/bandwidth_probe.txt 2> /dev/null
 echo "[collect] all done"
 # soak: 3 000 steps of the default engine with the line's self-check (NMS bit-equal to the oracle, every stored layer of two images) at the end
-python3 bench.py --no-cpu-baseline --no-latency --no-compare --no-host-leg --long 0 --prewarm 0.2 --steps 3000 --warmup 30 > $O/bench_soak3000.json 2> /dev/null || exit 1
+python3 bench.py --full --no-cpu-baseline --no-latency --no-compare --no-host-leg --long 0 --prewarm 0.2 --steps 3000 --warmup 30 > $O/bench_soak3000.json 2> /dev/null || exit 1
 echo "[collect] soak done"
