@@ -116,6 +116,28 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *det, const uint8_t *const *fr
                                   int stride_bytes, int mem_kind);
 int rtmodt_detector_fetch(rtmodt_detector *det, float *xyxy, float *conf, int32_t *cls, int32_t *n_out);
 
+/* Pixel formats of the frames enqueue_batch_fmt / preprocess_yuv420 take.  The 4:2:0 formats are converted on the GPU with
+ * OpenCV's integer BT.601 limited-range conversion (cv2.cvtColor COLOR_YUV2BGR_NV12 / _I420, restated in DESIGN.md section 3;
+ * PARITY UNPINNED: no OpenCV to run against) and then letterboxed exactly as BGR24 frames are. */
+#define RTMODT_PIX_BGR24 0      /* packed B, G, R                                                         */
+#define RTMODT_PIX_NV12 1       /* Y plane, then ONE interleaved U, V plane at half resolution (U first)  */
+#define RTMODT_PIX_I420 2       /* Y plane, then a U plane and a V plane at half resolution (yuv420p)     */
+typedef struct rtmodt_frame_format {
+    int32_t pixel_format;  /* RTMODT_PIX_*                                                                            */
+    int32_t colorspace;    /* 0 = BT.601 limited range (the only one); anything else RTMODT_E_UNSUPPORTED (4:2:0 only)  */
+    int32_t pitch;         /* bytes per row of the BGR image / of the Y plane; 0 = 3w / w                                */
+    int32_t chroma_pitch;  /* bytes per chroma row; 0 = pitch (NV12) or pitch / 2 (I420)                                  */
+    int64_t u_offset;      /* frame pointer -> UV (NV12) or U (I420) plane; 0 = pitch * h (decoders often pad: pitch * 1088) */
+    int64_t v_offset;      /* I420 only: frame pointer -> V plane; 0 = u_offset + chroma_pitch * h / 2                     */
+} rtmodt_frame_format;
+/* enqueue_batch for frames in the layout `fmt` describes (NULL = BGR24 with pitch 3w).  BGR24 is enqueue_batch exactly.  4:2:0
+ * frames: h and w even, every plane inside [frame, frame + span) and no two planes overlapping, else RTMODT_E_INVALID with
+ * nothing launched; host frames are staged as that one span per frame (RTMODT_E_CAPACITY beyond max_src's BGR bytes).  They
+ * take the letterbox kernel of resized BGR frames (never the stem's byte source or the in-place read of RTMODT_ZERO_COPY);
+ * results come out of rtmodt_detector_fetch and feed rtmodt_tracker_update_from_detector* as usual. */
+int rtmodt_detector_enqueue_batch_fmt(rtmodt_detector *det, const uint8_t *const *frames, int n, int h, int w,
+                                      const rtmodt_frame_format *fmt, int mem_kind);
+
 /* Introspection used by the parity tests and bench.py */
 int rtmodt_detector_info(rtmodt_detector *det, int32_t *scale_id, int32_t *nc, int32_t *n_anchors,
                          int32_t *n_convs, int64_t *conv_flops_per_frame, int64_t *arena_bytes);
@@ -158,6 +180,9 @@ int rtmodt_nms_pred(int device, const float *pred, int nc, int n_anchors, float 
  * out fp16 NHWC [in_h*in_w*3]. */
 int rtmodt_preprocess(int device, const uint8_t *bgr, int h, int w, int stride_bytes, int in_w, int in_h,
                       uint16_t *out_f16);
+/* The same for one 4:2:0 host frame (fmt: RTMODT_PIX_NV12 / RTMODT_PIX_I420): conversion + letterbox, the kernel alone. */
+int rtmodt_preprocess_yuv420(int device, const uint8_t *frame, int h, int w, const rtmodt_frame_format *fmt,
+                             int in_w, int in_h, uint16_t *out_f16);
 
 /* ---- tracker: replaces _ByteTrackCore (tracker.py:43-194) ---------------------------- */
 /* n_streams independent tracker states updated by ONE launch (one workgroup per stream). */

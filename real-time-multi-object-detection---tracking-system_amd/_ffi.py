@@ -17,6 +17,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rtmodt.h")
 
 OK, E_INVALID, E_IO, E_HIP, E_CAPACITY, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 MEM_HOST, MEM_DEVICE = 0, 1
+PIX_BGR24, PIX_NV12, PIX_I420 = 0, 1, 2
+PIXEL_FORMATS = {"bgr24": PIX_BGR24, "nv12": PIX_NV12, "i420": PIX_I420, "yuv420p": PIX_I420}
 ASSIGN_GREEDY, ASSIGN_LAPJV = 0, 1
 
 
@@ -32,6 +34,70 @@ class DetCfg(C.Structure):
                 ("iou", C.c_float), ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32), ("half", C.c_int32),
                 ("device", C.c_int32), ("max_det", C.c_int32), ("agnostic", C.c_int32), ("batch", C.c_int32),
                 ("max_src_w", C.c_int32), ("max_src_h", C.c_int32), ("use_graph", C.c_int32), ("autotune", C.c_int32), ("chains", C.c_int32), ("rect", C.c_int32)]
+
+
+class FrameFormat(C.Structure):                      # struct rtmodt_frame_format
+    _fields_ = [("pixel_format", C.c_int32), ("colorspace", C.c_int32), ("pitch", C.c_int32), ("chroma_pitch", C.c_int32),
+                ("u_offset", C.c_int64), ("v_offset", C.c_int64)]
+
+
+def pixel_format_id(name) -> int:
+    """``"bgr24" | "nv12" | "i420" | "yuv420p"`` (or an ``RTMODT_PIX_*`` value) -> the ``RTMODT_PIX_*`` value."""
+    if isinstance(name, (int, np.integer)) and int(name) in PIXEL_FORMATS.values():
+        return int(name)
+    key = str(name).lower()
+    if key not in PIXEL_FORMATS:
+        raise ValueError(f"unknown pixel format {name!r}; one of {sorted(PIXEL_FORMATS)}")
+    return PIXEL_FORMATS[key]
+
+
+def frame_format(pixel_format, h: int, w: int, pitch: int = 0, chroma_pitch: int = 0, u_offset: int = 0, v_offset: int = 0,
+                 colorspace: int = 0) -> FrameFormat:
+    """A checked ``rtmodt_frame_format`` for ``h x w`` frames: the library's own rules (csrc/engine.hip: resolve_frame_format),
+    applied here first so that a bad layout raises ``ValueError`` before any call.  Zeros mean the packed defaults."""
+    pf = pixel_format_id(pixel_format)
+    fmt = FrameFormat(pf, int(colorspace), int(pitch), int(chroma_pitch), int(u_offset), int(v_offset))
+    frame_span(fmt, h, w)
+    return fmt
+
+
+def frame_span(fmt: FrameFormat, h: int, w: int) -> int:
+    """Bytes from the frame pointer to the end of the last plane (what one host frame stages); raises ``ValueError`` on a layout the
+    library rejects with ``RTMODT_E_INVALID`` and ``NotImplementedError`` on one it rejects with ``RTMODT_E_UNSUPPORTED``."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"bad frame geometry {w}x{h}")
+    pf = pixel_format_id(fmt.pixel_format)
+    if pf == PIX_BGR24:
+        pitch = fmt.pitch or 3 * w
+        if pitch < 3 * w:
+            raise ValueError(f"BGR pitch {pitch} < {3 * w}")
+        return h * pitch
+    if fmt.colorspace != 0:
+        raise NotImplementedError(f"colorspace {fmt.colorspace}: only 0 (BT.601 limited range) is implemented")
+    if h % 2 or w % 2:
+        raise ValueError(f"a 4:2:0 frame needs an even width and height, got {w}x{h}")
+    nv12 = pf == PIX_NV12
+    pitch = fmt.pitch or w
+    crow = w if nv12 else w // 2
+    cp = fmt.chroma_pitch or (pitch if nv12 else pitch // 2)
+    if pitch < w:
+        raise ValueError(f"Y pitch {pitch} < width {w}")
+    if cp < crow:
+        raise ValueError(f"chroma pitch {cp} < {crow} bytes per chroma row")
+    uo = fmt.u_offset or pitch * h
+    vo = 0 if nv12 else (fmt.v_offset or uo + cp * (h // 2))
+    if uo <= 0 or vo < 0:
+        raise ValueError(f"negative plane offset (u {uo}, v {vo})")
+    planes = [("Y", 0, pitch * (h - 1) + w), ("UV" if nv12 else "U", uo, uo + cp * (h // 2 - 1) + crow)]
+    if not nv12:
+        planes.append(("V", vo, vo + cp * (h // 2 - 1) + crow))
+    for i in range(len(planes)):
+        for j in range(i):
+            a, b = planes[i], planes[j]
+            if not (a[2] <= b[1] or b[2] <= a[1]):
+                raise ValueError(f"the {a[0]} plane [{a[1]}, {a[2]}) overlaps the {b[0]} plane [{b[1]}, {b[2]})")
+    return max(p[2] for p in planes)
 
 
 class ZoneCfg(C.Structure):                          # struct rtmodt_zone_cfg
@@ -77,6 +143,7 @@ def lib() -> C.CDLL:
         "rtmodt_detector_detect_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
         "rtmodt_detector_enqueue_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtmodt_detector_fetch": (C.c_int, [vp, vp, vp, vp, vp]),
+        "rtmodt_detector_enqueue_batch_fmt": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(FrameFormat), C.c_int]),
         "rtmodt_detector_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                            C.POINTER(i64), C.POINTER(i64)]),
         "rtmodt_detector_chains": (C.c_int, [vp, C.POINTER(i32)]),
@@ -92,6 +159,7 @@ def lib() -> C.CDLL:
         "rtmodt_nms_pred": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, f32, f32, vp, C.c_int, C.c_int, C.c_int,
                                       vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_preprocess": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_preprocess_yuv420": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.POINTER(FrameFormat), C.c_int, C.c_int, vp]),
         "rtmodt_tracker_create": (C.c_int, [C.c_int, f32, C.c_int, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
         "rtmodt_tracker_destroy": (None, [vp]),
         "rtmodt_tracker_set_cost_limit": (C.c_int, [vp, C.c_double]),
@@ -200,6 +268,28 @@ def preprocess(frame: np.ndarray, in_w: int = 640, in_h: int = 640, device: int 
     h, w = frame.shape[:2]
     out = np.empty((in_h, in_w, 3), np.float16)
     check(lib().rtmodt_preprocess(device, ptr(frame), h, w, frame.strides[0], in_w, in_h, ptr(out)))
+    return out
+
+
+def preprocess_yuv420(frame: np.ndarray, fmt="nv12", in_w: int = 640, in_h: int = 640, device: int = 0, *, height: int = 0,
+                      width: int = 0) -> np.ndarray:
+    """One 4:2:0 host frame -> the letterboxed network input (``rtmodt_preprocess_yuv420``, the kernel alone).  ``frame``: the
+    packed ``(h * 3 // 2, w)`` uint8 array of cv2 / ffmpeg (``fmt`` a format name), or any uint8 buffer with ``fmt`` a
+    ``FrameFormat`` and ``height`` / ``width`` given."""
+    frame = np.ascontiguousarray(frame, np.uint8)
+    if isinstance(fmt, FrameFormat):
+        h, w = int(height), int(width)
+    else:
+        if frame.ndim != 2 or frame.shape[0] % 3:
+            raise ValueError(f"a packed 4:2:0 frame is a (h * 3 // 2, w) array, got shape {frame.shape}")
+        h, w = frame.shape[0] * 2 // 3, frame.shape[1]
+        fmt = frame_format(fmt, h, w, pitch=frame.strides[0])
+    if pixel_format_id(fmt.pixel_format) == PIX_BGR24:
+        raise ValueError("preprocess_yuv420 takes NV12 / I420 frames (BGR24: preprocess)")
+    if frame.nbytes < frame_span(fmt, h, w):
+        raise ValueError(f"the buffer holds {frame.nbytes} bytes, the layout spans {frame_span(fmt, h, w)}")
+    out = np.empty((in_h, in_w, 3), np.float16)
+    check(lib().rtmodt_preprocess_yuv420(device, ptr(frame), h, w, C.byref(fmt), in_w, in_h, ptr(out)))
     return out
 
 

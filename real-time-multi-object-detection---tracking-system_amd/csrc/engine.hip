@@ -1440,6 +1440,52 @@ static int run_nms(rtmodt_detector *d, const LbHost &g, int h, int w, rtmodt_det
     return launch_nms(a, d->nms_plan, d->post_stream);
 }
 
+// A frame layout resolved and checked (rtmodt_frame_format -> what the letterbox kernels take).  `span`: bytes from the frame
+// pointer to the end of its last plane -- what one host frame stages.  Nothing is launched before this has passed.
+struct FrameLayout { bool yuv = false; int pitch = 0; YuvLayout l{}; size_t span = 0; };
+static int resolve_frame_format(int h, int w, const rtmodt_frame_format *fmt, FrameLayout &o) {
+    RT_CHECK(h >= 1 && w >= 1, RTMODT_E_INVALID, "bad frame geometry %dx%d", w, h);
+    const int pf = fmt ? fmt->pixel_format : RTMODT_PIX_BGR24;
+    RT_CHECK(pf == RTMODT_PIX_BGR24 || pf == RTMODT_PIX_NV12 || pf == RTMODT_PIX_I420, RTMODT_E_INVALID, "unknown pixel format %d", pf);
+    if (pf == RTMODT_PIX_BGR24) {
+        o.yuv = false;
+        o.pitch = fmt && fmt->pitch ? fmt->pitch : 3 * w;
+        RT_CHECK(o.pitch >= 3 * w, RTMODT_E_INVALID, "bad frame geometry %dx%d pitch %d", w, h, o.pitch);
+        o.span = (size_t)h * o.pitch;
+        return RTMODT_OK;
+    }
+    const bool nv12 = pf == RTMODT_PIX_NV12;
+    RT_CHECK(fmt->colorspace == 0, RTMODT_E_UNSUPPORTED, "colorspace %d: only 0 (BT.601 limited range) is implemented", fmt->colorspace);
+    RT_CHECK(h % 2 == 0 && w % 2 == 0, RTMODT_E_INVALID, "a 4:2:0 frame needs an even width and height, got %dx%d", w, h);
+    const int64_t pitch = fmt->pitch ? fmt->pitch : w;
+    const int64_t crow = nv12 ? w : w / 2;                                      // bytes of one chroma row
+    const int64_t cp = fmt->chroma_pitch ? fmt->chroma_pitch : (nv12 ? pitch : pitch / 2);
+    RT_CHECK(pitch >= w, RTMODT_E_INVALID, "Y pitch %lld < width %d", (long long)pitch, w);
+    RT_CHECK(cp >= crow, RTMODT_E_INVALID, "chroma pitch %lld < %lld bytes per chroma row", (long long)cp, (long long)crow);
+    const int64_t uo = fmt->u_offset ? fmt->u_offset : pitch * h;
+    const int64_t vo = nv12 ? 0 : (fmt->v_offset ? fmt->v_offset : uo + cp * (h / 2));
+    RT_CHECK(uo > 0 && vo >= 0, RTMODT_E_INVALID, "negative plane offset (u %lld, v %lld)", (long long)uo, (long long)vo);
+    // byte ranges [start, end) of the planes
+    const int64_t y_end = pitch * (h - 1) + w, c_rows = h / 2;
+    const int64_t u_end = uo + cp * (c_rows - 1) + crow, v_end = nv12 ? 0 : vo + cp * (c_rows - 1) + crow;
+    auto apart = [](int64_t a0, int64_t a1, int64_t b0, int64_t b1) { return a1 <= b0 || b1 <= a0; };
+    RT_CHECK(apart(0, y_end, uo, u_end), RTMODT_E_INVALID, "the %s plane [%lld, %lld) overlaps the Y plane [0, %lld)", nv12 ? "UV" : "U",
+             (long long)uo, (long long)u_end, (long long)y_end);
+    if (!nv12) {
+        RT_CHECK(apart(0, y_end, vo, v_end), RTMODT_E_INVALID, "the V plane [%lld, %lld) overlaps the Y plane [0, %lld)", (long long)vo,
+                 (long long)v_end, (long long)y_end);
+        RT_CHECK(apart(uo, u_end, vo, v_end), RTMODT_E_INVALID, "the V plane [%lld, %lld) overlaps the U plane [%lld, %lld)", (long long)vo,
+                 (long long)v_end, (long long)uo, (long long)u_end);
+    }
+    const int64_t span = std::max(y_end, std::max(u_end, v_end));
+    RT_CHECK(pitch <= INT32_MAX && cp <= INT32_MAX && span <= ((int64_t)1 << 40), RTMODT_E_INVALID, "frame layout too large");
+    o.yuv = true;
+    o.pitch = (int)pitch;
+    o.l.u_off = uo; o.l.v_off = vo; o.l.pitch = (int)pitch; o.l.chroma_pitch = (int)cp; o.l.nv12 = nv12;
+    o.span = (size_t)span;
+    return RTMODT_OK;
+}
+
 int detector_outputs(rtmodt_detector *d, DetOutputs *o) {
     RT_CHECK(d && o, RTMODT_E_INVALID, "null argument");
     RT_CHECK(d->newest >= 0, RTMODT_E_INVALID, "detector has no enqueued batch");
@@ -1653,11 +1699,11 @@ int rtmodt_detector_create(const rtmodt_det_cfg *cfg, rtmodt_detector **out) {
     return RTMODT_OK;
 }
 
-int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *frames, int n, int h, int w, int stride_bytes,
-                                  int mem_kind) {
-    RT_CHECK(d && frames, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(n >= 1 && n <= d->B, RTMODT_E_INVALID, "n %d outside [1, batch %d]", n, d->B);
-    RT_CHECK(h >= 1 && w >= 1 && stride_bytes >= w * 3, RTMODT_E_INVALID, "bad frame geometry %dx%d pitch %d", w, h, stride_bytes);
+// Both enqueue entry points.  BGR24 frames (fl.yuv false) take the path enqueue_batch always took: the stem / front end reads their
+// bytes when they need no resize, page-locked ones in place under RTMODT_ZERO_COPY.  4:2:0 frames always go through the image tensor:
+// letterbox_yuv420 fills it, then the stem reads it as it does for resized BGR frames (last_fused false).
+static int enqueue_impl(rtmodt_detector *d, const uint8_t *const *frames, int n, int h, int w, const FrameLayout &fl, int mem_kind) {
+    const int stride_bytes = fl.pitch;
     RT_CHECK(d->n_pending < rtmodt_detector::RING_SLOTS, RTMODT_E_CAPACITY, "%d batches already in flight: fetch before enqueueing more",
              d->n_pending);
     RT_HIP(hipSetDevice(d->device));
@@ -1668,7 +1714,7 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *fram
     // resize are not copied -- the stem conv reads their bytes in place, over PCIe, once.  The caller keeps such frames
     // unchanged until the batch is fetched.
     bool in_place = false;
-    if (mem_kind == RTMODT_MEM_HOST && d->zero_copy && d->stem_fuse && !g.resize) {
+    if (mem_kind == RTMODT_MEM_HOST && d->zero_copy && d->stem_fuse && !g.resize && !fl.yuv) {
         in_place = true;
         for (int i = 0; i < n && in_place; ++i) {
             hipPointerAttribute_t at{};
@@ -1680,11 +1726,15 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *fram
     d->last_in_place = in_place;
     if (in_place) {
     } else if (mem_kind == RTMODT_MEM_HOST) {
-        RT_CHECK((size_t)h * stride_bytes <= d->stage_per, RTMODT_E_CAPACITY, "frame %dx%d exceeds max_src %dx%d", w, h, d->cfg.max_src_w,
-                 d->cfg.max_src_h);
+        if (fl.yuv)
+            RT_CHECK(fl.span <= d->stage_per, RTMODT_E_CAPACITY, "a %dx%d 4:2:0 frame spans %zu bytes, the staging area holds %zu per frame (max_src %dx%d)",
+                     w, h, fl.span, d->stage_per, d->cfg.max_src_w, d->cfg.max_src_h);
+        else
+            RT_CHECK((size_t)h * stride_bytes <= d->stage_per, RTMODT_E_CAPACITY, "frame %dx%d exceeds max_src %dx%d", w, h, d->cfg.max_src_w,
+                     d->cfg.max_src_h);
         uint8_t *area = d->stage + d->stage_per * d->B * d->head;
         // frames that sit back to back in the caller's (page-locked) ring slot travel as ONE copy
-        const size_t fbytes = (size_t)h * stride_bytes;
+        const size_t fbytes = fl.yuv ? fl.span : (size_t)h * stride_bytes;
         bool contig = n > 1;
         for (int i = 1; i < n && contig; ++i) contig = frames[i] == frames[0] + fbytes * i;
         const size_t dst_step = contig ? fbytes : d->stage_per;
@@ -1740,7 +1790,7 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *fram
     TensorView img; img.base = d->tensors[d->img_t].ptr; img.H = d->in_h; img.W = d->in_w; img.C = 4; img.pad = 1; img.c = 4;
     d->cur_dense = d->head;                            // ring slot == dense set
     d->last_lg = lg; d->last_pitch = stride_bytes;
-    d->last_fused = d->stem_fuse && !g.resize;
+    d->last_fused = d->stem_fuse && !g.resize && !fl.yuv;
     const bool graphs = (!d->graph_execs.empty() || (d->pipe && d->pipe_exec[0][0][0])) && !d->want_pred;
     const bool chained = graphs && d->n_chains > 1;
     // a lagging chain of the previous batch may still be reading what the main stream is about to overwrite or time
@@ -1757,7 +1807,8 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *fram
     RT_HIP(hipEventRecord(sl.ev0, d->stream));
     if (!d->last_fused) {
         if (graphs && d->pipe) img.base = (f16 *)((char *)img.base + (size_t)(d->batch_no % d->n_stages) * d->arena_stride);
-        RT_TRY(launch_letterbox(d->fptrs, stride_bytes, lg, d->tabs, img, d->B, d->stream));
+        if (fl.yuv) RT_TRY(launch_letterbox_yuv420(d->fptrs, fl.l, lg, d->tabs, img, d->B, d->stream));
+        else RT_TRY(launch_letterbox(d->fptrs, stride_bytes, lg, d->tabs, img, d->B, d->stream));
         if (chained) RT_HIP(hipEventRecord(sl.evp, d->stream));
     }
     sl.chained = chained; sl.joined = false;
@@ -1816,6 +1867,25 @@ int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *fram
     d->n_pending += 1;
     d->last_h = h; d->last_w = w;
     return RTMODT_OK;
+}
+
+int rtmodt_detector_enqueue_batch(rtmodt_detector *d, const uint8_t *const *frames, int n, int h, int w, int stride_bytes,
+                                  int mem_kind) {
+    RT_CHECK(d && frames, RTMODT_E_INVALID, "null argument");
+    RT_CHECK(n >= 1 && n <= d->B, RTMODT_E_INVALID, "n %d outside [1, batch %d]", n, d->B);
+    RT_CHECK(h >= 1 && w >= 1 && stride_bytes >= w * 3, RTMODT_E_INVALID, "bad frame geometry %dx%d pitch %d", w, h, stride_bytes);
+    FrameLayout fl;
+    fl.pitch = stride_bytes; fl.span = (size_t)h * stride_bytes;
+    return enqueue_impl(d, frames, n, h, w, fl, mem_kind);
+}
+
+int rtmodt_detector_enqueue_batch_fmt(rtmodt_detector *d, const uint8_t *const *frames, int n, int h, int w, const rtmodt_frame_format *fmt,
+                                      int mem_kind) {
+    RT_CHECK(d && frames, RTMODT_E_INVALID, "null argument");
+    RT_CHECK(n >= 1 && n <= d->B, RTMODT_E_INVALID, "n %d outside [1, batch %d]", n, d->B);
+    FrameLayout fl;
+    RT_TRY(resolve_frame_format(h, w, fmt, fl));
+    return enqueue_impl(d, frames, n, h, w, fl, mem_kind);
 }
 
 // ---- in-kernel shader clock ------------------------------------------------------------------------------------------
@@ -2199,6 +2269,53 @@ int rtmodt_preprocess(int device, const uint8_t *bgr, int h, int w, int stride_b
     LetterboxGeom lg{h, w, g.new_w, g.new_h, g.top, g.left, g.resize};
     TensorView img; img.base = dout; img.H = in_h; img.W = in_w; img.C = 4; img.pad = 1; img.c = 4;
     RT_TRY(launch_letterbox(fp, stride_bytes, lg, tabs, img, 1, nullptr));
+    RT_HIP(hipDeviceSynchronize());
+    std::vector<uint16_t> tmp(per);
+    RT_HIP(hipMemcpy(tmp.data(), dout, per * 2, hipMemcpyDeviceToHost));
+    for (int y = 0; y < in_h; ++y)
+        for (int x = 0; x < in_w; ++x)
+            memcpy(out_f16 + ((size_t)y * in_w + x) * 3, &tmp[((size_t)(y + 1) * (in_w + 2) + x + 1) * 4], 6);
+    return RTMODT_OK;
+}
+
+int rtmodt_preprocess_yuv420(int device, const uint8_t *frame, int h, int w, const rtmodt_frame_format *fmt, int in_w, int in_h,
+                             uint16_t *out_f16) {
+    RT_CHECK(frame && fmt && out_f16 && in_w >= 1 && in_h >= 1, RTMODT_E_INVALID, "bad argument");
+    RT_CHECK(fmt->pixel_format == RTMODT_PIX_NV12 || fmt->pixel_format == RTMODT_PIX_I420, RTMODT_E_INVALID,
+             "preprocess_yuv420: pixel format %d is not a 4:2:0 format", fmt->pixel_format);
+    FrameLayout fl;
+    RT_TRY(resolve_frame_format(h, w, fmt, fl));
+    RT_HIP(hipSetDevice(device));
+    struct Bufs {
+        std::vector<void *> p;
+        ~Bufs() { for (void *q : p) hipFree(q); }
+        int get(size_t bytes, void **o) { RT_HIP(hipMalloc(o, bytes)); p.push_back(*o); return RTMODT_OK; }
+    } bufs;
+    uint8_t *dimg; f16 *dout; int32_t *dtab;
+    size_t per = (size_t)(in_h + 2) * (in_w + 2) * 4;
+    RT_TRY(bufs.get(fl.span, (void **)&dimg));
+    RT_TRY(bufs.get(per * 2, (void **)&dout));
+    RT_HIP(hipMemset(dout, 0, per * 2));
+    RT_HIP(hipMemcpy(dimg, frame, fl.span, hipMemcpyHostToDevice));
+    FramePtrs fp{};
+    fp.p[0] = dimg;
+    LbHost g = letterbox_geometry(h, w, in_h, in_w);
+    ResizeTables tabs{};
+    if (g.resize) {
+        std::vector<int32_t> t[6];
+        build_resize_tables(g.new_w, w, t[0], t[1], t[2]);
+        build_resize_tables(g.new_h, h, t[3], t[4], t[5]);
+        RT_TRY(bufs.get((size_t)(g.new_w + g.new_h) * 3 * 4, (void **)&dtab));
+        const int32_t *dst[6]; int32_t *p = dtab;
+        for (int k = 0; k < 6; ++k) {
+            RT_HIP(hipMemcpy(p, t[k].data(), t[k].size() * 4, hipMemcpyHostToDevice));
+            dst[k] = p; p += t[k].size();
+        }
+        tabs = ResizeTables{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5]};
+    }
+    LetterboxGeom lg{h, w, g.new_w, g.new_h, g.top, g.left, g.resize};
+    TensorView img; img.base = dout; img.H = in_h; img.W = in_w; img.C = 4; img.pad = 1; img.c = 4;
+    RT_TRY(launch_letterbox_yuv420(fp, fl.l, lg, tabs, img, 1, nullptr));
     RT_HIP(hipDeviceSynchronize());
     std::vector<uint16_t> tmp(per);
     RT_HIP(hipMemcpy(tmp.data(), dout, per * 2, hipMemcpyDeviceToHost));

@@ -154,6 +154,12 @@ struct ResizeTables {          // device arrays, cv::resize INTER_LINEAR fixed-p
 };
 int launch_letterbox(const FramePtrs &frames, int pitch, const LetterboxGeom &g, const ResizeTables &t,
                      const TensorView &img4, int B, hipStream_t s);
+// 4:2:0 frames (NV12 / I420, BT.601 limited range as cv::cvtColor converts it) -> the same image tensor.  Byte offsets from
+// each frame pointer: Y row y at y * pitch; chroma row j (of h / 2) at u_off / v_off + j * chroma_pitch (NV12: interleaved
+// U, V at u_off; v_off unused).  Passed by value in the kernel arguments, like FramePtrs.
+struct YuvLayout { long u_off = 0, v_off = 0; int pitch = 0, chroma_pitch = 0, nv12 = 1; };
+int launch_letterbox_yuv420(const FramePtrs &frames, const YuvLayout &l, const LetterboxGeom &g, const ResizeTables &t,
+                            const TensorView &img4, int B, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // postprocess (postprocess.hip)

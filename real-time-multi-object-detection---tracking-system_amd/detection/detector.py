@@ -77,7 +77,10 @@ class Detector:
     ``chains`` picks the engine (``rtmodt_det_cfg.chains``): 0 automatic (two stages for ``batch >= 2``, the plain
     engine for ``batch == 1``), 1 plain, n > 1 sub-batch chains, -1 / -2 the staged engine with two / three stages
     (keep stages + 1 batches in flight through :meth:`enqueue` / :meth:`fetch`; three stages only when the frames are
-    already in device memory); ``rect`` the minimal-rectangle letterbox of ``predict`` on a ``.pt`` model."""
+    already in device memory); ``rect`` the minimal-rectangle letterbox of ``predict`` on a ``.pt`` model; ``pixel_format``
+    the frames' format: ``"bgr24"`` (``H x W x 3``), or ``"nv12"`` / ``"i420"`` (alias ``"yuv420p"``) -- a decoder's 4:2:0
+    output as the packed ``(H * 3 // 2, W)`` uint8 array of cv2 / ffmpeg, converted (BT.601 limited range, OpenCV's integer
+    conversion) and letterboxed on the GPU."""
 
     _WARMUP_ITERATIONS = 10
 
@@ -101,6 +104,7 @@ class Detector:
         chains: int = 0,
         warmup: bool = True,
         rect: bool = False,
+        pixel_format: str = "bgr24",
     ) -> None:
         self.input_size = input_size
         self.confidence = confidence
@@ -110,6 +114,8 @@ class Detector:
         self.max_det = max_det
         self.agnostic_nms = agnostic_nms
         self.batch = int(batch)
+        self._pix = _ffi.pixel_format_id(pixel_format)
+        self.pixel_format = self._fmt_name(self._pix)
         self._ordinal = _ffi.device_ordinal(device)
         primary = Path(model_path)
         if primary.exists():                              # detector.py:82-90
@@ -182,7 +188,7 @@ class Detector:
 
     # ------------------------------------------------------------------
     def detect(self, frame: np.ndarray) -> Detections:
-        """One BGR uint8 frame -> ``Detections`` (detector.py:98-112)."""
+        """One uint8 frame in the detector's ``pixel_format`` -> ``Detections`` (detector.py:98-112)."""
         return self.detect_batch([frame])[0]
 
     def detect_batch(self, frames: Sequence[np.ndarray]) -> list:
@@ -192,9 +198,13 @@ class Detector:
         self.enqueue(frames)
         return self.fetch()
 
-    def enqueue(self, frames: Sequence, height: int = 0, width: int = 0, pitch: int = 0) -> None:
-        """Asynchronous half of :meth:`detect_batch`.  ``frames``: NumPy BGR images, or raw
-        device addresses (ints) of BGR images with ``height/width/pitch`` given.
+    def enqueue(self, frames: Sequence, height: int = 0, width: int = 0, pitch: int = 0, *, pixel_format=None, chroma_pitch: int = 0,
+                u_offset: int = 0, v_offset: int = 0) -> None:
+        """Asynchronous half of :meth:`detect_batch`.  ``frames``: NumPy images in the pixel format (``H x W x 3`` BGR, or the
+        packed ``(H * 3 // 2, W)`` 4:2:0 array), or raw device addresses (ints) of frames with ``height/width/pitch`` given.
+        ``pixel_format`` overrides the detector's format for this call; ``chroma_pitch`` / ``u_offset`` / ``v_offset`` describe a
+        4:2:0 layout other than the packed one (``rtmodt_frame_format``: a decoder surface padded to 1088 rows has
+        ``u_offset = pitch * 1088``).  Zeros mean the packed defaults.
 
         Host frames in page-locked memory (``_ffi.PinnedArray`` / ``pipeline.PinnedFrameRing``) that need no resize are
         read by the stem kernel in place, other host frames are copied asynchronously: either way the caller must not
@@ -202,28 +212,48 @@ class Detector:
         n = len(frames)
         if n < 1 or n > self.batch:
             raise ValueError(f"{n} frames for a detector built with batch={self.batch}")
+        pix = self._pix if pixel_format is None else _ffi.pixel_format_id(pixel_format)
         arr = (C.c_void_p * n)()
         keep = None
         if isinstance(frames[0], (int, np.integer)):
-            kind, h, w, p = _ffi.MEM_DEVICE, height, width, pitch or width * 3
+            kind, h, w = _ffi.MEM_DEVICE, height, width
+            p = pitch or (width * 3 if pix == _ffi.PIX_BGR24 else width)
             for i, a in enumerate(frames):
                 arr[i] = int(a)
         else:
             kind = _ffi.MEM_HOST
             keep = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
-            h, w = keep[0].shape[:2]
+            if pix == _ffi.PIX_BGR24:
+                h, w = keep[0].shape[:2]
+                for a in keep:
+                    if a.shape[:2] != (h, w) or a.ndim != 3 or a.shape[2] != 3:
+                        raise ValueError("frames of one batch must share one H x W x 3 shape")
+            else:
+                rows, w = keep[0].shape[:2]
+                if keep[0].ndim != 2 or rows % 3:
+                    raise ValueError(f"a packed {self._fmt_name(pix)} frame is a (H * 3 // 2, W) uint8 array, got shape {keep[0].shape}")
+                h = rows * 2 // 3
+                for a in keep:
+                    if a.shape != keep[0].shape:
+                        raise ValueError("frames of one batch must share one shape")
             p = keep[0].strides[0]
             for i, a in enumerate(keep):
-                if a.shape[:2] != (h, w) or a.ndim != 3 or a.shape[2] != 3:
-                    raise ValueError("frames of one batch must share one H x W x 3 shape")
                 arr[i] = a.ctypes.data
+        fmt = None
+        if pix != _ffi.PIX_BGR24 or chroma_pitch or u_offset or v_offset:
+            fmt = _ffi.frame_format(pix, int(h), int(w), int(p), chroma_pitch, u_offset, v_offset)
+            if keep is not None and keep[0].nbytes < _ffi.frame_span(fmt, h, w):
+                raise ValueError(f"a host frame of {keep[0].nbytes} bytes is shorter than its layout ({_ffi.frame_span(fmt, h, w)} bytes)")
         if self.rect:
             want = self.rect_shape(int(h), int(w), self._side)
             if want != self.model.input_hw:
                 if self._in_flight:                       # they live in the other rectangle's engine
                     raise RuntimeError("fetch() the pending results before enqueueing frames of another size")
                 self.model = self._model_for(*want)
-        _ffi.check(_ffi.lib().rtmodt_detector_enqueue_batch(self.model.handle, arr, n, int(h), int(w), int(p), kind))
+        if fmt is None:                                  # BGR24: the original entry point
+            _ffi.check(_ffi.lib().rtmodt_detector_enqueue_batch(self.model.handle, arr, n, int(h), int(w), int(p), kind))
+        else:
+            _ffi.check(_ffi.lib().rtmodt_detector_enqueue_batch_fmt(self.model.handle, arr, n, int(h), int(w), C.byref(fmt), kind))
         self._in_flight.append(n)
         self._keepalive.append(keep)
 
@@ -263,8 +293,15 @@ class Detector:
         names = [self.model.names.get(int(c), str(c)) for c in cls]
         return Detections(self._xyxy[i, :k].copy(), self._conf[i, :k].copy(), cls, names)
 
+    @staticmethod
+    def _fmt_name(pix: int) -> str:
+        return {_ffi.PIX_BGR24: "bgr24", _ffi.PIX_NV12: "nv12", _ffi.PIX_I420: "i420"}[pix]
+
     def _warmup(self) -> None:
         dummy = np.zeros((*self.input_size[::-1], 3), dtype=np.uint8)     # detector.py:131-135
+        if self._pix != _ffi.PIX_BGR24:                                    # zero frames in the detector's own format
+            h, w = dummy.shape[:2]
+            dummy = np.zeros((h // 2 * 3, w // 2 * 2), dtype=np.uint8)
         for _ in range(self._WARMUP_ITERATIONS):
             self.detect(dummy)
 

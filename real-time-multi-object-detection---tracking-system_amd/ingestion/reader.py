@@ -8,7 +8,8 @@ so that ``pipeline.run`` takes either.  What is different, because the step afte
 * the reference decodes through ``cv2.VideoCapture`` (FFmpeg or a GStreamer string with NVIDIA's decoder element); neither
   OpenCV nor a video decoder is part of this build, so the capture device is a small protocol (``opened / grab() /
   retrieve() / release()``) with registered back-ends: ``"raw"`` -- BGR24 frames from a file, FIFO or pipe (what
-  ``ffmpeg -i rtsp://... -f rawvideo -pix_fmt bgr24 -`` writes), ``"synthetic"`` -- a generated ring; ``register_backend``
+  ``ffmpeg -i rtsp://... -f rawvideo -pix_fmt bgr24 -`` writes; ``pixel_format="nv12"`` / ``"yuv420p"`` for ``-pix_fmt nv12`` /
+  ``yuv420p``, which the detector converts on the GPU), ``"synthetic"`` -- a generated ring; ``register_backend``
   adds others (a ``cv2.VideoCapture`` wrapper is four lines and listed in INTEGRATION.md);
 * decoded frames land directly in a PAGE-LOCKED ring (``pipeline.PinnedFrameRing``) when one is given: the detector's upload
   of such a frame is one asynchronous DMA, and ``read(copy=False)`` hands out the slot itself instead of a copy -- as a
@@ -64,13 +65,27 @@ class SyntheticCapture:
 
 
 class RawVideoCapture:
-    """BGR24 frames of a fixed ``resolution`` (width, height) read back to back from a file, FIFO or ``-`` (stdin)."""
+    """Frames of a fixed ``resolution`` (width, height) read back to back from a file, FIFO or ``-`` (stdin): BGR24
+    (``-pix_fmt bgr24``, ``H x W x 3``) or, with ``pixel_format="nv12"`` / ``"yuv420p"`` (``"i420"``), a decoder's 4:2:0 output
+    as the packed ``(H * 3 // 2, W)`` array (``Detector(pixel_format=...)`` converts it on the GPU; half the bytes of BGR24)."""
 
-    def __init__(self, source: str, resolution: Optional[Tuple[int, int]] = None, **_):
+    _FORMATS = {"bgr24": "bgr24", "nv12": "nv12", "yuv420p": "i420", "i420": "i420"}
+
+    def __init__(self, source: str, resolution: Optional[Tuple[int, int]] = None, pixel_format: str = "bgr24", **_):
         if not resolution:
             raise ValueError("the raw back-end needs resolution=(width, height)")
         self._w, self._h = int(resolution[0]), int(resolution[1])
-        self._nbytes = self._w * self._h * 3
+        fmt = self._FORMATS.get(str(pixel_format).lower())
+        if fmt is None:
+            raise ValueError(f"unknown raw pixel format {pixel_format!r}; one of {sorted(self._FORMATS)}")
+        self.pixel_format = fmt
+        if fmt == "bgr24":
+            self._shape = (self._h, self._w, 3)
+        else:
+            if self._w % 2 or self._h % 2:
+                raise ValueError(f"4:2:0 frames need an even width and height, got {self._w}x{self._h}")
+            self._shape = (self._h * 3 // 2, self._w)
+        self._nbytes = int(np.prod(self._shape))
         import sys
         try:
             self._f = sys.stdin.buffer if source == "-" else open(source, "rb", buffering=0)
@@ -92,7 +107,7 @@ class RawVideoCapture:
         return True
 
     def retrieve(self, out: Optional[np.ndarray] = None):
-        src = np.frombuffer(self._buf, np.uint8).reshape(self._h, self._w, 3)
+        src = np.frombuffer(self._buf, np.uint8).reshape(self._shape)
         if out is None:
             return True, src.copy()
         np.copyto(out, src)
@@ -114,7 +129,8 @@ def register_backend(name: str, factory: Callable) -> None:
 
 
 class FrameReader:
-    """Thread-safe, latest-frame-only frame provider (same constructor and methods as the reference's ``RTSPReader``)."""
+    """Thread-safe, latest-frame-only frame provider (same constructor and methods as the reference's ``RTSPReader``).
+    Further keywords go to the back-end as they are: ``pixel_format="nv12"`` makes the raw back-end deliver 4:2:0 frames."""
 
     def __init__(self, source: str, backend: str = "raw", buffer_size: int = 1, target_fps: int = 30, reconnect_delay: float = 3.0,
                  max_reconnects: int = 10, resolution: Optional[Tuple[int, int]] = None, ring=None, **backend_kw) -> None:

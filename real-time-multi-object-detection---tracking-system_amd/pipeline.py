@@ -34,13 +34,22 @@ class SyntheticSource:
 
 class PinnedFrameRing:
     """The frame ring between a decoder and the detector: ``slots`` page-locked H x W x 3
-    uint8 images.  ``write(i, frame)`` is what a capture thread does with a decoded frame; ``frame(i)`` is the
+    uint8 images (``pixel_format="bgr24"``), or packed ``(H * 3 // 2, W)`` 4:2:0 frames (``"nv12"`` / ``"i420"`` /
+    ``"yuv420p"``: half the bytes).  ``write(i, frame)`` is what a capture thread does with a decoded frame; ``frame(i)`` is the
     view handed to ``Detector.enqueue`` -- its upload is then a true asynchronous DMA on the engine's copy stream."""
 
-    def __init__(self, slots: int, height: int, width: int, device=0):
+    def __init__(self, slots: int, height: int, width: int, device=0, *, pixel_format: str = "bgr24"):
         from . import _ffi
-        self._mem = _ffi.PinnedArray((slots, height, width, 3), np.uint8, _ffi.device_ordinal(device))
+        pix = _ffi.pixel_format_id(pixel_format)
+        if pix == _ffi.PIX_BGR24:
+            shape = (slots, height, width, 3)
+        else:
+            if height % 2 or width % 2:
+                raise ValueError(f"4:2:0 frames need an even width and height, got {width}x{height}")
+            shape = (slots, height * 3 // 2, width)
+        self._mem = _ffi.PinnedArray(shape, np.uint8, _ffi.device_ordinal(device))
         self.slots = slots
+        self.pixel_format = pixel_format
 
     def write(self, i: int, frame: np.ndarray) -> np.ndarray:
         dst = self._mem.array[i % self.slots]

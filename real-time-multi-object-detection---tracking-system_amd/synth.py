@@ -6,6 +6,8 @@ test and benchmark input is generated here from fixed seeds:
 * :func:`box_sequence`  -- constant-velocity boxes for the tracker (BASELINE
   configs 3 and 5: 200 boxes on 640x640, 500 boxes on 1280x1280).
 * :func:`frames`        -- uniform-random BGR uint8 video frames.
+* :func:`bgr_to_yuv420` / :func:`yuv420_frames` -- BGR frames as a decoder's 4:2:0
+  output (NV12 / I420, the packed ``(H * 3 // 2, W)`` layout of cv2 / ffmpeg).
 * :func:`planted_pred`  -- a pre-NMS ``(84, A)`` prediction tensor with planted
   box clusters whose survivors are known by construction (BASELINE config 2).
 """
@@ -58,6 +60,46 @@ def structured_frames(n: int, height: int = 640, width: int = 640, seed: int = 7
             img += w[..., None] * col
         out[i] = np.clip(img, 0, 255).astype(np.uint8)
     return out
+
+
+def bgr_to_yuv420(bgr: np.ndarray, pixel_format: str = "nv12", seed: int = 0, noise: float = 0.0) -> np.ndarray:
+    """``(..., H, W, 3)`` BGR uint8 -> ``(..., H * 3 // 2, W)`` uint8 NV12 or I420 (``"i420"`` / ``"yuv420p"``): BT.601 limited
+    range in floating point, chroma averaged over each 2 x 2 block, plus seeded Gaussian noise of ``noise`` code values.  The
+    result is only ever INPUT bytes (what a decoder would hand over); its rounding is not part of any contract."""
+    bgr = np.asarray(bgr, np.uint8)
+    h, w = bgr.shape[-3:-1]
+    if h % 2 or w % 2:
+        raise ValueError(f"4:2:0 needs an even width and height, got {w}x{h}")
+    f = bgr.astype(np.float32)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = 16 + (65.481 * r + 128.553 * g + 24.966 * b) / 255
+    u = 128 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255
+    v = 128 + (112.0 * r - 93.786 * g - 18.214 * b) / 255
+    sub = lambda c: c.reshape(*c.shape[:-2], h // 2, 2, w // 2, 2).mean(axis=(-3, -1))
+    u, v = sub(u), sub(v)
+    if noise:
+        rng = np.random.default_rng(seed)
+        y, u, v = (c + rng.normal(0.0, noise, size=c.shape) for c in (y, u, v))
+    y, u, v = (np.clip(np.rint(c), 0, 255).astype(np.uint8) for c in (y, u, v))
+    lead = bgr.shape[:-3]
+    out = np.empty((*lead, h * 3 // 2, w), np.uint8)
+    out[..., :h, :] = y
+    chroma = out[..., h:, :]
+    if pixel_format.lower() == "nv12":
+        uv = np.stack([u, v], axis=-1).reshape(*lead, h // 2, w)
+        chroma[...] = uv
+    elif pixel_format.lower() in ("i420", "yuv420p"):
+        chroma.reshape(*lead, h * w // 2)[..., :h * w // 4] = u.reshape(*lead, -1)
+        chroma.reshape(*lead, h * w // 2)[..., h * w // 4:] = v.reshape(*lead, -1)
+    else:
+        raise ValueError(f"unknown 4:2:0 format {pixel_format!r}")
+    return out
+
+
+def yuv420_frames(n: int, height: int = 640, width: int = 640, pixel_format: str = "nv12", seed: int = 7) -> np.ndarray:
+    """``n`` structured frames (:func:`structured_frames`, same seed) as NV12 / I420 ``(n, H * 3 // 2, W)`` uint8, with a little
+    seeded noise so that every code value of the planes occurs."""
+    return bgr_to_yuv420(structured_frames(n, height, width, seed), pixel_format, seed=seed, noise=6.0)
 
 
 def planted_pred(n_anchors: int = 8400, n_classes: int = 80, n_clusters: int = 40,
