@@ -40,6 +40,7 @@ extern "C" {
 typedef struct rtmodt_detector rtmodt_detector;
 typedef struct rtmodt_tracker rtmodt_tracker;
 typedef struct rtmodt_zones rtmodt_zones;
+typedef struct rtmodt_renderer rtmodt_renderer;
 
 /* ---- library / device ------------------------------------------------------------- */
 const char *rtmodt_last_error(void);
@@ -279,6 +280,53 @@ int rtmodt_zones_process_tracker(rtmodt_zones *z, rtmodt_tracker *trk, double no
  * [rows][n_zones] indexed by key (last_alert 0.0 = no entry).  Arrays sized 2 x max_tracks rows. */
 int rtmodt_zones_state(rtmodt_zones *z, int stream, int64_t *ids, uint32_t *occ_mask, double *first_seen,
                        double *last_alert, int32_t *n);
+
+/* ---- frame renderer: replaces FrameRenderer.render (src/visualization/renderer.py) ---------- */
+/* Annotates BGR24 frames in place, one launch per batch (csrc/render.hip, whose header comment states the paint rules; they
+ * restate cv2's drawing calls -- PARITY UNPINNED: no OpenCV to run against).  Per frame, in this order: zone tint (the
+ * zone engine's inside-or-on test) blended 0.25 / 0.75 with the frame, zone names drawn into the frame before the blend;
+ * then per track in list order: box outline, label box + label text, trail; then the HUD.  Strokes are "every pixel whose
+ * centre lies within distance 1 of the segment"; text uses the bundled bitmap fonts of csrc/font_atlas.h. */
+typedef struct rtmodt_render_cfg {
+    int32_t show_boxes, show_ids, show_trails, show_zones, show_fps;   /* renderer.py:32-38, all 1 by default      */
+    int32_t trail_length;           /* 1..1024: a trail draws its last trail_length points (renderer.py:87)             */
+    const uint8_t *palette_bgr;     /* n_palette x (B, G, R); NULL = the reference's 20 colours                          */
+    int32_t n_palette;              /* 1..256 when palette_bgr is given                                                  */
+} rtmodt_render_cfg;
+/* One track of a draw list (duck-typed Track: track_id / xyxy / label / trail). */
+typedef struct rtmodt_render_track {
+    int64_t track_id;               /* colour = palette[track_id mod n_palette], the mod taken as Python's % does          */
+    float xyxy[4];                  /* corners int(v) (truncation), clamped to +-2^20; NaN is RTMODT_E_INVALID           */
+    const char *label;              /* show_ids: the text above the box (the reference formats "ID:{id} {class_name}
+                                     * {conf:.2f}"), NUL-terminated, at most 255 bytes; bytes outside 32..126 draw as '?' */
+    const int32_t *trail_xy;        /* n_trail x (x, y), oldest first, each clamped to +-2^20                             */
+    int32_t n_trail;
+} rtmodt_render_track;
+typedef struct rtmodt_render_list {
+    const rtmodt_render_track *tracks;
+    int32_t n_tracks;               /* at most 65536 per frame                                                           */
+} rtmodt_render_list;
+
+int rtmodt_renderer_create(int device, const rtmodt_render_cfg *cfg, rtmodt_renderer **out);
+void rtmodt_renderer_destroy(rtmodt_renderer *r);
+/* The zones later batches tint (ZoneEventEngine.get_zone_polygons(): name + int32 polygon), uploaded once and cached;
+ * n_zones = 0 clears them.  At most 32 zones / 2048 points / 255-byte names, else RTMODT_E_CAPACITY.  A name is drawn at
+ * (int(m10 / m00) - 30, int(m01 / m00)) of the polygon's contour moments (float64), nothing when m00 == 0. */
+int rtmodt_renderer_set_zones(rtmodt_renderer *r, const int32_t *const *polygons_xy, const int32_t *n_points,
+                              const char *const *names, int n_zones);
+/* Draws lists[i] onto frames[i] (n frames of h x w, row pitch stride_bytes >= 3w; the bytes past 3w of a row are never
+ * touched).  mem_kind RTMODT_MEM_DEVICE: frames are device pointers, drawn in place; RTMODT_MEM_HOST: uploaded, drawn and
+ * copied back.  draw_zones = 1: the cached zones are drawn first (when show_zones).  fps / latency_ms feed the HUD
+ * ("FPS: %.1f | Latency: %.1fms").  All draw lists travel in one command buffer (one host-to-device copy); returns when
+ * the frames are final. */
+int rtmodt_render_batch(rtmodt_renderer *r, uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind,
+                        const rtmodt_render_list *lists, int draw_zones, double fps, double latency_ms);
+/* Device time (ms, HIP events) of the last render_batch's kernel. */
+int rtmodt_renderer_last_ms(rtmodt_renderer *r, float *kernel_ms);
+/* The command buffer render_batch would send for these lists (host only, no device needed; frame pointers left 0):
+ * *needed = its size; written to out when out_bytes >= *needed.  Layout: csrc/render.hip, "command buffer". */
+int rtmodt_render_pack(const rtmodt_render_cfg *cfg, const rtmodt_render_list *lists, int n, int h, int w, int draw_zones,
+                       double fps, double latency_ms, void *out, size_t out_bytes, size_t *needed);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,20 @@ class ZoneCfg(C.Structure):                          # struct rtmodt_zone_cfg
                 ("cooldown_sec", C.c_double), ("key", C.c_int32)]
 
 
+class RenderCfg(C.Structure):                        # struct rtmodt_render_cfg
+    _fields_ = [("show_boxes", C.c_int32), ("show_ids", C.c_int32), ("show_trails", C.c_int32), ("show_zones", C.c_int32),
+                ("show_fps", C.c_int32), ("trail_length", C.c_int32), ("palette_bgr", C.POINTER(C.c_uint8)), ("n_palette", C.c_int32)]
+
+
+class RenderTrack(C.Structure):                      # struct rtmodt_render_track
+    _fields_ = [("track_id", C.c_int64), ("xyxy", C.c_float * 4), ("label", C.c_char_p), ("trail_xy", C.POINTER(C.c_int32)),
+                ("n_trail", C.c_int32)]
+
+
+class RenderList(C.Structure):                       # struct rtmodt_render_list
+    _fields_ = [("tracks", C.POINTER(RenderTrack)), ("n_tracks", C.c_int32)]
+
+
 _lib = None
 
 
@@ -180,6 +194,14 @@ def lib() -> C.CDLL:
         "rtmodt_zones_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, i64, vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_zones_process_tracker": (C.c_int, [vp, vp, C.c_double, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
         "rtmodt_zones_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
+        "rtmodt_renderer_destroy": (None, [vp]),
+        "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "rtmodt_render_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RenderList), C.c_int,
+                                          C.c_double, C.c_double]),
+        "rtmodt_renderer_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_render_pack": (C.c_int, [C.POINTER(RenderCfg), C.POINTER(RenderList), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                         C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == header/library drift
@@ -306,6 +328,16 @@ class DeviceBuffer:
         host = np.ascontiguousarray(host)
         assert offset + host.nbytes <= self.nbytes
         check(lib().rtmodt_memcpy_h2d(self.device, C.c_void_p(self.ptr + offset), ptr(host), host.nbytes))
+
+    def download(self, nbytes: int | None = None, offset: int = 0) -> np.ndarray:
+        """``nbytes`` bytes from ``offset`` (default: the rest of the buffer) as a new host uint8 array."""
+        nbytes = self.nbytes - offset if nbytes is None else int(nbytes)
+        if offset < 0 or nbytes < 0 or offset + nbytes > self.nbytes:
+            raise ValueError(f"[{offset}, {offset + nbytes}) outside the {self.nbytes}-byte buffer")
+        out = np.empty(nbytes, np.uint8)
+        if nbytes:
+            check(lib().rtmodt_memcpy_d2h(self.device, ptr(out), C.c_void_p(self.ptr + offset), nbytes))
+        return out
 
     def free(self):
         if self.ptr:

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "polygon.h"
 
 namespace rtmodt {
 
@@ -56,26 +57,6 @@ struct ZoneArgs {
     // events [n_streams][max_events]
     int64_t *ev_id; int32_t *ev_track; int32_t *ev_zone; double *ev_dwell; float4 *ev_box; int2 *ev_c; int32_t *ev_cls; int32_t *ev_n;
 };
-
-// cv::pointPolygonTest(contour int32, integer point, measureDist=false) >= 0  (oracle/zone_oracle.py:point_polygon_test)
-__device__ __forceinline__ bool inside_or_on(const int2 *p, int total, int x, int y) {
-    if (total == 0) return false;
-    int counter = 0;
-    int2 v = p[total - 1];
-    for (int i = 0; i < total; ++i) {
-        const int2 v0 = v;
-        v = p[i];
-        if ((v0.y <= y && v.y <= y) || (v0.y > y && v.y > y) || (v0.x < x && v.x < x)) {
-            if (y == v.y && (x == v.x || (y == v0.y && ((v0.x <= x && x <= v.x) || (v.x <= x && x <= v0.x))))) return true;
-            continue;
-        }
-        long long dist = (long long)(y - v0.y) * (v.x - v0.x) - (long long)(x - v0.x) * (v.y - v0.y);
-        if (dist == 0) return true;
-        if (v.y < v0.y) dist = -dist;
-        counter += dist > 0;
-    }
-    return (counter & 1) != 0;
-}
 
 __device__ __forceinline__ int lower_bound_i64(const int64_t *a, int n, int64_t x) {     // first index with a[i] >= x
     int lo = 0, hi = n;

@@ -1,8 +1,8 @@
 """The hot loop of the reference's ``tools/run_pipeline.py:121-158`` around the native
 detector and tracker: read frame -> ``detector.detect`` ->
 ``tracker.update`` -> ``profiler.end_frame``, every stage bracketed by the sync-ing
-profiler exactly as the reference does.  RTSP ingestion, the zone engine and the renderer
-are out of scope; their stages are simply absent from the table.
+profiler exactly as the reference does.  The zone engine (``event_engine``) and the renderer
+(``renderer``, a ``FrameRenderer``) are optional; without them their stages are absent from the table.
 
 On top of the reference's three wall-clock stages (``decode``, ``inference``, ``tracking``)
 the loop records what the engine measured with HIP events inside ``inference``:
@@ -64,14 +64,18 @@ class PinnedFrameRing:
 
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
-        device_stages: bool = True, event_engine=None, device_handoff: bool = True) -> dict:
+        device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
     ``device_handoff`` (default): the tracker consumes the detector's detections where they are, on the device, and the
     zone engine the tracker's device-resident state (``tracker.update_from_detector`` / ``event_engine.process_tracker``);
     the host receives the detections (as the reference's ``Detector._parse`` does) and the events, never the track arrays.
-    ``False``: the reference's literal data flow -- ``tracker.update(detections)`` on host arrays, ``process(tracks)``."""
+    ``False``: the reference's literal data flow -- ``tracker.update(detections)`` on host arrays, ``process(tracks)``.
+
+    ``renderer``: each frame is annotated in place after the event stage, inside a ``visualization`` stage, as the reference
+    does (tools/run_pipeline.py:149-156).  It draws the materialised track list, so the event stage then takes that list too
+    (no device-only hand-off of the tracks)."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = 0
@@ -94,7 +98,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         handoff = device_handoff and hasattr(tracker, "update_from_detector") and hasattr(detector, "model")
         # the track list stays on the device only when the event stage can read it there; an engine with the reference's
         # host API alone (`process(tracks, fid)`) must be handed the materialised list, trails included
-        events_on_device = handoff and event_engine is not None and hasattr(event_engine, "process_tracker")
+        events_on_device = handoff and renderer is None and event_engine is not None and hasattr(event_engine, "process_tracker")
         profiler.tick("tracking")
         tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
         profiler.tock("tracking")
@@ -105,6 +109,12 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_events += len(event_engine.process(tracks, fid))
             profiler.tock("events")
+        if renderer is not None:                           # tools/run_pipeline.py:149-156
+            profiler.tick("visualization")
+            zones = event_engine.get_zone_polygons() if event_engine is not None else None
+            renderer.render(frame, tracks, zones=zones, fps=profiler.current_fps,
+                            latency_ms=sum(profiler._frame_ms.values()) if profiler._frame_ms else 0)
+            profiler.tock("visualization")
         profiler.end_frame()
     out = profiler.summary(p50=True)
     out["frames"] = max_frames
