@@ -328,6 +328,49 @@ int rtmodt_renderer_last_ms(rtmodt_renderer *r, float *kernel_ms);
 int rtmodt_render_pack(const rtmodt_render_cfg *cfg, const rtmodt_render_list *lists, int n, int h, int w, int draw_zones,
                        double fps, double latency_ms, void *out, size_t out_bytes, size_t *needed);
 
+/* ---- offline evaluation: replaces src/evaluation/metrics.py's pycocotools / motmetrics calls --------------------- */
+/* PARITY UNPINNED: neither library is installed anywhere this runs.  The rules are restated in csrc/eval.hip's header and
+ * INTEGRATION.md section 9 (pycocotools >= 2.0.7 COCOeval bbox, motmetrics >= 1.4.0 CLEAR MOT + IDF1, 'iou' distance);
+ * tests/eval_ref.py restates them in NumPy.  Device scratch is allocated and freed inside each call. */
+
+/* COCO bbox evaluate() + accumulate(), float64 throughout.  Thresholds are the caller's arrays, used as given (the
+ * Python side builds iouThrs / recThrs with np.linspace, so linspace(.5, .95, 10)[8] == 0.8999999999999999):
+ * iou_thrs[T], rec_thrs[R], max_dets[M] (ascending, max_dets[M-1] <= 1024), area_rng[A][2] (lo, hi; A * T <= 256).
+ * Cells: the non-empty (category, image) pairs, grouped by category index (cell_cat[n_cells], ascending) and, inside a
+ * category, in image order.  gt_start / dt_start[n_cells + 1] are CSR offsets into the GT and detection rows, each
+ * cell's rows in file order; boxes are x, y, w, h.  gt_area is the annotation's `area` field (the area-range test), the
+ * ignore flag is gt_crowd; gt_id == 0 makes a match count as unmatched (pycocotools' dtm > 0 test).  At most 1024 GTs and
+ * 4096 detections per cell, else RTMODT_E_CAPACITY before anything is launched.  Outputs (host):
+ * precision[T][R][K][A][M] and recall[T][K][A][M], -1 where a category has no cell or no non-ignored GT -- bit-identical
+ * to COCOeval.eval['precision'] / ['recall'] computed in float64 by the stated rules. */
+int rtmodt_coco_eval(int device, const double *iou_thrs, int T, const double *rec_thrs, int R, const int32_t *max_dets, int M,
+                     const double *area_rng, int A, int K, int n_cells, const int32_t *cell_cat, const int32_t *gt_start,
+                     const double *gt_box, const double *gt_area, const int32_t *gt_crowd, const int64_t *gt_id,
+                     const int32_t *dt_start, const double *dt_box, const double *dt_score, double *precision, double *recall);
+
+/* One sequence's CLEAR MOT / identity counts (motmetrics' compare_to_groundtruth(..., 'iou', distth=0.5)). */
+typedef struct rtmodt_mot_counts {
+    int64_t num_frames, num_objects, num_predictions;        /* frames = the union of both files' frame ids          */
+    int64_t num_matches, num_switches, num_misses, num_false_positives;
+    int64_t mostly_tracked, mostly_lost, num_unique_objects;  /* tracked / present >= 0.8, < 0.2 (float64)            */
+    int64_t idtp, idfp, idfn;                                 /* IDTP = max-weight one-to-one pairing of ids (exact)   */
+    double dist_sum;                                          /* sum of d = 1 - IoU over MATCH + SWITCH; motp = dist_sum
+                                                               * / (num_matches + num_switches)                       */
+} rtmodt_mot_counts;
+/* A batch of sequences in one launch.  seq_frame_start[n_seq + 1]: CSR into the frames, each sequence's frames ascending
+ * (frame_id[] only names a frame in error messages).  gt_start / hyp_start[n_frames + 1]: CSR into the GT / hypothesis
+ * rows, boxes x, y, w, h (the MOT file's corner minus 1); gt_oid / hyp_hid are dense ids within the sequence
+ * (0..seq_n_oid-1, 0..seq_n_hid-1), unique inside a frame.  Per frame: continuation of last frame's matches, then an
+ * assignment of maximum cardinality and, among those, minimum sum of d over pairs with d <= 0.5 (lap.h, lexicographic
+ * costs); MATCH / SWITCH / MISS / FP as motmetrics counts them.  Limits: 1024 rows per frame and side (checked before
+ * launch); 2^28 valid pairs (d <= 0.5) per call (checked after the count pass, before any pair is written); a frame whose
+ * contested remainder exceeds 256 rows / 256 columns / 2048 pairs fails with RTMODT_E_CAPACITY naming the sequence and
+ * frame.  The pairs are kept as a per-frame CSR and the IDF1 counts as a sparse (sequence, o, h) table: memory follows
+ * the valid pairs, not |O| x |H| or the id counts. */
+int rtmodt_mot_eval(int device, int n_seq, const int32_t *seq_frame_start, const int64_t *frame_id, const int32_t *gt_start,
+                    const int32_t *hyp_start, const int32_t *gt_oid, const double *gt_box, const int32_t *hyp_hid, const double *hyp_box,
+                    const int32_t *seq_n_oid, const int32_t *seq_n_hid, rtmodt_mot_counts *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ library being built):
                             (reference: src/visualization/renderer.py:28-96)
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158)
+* ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
+                            in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py)
 """
 import importlib as _importlib
 
@@ -43,6 +45,6 @@ def __getattr__(name):
         mod = _importlib.import_module(_LAZY[name], __name__)
         return getattr(mod, name)
     if name in ("synth", "weights", "_ffi", "detection", "tracking", "yolo_spec", "streams", "profiling", "pipeline", "events", "ingestion",
-                "visualization"):
+                "visualization", "evaluation"):
         return _importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -119,6 +119,12 @@ class RenderList(C.Structure):                       # struct rtmodt_render_list
     _fields_ = [("tracks", C.POINTER(RenderTrack)), ("n_tracks", C.c_int32)]
 
 
+class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
+    _fields_ = [(n, C.c_int64) for n in ("num_frames", "num_objects", "num_predictions", "num_matches", "num_switches", "num_misses",
+                                         "num_false_positives", "mostly_tracked", "mostly_lost", "num_unique_objects", "idtp", "idfp",
+                                         "idfn")] + [("dist_sum", C.c_double)]
+
+
 _lib = None
 
 
@@ -202,6 +208,9 @@ def lib() -> C.CDLL:
         "rtmodt_renderer_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_render_pack": (C.c_int, [C.POINTER(RenderCfg), C.POINTER(RenderList), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                          C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rtmodt_coco_eval": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                       vp, vp, vp, vp, vp, vp]),
+        "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == header/library drift

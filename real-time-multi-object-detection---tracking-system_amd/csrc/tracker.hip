@@ -18,6 +18,7 @@
 // Build with -ffp-contract=off: every float op below must round separately, exactly like
 // NumPy's float32 ufuncs (no FMA contraction of `a + b - w*h`).
 #include "kernels.h"
+#include "lap.h"
 
 #include <climits>
 
@@ -193,93 +194,8 @@ __device__ __forceinline__ void assoc_pass(const AssocSmem &s, const int *rows, 
 // A scene denser than the LDS budget raises the sticky error 2 (host: RTMODT_E_CAPACITY).
 // Output convention = assoc_pass: row r matched iff row_best[r] >= 0 && col_winner[row_best[r]] == r.
 // ---------------------------------------------------------------------------------------
-constexpr int LAP_ROWS = 256, LAP_COLS = 256, LAP_EDGES = 2048;
-struct LapSmem {
-    int *colmap;                   // [n_cols capacity] column -> local index among contested columns (-1 none, -2 marked)
-    double *ecost, *u, *v, *minv;  // [LAP_EDGES], [LAP_ROWS], [LAP_COLS], [LAP_COLS]
-    int *hrow, *hcol, *estart, *ecol;         // [LAP_ROWS], [LAP_COLS], [LAP_ROWS + 1], [LAP_EDGES]
-    int *p, *rm, *wayrow, *touched, *usedl;   // col -> row, row -> col, col -> row it was reached from, lists
-    unsigned char *used;           // [LAP_COLS]
-};
-static size_t lap_smem_bytes(int Nc) {
-    return (size_t)LAP_EDGES * 12 + (size_t)LAP_ROWS * (8 + 4 + 4 + 4) + (size_t)LAP_COLS * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 1) + (size_t)Nc * 4 + 64;
-}
-__device__ __forceinline__ LapSmem lap_carve(unsigned char *base, int Nc) {     // base 8-byte aligned
-    LapSmem L;
-    L.ecost = (double *)base;
-    L.u = L.ecost + LAP_EDGES;
-    L.v = L.u + LAP_ROWS;
-    L.minv = L.v + LAP_COLS;
-    L.colmap = (int *)(L.minv + LAP_COLS);
-    L.hrow = L.colmap + Nc;
-    L.hcol = L.hrow + LAP_ROWS;
-    L.estart = L.hcol + LAP_COLS;
-    L.ecol = L.estart + LAP_ROWS + 1;
-    L.p = L.ecol + LAP_EDGES;
-    L.rm = L.p + LAP_COLS;
-    L.wayrow = L.rm + LAP_ROWS;
-    L.touched = L.wayrow + LAP_COLS;
-    L.usedl = L.touched + LAP_COLS;
-    L.used = (unsigned char *)(L.usedl + LAP_COLS);
-    return L;
-}
-
-// exact sparse assignment of the contested sub-problem, run by ONE lane
-__device__ void lap_solve(const LapSmem &L, int nhr) {
-    const double INF = __builtin_huge_val();
-    for (int h0 = 0; h0 < nhr; ++h0) {
-        int nt = 0, nu = 0, i0 = h0, jend = -1, drow = -1;
-        double dmin = INF;
-        bool to_dummy = false;
-        while (true) {
-            const double ui = L.u[i0];
-            for (int e = L.estart[i0]; e < L.estart[i0 + 1]; ++e) {          // relax the real edges of row i0
-                const int j = L.ecol[e];
-                if (L.used[j]) continue;
-                const double cur = L.ecost[e] - ui - L.v[j];
-                if (L.minv[j] == INF) L.touched[nt++] = j;
-                if (cur < L.minv[j]) { L.minv[j] = cur; L.wayrow[j] = i0; }
-            }
-            if (0.0 - ui < dmin) { dmin = 0.0 - ui; drow = i0; }             // ... and its dummy edge
-            double delta = dmin;
-            int j1 = -1;
-            for (int t = 0; t < nt; ++t) {
-                const int j = L.touched[t];
-                if (!L.used[j] && L.minv[j] < delta) { delta = L.minv[j]; j1 = j; }
-            }
-            L.u[h0] += delta;
-            for (int t = 0; t < nu; ++t) { const int j = L.usedl[t]; L.u[L.p[j]] += delta; L.v[j] -= delta; }
-            for (int t = 0; t < nt; ++t) { const int j = L.touched[t]; if (!L.used[j]) L.minv[j] -= delta; }
-            dmin -= delta;
-            if (j1 < 0) { to_dummy = true; break; }
-            if (L.p[j1] < 0) { jend = j1; break; }
-            L.used[j1] = 1;
-            L.usedl[nu++] = j1;
-            i0 = L.p[j1];
-        }
-        if (to_dummy) {                                   // row drow gives up its column; shift the path back to h0
-            int i = drow, jfree = L.rm[i];
-            L.rm[i] = -1;
-            while (i != h0) {
-                const int j = jfree, ip = L.wayrow[j];
-                jfree = L.rm[ip];
-                L.p[j] = ip;
-                L.rm[ip] = j;
-                i = ip;
-            }
-        } else {
-            int j = jend;
-            while (true) {
-                const int ip = L.wayrow[j], jn = L.rm[ip];
-                L.p[j] = ip;
-                L.rm[ip] = j;
-                if (ip == h0) break;
-                j = jn;
-            }
-        }
-        for (int t = 0; t < nt; ++t) { const int j = L.touched[t]; L.minv[j] = INF; L.used[j] = 0; }
-    }
-}
+// (the exact solver of step 3 -- LapSmem, lap_carve, lap_solve -- is shared with the evaluator: lap.h)
+// ---------------------------------------------------------------------------------------
 
 // val(r, c): IoU (float32) of row r and column c of this pass
 template <typename F>
