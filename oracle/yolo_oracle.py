@@ -202,7 +202,8 @@ def upsample2(x):
 # ---------------------------------------------------------------------------
 # network forward
 # ---------------------------------------------------------------------------
-def forward(x, weights: dict, scale="s", nc=80, reg_max=16, taps: dict | None = None, force: dict | None = None, only=None):
+def forward(x, weights: dict, scale="s", nc=80, reg_max=16, taps: dict | None = None, force: dict | None = None, only=None,
+            inputs: dict | None = None):
     """x: (H,W,3) float32 RGB in [0,1].  ``weights[name] = (w, b)``.  Returns the three
     Detect maps ``[(H_i, W_i, 4*reg_max + nc)]`` (box logits first, then class logits).
 
@@ -214,7 +215,10 @@ def forward(x, weights: dict, scale="s", nc=80, reg_max=16, taps: dict | None = 
     ``only`` (optional set of conv names): ONLY these convs are computed, every other conv's output is taken
     from ``force`` (which must then hold it) -- teacher-forced checks of a few layers of a large net (YOLOv8m
     at 1280 x 1280 is 316 GFLOP of NumPy) without running the rest; ``taps`` then holds the computed ones only
-    (and the module outputs they feed, which are NOT meaningful: the Detect maps returned are not to be used)."""
+    (and the module outputs they feed, which are NOT meaningful: the Detect maps returned are not to be used).
+    ``inputs`` (optional dict) receives ``inputs[name] = (x, res)`` for every conv this call computes: the input tensor it
+    read and its residual (``None`` without one), after teacher forcing -- with ``force`` holding the engine's stored
+    tensors, exactly the fp16 values the engine read (tests/conv_ref64.py checks each conv against them in float64)."""
     mods, head = arch(scale, nc, reg_max)
     force = force or {}
 
@@ -232,6 +236,8 @@ def forward(x, weights: dict, scale="s", nc=80, reg_max=16, taps: dict | None = 
                 return np.asarray(f, dtype=F32)
             k = w.shape[1]
             return np.zeros(((t.shape[0] + 2 * (k // 2) - k) // stride + 1, (t.shape[1] + 2 * (k // 2) - k) // stride + 1, w.shape[0]), dtype=F32)
+        if inputs is not None:
+            inputs[name] = (t, res)
         y = conv2d_nhwc(t, w, b, stride=stride, act=act)
         if res is not None:
             y = (res + y).astype(F32)

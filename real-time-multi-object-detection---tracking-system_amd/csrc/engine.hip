@@ -651,7 +651,8 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
             st.front_w2 = cv.conv.wt; st.front_b2 = cv.conv.bias; st.front_kp2 = cv.conv.kp; st.front_c2 = cv.conv.cout;
             if (const char *e = rt_opt("FRONT")) {         // test hook (no autotune): force the fused front end on / off
                 st.front_on = atoi(e) != 0;
-                l1.skip = cv.skip = st.front_on;
+                l1.skip = st.front_on;
+                cv.skip = st.front_on || l1.tail_on;       // (with the front end off, a TAIL-hooked layer 1 still computes 2.cv1 itself)
             }
         }
     }

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import yolo_oracle as Y
+from tests import conv_ref64 as C
 
 pytestmark = pytest.mark.gpu
 
@@ -154,8 +155,9 @@ def layer_check(pkg, det, w, frame, scale, size):
     assert np.array_equal(inp.view(np.uint16), ref_in.view(np.uint16))
     names = [c.name for c in pkg.weights.spec(scale)]
     gpu = fetch_layers(pkg, det, names)
-    taps = {}
-    Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=gpu)
+    taps, inputs = {}, {}
+    Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=gpu)
+    C.check_layers(w, scale, inputs, gpu, what=f"{scale} @ {size}")
     worst = ("", 0.0)
     for n in gpu:
         ref, got = taps[n], gpu[n]
@@ -200,6 +202,7 @@ def test_forward_layers_yolov8s_640(pkg, wdir):
     ref_pred = Y.decode(maps)
     assert ref_pred.shape == pred.shape == (84, A)
     np.testing.assert_allclose(pred, ref_pred, rtol=2e-4, atol=2e-4)
+    C.check_decode(pred, maps, "s @ 640")                                  # float64 decode of the same fp16 logits, bound from decode_row's fp32 steps
     # NMS + rescale on the engine's own pre-NMS tensor: integer-exact
     dets, anchors = Y.non_max_suppression(pred, 0.35, 0.45, None, False, 100)
     ref_xyxy = Y.scale_boxes(dets[:, :4], 640, 640, 640, 640)
@@ -236,8 +239,9 @@ def test_tap_reuse_conv_tiles(pkg, wdir, monkeypatch, tile):
     for img in (0, 1):
         inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
         gpu = fetch_layers(pkg, det, names, img)
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, "s", inputs, gpu, what=f"tap-reuse tile {tile} img {img}")
         for n in gpu:
             tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
             err = float(np.abs(taps[n] - gpu[n]).max())
@@ -261,8 +265,9 @@ def test_fused_bottleneck_kernel(pkg, wdir, monkeypatch, scale, size, batch):
         inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
         gpu = fetch_layers(pkg, det, names, img)
         n_fused = len(names) - len(gpu)
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, scale, inputs, gpu, what=f"fused bottleneck {scale} @ {size} img {img}")
         for n in gpu:
             # the pair's intermediate is fp16 in LDS on the engine, fp32 in the oracle: one extra rounding
             tol = (4e-3 if ".m." in n and n.endswith(".cv2") else 2e-3) * np.abs(taps[n]).max() + 2e-3
@@ -481,6 +486,11 @@ def test_config5_yolov8m_1280_dense_scene(pkg, wdir):
     assert np.abs(t - gpu["2.m.0.cv1"]).max() <= 2e-3 * np.abs(t).max() + 2e-3
     t2 = Y.conv2d_nhwc(gpu["2.m.0.cv1"], *w["2.m.0.cv2"]) + gpu["2.cv1"][..., c:]
     assert np.abs(t2 - gpu["2.m.0.cv2"]).max() <= 2e-3 * np.abs(t2).max() + 2e-3
+    for n, r in (("0", C.conv64(inp, *w["0"], 2)), ("1", C.conv64(gpu["0"], *w["1"], 2)), ("2.m.0.cv1", C.conv64(gpu["2.cv1"][..., c:], *w["2.m.0.cv1"])),
+                 ("2.m.0.cv2", C.conv64(gpu["2.m.0.cv1"], *w["2.m.0.cv2"], res=gpu["2.cv1"][..., c:]))):
+        ok, frac, worst = r.check(gpu[n])
+        print(f"m @ 1280 {n}: K={r.K} exact {frac:.4f}, worst element {worst}")
+        assert ok and frac >= C.FLOOR_STORED, (n, frac, worst)
     # ... and, teacher-forced with the engine's own tensors, the layers whose tile paths depend on M at this size: the rest of C2f 2, one P4 and one
     # P5 C2f (persistent-tile ownership, ping-pong tiles at 80 x 80 / 40 x 40 with cin 192 / 288 / 576), SPPF's 9.cv2, and the three Detect stacks
     # (grouped launches over 160 / 80 / 40 pixel levels) -- about 100 GFLOP of im2col + sgemm instead of the net's 316
@@ -511,8 +521,9 @@ def test_config5_yolov8m_1280_dense_scene(pkg, wdir):
     want = {n for n in want if all(q in stored for q in producers(n))}
     assert {"2.cv2", "6.cv2", "8.cv2", "9.cv2", "3", "5", "16", "19", "4.cv1", "4.cv2", "15.cv1", "15.cv2", "18.cv1", "18.cv2"} <= want and sum(n.startswith("22.") for n in want) >= 6 and \
         sum(n.startswith("4.m.") for n in want) >= 4, sorted(want)
-    taps = {}
-    Y.forward(x, w, "m", taps=taps, force=stored, only=want)
+    taps, inputs = {}, {}
+    Y.forward(x, w, "m", taps=taps, inputs=inputs, force=stored, only=want)
+    C.check_layers(w, "m", inputs, stored, names=sorted(want), what="m @ 1280", verbose=True)
     worst = ("", 0.0)
     for n in sorted(want):
         tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
@@ -526,6 +537,7 @@ def test_config5_yolov8m_1280_dense_scene(pkg, wdir):
     for s_ in (160, 80, 40):
         maps.append(heads[off:off + s_ * s_ * 144].reshape(s_, s_, 144).astype(np.float32)); off += s_ * s_ * 144
     np.testing.assert_allclose(pred, Y.decode(maps), rtol=2e-4, atol=2e-4)
+    C.check_decode(pred, maps, "m @ 1280")
     dets, _ = Y.non_max_suppression(pred, 0.35, 0.45, None, False, 300)
     assert len(d) == len(dets)
     assert np.array_equal(d.xyxy.view(np.int32), Y.scale_boxes(dets[:, :4], 1280, 1280, 1280, 1280).view(np.int32))
@@ -572,8 +584,9 @@ def test_yolov8l_960_tuner_skips_tiles_that_do_not_fit(pkg, wdir, scale, size):
     only = {n for n in names if n.startswith("2.")} - (set() if "1" in stored else {"2.cv1"})
     want = only & set(stored)
     assert "2.cv2" in want and "2.m.2.cv2" in want and len(want) >= 4, sorted(want)
-    taps = {}
-    Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=stored, only=only)
+    taps, inputs = {}, {}
+    Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=stored, only=only)
+    C.check_layers(w, scale, inputs, stored, names=sorted(want), what=f"{scale} @ {size} layer 2")
     for n in sorted(want):
         tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
         assert float(np.abs(taps[n] - stored[n]).max()) <= tol, f"{scale} @ {size} layer {n}; launches: {prof[:12]}"
@@ -604,8 +617,9 @@ def test_odd_configurations(pkg, wdir, scale, size, batch, chains):
     only = {n for n in names if n.split(".")[0] in ("0", "1", "2", "3")}      # the oracle computes all of layers 0-3, each conv from the engine's tensor where one is stored
     want = only & set(stored)                                                    # (behind a fused launch: from its own fp32 value of the LDS-resident intermediate)
     assert len(want) >= 2 and "2.cv2" in want, sorted(want)
-    taps = {}
-    Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=stored, only=only)
+    taps, inputs = {}, {}
+    Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=stored, only=only)
+    C.check_layers(w, scale, inputs, stored, names=sorted(want), what=f"{scale} @ {size} batch {batch} layers 0-3")
     for n in sorted(want):
         tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
         assert float(np.abs(taps[n] - stored[n]).max()) <= tol, f"{scale} @ {size} batch {batch} layer {n}; launches: {launch_list(det)[:8]}"
@@ -744,8 +758,9 @@ def test_front_end_fused_is_bit_identical(pkg, wdir, monkeypatch, h, w, rect):
         preds = [det.debug_fetch(i, want_input=True, want_heads=False) for i in range(3)]
         if mode == "1" and not rect:                               # teacher-forced against the oracle: 0 and 1 are recomputed in fp32 from the engine's own input
             inp = preds[0][0]
-            taps = {}
-            Y.forward(inp.astype(np.float32), wts, "s", taps=taps, force={"2.cv1": layers[0]["2.cv1"].astype(np.float32)}, only={"0", "1", "2.cv1"})
+            taps, inputs = {}, {}
+            Y.forward(inp.astype(np.float32), wts, "s", taps=taps, inputs=inputs, force={"2.cv1": layers[0]["2.cv1"].astype(np.float32)}, only={"0", "1", "2.cv1"})
+            C.check_layers(wts, "s", inputs, {"2.cv1": layers[0]["2.cv1"]}, what=f"front end fused, {h}x{w}: 2.cv1 behind stem and layer 1")
             ref = taps["2.cv1"]
             err, tol = float(np.abs(ref - layers[0]["2.cv1"].astype(np.float32)).max()), 2e-3 * float(np.abs(ref).max()) + 2e-3
             print(f"front end fused, {h}x{w}: 2.cv1 err/tol {err / tol:.3f}")
@@ -759,6 +774,28 @@ def test_front_end_fused_is_bit_identical(pkg, wdir, monkeypatch, h, w, rect):
         assert np.array_equal(outs["0"][1][i][2], outs["1"][1][i][2]), f"pre-NMS tensor, image {i}"
         assert np.array_equal(outs["0"][2][i].xyxy, outs["1"][2][i].xyxy) and np.array_equal(outs["0"][2][i].confidence, outs["1"][2][i].confidence)
     buf.free()
+
+
+def test_forward_layers_tail_hook_with_front_end_off(pkg, wdir, monkeypatch):
+    """RTMODT_TAIL=1 with RTMODT_FRONT=0: layer 1 runs with 2.cv1 as its fused 1x1 tail, so 2.cv1's own launch must stay skipped.  The FRONT hook used to
+    clear that skip: 2.cv1 then ran a second time from layer 1's tensor, which the tail launch never writes, and overwrote the right result."""
+    monkeypatch.setenv("RTMODT_TAIL", "1")
+    monkeypatch.setenv("RTMODT_FRONT", "0")
+    det, w = make_detector(pkg, wdir, "s", 320, autotune=False)
+    frame = pkg.synth.frames(1, 320, 320, seed=1234)[0]
+    det.detect(frame)
+    prof = [n for n, _, _ in det.profile(1)]
+    assert "front end fused" not in prof[0] and prof[2].startswith("2.cv1") and "runs as the tail of the previous launch" in prof[2], prof[:4]
+    inp, _, _ = det.debug_fetch(0, want_heads=False, want_pred=False)
+    names = [c.name for c in pkg.weights.spec("s")]
+    gpu = fetch_layers(pkg, det, names)
+    assert "1" not in gpu and "2.cv1" in gpu, sorted(gpu)
+    taps, inputs = {}, {}
+    Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu, inputs=inputs)
+    for n in ("2.cv1", "2.cv2"):
+        assert float(np.abs(taps[n] - gpu[n]).max()) <= 2e-3 * np.abs(taps[n]).max() + 2e-3, n
+    C.check_layers(w, "s", inputs, gpu, what="TAIL=1 FRONT=0 (2.cv1 behind layer 1's tail launch)")
+    det.close()
 
 
 @pytest.mark.parametrize("chains", [1, 2, -1, -2], ids=["plain", "two-chains", "two-stages", "three-stages"])
@@ -971,8 +1008,9 @@ def test_conv_with_fused_1x1_tail(pkg, wdir, monkeypatch, size, batch):
             outs[mode].append(gpu)
             if mode == "1":
                 assert "1" not in gpu and "3" not in gpu and "2.cv1" in gpu and "4.cv1" in gpu
-                taps = {}
-                Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+                taps, inputs = {}, {}
+                Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+                C.check_layers(w, "s", inputs, gpu, what=f"1x1 tail @ {size} img {img}")
                 for n in gpu:
                     tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
                     assert float(np.abs(taps[n] - gpu[n]).max()) <= tol, (img, n)
@@ -1030,8 +1068,9 @@ def test_eight_wave_tiles(pkg, wdir, monkeypatch, tile):
         for img in (0, 1):
             inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
             gpu = fetch_layers(pkg, det, names, img)
-            taps = {}
-            Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+            taps, inputs = {}, {}
+            Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+            C.check_layers(w, "s", inputs, gpu, what=f"eight-wave tile {tile} epi {epi} img {img}")
             for n in gpu:
                 tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
                 err = float(np.abs(taps[n] - gpu[n]).max())
@@ -1064,8 +1103,9 @@ def test_bottleneck_with_c2f_cv2_tail(pkg, wdir, monkeypatch, size, batch):
             outs[mode].append(gpu)
             if mode == "1":
                 assert "2.m.0.cv2" not in gpu and "15.m.0.cv2" not in gpu and "2.cv2" in gpu and "15.cv2" in gpu and "4.m.1.cv2" in gpu
-                taps = {}
-                Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+                taps, inputs = {}, {}
+                Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+                C.check_layers(w, "s", inputs, gpu, what=f"C2f-cv2 tail @ {size} img {img}")
                 for n in gpu:
                     tol = 2e-3 * np.abs(taps[n]).max() + 2e-3      # (also behind the two LDS-resident fp16 intermediates: measured 0.2 of it)
                     assert float(np.abs(taps[n] - gpu[n]).max()) <= tol, (img, n)
@@ -1093,8 +1133,9 @@ def test_persistent_c2f32_kernel_is_bit_identical(pkg, wdir, monkeypatch, size, 
         if mode == "1":
             inp, _, _ = det.debug_fetch(0, want_heads=False, want_pred=False)
             lay = outs[mode][0][0]
-            taps = {}
-            Y.forward(inp.astype(np.float32), w, "s", taps=taps, force={n: lay[n].astype(np.float32) for n in ("2.cv1", "2.cv2")}, only={"2.m.0.cv1", "2.m.0.cv2", "2.cv2"})
+            taps, inputs = {}, {}
+            Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force={n: lay[n].astype(np.float32) for n in ("2.cv1", "2.cv2")}, only={"2.m.0.cv1", "2.m.0.cv2", "2.cv2"})
+            C.check_layers(w, "s", inputs, {n: lay[n] for n in ("2.cv1", "2.cv2")}, names=["2.cv2"], what=f"persistent c2f32 @ {size}: 2.cv2 behind bneck32's intermediates")
             err, tol = float(np.abs(taps["2.cv2"] - lay["2.cv2"].astype(np.float32)).max()), 2e-3 * float(np.abs(taps["2.cv2"]).max()) + 2e-3
             print(f"persistent c2f32 @ {size}: 2.cv2 err/tol {err / tol:.3f}")
             assert err <= tol, (err, tol)
@@ -1198,8 +1239,9 @@ def test_staged_pipeline_matches_single_stream_engine(pkg, wdir, monkeypatch, sr
             det.fetch()
             inp, _, _ = det.debug_fetch(B - 1, want_heads=False, want_pred=False)
             gpu = fetch_layers(pkg, det, names, B - 1)
-            taps = {}
-            Y.forward(inp.astype(np.float32), wts, "s", taps=taps, force=gpu)
+            taps, inputs = {}, {}
+            Y.forward(inp.astype(np.float32), wts, "s", taps=taps, inputs=inputs, force=gpu)
+            C.check_layers(wts, "s", inputs, gpu, what=f"staged engine, chains {chains}")
             for n in gpu:
                 assert float(np.abs(taps[n] - gpu[n]).max()) <= 2e-3 * np.abs(taps[n]).max() + 2e-3, n
             assert np.array_equal(inp.astype(np.float32), Y.preprocess(frames[0][B - 1], 320, 320).astype(np.float16).astype(np.float32))
@@ -1240,8 +1282,9 @@ def test_neck_concat_read_from_half_resolution(pkg, wdir, monkeypatch, size, bat
             inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
             gpu = fetch_layers(pkg, det, names, img)
             outs[mode].append(gpu)
-            taps = {}
-            Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+            taps, inputs = {}, {}
+            Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+            C.check_layers(w, "s", inputs, gpu, names=("12.cv1", "15.cv1", "12.cv2", "9.cv2"), what=f"neck up-read {mode} img {img}")
             for n in ("12.cv1", "15.cv1", "12.cv2", "9.cv2"):
                 assert float(np.abs(taps[n] - gpu[n]).max()) <= 2e-3 * np.abs(taps[n]).max() + 2e-3, (mode, img, n)
         det.close()
@@ -1313,8 +1356,9 @@ def test_benchmarked_shape_parity(pkg, wdir):
         assert np.array_equal(inp.astype(np.float32), Y.preprocess(frames[steps - 1][f][s], size, size).astype(np.float16).astype(np.float32))
         gpu = fetch_layers(pkg, det, names, img)
         assert len(gpu) >= 50
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, "s", taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, "s", taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, "s", inputs, gpu, what=f"benchmarked shape img {img}", verbose=True)
         worst = {"plain": ("", 0.0), "behind an LDS-resident fp16 intermediate": ("", 0.0)}
         for n in gpu:
             tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
@@ -1397,8 +1441,9 @@ def test_autotune_cache_rejects_foreign_and_illegal_entries(pkg, wdir, monkeypat
     inp, _, _ = c.debug_fetch(0, want_heads=False, want_pred=False) if c.detect_batch(frames) else (None, None, None)
     names = [x.name for x in pkg.weights.spec("n")]
     gpu = fetch_layers(pkg, c, names, 0)
-    taps = {}
-    Y.forward(inp.astype(np.float32), w, "n", taps=taps, force=gpu)
+    taps, inputs = {}, {}
+    Y.forward(inp.astype(np.float32), w, "n", taps=taps, inputs=inputs, force=gpu)
+    C.check_layers(w, "n", inputs, gpu, what="autotune cache with illegal entries")
     for n in gpu:
         assert float(np.abs(taps[n] - gpu[n]).max()) <= 4e-3 * np.abs(taps[n]).max() + 2e-3, n
     c.close()
@@ -1429,8 +1474,9 @@ def test_persistent_tile_kernel(pkg, wdir, monkeypatch, tile, size, batch, up_re
     for img in sorted({0, batch - 1}):
         inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
         gpu = fetch_layers(pkg, det, names, img)
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, scale, inputs, gpu, what=f"persistent tile {tile} {scale} @ {size} img {img}")
         for n in gpu:
             tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
             err = float(np.abs(taps[n] - gpu[n]).max())
@@ -1496,8 +1542,9 @@ def test_ping_pong_3x3_kernel(pkg, wdir, monkeypatch, tile, size, batch, scale):
     for img in sorted({0, batch - 1}):
         inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
         gpu = fetch_layers(pkg, det, names, img)
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, scale, inputs, gpu, what=f"ping-pong 3x3 {tile} {scale} @ {size} img {img}")
         for n in gpu:
             tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
             err = float(np.abs(taps[n] - gpu[n]).max())
@@ -1524,8 +1571,9 @@ def test_ping_pong_tile_kernel(pkg, wdir, monkeypatch, tile, size, batch, up_rea
     for img in sorted({0, batch - 1}):
         inp, _, _ = det.debug_fetch(img, want_heads=False, want_pred=False)
         gpu = fetch_layers(pkg, det, names, img)
-        taps = {}
-        Y.forward(inp.astype(np.float32), w, scale, taps=taps, force=gpu)
+        taps, inputs = {}, {}
+        Y.forward(inp.astype(np.float32), w, scale, taps=taps, inputs=inputs, force=gpu)
+        C.check_layers(w, scale, inputs, gpu, what=f"pp tile {tile} {scale} @ {size} img {img}")
         for n in gpu:
             tol = 2e-3 * np.abs(taps[n]).max() + 2e-3
             err = float(np.abs(taps[n] - gpu[n]).max())
