@@ -467,12 +467,24 @@ static int make_conv(rtmodt_detector *d, WeightFile &wf, const std::vector<std::
     return RTMODT_OK;
 }
 
+// depth multiple, width multiple, max channels of YOLOv8 n, s, m, l, x
+static const double SCALES[5][3] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 768}, {1.00, 1.00, 512}, {1.00, 1.25, 512}};
+static int scaled_channels(int scale_id, int c) { return (int)(std::ceil(std::min((double)c, SCALES[scale_id][2]) * SCALES[scale_id][1] / 8.0) * 8); }
+
+// Detect's inner widths: box branch cbox, class branch ccls = max(P3 channels, min(nc, 100)).  The first convs of both branches
+// write one tensor of cbox + ccls channels, which the conv launches read as a whole (C % 8) and the class branch's 3x3 reads
+// ccls of; widths that break either are refused at create (n with nc 65..100 not a multiple of 8, or nc > 100: ccls = 100).
+static void head_widths(int scale_id, int nc, int &cbox, int &ccls) {
+    const int c3 = scaled_channels(scale_id, 256);
+    cbox = std::max(16, std::max(c3 / 4, 64));
+    ccls = std::max(c3, std::min(nc, 100));
+}
+
 static int build_graph(rtmodt_detector *d, WeightFile &wf) {
-    static const double SC[5][3] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 768}, {1.00, 1.00, 512}, {1.00, 1.25, 512}};
     RT_CHECK(d->scale_id >= 0 && d->scale_id < 5, RTMODT_E_IO, "bad model scale id %d", d->scale_id);
     RT_CHECK(wf.reg_max == 16, RTMODT_E_UNSUPPORTED, "reg_max %d (only 16 built)", wf.reg_max);
-    const double dep = SC[d->scale_id][0], wid = SC[d->scale_id][1], mx = SC[d->scale_id][2];
-    auto ch = [&](int c) { return (int)(std::ceil(std::min((double)c, mx) * wid / 8.0) * 8); };
+    const double dep = SCALES[d->scale_id][0];
+    auto ch = [&](int c) { return scaled_channels(d->scale_id, c); };
     auto rep = [&](int n) { return std::max((int)std::nearbyint(n * dep), 1); };   // Python round(): half-even
     Builder bld{d, &wf};
     auto T = [&](int H, int W, int C, int pad) { return bld.T(H, W, C, pad); };
@@ -657,7 +669,8 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
         }
     }
     // Detect head: the two first 3x3 convs of a level share their input -> one conv, cout = cbox + ccls
-    const int cbox = std::max(16, std::max(c3 / 4, 64)), ccls = std::max(c3, std::min(d->nc, 100));
+    int cbox, ccls;
+    head_widths(d->scale_id, d->nc, cbox, ccls);
     const int nc4 = (int)align_up(d->nc, 4), no = 64 + (int)align_up(d->nc, 8);
     const int src[3] = {t15, t18, t21};
     std::vector<Op> hops;                                   // 5 convs per level: A, B2, B3, C2, C3
@@ -1614,6 +1627,13 @@ static int detector_create_impl(const rtmodt_det_cfg *cfg, rtmodt_detector *d) {
     RT_TRY(read_weight_file(d->weight_path.c_str(), wf));
     d->scale_id = wf.scale_id; d->nc = wf.nc; d->reg_max = wf.reg_max;
     RT_CHECK(d->nc >= 1 && d->nc <= 128, RTMODT_E_UNSUPPORTED, "nc %d (1..128 supported)", d->nc);
+    if (d->scale_id >= 0 && d->scale_id < 5) {            // (an unknown scale id is refused by build_graph)
+        int cbox, ccls;
+        head_widths(d->scale_id, d->nc, cbox, ccls);
+        RT_CHECK((cbox + ccls) % 8 == 0 && ccls % 8 == 0, RTMODT_E_UNSUPPORTED,
+                 "YOLOv8%c with nc %d: Detect class branch width ccls %d is not a multiple of 8 (supported on this scale: nc <= 64 or 72, 80, 88, 96)",
+                 "nsmlx"[d->scale_id], d->nc, ccls);
+    }
     RT_HIP(hipSetDevice(d->device));
     RT_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     if (const char *e = rt_diag("POST_PRIO")) {     // experiment hook: the post-processing stream (one workgroup per image / stream) at another priority

@@ -157,15 +157,15 @@ def randomise_and_calibrate(model, x, seed=0, cls_bias=-4.1):
         h.remove()
 
 
-def make_checkpoint(pkg, tmp_path, scale="n", size=320, seed=0):
-    """A calibrated fake-Ultralytics checkpoint on disk (fp16 like the real ones) + its converted RTMODTW1 file.
+def make_checkpoint(pkg, tmp_path, scale="n", size=320, seed=0, nc=80):
+    """A calibrated fake-Ultralytics checkpoint of `nc` classes on disk (fp16 like the real ones) + its converted RTMODTW1 file.
     Returns (unfolded fp32 torch model holding exactly the checkpoint's fp16 values, .rtw path, calibration frame)."""
     fake, DetectionModel = build_fake_ultralytics()
     torch.manual_seed(seed)
-    model = DetectionModel(scale, 80).eval()
+    model = DetectionModel(scale, nc).eval()
     frame = pkg.synth.frames(1, size, size, seed=4321)[0]
     x = torch.from_numpy(np.ascontiguousarray(Y.preprocess(frame, size, size).transpose(2, 0, 1)))[None]
-    randomise_and_calibrate(model, x, seed=seed, cls_bias=-3.3)
+    randomise_and_calibrate(model, x, seed=seed, cls_bias=-3.3 if nc == 80 else -1.0)      # (fewer classes: a higher bias, a similar candidate count)
     pt = str(tmp_path / f"yolov8{scale}_fake.pt")
     sys.modules.update(fake)
     try:
@@ -174,5 +174,5 @@ def make_checkpoint(pkg, tmp_path, scale="n", size=320, seed=0):
         for k in fake:
             sys.modules.pop(k, None)
     out = str(tmp_path / f"yolov8{scale}_converted.rtw")
-    assert pkg.weights.convert_pt(pt, out) == (scale, 80)
+    assert pkg.weights.convert_pt(pt, out) == (scale, nc)
     return model.float(), out, frame

@@ -118,3 +118,20 @@ def test_runtime_options_live_in_one_table():
     assert used <= table, sorted(used - table)
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "DIAG ?= 0" in mk
+
+
+@pytest.mark.parametrize("nc", [90, 100, 128, 65, 97])
+def test_create_refuses_unsupported_head_widths(pkg, tmp_path, nc):
+    """YOLOv8n's Detect class branch is ccls = max(64, min(nc, 100)) channels wide and its first convs write 64 + ccls; the conv
+    launches need both in multiples of 8.  rtmodt_detector_create refuses other widths with RTMODT_E_UNSUPPORTED before it makes
+    any HIP call, so the refusal is the same on a machine without a GPU (called through the C ABI: `Detector` asks for the device
+    count first)."""
+    import ctypes as C
+    path = str(tmp_path / f"yolov8n_nc{nc}.rtw")
+    pkg.weights.save(path, pkg.weights.synthetic("n", nc=nc, calibrate=None), "n", nc)
+    cfg = pkg._ffi.DetCfg(path.encode(), 320, 320, 0.35, 0.45, None, 0, 1, 0, 100, 0, 1, 320, 320, 1, 0, 1, 0)
+    h = C.c_void_p()
+    L = pkg._ffi.lib()
+    assert L.rtmodt_detector_create(C.byref(cfg), C.byref(h)) == pkg._ffi.E_UNSUPPORTED and not h.value
+    msg = L.rtmodt_last_error().decode()
+    assert "YOLOv8n" in msg and f"nc {nc}" in msg and f"ccls {min(nc, 100)}" in msg, msg

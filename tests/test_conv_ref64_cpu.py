@@ -189,6 +189,46 @@ def test_planted_bug_is_rejected(bug):
     assert not passed, (bug, frac, worst)
 
 
+# Detect's class-branch shapes at class counts other than 80: name: (h, w, cin, cout, k, act).  cv3.l.2 has cout = align4(nc)
+# (4 for nc 1..4, 8 for nc 5..8) and no activation; on n, ccls = max(64, min(nc, 100)) is the cin of cv3.l.1 (3x3) and cv3.l.2
+HEAD_CLASSES = {
+    "head 1x1 cin64 cout4 (n, nc 1..4)": (24, 22, 64, 4, 1, 0),
+    "head 1x1 cin128 cout8 (s, nc 5..8)": (24, 22, 128, 8, 1, 0),
+    "head 1x1 cin88 cout88 (n, nc 88)": (24, 22, 88, 88, 1, 0),
+    "head 3x3 cin88 (n, nc 88)": (24, 22, 88, 88, 3, 1),
+    "head 3x3 cin100 (ccls 100)": (24, 22, 100, 100, 3, 1),
+}
+
+
+@pytest.mark.parametrize("cls", list(HEAD_CLASSES))
+def test_emulated_contract_passes_head_widths(cls):
+    h, w, cin, cout, k, act = HEAD_CLASSES[cls]
+    rng = np.random.default_rng(zlib.crc32(cls.encode()))
+    x, wt, b = data(rng, h, w, cin, cout, k)
+    got = emulate(x, wt, b, 1, act)
+    r = C.conv64(x, wt, b, 1, act)
+    ok, frac, worst = r.check(got)
+    print(f"{cls}: K={r.K} exact_frac {frac:.4f}, worst {worst['ratio']:.3f} of bracket")
+    assert ok, worst
+    assert frac >= C.FLOOR_STORED, frac
+
+
+@pytest.mark.parametrize("cls,bug", [(c, m) for c, v in HEAD_CLASSES.items() for m in MUTATIONS
+                                     if not m.startswith("res_") and not (m == "tap_drop" and v[4] == 1) and not (m == "silu16" and not v[5])])
+def test_planted_bug_is_rejected_at_head_widths(cls, bug):
+    """The planted bugs that apply to a conv without a residual (and, for tap_drop, with taps; silu16, with an activation) are
+    rejected at the narrow head couts and the cin 88 / 100 K-chunk shapes too."""
+    h, w, cin, cout, k, act = HEAD_CLASSES[cls]
+    rng = np.random.default_rng(zlib.crc32(cls.encode()))
+    x, wt, b = data(rng, h, w, cin, cout, k)
+    r = C.conv64(x, wt, b, 1, act)
+    assert new_ok(r, emulate(x, wt, b, 1, act), C.FLOOR_STORED)[0]
+    passed, bracket, frac, worst = new_ok(r, emulate(x, wt, b, 1, act, bug=bug), C.FLOOR_STORED)
+    print(f"{cls} {bug}: bracket {'ok' if bracket else 'VIOLATED'}, exact_frac {frac:.4f}")
+    assert not passed, (cls, bug, frac, worst)
+
+
+
 # ---------------------------------------------------------------------------------------------------------------- decode
 def decode_f32(maps, bug=None, strides=(8, 16, 32), nc=80):
     """decode_row in float32 (NumPy): the kernel's operation order; ``bug`` plants a half-pixel anchor shift or an fp16 softmax."""

@@ -6,6 +6,7 @@ layout conversion reproduce the torch model's own forward pass through the oracl
 import sys
 
 import numpy as np
+import pytest
 import torch
 import torch.nn as nn
 
@@ -15,10 +16,11 @@ from oracle import yolo_oracle as Y
 from fake_ultralytics import build_fake_ultralytics, make_checkpoint
 
 
-def test_convert_pt_without_ultralytics(pkg, tmp_path):
+@pytest.mark.parametrize("nc", [80, 2])
+def test_convert_pt_without_ultralytics(pkg, tmp_path, nc):
     fake, DetectionModel = build_fake_ultralytics()
     torch.manual_seed(0)
-    model = DetectionModel("n", 80).eval()
+    model = DetectionModel("n", nc).eval()
     for m in model.modules():                      # non-trivial BN statistics
         if isinstance(m, nn.BatchNorm2d):
             m.weight.data.uniform_(0.5, 1.5); m.bias.data.normal_(0, 0.2)
@@ -40,8 +42,9 @@ def test_convert_pt_without_ultralytics(pkg, tmp_path):
             np.testing.assert_allclose(sd[k].astype(np.float32), ref_sd[k].astype(np.float16).astype(np.float32), rtol=0, atol=0, err_msg=k)
     assert pkg.weights.infer_scale(sd) == "n"
     out = str(tmp_path / "yolov8n.rtw")
-    assert pkg.weights.convert_pt(pt, out) == ("n", 80)
-    w, scale, nc, _ = pkg.weights.load(out)
+    assert pkg.weights.convert_pt(pt, out) == ("n", nc)
+    w, scale, file_nc, _ = pkg.weights.load(out)
+    assert (scale, file_nc) == ("n", nc) and w["22.cv3.0.2"][0].shape == (nc, 1, 1, max(64, min(nc, 100))) and w["22.cv3.2.2"][1].shape == (nc,)
     # folded weights reproduce the torch model's own Conv+BN+SiLU on a stem-to-layer-2 slice
     model = model.float()
     x = np.random.default_rng(0).uniform(size=(64, 64, 3)).astype(np.float32)
@@ -66,25 +69,28 @@ def test_read_pt_rejects_non_checkpoints(pkg, tmp_path):
         pkg.weights.read_pt(str(p))
 
 
-def test_converted_checkpoint_reproduces_the_unfolded_model_end_to_end(pkg, tmp_path):
+@pytest.mark.parametrize("nc", [80, 2])
+def test_converted_checkpoint_reproduces_the_unfolded_model_end_to_end(pkg, tmp_path, nc):
     """`.pt` -> restricted read -> BN fold -> NHWC fp16 -> RTMODTW1, then the WHOLE net: the oracle run on the converted file
     against torch running the checkpoint's own unfolded Conv + BatchNorm + SiLU graph -- all three Detect maps, and the
     detections after decode + NMS decision by decision (the only differences: folded weights are rounded to fp16 once more)."""
     import nms_audit as NA
     from fake_ultralytics import forward_heads
-    model, rtw, _ = make_checkpoint(pkg, tmp_path)
-    w, scale, nc, _ = pkg.weights.load(rtw)
+    model, rtw, _ = make_checkpoint(pkg, tmp_path, nc=nc)
+    w, scale, file_nc, _ = pkg.weights.load(rtw)
+    assert file_nc == nc
     frame = pkg.synth.frames(1, 320, 320, seed=77)[0]
     x = Y.preprocess(frame, 320, 320)
     with torch.no_grad():
         ref = [h[0].permute(1, 2, 0).numpy() for h in forward_heads(model, torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1)))[None])]
-    got = Y.forward(x, w, scale)
+    got = Y.forward(x, w, scale, nc)
     for lvl in range(3):
         e = np.abs(got[lvl] - ref[lvl])
         assert np.isfinite(ref[lvl]).all() and ref[lvl][..., :64].std() > 0.5          # a live net, not one that decayed to its biases
         assert np.percentile(e, 99) < 0.02 and e.max() < 0.1, (lvl, float(np.percentile(e, 99)), float(e.max()))
-    po, pr = Y.decode(got), Y.decode(ref)
+    po, pr = Y.decode(got, nc), Y.decode(ref, nc)
+    assert po.shape == pr.shape == (4 + nc, 2100)
     n_cand = int((pr[4:].max(0) > 0.35).sum())
     assert 10 < n_cand < 1500, n_cand
-    res = NA.audit(po, pr, 0.35, 0.45, None, score_tol=0.001, iou_tol=0.002)
+    res = NA.audit(po, pr, 0.35, 0.45, None, nc=nc, score_tol=0.001, iou_tol=0.002)
     assert not res["hard"], NA.describe(res)
