@@ -41,6 +41,7 @@ typedef struct rtmodt_detector rtmodt_detector;
 typedef struct rtmodt_tracker rtmodt_tracker;
 typedef struct rtmodt_zones rtmodt_zones;
 typedef struct rtmodt_renderer rtmodt_renderer;
+typedef struct rtmodt_jpeg rtmodt_jpeg;
 
 /* ---- library / device ------------------------------------------------------------- */
 const char *rtmodt_last_error(void);
@@ -327,6 +328,33 @@ int rtmodt_renderer_last_ms(rtmodt_renderer *r, float *kernel_ms);
  * *needed = its size; written to out when out_bytes >= *needed.  Layout: csrc/render.hip, "command buffer". */
 int rtmodt_render_pack(const rtmodt_render_cfg *cfg, const rtmodt_render_list *lists, int n, int h, int w, int draw_zones,
                        double fps, double latency_ms, void *out, size_t out_bytes, size_t *needed);
+
+/* ---- JPEG / Motion-JPEG encoder: replaces cv2.VideoWriter on the annotated frame (tools/run_pipeline.py:112-117,160-161) ---- */
+/* Batches of BGR24 frames (the renderer's frame convention, so render_batch's output is encoded where it lies) become complete
+ * baseline JPEG files: JFIF, YCbCr 4:2:0, the Annex K Huffman tables, one restart interval per MCU row (csrc/jpeg.hip, whose
+ * header comment states the stream and the integer arithmetic; tests/jpeg_ref.py restates both).  The rules are libjpeg's:
+ * PARITY PINNED -- the files equal libjpeg-turbo 3.1's (Pillow, restart_marker_rows=1, optimize=False) byte for byte. */
+typedef struct rtmodt_jpeg_cfg {
+    int32_t quality;        /* 1..100; 0 = 95 (cv2.imencode's default)                      */
+    int32_t subsampling;    /* 0 = 4:2:0, the only one; anything else RTMODT_E_UNSUPPORTED  */
+    int32_t max_h, max_w;   /* largest frame the handle is sized for (<= 8192 each)         */
+    int32_t max_batch;      /* frames per call                                              */
+} rtmodt_jpeg_cfg;
+/* Scratch: 768 bytes per MCU of max_batch frames of max_h x max_w (6.3 MB per 1080p frame). */
+int rtmodt_jpeg_create(int device, const rtmodt_jpeg_cfg *cfg, rtmodt_jpeg **out);
+void rtmodt_jpeg_destroy(rtmodt_jpeg *j);
+/* video_writer.write(annotated) (run_pipeline.py:160-161) for n frames of h x w, row pitch stride_bytes >= 3w, mem_kind as in
+ * rtmodt_render_batch; the frames are only read.  Frame i's file (SOI .. EOI) is written to out + i * slot_bytes (host memory)
+ * and sizes[i] is its length.  RTMODT_E_CAPACITY when n, h or w exceed the handle (nothing launched), and when a file does not
+ * fit slot_bytes: the message names the first such frame and the bytes it needs, sizes[i] holds the needed size of every
+ * frame, the frames that fit are complete, and no byte past any slot's sizes[i] is touched.  n = 0: success, nothing launched. */
+int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind,
+                             uint8_t *out, size_t slot_bytes, uint32_t *sizes);
+/* Device time (ms, HIP events) of the last encode_batch's kernels. */
+int rtmodt_jpeg_last_ms(rtmodt_jpeg *j, float *kernel_ms);
+/* Host only, no device needed: everything from SOI up to and including the SOS header of an h x w file at `quality` (1..100).
+ * *needed = its size; written to out when out_bytes >= *needed. */
+int rtmodt_jpeg_header(int quality, int h, int w, uint8_t *out, size_t out_bytes, size_t *needed);
 
 /* ---- offline evaluation: replaces src/evaluation/metrics.py's pycocotools / motmetrics calls --------------------- */
 /* PARITY UNPINNED: neither library is installed anywhere this runs.  The rules are restated in csrc/eval.hip's header and

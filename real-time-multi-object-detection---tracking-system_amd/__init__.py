@@ -18,7 +18,8 @@ library being built):
 * ``events``             -- ``ZoneEventEngine`` on device-resident tracks (reference: src/events/zone_engine.py:64-157)
 * ``pipeline``           -- the reference's per-frame loop (tools/run_pipeline.py:121-158) around the native classes
 * ``visualization``      -- ``FrameRenderer``: boxes, labels, trails, zones and HUD drawn into frames on the GPU
-                            (reference: src/visualization/renderer.py:28-96)
+                            (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
+                            frames as JPEG / Motion-JPEG, encoded on the GPU (reference: tools/run_pipeline.py:112-117,160-161)
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158)
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
@@ -37,6 +38,9 @@ _LAZY = {
     "FrameReader": ".ingestion.reader",
     "RTSPReader": ".ingestion.reader",
     "FrameRenderer": ".visualization.renderer",
+    "JpegEncoder": ".visualization.jpeg",
+    "MjpegWriter": ".visualization.jpeg",
+    "MjpegRecorder": ".visualization.jpeg",
 }
 
 

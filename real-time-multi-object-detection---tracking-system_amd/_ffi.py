@@ -119,6 +119,10 @@ class RenderList(C.Structure):                       # struct rtmodt_render_list
     _fields_ = [("tracks", C.POINTER(RenderTrack)), ("n_tracks", C.c_int32)]
 
 
+class JpegCfg(C.Structure):                          # struct rtmodt_jpeg_cfg
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("max_h", C.c_int32), ("max_w", C.c_int32), ("max_batch", C.c_int32)]
+
+
 class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
     _fields_ = [(n, C.c_int64) for n in ("num_frames", "num_objects", "num_predictions", "num_matches", "num_switches", "num_misses",
                                          "num_false_positives", "mostly_tracked", "mostly_lost", "num_unique_objects", "idtp", "idfp",
@@ -208,6 +212,11 @@ def lib() -> C.CDLL:
         "rtmodt_renderer_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_render_pack": (C.c_int, [C.POINTER(RenderCfg), C.POINTER(RenderList), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                          C.c_double, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rtmodt_jpeg_create": (C.c_int, [C.c_int, C.POINTER(JpegCfg), C.POINTER(vp)]),
+        "rtmodt_jpeg_destroy": (None, [vp]),
+        "rtmodt_jpeg_encode_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
+        "rtmodt_jpeg_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "rtmodt_coco_eval": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp]),
         "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),

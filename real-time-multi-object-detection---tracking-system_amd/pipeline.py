@@ -64,7 +64,7 @@ class PinnedFrameRing:
 
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
-        device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None) -> dict:
+        device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -75,7 +75,11 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
 
     ``renderer``: each frame is annotated in place after the event stage, inside a ``visualization`` stage, as the reference
     does (tools/run_pipeline.py:149-156).  It draws the materialised track list, so the event stage then takes that list too
-    (no device-only hand-off of the tracks)."""
+    (no device-only hand-off of the tracks).
+
+    ``recorder``: ``recorder.write(frame)`` is called with the (annotated) frame after ``profiler.end_frame()``, where the
+    reference calls ``video_writer.write(annotated)`` (tools/run_pipeline.py:160-161) -- outside every profiler stage.  A
+    ``visualization.MjpegRecorder`` encodes it on the GPU and appends it to an AVI."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = 0
@@ -116,6 +120,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
                             latency_ms=sum(profiler._frame_ms.values()) if profiler._frame_ms else 0)
             profiler.tock("visualization")
         profiler.end_frame()
+        if recorder is not None:                           # tools/run_pipeline.py:160-161
+            recorder.write(frame)
     out = profiler.summary(p50=True)
     out["frames"] = max_frames
     out["last_detections"] = 0 if detections is None else len(detections)

@@ -1,3 +1,4 @@
+from .jpeg import JpegEncoder, MjpegRecorder, MjpegWriter, multipart_chunk
 from .renderer import FrameRenderer
 
-__all__ = ["FrameRenderer"]
+__all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk"]
