@@ -256,7 +256,14 @@ typedef struct rtmodt_zone_cfg {
 /* n_streams independent ledgers (occupancy + cooldown per track id and zone), at most 32 zones /
  * 2048 polygon points.  max_idle_frames: a track id not passed for more than this many frames loses
  * its cooldown entries (the reference never drops them, zone_engine.py:76; pass INT64_MAX/2 to
- * mirror that until the 2 x max_tracks ledger fills -> RTMODT_E_CAPACITY). */
+ * mirror that until the 2 x max_tracks ledger fills -> RTMODT_E_CAPACITY).  "More than": an id
+ * passed at frame_id f with f - (frame_id it was last passed at) > max_idle_frames has lost them,
+ * whether or not a call was made in between; with 0 no cooldown entry outlives a frame.
+ * A frame passes while its tracks + the retained idle rows <= 2 x max_tracks.  The frame that
+ * exceeds it, and one with more than max_events events, returns RTMODT_E_CAPACITY and leaves that
+ * stream in error for good: every later _process, _process_tracker and _state that touches the
+ * stream returns RTMODT_E_CAPACITY again (the idle rows were dropped to make room, so its cooldown
+ * ledger is no longer what the caller built up).  Destroy the handle and create a larger one. */
 int rtmodt_zones_create(int device, const rtmodt_zone_cfg *zones, int n_zones, int n_streams, int max_tracks,
                         int max_events, int64_t max_idle_frames, rtmodt_zones **out);
 void rtmodt_zones_destroy(rtmodt_zones *z);

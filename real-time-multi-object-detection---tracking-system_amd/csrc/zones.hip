@@ -172,9 +172,12 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
         uint32_t mask = j >= 0 ? o_mask[j] : 0u;
         uint32_t ev = 0u;
         double *nf = n_first + (size_t)np * Z, *na = n_alert + (size_t)np * Z;
+        // an id last passed more than max_idle frames ago has lost its cooldown entries even when it comes back in this
+        // very frame (no earlier call dropped the row: none was made, or it was in every list while the frame ids jumped)
+        const bool expired = j >= 0 && a.max_idle >= 0 && a.frame_id - o_seen[j] > a.max_idle;
         for (int z = 0; z < Z; ++z) {                                         // carry the old row over
             nf[z] = j >= 0 ? o_first[(size_t)j * Z + z] : 0.0;
-            na[z] = j >= 0 ? o_alert[(size_t)j * Z + z] : 0.0;
+            na[z] = j >= 0 && !expired ? o_alert[(size_t)j * Z + z] : 0.0;
         }
         if (active) {
             const float4 b = box[i];

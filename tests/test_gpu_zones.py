@@ -11,6 +11,7 @@ import pytest
 from oracle import tracker_oracle as T
 from oracle import zone_oracle as Z
 from conftest import GOLDEN
+import zone_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -147,3 +148,188 @@ def test_pipeline_loop_with_event_stage(pkg, tmp_path_factory, tmp_path):
         reported |= {t.track_id for t in trk2.update(det.detect(frames[i % 4]))}
     assert out["events"] == len(reported) > 0              # cooldown 1e9: exactly one event per track id ever reported
     det.close(); eng.close()
+
+
+# ======================================================================================================================
+# The ledger at scale, under churn and at its limits: the engine against tests/zone_ref.py (ZoneOracle + the documented
+# max_idle_frames / capacity contract) on every call -- events, occupancy and cooldown, compared with ==.  The scenarios
+# and their non-vacuity guards are shared with tests/test_zone_ref_cpu.py, where the guards already ran without a GPU.
+# ======================================================================================================================
+def ns(tracks):
+    return [SimpleNamespace(track_id=i, xyxy=b, class_id=k, class_name="") for i, b, k in tracks]
+
+
+def check_call(eng, model, stream, frame_id, now, tracks, where):
+    want = model.process(tracks, frame_id, now)
+    got = [as_dict(e) for e in eng.process(ns(tracks), frame_id, stream=stream, now=now)]
+    if got != want:                                             # name the first difference: frame, stream and id
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert g == w, f"{where}: event {k} of {len(got)} / {len(want)}"
+        assert len(got) == len(want), f"{where}: {len(got)} events, expected {len(want)}; first extra {(got + want)[min(len(got), len(want))]}"
+    snap, ref = eng.snapshot(stream), model.snapshot()
+    for part in ("occupancy", "cooldown"):
+        if snap[part] != ref[part]:
+            extra = [r for r in snap[part] if r not in ref[part]][:3]
+            missing = [r for r in ref[part] if r not in snap[part]][:3]
+            assert False, f"{where}: {part} differs: engine only {extra}, model only {missing}"
+
+
+@pytest.mark.parametrize("max_idle", R.CHURN_IDLE)
+def test_ledger_churn_at_scale_three_streams(pkg, tmp_path, max_idle):
+    """a. ~1500 ids per stream leaving and returning, 300-700 passed per call, three streams of one engine interleaved
+    (stream_base), n_old and n both far above 256: every rank of the merge, every pass of the prefix, expiry on both
+    sides of max_idle_frames."""
+    S = R.CHURN["n_streams"]
+    eng = pkg.events.ZoneEventEngine(R.CHURN_ZONES, log_path=str(tmp_path / "e.jsonl"), n_streams=S, max_tracks=R.CHURN["max_tracks"],
+                                     max_events=R.CHURN["max_events"], max_idle_frames=max_idle)
+    models = [R.ZoneLedgerRef(R.CHURN_ZONES, R.CHURN["max_tracks"], max_idle) for _ in range(S)]
+    for k, (s, frame_id, now, tracks) in enumerate(R.churn_scenario()):
+        check_call(eng, models[s], s, frame_id, now, tracks, f"max_idle {max_idle} call {k} stream {s} frame {frame_id}")
+    print("churn", max_idle, R.churn_guards(models, max_idle))
+    eng.close()
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["distinct_names", "shared_names"])
+def test_thirty_two_zones_and_a_full_point_table(pkg, tmp_path, shared):
+    """b. Z = 32 (key 31, event bit 31), 1954 of 2048 points with a 1500-vertex star and 0- / 1-point / repeated-vertex
+    polygons, 600 tracks per frame with idle rows kept for 5 frames; then names z{i % 11}: shared keys in threes."""
+    zones, calls = R.full_table_zones(shared), R.full_table_calls()
+    eng = pkg.events.ZoneEventEngine(zones, log_path=str(tmp_path / "e.jsonl"), max_tracks=R.FULL["max_tracks"], max_events=R.FULL["max_events"],
+                                     max_idle_frames=R.FULL["max_idle"])
+    model = R.ZoneLedgerRef(zones, R.FULL["max_tracks"], R.FULL["max_idle"])
+    for k, (s, frame_id, now, tracks) in enumerate(calls):
+        check_call(eng, model, s, frame_id, now, tracks, f"call {k} frame {frame_id}")
+    print("full table", shared, R.full_table_guards(model, zones, calls, shared))
+    eng.close()
+
+
+def test_zone_construction_limits(pkg, tmp_path):
+    """b. 33 zones and 2049 points are refused; 32 zones with exactly 2048 points are not."""
+    sq = [[0, 0], [10, 0], [10, 10], [0, 10]]
+    mk = lambda polys: [{"name": f"z{i}", "polygon": p, "dwell_time_sec": 0.0, "cooldown_sec": 0.0} for i, p in enumerate(polys)]
+    for polys in ([sq] * 33, [R.ngon(300, 300, 250, 2045), sq]):
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            pkg.events.ZoneEventEngine(mk(polys), log_path=str(tmp_path / "e.jsonl"), max_tracks=8)
+        assert e.value.code == pkg._ffi.E_INVALID
+    zones = mk([R.ngon(300, 300, 250, 2048 - 31 * 4)] + [sq] * 31)
+    eng = pkg.events.ZoneEventEngine(zones, log_path=str(tmp_path / "e.jsonl"), max_tracks=8)
+    model = R.ZoneLedgerRef(zones, 8)
+    tracks = [(1, np.array([0, 0, 10, 10], np.float32), 0), (2, np.array([290, 290, 310, 310], np.float32), 1), (3, np.array([900, 0, 910, 10], np.float32), 2)]
+    check_call(eng, model, 0, 0, 1.7e9, tracks, "full table")
+    assert model.n_events == 32
+    eng.close()
+
+
+@pytest.mark.parametrize("step", [0.25, 0.1])
+def test_thresholds_met_exactly(pkg, tmp_path, step):
+    """c. Clock steps of 0.25 (exact in double): now - first == dwell and now - last == cooldown occur as equalities and
+    fire (>=); steps of 0.1: the rounded differences land on either side and the model decides.  One negative dwell."""
+    eng = pkg.events.ZoneEventEngine(R.THRESH_ZONES, log_path=str(tmp_path / "e.jsonl"), max_tracks=64, max_events=256)
+    model = R.ZoneLedgerRef(R.THRESH_ZONES, 64)
+    for s, frame_id, now, tracks in R.threshold_calls(step):
+        check_call(eng, model, s, frame_id, now, tracks, f"step {step} frame {frame_id}")
+    print("thresholds", step, model.n_events, model.exact_threshold_firings)
+    assert model.n_events > 100 and model.events_by_zone["neg"] > 0
+    if step == 0.25:
+        assert model.exact_threshold_firings >= 5
+    eng.close()
+
+
+def test_centroids_truncate_and_round_like_float32(pkg, tmp_path):
+    """d. (x1 + x2) / 2 in float32, truncated toward zero: negative fractions, exact halves, sums above 2^24 that round;
+    zone corners and edges on the truncated value and one pixel either side.  |coordinate| <= 2^26 (stated condition:
+    the int32 differences of polygon.h, which mirror OpenCV's, cannot overflow there)."""
+    zones, tracks = R.centroid_scenario()
+    eng = pkg.events.ZoneEventEngine(zones, log_path=str(tmp_path / "e.jsonl"), max_tracks=16, max_events=256)
+    model = R.ZoneLedgerRef(zones, 16)
+    check_call(eng, model, 0, 0, 1.7e9, tracks, "frame 0")
+    check_call(eng, model, 0, 1, 1.7e9 + 1.0, tracks[::-1], "frame 1")
+    assert model.n_events == 4 * len(tracks)                    # per track and frame: the corner zone and the edge zone
+    got = {e.track_id: e.centroid[0] for e in eng.process(ns(tracks), 2, now=1.7e9 + 2.0)}
+    assert got == {i + 1: R.CENTROID_CASES[i][1] for i in range(len(tracks))}
+    eng.close()
+
+
+def test_ledger_full(pkg, tmp_path):
+    """e. max_tracks = 8: frames pass while passed + retained idle rows <= 16, the frame with exactly 16 included; the
+    frame the model predicts raises E_CAPACITY, and from then on the handle stays in error: process and snapshot keep
+    raising (include/rtmodt.h, rtmodt_zones_create)."""
+    eng = pkg.events.ZoneEventEngine(R.EXPIRY_ZONE, log_path=str(tmp_path / "e.jsonl"), max_tracks=8, max_events=64)
+    model = R.ZoneLedgerRef(R.EXPIRY_ZONE, 8)
+    mk = lambda ids: [(i, np.array([10, 10, 20, 20], np.float32), 1) for i in ids]
+    for frame_id, ids in R.LEDGER_FULL_CALLS[:-1]:
+        check_call(eng, model, 0, frame_id, 1.7e9 + frame_id, mk(ids), f"frame {frame_id}")
+    assert model.rows == 16 and model.overflow is None
+    frame_id, ids = R.LEDGER_FULL_CALLS[-1]
+    model.process(mk(ids), frame_id, 1.7e9 + frame_id)
+    assert model.overflow == frame_id and model.rows == 17
+    for attempt in (mk(ids), mk([1]), []):                      # the overflowing call, then any other
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            eng.process(ns(attempt), frame_id, now=1.7e9 + frame_id)
+        assert e.value.code == pkg._ffi.E_CAPACITY
+    with pytest.raises(pkg._ffi.RtmodtError) as e:
+        eng.snapshot()
+    assert e.value.code == pkg._ffi.E_CAPACITY
+    eng.close()
+
+
+@pytest.mark.parametrize("name", ["calls_on_every_frame", "frame_ids_jump", "zero"])
+def test_expiry_cases_derived_by_hand_on_engine(pkg, tmp_path, name):
+    """The hand-derived cases of tests/test_zone_ref_cpu.py on the engine: max_idle_frames = 3 (0 for "zero"), zero dwell,
+    cooldown 1e9 -- an id stays silent up to a gap of 3 frame ids and fires again from 4, whether or not calls were made
+    in between."""
+    calls, idle = (R.EXPIRY_ZERO, 0) if name == "zero" else (R.EXPIRY_CASES[name], 3)
+    eng = pkg.events.ZoneEventEngine(R.EXPIRY_ZONE, log_path=str(tmp_path / "e.jsonl"), max_tracks=8, max_events=64, max_idle_frames=idle)
+    model = R.ZoneLedgerRef(R.EXPIRY_ZONE, 8, idle)
+    for k, (frame_id, ids, fires) in enumerate(calls):
+        tracks = [(i, np.array([10, 10, 20, 20], np.float32), 0) for i in ids]
+        got = sorted(e.track_id for e in eng.process(ns(tracks), frame_id, now=1.7e9 + 0.5 * k))
+        assert got == sorted(fires), f"frame {frame_id}"
+        model.process(tracks, frame_id, 1.7e9 + 0.5 * k)
+        assert eng.snapshot() == model.snapshot(), f"frame {frame_id}"
+    eng.close()
+
+
+def test_tracker_source_at_scale(pkg, tmp_path):
+    """f. process_tracker on four streams of 400-600 boxes with 15-30 % of the detections away at any time: lost tracks,
+    expiry and compaction in the middle of the list, more than 512 rows in a stream -- against the tracker oracle plus
+    the model's tracker-source mode.  One more frame with report="reference": nothing is passed, so no events, empty
+    occupancy, cooldown untouched."""
+    P = R.TRACKER
+    S, N = P["n_streams"], P["max_dets"]
+    core = pkg.tracking.tracker._ByteTrackCore(n_streams=S, max_dets=N, max_tracks=P["max_tracks"], track_buffer=P["track_buffer"])
+    eng = pkg.events.ZoneEventEngine(R.TRACKER_ZONES, log_path=str(tmp_path / "e.jsonl"), n_streams=S, max_tracks=P["max_tracks"], max_events=4096)
+    tor = [T.TrackerOracle(track_buffer=P["track_buffer"]) for _ in range(S)]
+    models = [R.ZoneLedgerRef(R.TRACKER_ZONES, P["max_tracks"]) for _ in range(S)]
+    frames, clock = R.tracker_inputs(pkg.synth.box_sequence)
+
+    def step(f, report):
+        xyxy = np.zeros((S, N, 4), np.float32); conf = np.zeros((S, N), np.float32); cls = np.zeros((S, N), np.int32)
+        cnt = np.zeros(S, np.int32)
+        for s in range(S):
+            b, c, k = frames[f][s]
+            xyxy[s, :len(c)], conf[s, :len(c)], cls[s, :len(c)], cnt[s] = b, c, k, len(c)
+        core.update_batch(xyxy, conf, cls, cnt)
+        got = eng.process_tracker(SimpleNamespace(_core=core, report=report), f, now=clock[f])
+        for s in range(S):
+            tor[s].update(*frames[f][s])
+            st = tor[s].snapshot()
+            dev = core.snapshot(s)
+            assert np.array_equal(dev["ids"], st["ids"]) and np.array_equal(dev["tsu"], st["tsu"]), f"frame {f} stream {s}: the tracker itself differs"
+            want = models[s].process_tracker(st["ids"], st["tsu"], st["xyxy"], st["cls"], 1 if report == "matched" else 0, f, clock[f])
+            assert [as_dict(e) for e in got[s]] == want, f"frame {f} stream {s}"
+            assert eng.snapshot(s) == models[s].snapshot(), f"frame {f} stream {s}"
+        return got
+
+    for f in range(P["n_frames"]):
+        step(f, "matched")
+    print("tracker", R.tracker_guards(models))
+    before = [m.snapshot()["cooldown"] for m in models]
+    dead_before = [m.tracker_expired for m in models]
+    got = step(P["n_frames"], "reference")
+    for s in range(S):
+        live = set(int(i) for i in tor[s].ids)
+        assert got[s] == [] and eng.snapshot(s)["occupancy"] == []
+        assert eng.snapshot(s)["cooldown"] == [r for r in before[s] if r[0] in live] and len(before[s]) > 50
+    assert sum(m.tracker_expired for m in models) > sum(dead_before)         # ... while rows still leave with their tracks
+    core.close(); eng.close()
