@@ -42,6 +42,7 @@ typedef struct rtmodt_tracker rtmodt_tracker;
 typedef struct rtmodt_zones rtmodt_zones;
 typedef struct rtmodt_renderer rtmodt_renderer;
 typedef struct rtmodt_jpeg rtmodt_jpeg;
+typedef struct rtmodt_deepsort rtmodt_deepsort;
 
 /* ---- library / device ------------------------------------------------------------- */
 const char *rtmodt_last_error(void);
@@ -241,6 +242,68 @@ int rtmodt_assign_greedy(int device, const float *iou, int m, int n, float thres
  * are contested (share a row or column with another candidate pair). */
 int rtmodt_assign_lapjv(int device, const float *iou, int m, int n, double cost_limit, int32_t *row_to_col,
                         int32_t *col_used);
+
+/* ---- DeepSORT: the tracker config/default.yaml:47 offers as `algorithm: "deepsort"` and src/tracking/tracker.py:212-214 never wired ---- */
+/* The published algorithm (Wojke et al.; deep_sort's tracker.py, linear_assignment.py, nn_matching.py, kalman_filter.py) with the
+ * state resident on the device: csrc/deepsort.hip states the rules, tests/deepsort_ref.py restates them.  PARITY UNPINNED:
+ * deep_sort_realtime is installed nowhere this runs.  Limits: 256 tracks and 1024 detections per stream, nn_budget <= 128, 64
+ * streams, and the contested-pair limits of rtmodt_assign_lapjv; beyond them RTMODT_E_CAPACITY, never a fault. */
+typedef struct rtmodt_deepsort_cfg {
+    double max_dist;            /* default.yaml:54  0.2: a pair is admissible when max(0, 16129 - dotmax) <= floor(max_dist * 16129) */
+    float min_confidence;       /* default.yaml:55  0.3: detections below it are dropped (float32 >=)                            */
+    double max_iou_distance;    /* default.yaml:56  0.7: IoU stage, 1 - iou <= max_iou_distance                                  */
+    int32_t max_age;            /* default.yaml:57  70: an unmatched confirmed track dies when time_since_update > max_age       */
+    int32_t n_init;             /* default.yaml:58  3: hits before a tentative track is confirmed                                */
+    int32_t nn_budget;          /* default.yaml:59  100: descriptors kept per track (a ring of the last nn_budget since birth)    */
+    const char *embedder;       /* default.yaml:60: NULL, "" or "colorhist" = the built-in descriptor; a model file is
+                                 * RTMODT_E_UNSUPPORTED (no embedding network here: bring its output as caller descriptors)      */
+    int32_t dim;                /* descriptor dimension: 0 = 192 (built-in); 64..512 in multiples of 64 for caller descriptors    */
+    int32_t max_tracks, max_dets, n_streams, device;
+} rtmodt_deepsort_cfg;
+int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out);
+void rtmodt_deepsort_destroy(rtmodt_deepsort *ds);
+int rtmodt_deepsort_reset(rtmodt_deepsort *ds, int stream);   /* stream < 0: all */
+
+/* The built-in appearance descriptor (the "colour histogram per track" of TECHNICAL_DESIGN_DOCUMENT.md B.4, standing in for
+ * default.yaml:60's embedder) of max_boxes box slots per frame: frames as in rtmodt_render_batch (BGR24, h x w, pitch
+ * stride_bytes >= 3w, host or device pointers, only read), xyxy[n_frames][max_boxes][4], n_boxes[n_frames].  Outputs (host):
+ * desc[n_frames][max_boxes][192] int8 and, when not NULL, counts[n_frames][max_boxes][192] int32 -- rows past n_boxes are zero.
+ * Rules: csrc/appearance.hip.  Two launches whatever the number of boxes.  At most 64 frames and 1024 boxes per frame. */
+int rtmodt_appearance_describe(int device, const uint8_t *const *frames, int n_frames, int h, int w, int stride_bytes, int mem_kind,
+                               const float *xyxy, const int32_t *n_boxes, int max_boxes, int8_t *desc, int32_t *counts);
+/* Host only, no device needed: float rows x[n][dim] of an embedder that runs elsewhere (default.yaml:60) -> int8 rows,
+ * rint(127 * x / ||x||) in float64 (norm by sequential summation), a zero row gives zeros.  dim 64..512 in multiples of 64. */
+int rtmodt_appearance_quantize(const float *x, int n, int dim, int8_t *out);
+/* The gallery distance alone (default.yaml:54, :59), as rtmodt_iou_matrix exposes the IoU alone: gallery[n_tracks][budget][dim]
+ * int8 with counts[n_tracks] valid rows each, dets[n_dets][dim]; out[n_tracks][n_dets] = the maximum over a track's rows of the
+ * int8 dot product with the detection (exact, int32), INT32_MIN for a track without rows.  v_mfma_i32_16x16x64_i8. */
+int rtmodt_appearance_dotmax(int device, const int8_t *gallery, const int32_t *counts, int n_tracks, int budget, const int8_t *dets,
+                             int n_dets, int dim, int32_t *out);
+
+/* One frame for every stream (default.yaml:53-60): xyxy[n_streams][max_dets][4], conf / cls[n_streams][max_dets], n[n_streams],
+ * plus EITHER frames[n_streams] (the frame each stream's boxes lie on; descriptors are computed on the GPU) OR
+ * desc[n_streams][max_dets][dim] int8 caller descriptors -- never both; neither is needed when every n is 0.
+ * n_returned_out[n_streams] (may be NULL) = confirmed tracks matched in this frame (what update() returns). */
+int rtmodt_deepsort_update_batch(rtmodt_deepsort *ds, const float *xyxy, const float *conf, const int32_t *cls, const int32_t *n,
+                                 const uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind, const int8_t *desc,
+                                 int32_t *n_returned_out);
+/* The same on the device-resident detections of det's last enqueue_batch (stream i <- frame i; frames[n_frames] are the frames
+ * that batch was made of), queued on det's HIP stream behind its NMS: the detections never visit the host.  With
+ * RTMODT_MEM_DEVICE frames the call is asynchronous; the frames must stay valid and unchanged until the work is done
+ * (rtmodt_deepsort_state, rtmodt_deepsort_last_ms and rtmodt_synchronize all wait for it).  With RTMODT_MEM_HOST frames they are
+ * first copied to a staging area on that stream: the copy of pageable memory blocks the calling thread, the frames must stay
+ * valid until a synchronisation, and a call that has to grow the staging area (the first one, or larger frames) waits for the
+ * stream first.  Use device frames (where the detector read them) for the asynchronous path. */
+int rtmodt_deepsort_update_from_detector(rtmodt_deepsort *ds, rtmodt_detector *det, const uint8_t *const *frames, int n_frames, int h,
+                                         int w, int stride_bytes, int mem_kind);
+/* A stream's tracks in list order (creation order, deletions compacted); arrays sized max_tracks, any may be NULL.  state: 1
+ * tentative, 2 confirmed; xyxy / conf / cls: the last matched detection; mean[n][8], cov[n][12] as rtmodt_tracker_kalman_state;
+ * gallery_count[n] = stored descriptors, gallery[n][nn_budget][dim] = those rows oldest first (the rest zero). */
+int rtmodt_deepsort_state(rtmodt_deepsort *ds, int stream, int64_t *ids, int32_t *state, int32_t *hits, int32_t *age, int32_t *tsu,
+                          float *xyxy, float *conf, int32_t *cls, float *mean, float *cov, int32_t *gallery_count, int8_t *gallery,
+                          int32_t *n, int64_t *next_id);
+/* Device time (ms, HIP events) of the last update's three parts: descriptors (0 with caller descriptors), distance, update. */
+int rtmodt_deepsort_last_ms(rtmodt_deepsort *ds, float *describe_ms, float *distance_ms, float *update_ms);
 
 /* ---- zone events: replaces ZoneEventEngine.process (src/events/zone_engine.py:82-132) -------- */
 /* One polygon zone (zone_engine.py:50-58, :142-151).  `key` = index of the FIRST zone carrying the

@@ -10,6 +10,7 @@ library being built):
 
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
 * ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
+* ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``_ffi``               -- ctypes binding of ``include/rtmodt.h`` (librtmodt_hip.so)
 * ``weights``            -- flat fused-conv weight format, synthetic weights, BN folding
 * ``synth``              -- deterministic synthetic frames / box sequences
@@ -27,13 +28,14 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track"]
+__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
     "Detections": ".detection.detector",
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
+    "DeepSortTracker": ".tracking.deepsort",
     "ZoneEventEngine": ".events.zone_engine",
     "FrameReader": ".ingestion.reader",
     "RTSPReader": ".ingestion.reader",

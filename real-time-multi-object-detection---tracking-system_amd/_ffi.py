@@ -123,6 +123,12 @@ class JpegCfg(C.Structure):                          # struct rtmodt_jpeg_cfg
     _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("max_h", C.c_int32), ("max_w", C.c_int32), ("max_batch", C.c_int32)]
 
 
+class DeepSortCfg(C.Structure):                     # struct rtmodt_deepsort_cfg
+    _fields_ = [("max_dist", C.c_double), ("min_confidence", C.c_float), ("max_iou_distance", C.c_double), ("max_age", C.c_int32),
+                ("n_init", C.c_int32), ("nn_budget", C.c_int32), ("embedder", C.c_char_p), ("dim", C.c_int32), ("max_tracks", C.c_int32),
+                ("max_dets", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
+
+
 class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
     _fields_ = [(n, C.c_int64) for n in ("num_frames", "num_objects", "num_predictions", "num_matches", "num_switches", "num_misses",
                                          "num_false_positives", "mostly_tracked", "mostly_lost", "num_unique_objects", "idtp", "idfp",
@@ -199,6 +205,16 @@ def lib() -> C.CDLL:
         "rtmodt_iou_matrix": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp]),
         "rtmodt_assign_greedy": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, f32, vp, vp]),
         "rtmodt_assign_lapjv": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_double, vp, vp]),
+        "rtmodt_deepsort_create": (C.c_int, [C.POINTER(DeepSortCfg), C.POINTER(vp)]),
+        "rtmodt_deepsort_destroy": (None, [vp]),
+        "rtmodt_deepsort_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_appearance_describe": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+        "rtmodt_appearance_quantize": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "rtmodt_appearance_dotmax": (C.c_int, [C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),
+        "rtmodt_deepsort_update_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "rtmodt_deepsort_update_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_deepsort_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i64)]),
+        "rtmodt_deepsort_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
         "rtmodt_zones_create": (C.c_int, [C.c_int, C.POINTER(ZoneCfg), C.c_int, C.c_int, C.c_int, C.c_int, i64, C.POINTER(vp)]),
         "rtmodt_zones_destroy": (None, [vp]),
         "rtmodt_zones_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, i64, vp, vp, vp, vp, C.POINTER(i32)]),
@@ -330,6 +346,70 @@ def preprocess_yuv420(frame: np.ndarray, fmt="nv12", in_w: int = 640, in_h: int 
         raise ValueError(f"the buffer holds {frame.nbytes} bytes, the layout spans {frame_span(fmt, h, w)}")
     out = np.empty((in_h, in_w, 3), np.float16)
     check(lib().rtmodt_preprocess_yuv420(device, ptr(frame), h, w, C.byref(fmt), in_w, in_h, ptr(out)))
+    return out
+
+
+def appearance_quantize(x: np.ndarray) -> np.ndarray:
+    """Float embedding rows ``(n, dim)`` -> the int8 rows the DeepSORT gallery stores (``rtmodt_appearance_quantize``, host only)."""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2:
+        raise ValueError(f"embeddings are a (n, dim) array, got shape {x.shape}")
+    out = np.zeros(x.shape, np.int8)
+    check(lib().rtmodt_appearance_quantize(ptr(x), x.shape[0], x.shape[1], ptr(out)))
+    return out
+
+
+def frame_pointers(frames, mem_kind: int, height: int = 0, width: int = 0, stride: int = 0):
+    """``frames`` -> (``uint8_t *[n]`` array, keep-alive list, height, width, row pitch).  Device frames (``mem_kind == MEM_DEVICE``) are
+    addresses and the geometry is the caller's.  Host frames are ``(h, w, 3)`` uint8 arrays whose pixels are 3 contiguous bytes (rows may
+    be padded); the geometry is read from the arrays, which must agree.  Anything else (another dtype, a BGRA view, a negative
+    stride) is refused: a silent copy would change the pitch under the caller's feet."""
+    if mem_kind == MEM_DEVICE:
+        return (C.c_void_p * len(frames))(*[int(p) for p in frames]), [], int(height), int(width), int(stride)
+    keep = []
+    for i, f in enumerate(frames):
+        if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3 \
+                or f.strides[0] < 3 * f.shape[1]:
+            raise ValueError(f"frame {i}: a host frame is an (h, w, 3) uint8 array with packed pixels and a row pitch >= 3w "
+                             f"(got {getattr(f, 'dtype', type(f))}, shape {getattr(f, 'shape', None)}, strides {getattr(f, 'strides', None)})")
+        keep.append(f)
+    if not keep:
+        return (C.c_void_p * 0)(), keep, 0, 0, 0
+    h, w, pitch = keep[0].shape[0], keep[0].shape[1], keep[0].strides[0]
+    if any(k.shape[:2] != (h, w) or k.strides[0] != pitch for k in keep):
+        raise ValueError("the frames of one call share their size and row pitch")
+    return (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep]), keep, h, w, pitch
+
+
+def appearance_describe(frames, boxes, *, height: int = 0, width: int = 0, stride: int = 0, mem_kind: int = MEM_HOST, device: int = 0,
+                        want_counts: bool = False):
+    """Descriptors of ``boxes[i]`` (an ``(n_i, 4)`` xyxy array) on ``frames[i]`` (``rtmodt_appearance_describe``): a list of
+    ``(n_i, 192)`` int8 arrays, and the int32 counts too with ``want_counts``.  Host frames are ``(h, w, 3)`` uint8 arrays (row
+    pitch = ``strides[0]``); device frames are addresses with ``height`` / ``width`` / ``stride`` given."""
+    n = len(frames)
+    boxes = [np.ascontiguousarray(b, np.float32).reshape(-1, 4) for b in boxes]
+    fp, keep, height, width, stride = frame_pointers(frames, mem_kind, height, width, stride)
+    mb = max(1, max(len(b) for b in boxes))
+    xy = np.zeros((n, mb, 4), np.float32)
+    for i, b in enumerate(boxes):
+        xy[i, :len(b)] = b
+    cnt = np.asarray([len(b) for b in boxes], np.int32)
+    desc = np.zeros((n, mb, 192), np.int8)
+    counts = np.zeros((n, mb, 192), np.int32) if want_counts else None
+    check(lib().rtmodt_appearance_describe(device, fp, n, int(height), int(width), int(stride), mem_kind, ptr(xy), ptr(cnt), mb, ptr(desc),
+                                           ptr(counts)))
+    d = [desc[i, :len(b)].copy() for i, b in enumerate(boxes)]
+    return (d, [counts[i, :len(b)].copy() for i, b in enumerate(boxes)]) if want_counts else d
+
+
+def appearance_dotmax(gallery: np.ndarray, counts, dets: np.ndarray, device: int = 0) -> np.ndarray:
+    """``gallery (T, budget, dim)`` int8 with ``counts[T]`` valid rows, ``dets (N, dim)`` int8 -> ``(T, N)`` int32 (``rtmodt_appearance_dotmax``)."""
+    gallery = np.ascontiguousarray(gallery, np.int8)
+    dets = np.ascontiguousarray(dets, np.int8)
+    counts = np.ascontiguousarray(counts, np.int32)
+    T, budget, dim = gallery.shape
+    out = np.zeros((T, dets.shape[0]), np.int32)
+    check(lib().rtmodt_appearance_dotmax(device, ptr(gallery), ptr(counts), T, budget, ptr(dets), dets.shape[0], dim, ptr(out)))
     return out
 
 

@@ -246,6 +246,39 @@ int launch_assign_greedy(const float *iou, int m, int n, float thresh, int32_t *
 int launch_assign_lapjv(const float *iou, int m, int n, double cost_limit, int32_t *row_to_col, int32_t *col_used, int32_t *err,
                         hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// appearance descriptors + DeepSORT (appearance.hip, deepsort.hip)
+// ---------------------------------------------------------------------------------------
+constexpr int APP_DIM = 192;               // built-in descriptor: 4 stripes x (B, G, R) x 16 bins
+constexpr int DS_MAX_TRACKS = 256, DS_MAX_DETS = 1024, DS_MAX_BUDGET = 128, DS_MAX_STREAMS = 64;
+struct AppFrames { const uint8_t *p[DS_MAX_STREAMS]; };      // device pointers, by value in the kernel arguments
+struct DescribeArgs {
+    AppFrames frames; int h, w, pitch;      // BGR24, one frame per stream
+    const float4 *box; const int32_t *box_n; int box_stride;   // boxes [stream][box_stride], counts [stream] (device)
+    int max_boxes;                          // box slots launched per stream (= row stride of counts)
+    int32_t *counts;                        // [stream][max_boxes][APP_DIM]
+    int8_t *desc; int desc_stride;          // [stream][desc_stride][APP_DIM]
+};
+int launch_describe(const DescribeArgs &a, int n_streams, hipStream_t s);
+
+struct DsState {               // one stream; device pointers; double-buffered like TrackerState
+    int64_t *ids[2]; float4 *dbox[2]; float *conf[2]; int32_t *cls[2];
+    int32_t *flag[2], *hits[2], *age[2], *tsu[2];      // flag: 1 tentative, 2 confirmed
+    int32_t *slot[2], *gcount[2];                       // gallery slot; descriptors appended since birth (ring position = gcount % budget)
+    float4 *kf[2];                                      // [5][max_tracks], as TrackerState::kf
+    int32_t *slot_used;                                 // [max_tracks]
+};
+struct DotmaxArgs {
+    const int8_t *gallery; size_t gallery_stream_stride;        // [stream][slot][budget][dim]
+    const int32_t *counts;                                      // standalone: samples per track (slot == track)
+    const DsState *states; const int64_t *meta;                 // tracker: slot / gcount / track count come from the state
+    int budget, dim;
+    const int8_t *dets; int det_stride;                         // [stream][det_stride][dim]
+    int n_tracks, n_dets; const int32_t *n_dets_dev; int max_dets;
+    int32_t *out; size_t out_stream_stride; int out_row_stride; // out[stream][track][det]
+};
+int launch_dotmax(const DotmaxArgs &a, int grid_tracks, int grid_dets, int n_streams, hipStream_t s);
+
 // the tracker's device-resident state (tracker_api.hip), consumed by the zone engine (zones.hip):
 // states[n_streams], meta[n_streams][8] = {cur, n_tracks, err, n_active, next_id, ...}; `stream` is the HIP stream
 // the tracker's most recent update was launched on

@@ -56,9 +56,10 @@ using LapSmem = LapSmemT<double>;
 static inline size_t lap_smem_bytes(int Nc) {
     return (size_t)LAP_EDGES * 12 + (size_t)LAP_ROWS * (8 + 4 + 4 + 4) + (size_t)LAP_COLS * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 1) + (size_t)Nc * 4 + 64;
 }
-__device__ __forceinline__ LapSmem lap_carve(unsigned char *base, int Nc) {     // base 8-byte aligned
-    LapSmem L;
-    L.ecost = (double *)base;
+template <typename C> __device__ __forceinline__ LapSmemT<C> lap_carve_t(unsigned char *base, int Nc) {     // base 8-byte aligned; any 8-byte cost type
+    static_assert(sizeof(C) == 8, "lap_smem_bytes counts 8 bytes per cost");
+    LapSmemT<C> L;
+    L.ecost = (C *)base;
     L.u = L.ecost + LAP_EDGES;
     L.v = L.u + LAP_ROWS;
     L.minv = L.v + LAP_COLS;
@@ -75,6 +76,8 @@ __device__ __forceinline__ LapSmem lap_carve(unsigned char *base, int Nc) {     
     L.used = (unsigned char *)(L.usedl + LAP_COLS);
     return L;
 }
+
+__device__ __forceinline__ LapSmem lap_carve(unsigned char *base, int Nc) { return lap_carve_t<double>(base, Nc); }
 
 // Exact sparse assignment, run by ONE lane (or the host).  On entry: u[0..nhr) = 0, rm = -1; for every column v = 0,
 // minv = inf, p = -1, used = 0.  On exit rm[row] is the row's column or -1 (its dummy).  Only the source row's edges can

@@ -24,109 +24,7 @@
 
 namespace rtmodt {
 
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ float iou_ref(const float4 a, const float4 b) {
-    float x1 = fmaxf(a.x, b.x), y1 = fmaxf(a.y, b.y);
-    float x2 = fminf(a.z, b.z), y2 = fminf(a.w, b.w);
-    float w = fmaxf(0.0f, x2 - x1), h = fmaxf(0.0f, y2 - y1);
-    float inter = w * h;
-    float area_a = (a.z - a.x) * (a.w - a.y);
-    float area_b = (b.z - b.x) * (b.w - b.y);
-    float uni = (area_a + area_b) - inter;
-    return inter / (uni + 1e-6f);
-}
-
-// ---------------------------------------------------------------------------------------
-// Opt-in Kalman motion model (TrackerArgs::kalman; oracle/kalman_oracle.py states the algorithm and its provenance:
-// ByteTrack's published 8-state constant-velocity filter -- the reference itself has none, tracker.py:99-104).
-// F, H, Q, R and the initial P keep P block-diagonal, so the filter is four independent (position, velocity) pairs
-// with covariance [[a, b], [b, c]] whose only coupling is the noise scale h.  float32, one rounding per operation in
-// exactly the oracle's order (this file is built with FMA contraction off and correctly rounded division).
-// ---------------------------------------------------------------------------------------
-struct Kf { float4 pos, vel, pa, pb, pc; };
-constexpr float KF_WP = 0.05f, KF_WV = 0.00625f;
-__device__ __forceinline__ Kf kf_load(const float4 *kf, int Mc, int i) { return Kf{kf[i], kf[Mc + i], kf[2 * Mc + i], kf[3 * Mc + i], kf[4 * Mc + i]}; }
-__device__ __forceinline__ void kf_store(float4 *kf, int Mc, int i, const Kf &k) {
-    kf[i] = k.pos; kf[Mc + i] = k.vel; kf[2 * Mc + i] = k.pa; kf[3 * Mc + i] = k.pb; kf[4 * Mc + i] = k.pc;
-}
-__device__ __forceinline__ float4 xyxy_to_xyah(const float4 b) {
-    const float w = b.z - b.x, h = b.w - b.y;
-    return float4{b.x + w * 0.5f, b.y + h * 0.5f, w / fmaxf(h, 1e-6f), h};
-}
-__device__ __forceinline__ float4 xyah_to_xyxy(const float4 m) {
-    const float w = m.z * m.w;
-    const float x1 = m.x - w * 0.5f, y1 = m.y - m.w * 0.5f;
-    return float4{x1, y1, x1 + w, y1 + m.w};
-}
-__device__ __forceinline__ Kf kf_initiate(const float4 z) {
-    const float sp = (2.0f * KF_WP) * z.w, sv = (10.0f * KF_WV) * z.w;
-    const float p2 = sp * sp, v2 = sv * sv;
-    Kf k;
-    k.pos = z; k.vel = float4{0.f, 0.f, 0.f, 0.f};
-    k.pa = float4{p2, p2, 1e-2f * 1e-2f, p2};
-    k.pb = float4{0.f, 0.f, 0.f, 0.f};
-    k.pc = float4{v2, v2, 1e-5f * 1e-5f, v2};
-    return k;
-}
-__device__ __forceinline__ void kf_predict1(float &p, const float v, float &a, float &b, float &c, const float qp, const float qv) {
-    const float a0 = a, b0 = b, c0 = c;
-    p = p + v;
-    a = ((a0 + (b0 + b0)) + c0) + qp;
-    b = b0 + c0;
-    c = c0 + qv;
-}
-__device__ __forceinline__ void kf_predict(Kf &k) {
-    const float h = k.pos.w;
-    const float sp = KF_WP * h, sv = KF_WV * h;
-    const float qp = sp * sp, qv = sv * sv;
-    kf_predict1(k.pos.x, k.vel.x, k.pa.x, k.pb.x, k.pc.x, qp, qv);
-    kf_predict1(k.pos.y, k.vel.y, k.pa.y, k.pb.y, k.pc.y, qp, qv);
-    kf_predict1(k.pos.z, k.vel.z, k.pa.z, k.pb.z, k.pc.z, 1e-2f * 1e-2f, 1e-5f * 1e-5f);
-    kf_predict1(k.pos.w, k.vel.w, k.pa.w, k.pb.w, k.pc.w, qp, qv);
-}
-__device__ __forceinline__ void kf_update1(float &p, float &v, float &a, float &b, float &c, const float z, const float r) {
-    const float a0 = a, b0 = b, c0 = c;
-    const float s = a0 + r;
-    const float k0 = a0 / s, k1 = b0 / s;
-    const float y = z - p;
-    p = p + k0 * y;
-    v = v + k1 * y;
-    a = a0 - k0 * a0;
-    b = b0 - k0 * b0;
-    c = c0 - k1 * b0;
-}
-__device__ __forceinline__ void kf_update(Kf &k, const float4 z) {
-    const float sp = KF_WP * k.pos.w;
-    const float r = sp * sp;
-    kf_update1(k.pos.x, k.vel.x, k.pa.x, k.pb.x, k.pc.x, z.x, r);
-    kf_update1(k.pos.y, k.vel.y, k.pa.y, k.pb.y, k.pc.y, z.y, r);
-    kf_update1(k.pos.z, k.vel.z, k.pa.z, k.pb.z, k.pc.z, z.z, 1e-1f * 1e-1f);
-    kf_update1(k.pos.w, k.vel.w, k.pa.w, k.pb.w, k.pc.w, z.w, r);
-}
-
-constexpr int TRK_THREADS = 1024;
-constexpr int TRK_WAVES = TRK_THREADS / 64;
-
-// exclusive prefix of a per-thread flag over the workgroup (thread order); returns position,
-// writes the total.  Two barriers.  wsum: LDS int[TRK_WAVES + 1].
-__device__ __forceinline__ int block_scan_flag(bool flag, int *wsum, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long m = __ballot(flag);
-    int within = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < TRK_WAVES; ++w) {
-        int v = wsum[w];
-        if (w < wave) off += v;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return off + within;
-}
+#include "track_dev.h"
 
 struct AssocSmem {
     float4 *tbox;      // [max_tracks] track boxes (state before this frame's commits)
@@ -194,114 +92,19 @@ __device__ __forceinline__ void assoc_pass(const AssocSmem &s, const int *rows, 
 // A scene denser than the LDS budget raises the sticky error 2 (host: RTMODT_E_CAPACITY).
 // Output convention = assoc_pass: row r matched iff row_best[r] >= 0 && col_winner[row_best[r]] == r.
 // ---------------------------------------------------------------------------------------
-// (the exact solver of step 3 -- LapSmem, lap_carve, lap_solve -- is shared with the evaluator: lap.h)
+// (the exact solver of step 3 -- LapSmem, lap_carve, lap_solve -- is shared with the evaluator: lap.h; steps 1-4 themselves are
+//  assoc_sparse in track_dev.h, shared with the DeepSORT tracker)
 // ---------------------------------------------------------------------------------------
 
 // val(r, c): IoU (float32) of row r and column c of this pass
 template <typename F>
 __device__ __forceinline__ void assoc_lap(F val, int n_rows, int n_cols, double limit, int *row_best, int *col_winner, int *rowcand,
                                           const LapSmem &L, int *wsum, int *err) {
-    const int tid = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = tid; c < n_cols; c += TRK_THREADS) { col_winner[c] = 0; L.colmap[c] = -1; }
-    __syncthreads();
-    // ---- 1. degrees ----
-    int R = 64;
-    while (R > 1 && (n_rows * R > TRK_THREADS || (R >> 1) >= n_cols)) R >>= 1;
-    const int groups = TRK_THREADS / R;
-    const int gid = threadIdx.x / R, sub = threadIdx.x & (R - 1);
-    for (int r = gid; r < n_rows; r += groups) {
-        int deg = 0, last = -1;
-        for (int c = sub; c < n_cols; c += R) {
-            const float v = val(r, c);
-            if ((double)(1.0f - v) < limit) { ++deg; last = c; atomicAdd(&col_winner[c], 1); }
-        }
-        for (int d = R >> 1; d >= 1; d >>= 1) {
-            deg += __shfl_xor(deg, d);
-            last = max(last, __shfl_xor(last, d));
-        }
-        if (sub == 0) { row_best[r] = deg; rowcand[r] = last; }
-    }
-    __syncthreads();
-    // ---- 2. isolated edges vs contested rows (ascending) ----
-    int nhr = 0;
-    for (int base = 0; base < n_rows; base += TRK_THREADS) {
-        const int r = base + tid;
-        bool hard = false;
-        if (r < n_rows) {
-            const int deg = row_best[r];
-            hard = deg >= 2 || (deg == 1 && col_winner[rowcand[r]] != 1);
-            if (deg != 1 || hard) rowcand[r] = -1;          // rowcand >= 0 from here on == isolated edge
-        }
-        int tot;
-        const int pos = block_scan_flag(hard, wsum, tot);
-        if (hard && nhr + pos < LAP_ROWS) L.hrow[nhr + pos] = r;
-        nhr += tot;
-    }
-    bool dense = nhr > LAP_ROWS;
-    if (dense) nhr = 0;
-    __syncthreads();                                       // hrow[] is written after the scan's own barriers
-    if (tid == 0) {
-        int e = 0;
-        for (int h = 0; h < nhr; ++h) { L.estart[h] = e; e += row_best[L.hrow[h]]; }
-        L.estart[nhr] = e;
-    }
-    __syncthreads();
-    int ne = L.estart[nhr];
-    if (ne > LAP_EDGES) { dense = true; nhr = 0; ne = 0; }
-    // ---- 3. edges of the contested rows, columns ascending: one wave per row ----
-    for (int h = wave; h < nhr; h += TRK_WAVES) {
-        const int r = L.hrow[h];
-        int e0 = L.estart[h];
-        for (int cb = 0; cb < n_cols; cb += 64) {
-            const int c = cb + lane;
-            bool f = false;
-            double cost = 0.0;
-            if (c < n_cols) { cost = (double)(1.0f - val(r, c)); f = cost < limit; }
-            const unsigned long long m = __ballot(f);
-            if (f) {
-                const int e = e0 + __popcll(m & ((1ull << lane) - 1ull));
-                L.ecol[e] = c;
-                L.ecost[e] = cost - limit;
-                L.colmap[c] = -2;
-            }
-            e0 += __popcll(m);
-        }
-    }
-    __syncthreads();
-    int nhc = 0;
-    for (int base = 0; base < n_cols; base += TRK_THREADS) {
-        const int c = base + tid;
-        const bool f = c < n_cols && L.colmap[c] == -2;
-        int tot;
-        const int pos = block_scan_flag(f, wsum, tot);
-        if (f && nhc + pos < LAP_COLS) { L.colmap[c] = nhc + pos; L.hcol[nhc + pos] = c; }
-        nhc += tot;
-    }
-    if (nhc > LAP_COLS) { dense = true; nhr = 0; ne = 0; nhc = 0; }
-    __syncthreads();
-    for (int e = tid; e < ne; e += TRK_THREADS) L.ecol[e] = L.colmap[L.ecol[e]];
-    for (int h = tid; h < nhr; h += TRK_THREADS) { L.u[h] = 0.0; L.rm[h] = -1; }
-    for (int j = tid; j < nhc; j += TRK_THREADS) { L.v[j] = 0.0; L.minv[j] = __builtin_huge_val(); L.p[j] = -1; L.used[j] = 0; }
-    for (int c = tid; c < n_cols; c += TRK_THREADS) col_winner[c] = INT_MAX;
-    __syncthreads();
-    for (int r = tid; r < n_rows; r += TRK_THREADS) {
-        const int c = rowcand[r];
-        row_best[r] = c;
-        if (c >= 0) col_winner[c] = r;
-    }
-    __syncthreads();
-    // ---- 4. the contested sub-problem ----
-    if (tid == 0) {
-        if (dense) *err = 2;
-        lap_solve(L, nhr);
-        for (int h = 0; h < nhr; ++h)
-            if (L.rm[h] >= 0) {
-                const int r = L.hrow[h], c = L.hcol[L.rm[h]];
-                row_best[r] = c;
-                col_winner[c] = r;
-            }
-    }
-    __syncthreads();
+    assoc_sparse<double>([&](int r, int c, double &cost) -> bool {
+        const double cd = (double)(1.0f - val(r, c));
+        cost = cd - limit;
+        return cd < limit;
+    }, n_rows, n_cols, row_best, col_winner, rowcand, L, wsum, err);
 }
 
 // one frame of one stream (tracker.py:58-141); `didx` = which detection slot feeds it.  Every thread of the workgroup

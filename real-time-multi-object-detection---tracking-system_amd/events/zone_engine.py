@@ -115,6 +115,10 @@ class ZoneEventEngine:
     def process_tracker(self, tracker, frame_id: int, *, now: Optional[float] = None, class_names=None) -> list:
         """All streams of ``tracker`` at once, on its device-resident state.  Returns one event list per stream."""
         core = getattr(tracker, "_core", tracker)
+        from ..tracking.tracker import _ByteTrackCore
+        if not isinstance(core, _ByteTrackCore):           # rtmodt_zones_process_tracker reads an rtmodt_tracker handle and nothing else
+            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack tracker; hand the tracks of a "
+                            f"{type(tracker).__name__} over as a list: process(tracks, frame_id)")
         report = getattr(tracker, "report", "matched")
         now = time.time() if now is None else float(now)
         S, E = core.n_streams, self.max_events

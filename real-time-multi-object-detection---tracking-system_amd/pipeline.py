@@ -102,9 +102,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         handoff = device_handoff and hasattr(tracker, "update_from_detector") and hasattr(detector, "model")
         # the track list stays on the device only when the event stage can read it there; an engine with the reference's
         # host API alone (`process(tracks, fid)`) must be handed the materialised list, trails included
-        events_on_device = handoff and renderer is None and event_engine is not None and hasattr(event_engine, "process_tracker")
+        # (and only a ByteTrack handle can be read there: the DeepSORT tracker hands its tracks over as a list, through process())
+        needs_frame = bool(getattr(tracker, "needs_frame", False))
+        events_on_device = (handoff and not needs_frame and renderer is None and event_engine is not None
+                            and hasattr(event_engine, "process_tracker"))
         profiler.tick("tracking")
-        tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
+        if needs_frame:                                    # a tracker that describes its detections on the frame (DeepSortTracker)
+            tracks = tracker.update_from_detector(detector, frame=frame, materialize=not events_on_device) if handoff else tracker.update(detections, frame=frame)
+        else:
+            tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
         profiler.tock("tracking")
         if event_engine is not None:                       # tools/run_pipeline.py:141-146
             profiler.tick("events")

@@ -1,3 +1,4 @@
+from .deepsort import DeepSortTracker
 from .tracker import MultiObjectTracker, Track
 
-__all__ = ["MultiObjectTracker", "Track"]
+__all__ = ["DeepSortTracker", "MultiObjectTracker", "Track"]
