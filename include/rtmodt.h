@@ -43,6 +43,7 @@ typedef struct rtmodt_zones rtmodt_zones;
 typedef struct rtmodt_renderer rtmodt_renderer;
 typedef struct rtmodt_jpeg rtmodt_jpeg;
 typedef struct rtmodt_deepsort rtmodt_deepsort;
+typedef struct rtmodt_reid rtmodt_reid;
 
 /* ---- library / device ------------------------------------------------------------- */
 const char *rtmodt_last_error(void);
@@ -255,9 +256,13 @@ typedef struct rtmodt_deepsort_cfg {
     int32_t max_age;            /* default.yaml:57  70: an unmatched confirmed track dies when time_since_update > max_age       */
     int32_t n_init;             /* default.yaml:58  3: hits before a tentative track is confirmed                                */
     int32_t nn_budget;          /* default.yaml:59  100: descriptors kept per track (a ring of the last nn_budget since birth)    */
-    const char *embedder;       /* default.yaml:60: NULL, "" or "colorhist" = the built-in descriptor; a model file is
-                                 * RTMODT_E_UNSUPPORTED (no embedding network here: bring its output as caller descriptors)      */
-    int32_t dim;                /* descriptor dimension: 0 = 192 (built-in); 64..512 in multiples of 64 for caller descriptors    */
+    const char *embedder;       /* default.yaml:60: NULL, "" or "colorhist" = the built-in descriptor; a path ending in ".rtreid" =
+                                 * the OSNet x0.25 network of rtmodt_reid_* on that weight file, built inside the tracker (frames are
+                                 * then described by the network, caller descriptors are refused, RTMODT_E_INVALID when the file is
+                                 * missing or damaged); any other model file (".onnx" included) is RTMODT_E_UNSUPPORTED: convert the
+                                 * checkpoint with tools/convert_weights.py --reid, or bring its output as caller descriptors      */
+    int32_t dim;                /* descriptor dimension: 0 = 192 (built-in) or 512 (network); 64..512 in multiples of 64 for caller
+                                 * descriptors; with a network 0 or 512                                                          */
     int32_t max_tracks, max_dets, n_streams, device;
 } rtmodt_deepsort_cfg;
 int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out);
@@ -304,6 +309,40 @@ int rtmodt_deepsort_state(rtmodt_deepsort *ds, int stream, int64_t *ids, int32_t
                           int32_t *n, int64_t *next_id);
 /* Device time (ms, HIP events) of the last update's three parts: descriptors (0 with caller descriptors), distance, update. */
 int rtmodt_deepsort_last_ms(rtmodt_deepsort *ds, float *describe_ms, float *distance_ms, float *update_ms);
+
+/* ---- the embedder of default.yaml:60 (`tracking.deepsort.embedder: "weights/osnet_x0_25.onnx"`): OSNet x0.25 on the GPU ---- */
+/* csrc/reid.hip states the crop rule, the rounding contract and the launches; tests/reid_ref.py restates them.  PINNED: the crop
+ * and the int8 quantiser exactly, the network within a measured fp16 bound of float64 (profiles/reid/README.md).  PARITY
+ * UNPINNED: torchreid, cv2.resize and deep_sort_realtime are installed nowhere this runs.  The weight file is the project's
+ * .rtreid (reid_weights.py; tools/convert_weights.py --reid converts a torchreid checkpoint); an .onnx file is not read. */
+typedef struct rtmodt_reid_cfg {
+    const char *weight_path;    /* default.yaml:60: the .rtreid file                                                             */
+    int32_t device;
+    int32_t max_frames;         /* frames per call, 1..64                                                                        */
+    int32_t max_boxes;          /* boxes per frame, 1..1024; max_frames * max_boxes <= 8192 (2.9 MB of device memory per crop)   */
+} rtmodt_reid_cfg;
+/* default.yaml:60.  A missing, foreign or damaged file (CRC-32 digest) and non-positive sizes are RTMODT_E_INVALID, sizes past
+ * the limits RTMODT_E_CAPACITY -- all before the device is touched. */
+int rtmodt_reid_create(const rtmodt_reid_cfg *cfg, rtmodt_reid **out);
+/* default.yaml:60.  Frames and boxes as rtmodt_appearance_describe: xyxy[n_frames][max_boxes][4], n_boxes[n_frames].  Outputs
+ * (host): desc[n_frames][max_boxes][512] int8 and, when not NULL, feat[n_frames][max_boxes][512] float32 (the network's
+ * feature after fc); rows past n_boxes and rows of empty boxes are zero.  n_frames > max_frames, max_boxes or n_boxes past the
+ * handle's: RTMODT_E_CAPACITY before anything is launched.  The number of launches does not depend on the boxes. */
+int rtmodt_reid_embed(rtmodt_reid *r, const uint8_t *const *frames, int n_frames, int h, int w, int stride_bytes, int mem_kind,
+                      const float *xyxy, const int32_t *n_boxes, int max_boxes, float *feat, int8_t *desc);
+/* default.yaml:60.  One of the 13 tensors the last embed left in HBM, for every crop slot of the handle ([max_frames][max_boxes]
+ * rows): "crop" uint8 [256][128][3] RGB; "conv1" [128][64][16], "maxpool" [64][32][16], "conv2.0" / "conv2.1" [64][32][64],
+ * "conv2.2" [32][16][64], "conv3.0" / "conv3.1" [32][16][96], "conv3.2" [16][8][96], "conv4.0" / "conv4.1" / "conv5"
+ * [16][8][128], all fp16 NHWC; "feat" float32 [512].  *needed = the size in bytes; copied when out is not NULL and out_bytes
+ * suffices (else RTMODT_E_CAPACITY).  Rows of slots without a box, or with an empty one, hold stale bytes (feat: zeros). */
+int rtmodt_reid_tap(rtmodt_reid *r, const char *name, void *out, size_t out_bytes, size_t *needed);
+/* default.yaml:60.  Device time (ms, HIP events) of the last embed: the crop kernel, and everything after it. */
+int rtmodt_reid_last_ms(rtmodt_reid *r, float *crop_ms, float *net_ms);
+void rtmodt_reid_destroy(rtmodt_reid *r);   /* default.yaml:60 */
+/* default.yaml:60.  The network's input values as the library builds them on the host: out[v][c] = RNE16((v / 255 - mean_c) /
+ * std_c) evaluated in float32, as float32[256][3] (c in R, G, B; ImageNet mean and std).  Needs no device and no handle; a
+ * buffer smaller than 3072 bytes is RTMODT_E_INVALID. */
+int rtmodt_reid_norm_table(float *out, size_t out_bytes);
 
 /* ---- zone events: replaces ZoneEventEngine.process (src/events/zone_engine.py:82-132) -------- */
 /* One polygon zone (zone_engine.py:50-58, :142-151).  `key` = index of the FIRST zone carrying the

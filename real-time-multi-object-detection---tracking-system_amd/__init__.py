@@ -11,6 +11,8 @@ library being built):
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
 * ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
+* ``tracking.reid``      -- ``ReidEmbedder``: the OSNet x0.25 re-identification network on the GPU (reference: config/default.yaml:60)
+* ``reid_weights``       -- its ``.rtreid`` weight file, synthetic weights, torchreid ``state_dict`` conversion
 * ``_ffi``               -- ctypes binding of ``include/rtmodt.h`` (librtmodt_hip.so)
 * ``weights``            -- flat fused-conv weight format, synthetic weights, BN folding
 * ``synth``              -- deterministic synthetic frames / box sequences
@@ -50,7 +52,7 @@ def __getattr__(name):
     if name in _LAZY:
         mod = _importlib.import_module(_LAZY[name], __name__)
         return getattr(mod, name)
-    if name in ("synth", "weights", "_ffi", "detection", "tracking", "yolo_spec", "streams", "profiling", "pipeline", "events", "ingestion",
+    if name in ("synth", "weights", "reid_weights", "_ffi", "detection", "tracking", "yolo_spec", "streams", "profiling", "pipeline", "events", "ingestion",
                 "visualization", "evaluation"):
         return _importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -129,6 +129,10 @@ class DeepSortCfg(C.Structure):                     # struct rtmodt_deepsort_cfg
                 ("max_dets", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
 
 
+class ReidCfg(C.Structure):                         # struct rtmodt_reid_cfg
+    _fields_ = [("weight_path", C.c_char_p), ("device", C.c_int32), ("max_frames", C.c_int32), ("max_boxes", C.c_int32)]
+
+
 class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
     _fields_ = [(n, C.c_int64) for n in ("num_frames", "num_objects", "num_predictions", "num_matches", "num_switches", "num_misses",
                                          "num_false_positives", "mostly_tracked", "mostly_lost", "num_unique_objects", "idtp", "idfp",
@@ -215,6 +219,12 @@ def lib() -> C.CDLL:
         "rtmodt_deepsort_update_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtmodt_deepsort_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i64)]),
         "rtmodt_deepsort_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_reid_create": (C.c_int, [C.POINTER(ReidCfg), C.POINTER(vp)]),
+        "rtmodt_reid_destroy": (None, [vp]),
+        "rtmodt_reid_embed": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+        "rtmodt_reid_tap": (C.c_int, [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rtmodt_reid_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_reid_norm_table": (C.c_int, [vp, C.c_size_t]),
         "rtmodt_zones_create": (C.c_int, [C.c_int, C.POINTER(ZoneCfg), C.c_int, C.c_int, C.c_int, C.c_int, i64, C.POINTER(vp)]),
         "rtmodt_zones_destroy": (None, [vp]),
         "rtmodt_zones_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, i64, vp, vp, vp, vp, C.POINTER(i32)]),

@@ -293,6 +293,7 @@ struct rtmodt_deepsort {
     float4 *d_box = nullptr; float *d_conf = nullptr; int32_t *d_cls = nullptr, *d_n = nullptr, *h_n = nullptr;
     int8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_dotmax = nullptr;
     uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
+    rtmodt_reid *reid = nullptr;             // embedder = a .rtreid file: the network of reid.hip describes the boxes instead of the histogram
 };
 
 static const int64_t ds_init_meta[8] = {0, 0, 0, 0, 1, 0, 0, 0};
@@ -353,7 +354,9 @@ static int ds_create_impl(rtmodt_deepsort *t) {
 static int ds_run(rtmodt_deepsort *t, DsArgs a, int count, const AppFrames *frames, int fh, int fw, int pitch, hipStream_t q) {
     RT_HIP(hipEventRecord(t->ev[0], q));
     t->described = frames != nullptr;
-    if (frames) {
+    if (frames && t->reid) {
+        RT_TRY(reid_run(t->reid, *frames, count, fh, fw, pitch, a.det_box, a.det_n, a.det_stride, std::min(a.det_stride, t->Nc), t->d_desc, t->Nc, q));
+    } else if (frames) {
         DescribeArgs d{};
         d.frames = *frames; d.h = fh; d.w = fw; d.pitch = pitch;
         d.box = a.det_box; d.box_n = a.det_n; d.box_stride = a.det_stride; d.max_boxes = std::min(a.det_stride, t->Nc);
@@ -393,7 +396,7 @@ static int ds_check_sticky(rtmodt_deepsort *t, int s, int64_t err) {
 
 // frames of a call -> device pointers (host frames are staged on stream q)
 static int ds_frames(rtmodt_deepsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
-    RT_CHECK(t->dim == APP_DIM, RTMODT_E_INVALID, "this handle takes caller descriptors of dimension %d; the built-in descriptor has %d", t->dim, APP_DIM);
+    RT_CHECK(t->reid || t->dim == APP_DIM, RTMODT_E_INVALID, "this handle takes caller descriptors of dimension %d; the built-in descriptor has %d", t->dim, APP_DIM);
     RT_CHECK(fh >= 1 && fw >= 1 && fh <= 16384 && fw <= 16384 && pitch >= 3 * fw, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", fw, fh, pitch);
     RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
     for (int i = 0; i < count; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
@@ -427,6 +430,7 @@ void rtmodt_deepsort_destroy(rtmodt_deepsort *t) {
     hipFree(t->pool); hipFree(t->gallery); hipFree(t->d_states); hipFree(t->d_meta);
     hipFree(t->d_box); hipFree(t->d_conf); hipFree(t->d_cls); hipFree(t->d_n); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dotmax);
     hipFree(t->d_frames);
+    reid_close(t->reid);
     hipHostFree(t->h_meta); hipHostFree(t->h_n);
     if (t->stream) hipStreamDestroy(t->stream);
     delete t;
@@ -434,10 +438,13 @@ void rtmodt_deepsort_destroy(rtmodt_deepsort *t) {
 
 int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out) {
     RT_CHECK(cfg && out, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(!cfg->embedder || !*cfg->embedder || strcmp(cfg->embedder, "colorhist") == 0, RTMODT_E_UNSUPPORTED,
-             "embedder '%s': only the built-in \"colorhist\" descriptor is computed here; bring embeddings of another model as caller descriptors",
-             cfg->embedder);
-    const int dim = cfg->dim ? cfg->dim : APP_DIM;
+    const size_t elen = cfg->embedder ? strlen(cfg->embedder) : 0;
+    const bool net = elen > 7 && strcmp(cfg->embedder + elen - 7, ".rtreid") == 0;
+    RT_CHECK(net || !cfg->embedder || !*cfg->embedder || strcmp(cfg->embedder, "colorhist") == 0, RTMODT_E_UNSUPPORTED,
+             "embedder '%s': only the built-in \"colorhist\" descriptor and an OSNet x0.25 .rtreid file (tools/convert_weights.py --reid) are computed "
+             "here; bring embeddings of another model as caller descriptors", cfg->embedder);
+    RT_CHECK(!net || cfg->dim == 0 || cfg->dim == 512, RTMODT_E_INVALID, "descriptor dimension %d: the network's is 512 (or 0)", cfg->dim);
+    const int dim = net ? 512 : cfg->dim ? cfg->dim : APP_DIM;
     RT_CHECK(dim >= 64 && dim <= 512 && dim % 64 == 0, RTMODT_E_INVALID, "descriptor dimension %d: 64..512 in multiples of 64", dim);
     RT_CHECK(cfg->max_dist == cfg->max_dist && cfg->max_dist >= 0 && cfg->max_dist <= 2 && cfg->max_iou_distance == cfg->max_iou_distance &&
                  cfg->min_confidence == cfg->min_confidence && cfg->max_age >= 1 && cfg->n_init >= 1, RTMODT_E_INVALID,
@@ -452,7 +459,8 @@ int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out
     t->device = cfg->device; t->S = cfg->n_streams; t->Mc = cfg->max_tracks; t->Nc = cfg->max_dets; t->budget = cfg->nn_budget; t->dim = dim;
     t->min_conf = cfg->min_confidence; t->max_dist = cfg->max_dist; t->max_iou = cfg->max_iou_distance; t->max_age = cfg->max_age; t->n_init = cfg->n_init;
     t->thr = (long long)std::floor(cfg->max_dist * 16129.0);
-    const int rc = ds_create_impl(t);
+    int rc = net ? reid_open(cfg->embedder, cfg->device, cfg->n_streams, cfg->max_dets, false, &t->reid) : RTMODT_OK;     // the file is checked before the device is touched
+    if (rc == RTMODT_OK) rc = ds_create_impl(t);
     if (rc != RTMODT_OK) {
         std::string keep = last_error();
         rtmodt_deepsort_destroy(t);
@@ -488,6 +496,7 @@ int rtmodt_deepsort_update_batch(rtmodt_deepsort *t, const float *xyxy, const fl
     }
     RT_CHECK(!any || (xyxy && conf && cls), RTMODT_E_INVALID, "null detections");
     RT_CHECK(!(frames && desc), RTMODT_E_INVALID, "give frames or descriptors, not both");
+    RT_CHECK(!(t->reid && desc), RTMODT_E_INVALID, "this handle computes its descriptors with its embedder network: give frames, not descriptors");
     RT_CHECK(!any || frames || desc, RTMODT_E_INVALID, "detections need frames (built-in descriptor) or caller descriptors");
     RT_HIP(hipSetDevice(t->device));
     RT_TRY(ds_join(t));

@@ -279,6 +279,13 @@ struct DotmaxArgs {
 };
 int launch_dotmax(const DotmaxArgs &a, int grid_tracks, int grid_dets, int n_streams, hipStream_t s);
 
+// the re-identification network (reid.hip): an engine sized for max_frames x max_boxes crops.  reid_open checks the file before the
+// device is touched; reid_run queues every launch of one batch on q and leaves the int8 rows in desc[stream][desc_stride][512].
+int reid_open(const char *path, int device, int max_frames, int max_boxes, bool own_stream, rtmodt_reid **out);
+void reid_close(rtmodt_reid *e);
+int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, int pitch, const float4 *box, const int32_t *box_n, int box_stride,
+             int launch_mb, int8_t *desc, int desc_stride, hipStream_t q);
+
 // the tracker's device-resident state (tracker_api.hip), consumed by the zone engine (zones.hip):
 // states[n_streams], meta[n_streams][8] = {cur, n_tracks, err, n_active, next_id, ...}; `stream` is the HIP stream
 // the tracker's most recent update was launched on

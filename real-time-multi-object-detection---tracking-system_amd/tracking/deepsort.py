@@ -5,8 +5,9 @@ raises the same error, as the reference does; this class is the way in).
 The algorithm is the published one (Wojke et al.; deep_sort's tracker / linear_assignment / nn_matching / kalman_filter), with the
 state resident on the GPU behind ``rtmodt_deepsort_*`` (``include/rtmodt.h``, ``csrc/deepsort.hip``).  PARITY UNPINNED:
 ``deep_sort_realtime`` is not installed anywhere this runs.  The appearance descriptor is the colour histogram of the reference's
-design document (B.4), computed on the GPU from the frame; embeddings of a network that runs elsewhere come in through
-``embeddings=``.
+design document (B.4), computed on the GPU from the frame, or -- with ``embedder="<file>.rtreid"`` -- the OSNet x0.25 network the
+config's ``embedder`` names (``tracking.reid``, ``csrc/reid.hip``), also from the frame on the GPU; embeddings of a network that
+runs elsewhere come in through ``embeddings=``.
 """
 from __future__ import annotations
 
@@ -16,9 +17,14 @@ from collections import defaultdict
 import numpy as np
 
 from .. import _ffi
+from ..reid_weights import FEAT_DIM, SUFFIX
+from .reid import check_weights_path
 from .tracker import Track
 
 TENTATIVE, CONFIRMED = 1, 2
+DEFAULT_MAX_DETS = 1024
+#: with an embedder network every detection slot holds the crop's 13 tap tensors and scratch: 2.9 MB of device memory
+DEFAULT_MAX_DETS_NETWORK = 128
 BUILTIN_EMBEDDER = "colorhist"
 BUILTIN_DIM = 192
 
@@ -38,7 +44,7 @@ class _DeepSortCore:
     def __init__(self, max_dist=0.2, min_confidence=0.3, max_iou_distance=0.7, max_age=70, n_init=3, nn_budget=100, embedder=BUILTIN_EMBEDDER, *,
                  dim: int = 0, device=0, max_tracks: int = 256, max_dets: int = 1024, n_streams: int = 1) -> None:
         self.max_tracks, self.max_dets, self.n_streams, self.nn_budget = int(max_tracks), int(max_dets), int(n_streams), int(nn_budget)
-        self.dim = int(dim) or BUILTIN_DIM
+        self.dim = int(dim) or (FEAT_DIM if embedder is not None and str(embedder).endswith(SUFFIX) else BUILTIN_DIM)
         self._device = _ffi.device_ordinal(device)
         emb = None if embedder is None else str(embedder).encode()
         cfg = _ffi.DeepSortCfg(float(max_dist), float(min_confidence), float(max_iou_distance), int(max_age), int(n_init), int(nn_budget), emb,
@@ -140,21 +146,34 @@ class _DeepSortCore:
 
 class DeepSortTracker:
     """``update(detections, frame=...) -> list[Track]``: the confirmed tracks matched in this frame (deep_sort's
-    ``is_confirmed() and time_since_update == 0``), ``xyxy`` = the posterior mean box, trails as ``MultiObjectTracker`` keeps them."""
+    ``is_confirmed() and time_since_update == 0``), ``xyxy`` = the posterior mean box, trails as ``MultiObjectTracker`` keeps them.
+
+    ``max_dets`` (detections per frame the handle is sized for) defaults to 1024 with the built-in descriptor or caller descriptors,
+    and to 128 with an embedder network: the network keeps 2.9 MB of device memory per detection slot (128 slots = 0.37 GB; 1024
+    would be 3 GB for one stream).  A detector feeding ``update_from_detector`` must have ``max_det <= max_dets``."""
 
     #: ``pipeline.run`` hands the frame to a tracker that asks for it
     needs_frame = True
 
     def __init__(self, max_dist: float = 0.2, min_confidence: float = 0.3, max_iou_distance: float = 0.7, max_age: int = 70, n_init: int = 3,
                  nn_budget: int = 100, embedder: str = BUILTIN_EMBEDDER, *, embedding_dim: int = 0, device=0, max_tracks: int = 256,
-                 max_dets: int = 1024) -> None:
-        if embedder not in (None, "", BUILTIN_EMBEDDER):
+                 max_dets: int | None = None) -> None:
+        if embedder in (None, ""):
+            embedder = BUILTIN_EMBEDDER
+        if str(embedder).endswith(SUFFIX):
+            embedder = check_weights_path(embedder)             # FileNotFoundError, as the detector words it
+            if embedding_dim not in (0, FEAT_DIM):
+                raise ValueError(f"embedding_dim {embedding_dim}: the network's descriptor has {FEAT_DIM} values")
+        elif embedder != BUILTIN_EMBEDDER:
             raise NotImplementedError(
                 f"embedder {embedder!r}: no embedding network runs here, only the built-in {BUILTIN_EMBEDDER!r} descriptor. Run the model "
-                "yourself and pass its output per detection as update(..., embeddings=) on a tracker built with embedding_dim=<its dimension>")
+                "yourself and pass its output per detection as update(..., embeddings=) on a tracker built with embedding_dim=<its dimension>. "
+                f"An OSNet x0.25 checkpoint converted with tools/convert_weights.py --reid (a {SUFFIX} file) does run here.")
+        if max_dets is None:
+            max_dets = DEFAULT_MAX_DETS_NETWORK if embedder != BUILTIN_EMBEDDER else DEFAULT_MAX_DETS
         self.algorithm = "deepsort"
-        self.embedder = BUILTIN_EMBEDDER
-        self._core = _DeepSortCore(max_dist, min_confidence, max_iou_distance, max_age, n_init, nn_budget, BUILTIN_EMBEDDER, dim=embedding_dim,
+        self.embedder = embedder
+        self._core = _DeepSortCore(max_dist, min_confidence, max_iou_distance, max_age, n_init, nn_budget, embedder, dim=embedding_dim,
                                    device=device, max_tracks=max_tracks, max_dets=max_dets)
         self._trail_map = defaultdict(list)
         self._trail_maxlen = 30
@@ -162,7 +181,8 @@ class DeepSortTracker:
     @classmethod
     def from_config(cls, tracking_cfg: dict, **extra) -> "DeepSortTracker":
         """``cfg["tracking"]`` of the reference's YAML (config/default.yaml:46-60): reads its ``deepsort:`` block.  The block's
-        ``embedder`` names a model file no machine has; it is refused as in the constructor unless ``embedder=`` overrides it."""
+        ``embedder`` names an ``.onnx`` file, which is not read; it is refused as in the constructor unless ``embedder=`` overrides it
+        (``"colorhist"``, or the ``.rtreid`` conversion of that model)."""
         p = dict(tracking_cfg.get("deepsort", {}))
         p.update(extra)
         known = ("max_dist", "min_confidence", "max_iou_distance", "max_age", "n_init", "nn_budget", "embedder", "embedding_dim", "device",
@@ -173,6 +193,8 @@ class DeepSortTracker:
         n = len(detections.confidence)
         if n and (frame is None) == (embeddings is None):
             raise ValueError("update() needs exactly one of frame= (built-in descriptor) or embeddings= (one row per detection)")
+        if embeddings is not None and self.embedder != BUILTIN_EMBEDDER:
+            raise ValueError("this tracker computes its descriptors with its embedder network: give frame=, not embeddings=")
         if embeddings is not None:
             embeddings = np.asarray(embeddings)
             if embeddings.dtype != np.int8:

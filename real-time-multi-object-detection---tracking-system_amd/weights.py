@@ -207,12 +207,13 @@ def load(path: str):
     return out, scale, nc, reg_max
 
 
-def fold_bn(conv_w_oihw: np.ndarray, gamma, beta, mean, var, eps: float = 1e-3):
-    """Conv(bias=False)+BatchNorm2d(eps=1e-3) -> conv+bias; returns ``(w[cout,kh,kw,cin], b)``."""
+def fold_bn(conv_w_oihw: np.ndarray, gamma, beta, mean, var, eps: float = 1e-3, dtype=np.float32):
+    """Conv(bias=False)+BatchNorm2d(eps=1e-3) -> conv+bias; returns ``(w[cout,kh,kw,cin], b)``, folded in float64 and cast once
+    to ``dtype``."""
     s = np.asarray(gamma, np.float64) / np.sqrt(np.asarray(var, np.float64) + eps)
     w = np.asarray(conv_w_oihw, np.float64) * s[:, None, None, None]
     b = np.asarray(beta, np.float64) - np.asarray(mean, np.float64) * s
-    return np.ascontiguousarray(w.transpose(0, 2, 3, 1)).astype(np.float32), b.astype(np.float32)
+    return np.ascontiguousarray(w.transpose(0, 2, 3, 1)).astype(dtype), b.astype(dtype)
 
 
 def from_state_dict(sd: dict, scale: str = "s", nc: int = 80, reg_max: int = 16) -> dict:
