@@ -391,6 +391,90 @@ int rtmodt_zones_process_tracker(rtmodt_zones *z, rtmodt_tracker *trk, double no
 int rtmodt_zones_state(rtmodt_zones *z, int stream, int64_t *ids, uint32_t *occ_mask, double *first_seen,
                        double *last_alert, int32_t *n);
 
+/* ---- crossing counter: directional line and gate counts on device-resident tracks ----------- */
+/* Completes what config/default.yaml:73-77 offers (`exit_gate`: trigger "crossing", direction "left_to_right") and the
+ * reference never implements: zone_engine.py:150 parses `direction` and nothing reads it, so its "crossing" zone is an intrusion
+ * zone under another name.  csrc/crossing.hip, one launch per frame for all streams; tests/crossing_ref.py states the rules and the
+ * kernel equals it exactly ("Crossing counter").  PARITY UNPINNED against any third-party counter.
+ * Centroid = the zone engine's (int((x1+x2)/2), int((y1+y2)/2) in float32), clamped to [-2^20, 2^20]; a track whose box has a
+ * non-finite coordinate is not passed that frame.  Line endpoints and gate vertices outside that range are RTMODT_E_INVALID. */
+#define RTMODT_LINE_BOTH 0
+#define RTMODT_LINE_POS 1   /* the crossing ends on the side where (B - A) x (P - A) > 0 */
+#define RTMODT_LINE_NEG 2
+#define RTMODT_GATE_ANY 0   /* no direction: every exit fires */
+#define RTMODT_GATE_LEFT_TO_RIGHT 1
+#define RTMODT_GATE_RIGHT_TO_LEFT 2
+#define RTMODT_GATE_TOP_TO_BOTTOM 3
+#define RTMODT_GATE_BOTTOM_TO_TOP 4
+#define RTMODT_CROSSING_LINE 0
+#define RTMODT_CROSSING_GATE 1
+typedef struct rtmodt_crossing rtmodt_crossing;
+/* A tripwire: the directed segment A -> B.  A passed track with centroid P crosses it when P is off the infinite line, the last
+ * non-zero side stored for the track differs from P's, and the path from the previous passed centroid to P meets the closed
+ * segment.  `direction` selects which crossings are counted and reported (RTMODT_LINE_*). */
+typedef struct rtmodt_line_cfg {
+    int32_t ax, ay, bx, by;
+    int32_t direction;
+} rtmodt_line_cfg;
+/* A gate: a polygon (the zone engine's inside-or-on test) and an optional direction (RTMODT_GATE_*): the zone of default.yaml:73-77.
+ * It fires when a track leaves it and the displacement from the centroid it entered at agrees with the direction (dominant axis,
+ * ties included: left_to_right is dx > 0 and dx >= |dy|). */
+typedef struct rtmodt_gate_cfg {
+    const int32_t *polygon_xy;  /* n_points x (x, y) */
+    int32_t n_points;
+    int32_t direction;
+} rtmodt_gate_cfg;
+/* One crossing.  `track`: index into the caller's list (rtmodt_crossing_process) or into the tracker's list.  `direction`:
+ * RTMODT_LINE_POS / _NEG for a line, the gate's own direction for a gate.  `prev`: the previous passed centroid (line) or the entry
+ * centroid (gate); `frames`: frame_id minus the frame of that point. */
+typedef struct rtmodt_crossing_event {
+    int64_t track_id;
+    int64_t frames;
+    float xyxy[4];
+    int32_t centroid[2];
+    int32_t prev[2];
+    int32_t track, kind, index, direction, cls, reserved;
+} rtmodt_crossing_event;
+/* n_streams independent ledgers and count sets; at most 32 lines, 32 gates, 2048 gate vertices, n_classes in 1..256 (a crossing
+ * whose class id lies outside [0, n_classes) enters the totals only).  A ledger row (per track id: last passed frame, previous
+ * centroid, last non-zero side per line, inside bit + entry centroid and frame per gate) is dropped once frame_id - (the frame it
+ * was last passed at) > max_gap_frames; the id then starts fresh and causes no crossing on the frame it returns.  Within the gap the
+ * row is kept as it is.  A ledger holds 2 x max_tracks rows: the frame that needs more returns RTMODT_E_CAPACITY, the idle rows are
+ * dropped to make room, and the stream stays in error for good (every later _process*, and _state, of that stream returns
+ * RTMODT_E_CAPACITY; the counts remain readable, and passed tracks that cross keep entering them).  Destroy the handle and create a larger
+ * one.  Track ids are taken to name one object for the handle's lifetime: after rtmodt_tracker_reset / rtmodt_deepsort_reset, or with a new
+ * tracker handle, ids start again at 1, so create a new counter with it (rows kept within the gap would be taken for the new tracks). */
+int rtmodt_crossing_create(int device, const rtmodt_line_cfg *lines, int n_lines, const rtmodt_gate_cfg *gates, int n_gates,
+                           int n_classes, int n_streams, int max_tracks, int max_events, int64_t max_gap_frames,
+                           rtmodt_crossing **out);
+/* Waits for the work queued on the handle's own stream, then frees the ledgers, the counts and the handle; null is allowed. */
+void rtmodt_crossing_destroy(rtmodt_crossing *c);
+/* One stream, a caller-supplied track list (any order, unique ids, at most max_tracks); every listed track is passed.  Events come
+ * back in (list order, lines in order, gates in order); `events` holds max_events records.  A frame with more events returns
+ * RTMODT_E_CAPACITY with the first max_events of them delivered and the counts complete; the stream goes on working. */
+int rtmodt_crossing_process(rtmodt_crossing *c, int stream, const int64_t *track_ids, const float *xyxy, const int32_t *cls,
+                            int n, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events);
+/* default.yaml:73-77 on every stream of a ByteTrack handle at once, straight on its device-resident state and on the HIP stream its
+ * last update ran on.  Passed = time_since_update == report_tsu (1 = matched or spawned this frame, as rtmodt_zones_process_tracker).
+ * events is [n_streams][max_events], n_events[n_streams]. */
+int rtmodt_crossing_process_tracker(rtmodt_crossing *c, rtmodt_tracker *trk, int64_t frame_id, int report_tsu,
+                                    rtmodt_crossing_event *events, int32_t *n_events);
+/* The same on a DeepSORT handle (zone_engine.py:150 never reached any tracker's state): passed = confirmed and
+ * time_since_update == report_tsu (0 = matched this frame); the box is the matched detection's (rtmodt_deepsort_state: xyxy). */
+int rtmodt_crossing_process_deepsort(rtmodt_crossing *c, rtmodt_deepsort *ds, int64_t frame_id, int report_tsu,
+                                     rtmodt_crossing_event *events, int32_t *n_events);
+/* One stream's counts since creation or the last reset (default.yaml:73-77): line_total [n_lines][2] (pos, neg),
+ * line_class [n_lines][2][n_classes], gate_total [n_gates], gate_class [n_gates][n_classes]; any pointer may be null. */
+int rtmodt_crossing_counts(rtmodt_crossing *c, int stream, int64_t *line_total, int64_t *line_class, int64_t *gate_total,
+                           int64_t *gate_class);
+/* Zeroes the counts of every stream; the ledgers stay (a track halfway through a gate still fires on exit). */
+int rtmodt_crossing_reset_counts(rtmodt_crossing *c);
+/* Ledger snapshot of one stream, rows in ascending track id (the parity surface of tests/crossing_ref.py): side_pos / side_neg bit l
+ * <=> the side stored for line l is +1 / -1; inside bit g <=> the track is in gate g, and then entry_xy[row][g] / entry_frame[row][g]
+ * hold where and when it entered (other cells are unspecified).  Arrays sized 2 x max_tracks rows. */
+int rtmodt_crossing_state(rtmodt_crossing *c, int stream, int64_t *ids, int64_t *last_frame, int32_t *prev_xy, uint32_t *side_pos,
+                          uint32_t *side_neg, uint32_t *inside, int32_t *entry_xy, int64_t *entry_frame, int32_t *n);
+
 /* ---- frame renderer: replaces FrameRenderer.render (src/visualization/renderer.py) ---------- */
 /* Annotates BGR24 frames in place, one launch per batch (csrc/render.hip, whose header comment states the paint rules; they
  * restate cv2's drawing calls -- PARITY UNPINNED: no OpenCV to run against).  Per frame, in this order: zone tint (the

@@ -18,7 +18,8 @@ library being built):
 * ``synth``              -- deterministic synthetic frames / box sequences
 * ``streams``            -- stream sharding across GPUs + barrier / max-time / stats reduce (RCCL or gloo)
 * ``profiling``          -- ``LatencyProfiler`` (reference: src/profiling/latency_profiler.py:35-143)
-* ``events``             -- ``ZoneEventEngine`` on device-resident tracks (reference: src/events/zone_engine.py:64-157)
+* ``events``             -- ``ZoneEventEngine`` on device-resident tracks (reference: src/events/zone_engine.py:64-157);
+                            ``CrossingCounter``: directional line / gate counts (what config/default.yaml:73-77 promises)
 * ``pipeline``           -- the reference's per-frame loop (tools/run_pipeline.py:121-158) around the native classes
 * ``visualization``      -- ``FrameRenderer``: boxes, labels, trails, zones and HUD drawn into frames on the GPU
                             (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
@@ -39,6 +40,7 @@ _LAZY = {
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",
     "ZoneEventEngine": ".events.zone_engine",
+    "CrossingCounter": ".events.crossing",
     "FrameReader": ".ingestion.reader",
     "RTSPReader": ".ingestion.reader",
     "FrameRenderer": ".visualization.renderer",

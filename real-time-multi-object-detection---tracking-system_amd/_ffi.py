@@ -105,6 +105,20 @@ class ZoneCfg(C.Structure):                          # struct rtmodt_zone_cfg
                 ("cooldown_sec", C.c_double), ("key", C.c_int32)]
 
 
+class LineCfg(C.Structure):                          # struct rtmodt_line_cfg
+    _fields_ = [("ax", C.c_int32), ("ay", C.c_int32), ("bx", C.c_int32), ("by", C.c_int32), ("direction", C.c_int32)]
+
+
+class GateCfg(C.Structure):                          # struct rtmodt_gate_cfg
+    _fields_ = [("polygon_xy", C.POINTER(C.c_int32)), ("n_points", C.c_int32), ("direction", C.c_int32)]
+
+
+class CrossingEventRec(C.Structure):                 # struct rtmodt_crossing_event
+    _fields_ = [("track_id", C.c_int64), ("frames", C.c_int64), ("xyxy", C.c_float * 4), ("centroid", C.c_int32 * 2), ("prev", C.c_int32 * 2),
+                ("track", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("direction", C.c_int32), ("cls", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class RenderCfg(C.Structure):                        # struct rtmodt_render_cfg
     _fields_ = [("show_boxes", C.c_int32), ("show_ids", C.c_int32), ("show_trails", C.c_int32), ("show_zones", C.c_int32),
                 ("show_fps", C.c_int32), ("trail_length", C.c_int32), ("palette_bgr", C.POINTER(C.c_uint8)), ("n_palette", C.c_int32)]
@@ -230,6 +244,15 @@ def lib() -> C.CDLL:
         "rtmodt_zones_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, C.c_double, i64, vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_zones_process_tracker": (C.c_int, [vp, vp, C.c_double, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
         "rtmodt_zones_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_crossing_create": (C.c_int, [C.c_int, C.POINTER(LineCfg), C.c_int, C.POINTER(GateCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             i64, C.POINTER(vp)]),
+        "rtmodt_crossing_destroy": (None, [vp]),
+        "rtmodt_crossing_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, i64, vp, C.POINTER(i32)]),
+        "rtmodt_crossing_process_tracker": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
+        "rtmodt_crossing_process_deepsort": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
+        "rtmodt_crossing_counts": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "rtmodt_crossing_reset_counts": (C.c_int, [vp]),
+        "rtmodt_crossing_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -307,6 +307,14 @@ static int ds_join(rtmodt_deepsort *t) {
     return RTMODT_OK;
 }
 
+namespace rtmodt {
+int deepsort_device_view(rtmodt_deepsort *t, DsDeviceView *out) {
+    RT_CHECK(t && out, RTMODT_E_INVALID, "null argument");
+    *out = DsDeviceView{t->d_states, t->d_meta, t->S, t->Mc, t->device, t->stream};
+    return ds_join(t);                                     // the caller's work on t->stream is ordered behind every update
+}
+}  // namespace rtmodt
+
 static int ds_create_impl(rtmodt_deepsort *t) {
     RT_HIP(hipSetDevice(t->device));
     RT_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));

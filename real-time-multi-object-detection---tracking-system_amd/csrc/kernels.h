@@ -291,6 +291,9 @@ int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, i
 // the tracker's most recent update was launched on
 struct TrackerDeviceView { const TrackerState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
 int tracker_device_view(rtmodt_tracker *trk, TrackerDeviceView *out);
+// the same of the DeepSORT tracker (deepsort.hip), consumed by the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, ...}
+struct DsDeviceView { const DsState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+int deepsort_device_view(rtmodt_deepsort *ds, DsDeviceView *out);
 
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };

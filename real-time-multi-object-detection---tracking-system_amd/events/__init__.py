@@ -1,3 +1,4 @@
+from .crossing import CrossingCounter, CrossingEvent
 from .zone_engine import Zone, ZoneEvent, ZoneEventEngine
 
-__all__ = ["ZoneEventEngine", "ZoneEvent", "Zone"]
+__all__ = ["ZoneEventEngine", "ZoneEvent", "Zone", "CrossingCounter", "CrossingEvent"]

@@ -64,7 +64,8 @@ class PinnedFrameRing:
 
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
-        device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None) -> dict:
+        device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
+        crossing_counter=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -79,10 +80,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
 
     ``recorder``: ``recorder.write(frame)`` is called with the (annotated) frame after ``profiler.end_frame()``, where the
     reference calls ``video_writer.write(annotated)`` (tools/run_pipeline.py:160-161) -- outside every profiler stage.  A
-    ``visualization.MjpegRecorder`` encodes it on the GPU and appends it to an AVI."""
+    ``visualization.MjpegRecorder`` encodes it on the GPU and appends it to an AVI.
+
+    ``crossing_counter``: an ``events.CrossingCounter``, called where the event engine is called, inside a ``crossings`` stage: on
+    the tracker's device-resident state when the track list was not materialised (ByteTrack and DeepSORT alike), else on the list.
+    The summary then carries ``crossings``, the number of crossing events of stream 0."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
-    n_events = 0
+    n_events = n_crossings = 0
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
@@ -106,6 +111,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         needs_frame = bool(getattr(tracker, "needs_frame", False))
         events_on_device = (handoff and not needs_frame and renderer is None and event_engine is not None
                             and hasattr(event_engine, "process_tracker"))
+        # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
+        crossings_on_device = events_on_device
+        if crossing_counter is not None and event_engine is None and renderer is None and handoff:
+            events_on_device = crossings_on_device = True
         profiler.tick("tracking")
         if needs_frame:                                    # a tracker that describes its detections on the frame (DeepSortTracker)
             tracks = tracker.update_from_detector(detector, frame=frame, materialize=not events_on_device) if handoff else tracker.update(detections, frame=frame)
@@ -119,6 +128,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_events += len(event_engine.process(tracks, fid))
             profiler.tock("events")
+        if crossing_counter is not None:
+            profiler.tick("crossings")
+            if crossings_on_device:
+                n_crossings += len(crossing_counter.process_tracker(tracker, fid, class_names=getattr(detector.model, "names", None))[0])
+            else:
+                n_crossings += len(crossing_counter.process(tracks, fid))
+            profiler.tock("crossings")
         if renderer is not None:                           # tools/run_pipeline.py:149-156
             profiler.tick("visualization")
             zones = event_engine.get_zone_polygons() if event_engine is not None else None
@@ -136,4 +152,6 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     else:
         out["last_tracks"] = 0 if tracks is None else len(tracks)
     out["events"] = n_events
+    if crossing_counter is not None:
+        out["crossings"] = n_crossings
     return out
