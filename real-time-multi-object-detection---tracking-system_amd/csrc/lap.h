@@ -17,6 +17,8 @@
 
 namespace rtmodt {
 
+// Capacities of the arrays below, inclusive: a problem of <= 256 rows, <= 256 columns and <= 2048 edges is solved; the callers
+// that compact into them (assoc_sparse in track_dev.h, mot_accumulate in eval.hip) refuse one more of any with a capacity error.
 constexpr int LAP_ROWS = 256, LAP_COLS = 256, LAP_EDGES = 2048;
 
 struct LexCost {

@@ -481,3 +481,26 @@ def embedded_inputs(name):
     params, dim, factory = EMBEDDED[name]
     scene, _, _ = factory()
     return params, dim, [(x, xy, cf, cl, ids) for xy, cf, cl, ids, x in scene]
+
+
+def pair_limit_frames(extra: bool, seed=2048):
+    """Two frames that put the IoU stage at the contested-pair limit of csrc/lap.h: frame 1 has 32 detections (33 with ``extra``)
+    that become tentative tracks, frame 2 has 64 detections.  Every box is the 40 x 40 box at (10, 10) moved by less than 1 px,
+    except the last detection of frame 2, 16 px to the right (IoU 0.35 or more with the 32 tracks: admissible, IoU >= 0.3), so all
+    32 x 64 = 2048 pairs are admissible and none is isolated.  The extra track sits 32 px to the right: admissible with that last
+    detection alone (IoU 0.37 or more; 0.15 or less with the others), the 2049th pair.  Caller descriptors (no track is confirmed:
+    the appearance cascade has no rows).  Returns (tracker parameters, [(xyxy, conf, cls, int8 descriptors) per frame])."""
+    rng = np.random.default_rng(seed)
+
+    def boxes(n, dx=0.0):
+        j = rng.uniform(-1, 1, (n, 2)) + np.asarray([dx, 0.0])
+        return np.concatenate([10 + j, 50 + j], axis=1).astype(F32)
+
+    f1 = boxes(32)
+    if extra:
+        f1 = np.concatenate([f1, boxes(1, 32.0)])
+    f2 = np.concatenate([boxes(63), boxes(1, 16.0)])
+    out = []
+    for b in (f1, f2):
+        out.append((b, np.full(len(b), 0.9, F32), np.zeros(len(b), np.int32), rng.integers(-127, 128, (len(b), DIM)).astype(np.int8)))
+    return dict(max_age=3, n_init=3, nn_budget=4), out

@@ -238,9 +238,10 @@ def box_iou(a, b):
     return 0.0 if i == 0 else i / u
 
 
-def mot_ref(gt, hyp, assign=assign_lex):
+def mot_ref(gt, hyp, assign=assign_lex, weight=max_weight):
     """``(n, 6)`` rows ``frame, id, x, y, w, h`` (0-based boxes) -> dict of counts (+ ``dist_sum``, ``events``: per
-    frame the list of (kind, oid, hid))."""
+    frame the list of (kind, oid, hid)).  ``assign`` / ``weight``: the per-frame assignment and the IDTP matching; crowded
+    frames pass faster equivalents (tests/test_gpu_eval_lap.py), the pure-Python ones being cubic in rows + columns."""
     gt = np.asarray(gt, np.float64).reshape(-1, 6)
     hyp = np.asarray(hyp, np.float64).reshape(-1, 6)
     frames = np.union1d(gt[:, 0], hyp[:, 0])
@@ -313,7 +314,7 @@ def mot_ref(gt, hyp, assign=assign_lex):
     W = np.zeros((len(go), len(ho)), np.int64)
     for (o, h), n in n_oh.items():
         W[go.index(o), ho.index(h)] = n
-    c["idtp"] = max_weight(W)
+    c["idtp"] = weight(W)
     c["idfp"] = c["num_predictions"] - c["idtp"]
     c["idfn"] = c["num_objects"] - c["idtp"]
     c["dist_sum"] = dist_sum

@@ -90,6 +90,36 @@ def test_matching_equals_scipy_and_every_optimum_is_unique(name):
     assert not_unique == 0
 
 
+def test_pair_limit_frame_has_2048_pairs_equals_scipy_and_its_optimum_is_unique():
+    """The IoU-stage frame of the GPU suite that sits exactly at lap.h's 2048 contested pairs (deepsort_ref.pair_limit_frames):
+    32 tentative tracks x 64 detections, every pair admissible; the restatement's matching equals scipy's run the way
+    min_cost_matching runs it, and forbidding any matched pair makes scipy's best total rise, so the optimum is unique.  With
+    the extra track there are 2049 admissible pairs, the extra row's only one in a contested column."""
+    from scipy.optimize import linear_sum_assignment
+    for extra in (False, True):
+        params, frames = R.pair_limit_frames(extra)
+        record = []
+        trk = R.DeepSortRef(record=record, **params)
+        for xy, cf, cl, desc in frames:
+            trk.update(xy, cf, cl, desc)
+        assert [r["kind"] for r in record] == ["iou"]
+        gain, cost, pairs = record[0]["gain"], record[0]["cost"], record[0]["pairs"]
+        adm = np.asarray([[g is not None for g in row] for row in gain])
+        assert adm.shape == (32 + extra, 64) and int(adm.sum()) == 2048 + extra and adm[:32].all()
+        if extra:
+            assert adm[32].tolist() == [False] * 63 + [True]
+        maxd = trk.max_iou_distance
+        dense = np.where(adm, cost, maxd + 1e-5)
+        rr, cc = linear_sum_assignment(dense)
+        assert sorted((int(r), int(c)) for r, c in zip(rr, cc) if dense[r, c] <= maxd) == pairs and len(pairs) == 32 + extra
+        best = dense[rr, cc].sum()
+        for r, c in pairs:                                     # gain = limit - cost and every optimum matches all rows: least cost = most gain
+            d = dense.copy()
+            d[r, c] = 10.0
+            r2, c2 = linear_sum_assignment(d)
+            assert d[r2, c2].sum() > best + 1e-9, (r, c)
+
+
 def test_descriptor_equals_per_pixel_loop_and_quantiser_properties():
     rng = np.random.default_rng(5)
     frame = rng.integers(0, 256, (37, 53, 3), dtype=np.uint8)

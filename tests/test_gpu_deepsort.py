@@ -287,6 +287,32 @@ def test_limits_and_bad_arguments_return_codes(pkg):
     del keep
 
 
+def test_iou_stage_at_the_contested_pair_limit(pkg):
+    """32 tentative tracks against 64 detections that all overlap them: exactly 2048 admissible pairs, none isolated -- the most
+    lap.h's edge array holds -- and the state equals the restatement bit for bit (tests/test_deepsort_cpu.py shows that frame's
+    optimum unique and equal to scipy's).  One more track with a single pair into a contested column, 2049, is refused."""
+    ffi = pkg._ffi
+    params, frames = R.pair_limit_frames(False)
+    core = core_cls(pkg)(n_streams=1, max_tracks=128, max_dets=64, **params)
+    ref = R.DeepSortRef(**params)
+    for f, (xy, cf, cl, desc) in enumerate(frames):
+        ref.update(xy, cf, cl, desc)
+        core.update(xy, cf, cl, embeddings=desc)
+        assert R.snapshots_equal(core.snapshot(0), ref.snapshot()) is None, (f, R.snapshots_equal(core.snapshot(0), ref.snapshot()))
+    assert len(ref.ids) == 64 and sum(h == 2 for h in ref.hits) == 32      # all 32 tracks matched, 32 detections left over
+    core.reset()
+    params, frames = R.pair_limit_frames(True)
+    core.update(*frames[0][:3], embeddings=frames[0][3])
+    assert len(core.snapshot(0)["ids"]) == 33
+    with pytest.raises(ffi.RtmodtError) as e:
+        core.update(*frames[1][:3], embeddings=frames[1][3])
+    assert e.value.code == ffi.E_CAPACITY and "contested" in e.value.msg
+    core.reset()                                               # the handle answers again
+    xy, cf, cl, desc = frames[0]
+    assert core.update(xy[:3], cf[:3], cl[:3], embeddings=desc[:3]) == 0 and len(core.snapshot(0)["ids"]) == 3
+    core.close()
+
+
 # -------------------------------------------------------------------------------------------------------------- facade
 def test_facade_is_switch_free_on_the_rendered_crossing_scene(pkg):
     """DeepSortTracker.update on the rendered frames of the CPU behaviour test, descriptors computed on the GPU: the tracks it
