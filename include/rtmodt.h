@@ -592,6 +592,53 @@ int rtmodt_mot_eval(int device, int n_seq, const int32_t *seq_frame_start, const
                     const int32_t *hyp_start, const int32_t *gt_oid, const double *gt_box, const int32_t *hyp_hid, const double *hyp_box,
                     const int32_t *seq_n_oid, const int32_t *seq_n_hid, rtmodt_mot_counts *out);
 
+/* ---- detection error analysis: what the detector gets wrong ---------------------------------------------------- */
+/* TECHNICAL_DESIGN_DOCUMENT.md D.5 defines five error types (localization, classification, duplicate, background false
+ * positive, missed) to be clustered by image region and object size, D.4 asks for the per-class breakdown and D.6 step 4
+ * plots a confusion matrix from a GT and a predictions file; the reference implements only build_confusion_matrix
+ * (src/evaluation/metrics.py:110-123) on label pairs that nothing produces.  csrc/errors.hip, one launch for all images;
+ * the rules are INTEGRATION.md section 14 and tests/errors_ref.py restates them in NumPy.  PARITY UNPINNED: neither tidecv
+ * nor ultralytics is installed anywhere this runs. */
+#define RTMODT_ERR_TP 0             /* detection types 0..5 are also the histogram columns 0..5 */
+#define RTMODT_ERR_LOCALIZATION 1
+#define RTMODT_ERR_CLASSIFICATION 2
+#define RTMODT_ERR_BOTH 3
+#define RTMODT_ERR_DUPLICATE 4
+#define RTMODT_ERR_BACKGROUND 5
+#define RTMODT_ERR_MISSED 6         /* histogram column 6: MISSED_COVERED + MISSED ground truths */
+#define RTMODT_ERR_IGNORED 6        /* detection type: matched to a crowd GT; counted nowhere */
+#define RTMODT_ERR_NOT_EVALUATED 7  /* detection type: below conf_thr or behind the max_det cut; counted nowhere */
+#define RTMODT_GT_CROWD 0
+#define RTMODT_GT_MATCHED 1
+#define RTMODT_GT_MISSED_COVERED 2  /* unmatched, but a LOCALIZATION / CLASSIFICATION detection points at it */
+#define RTMODT_GT_MISSED 3
+typedef struct rtmodt_error_params {
+    double conf_thr;        /* detections with score >= conf_thr are ranked by (-score, file index)        (0.25) */
+    double iou_fg, iou_bg;  /* foreground / background IoU, iou_bg <= iou_fg                           (0.5, 0.1) */
+    double cm_iou;          /* IoU of the class-agnostic matching behind the confusion matrix              (0.45) */
+    int32_t max_det;        /* kept detections per image, 1..1024                                           (100) */
+    int32_t grid_x, grid_y; /* by_cell columns and rows, 1..64 each                                        (8, 8) */
+    int32_t reserved;       /* 0 */
+} rtmodt_error_params;
+/* Images are CSR slices: gt_start / dt_start[n_img + 1] into the GT / detection rows, each image's rows in file order;
+ * gt_cat / dt_cat are dense category indices 0..K-1; boxes are x, y, w, h, float64; img_wh[n_img][2] is every image's
+ * width and height (> 0).  Every IoU threshold is used as min(t, 1 - 1e-10) and compared with >=.  Outputs (host): per
+ * detection row dt_type (RTMODT_ERR_*) and dt_gt (the GT row that decided the type, -1 none); per GT row gt_state
+ * (RTMODT_GT_*) and gt_dt (the detection row matched to it, -1 none); int64 histograms by_class[K][7], by_size[3][7]
+ * (area < 32^2, < 96^2, the rest; a detection's area is w * h, a GT's its `area` field), by_cell[grid_y][grid_x][7] (the
+ * cell of the box centre in the image's own frame), missed_uncovered[K], the confusion matrix cm[K + 1][K + 1] (rows
+ * ground truth, columns prediction, index K background) and cm_dropped[K] (free detections on a crowd GT of their class).
+ * Every argument check runs before the first HIP call: RTMODT_E_INVALID for a null pointer, a NaN threshold, score, area
+ * or a non-finite box, iou_bg > iou_fg, max_det or grid out of range, a non-positive image size, a category index outside
+ * 0..K-1; RTMODT_E_CAPACITY for an image with more than 1024 GTs or 4096 detections (the message names the image), with
+ * nothing launched.  Device scratch is allocated and freed inside the call. */
+int rtmodt_detection_errors(int device, const rtmodt_error_params *params, int K, int n_img, const double *img_wh,
+                            const int32_t *gt_start, const int32_t *gt_cat, const double *gt_box, const double *gt_area,
+                            const int32_t *gt_crowd, const int32_t *dt_start, const int32_t *dt_cat, const double *dt_box,
+                            const double *dt_score, int32_t *dt_type, int32_t *dt_gt, int32_t *gt_state, int32_t *gt_dt,
+                            int64_t *by_class, int64_t *by_size, int64_t *by_cell, int64_t *missed_uncovered, int64_t *cm,
+                            int64_t *cm_dropped);
+
 #ifdef __cplusplus
 }
 #endif

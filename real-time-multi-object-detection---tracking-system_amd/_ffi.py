@@ -153,6 +153,11 @@ class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
                                          "idfn")] + [("dist_sum", C.c_double)]
 
 
+class ErrorParams(C.Structure):                      # struct rtmodt_error_params
+    _fields_ = [("conf_thr", C.c_double), ("iou_fg", C.c_double), ("iou_bg", C.c_double), ("cm_iou", C.c_double), ("max_det", C.c_int32),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("reserved", C.c_int32)]
+
+
 _lib = None
 
 
@@ -269,6 +274,7 @@ def lib() -> C.CDLL:
         "rtmodt_coco_eval": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp]),
         "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),
+        "rtmodt_detection_errors": (C.c_int, [C.c_int, C.POINTER(ErrorParams), C.c_int, C.c_int] + [vp] * 20),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == header/library drift

@@ -28,6 +28,7 @@
 //
 // Built with -ffp-contract=off: every float64 operation rounds separately, as NumPy's do.
 #include "common.h"
+#include "eval_dev.h"
 #include "lap.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -84,25 +85,6 @@ struct CocoArgs {
     int32_t *npig;                          // [n_cells][A]
     int max_gt, max_dt;                     // LDS sizing (largest cell)
 };
-
-// pycocotools' bbIou (maskApi.c): det d, GT g as x, y, w, h; the union of a crowd GT is the detection's area
-__device__ __forceinline__ double coco_iou(const double4 d, const double4 g, bool crowd) {
-    double w = fmin(d.x + d.z, g.x + g.z) - fmax(d.x, g.x);
-    if (w <= 0) return 0.0;
-    double h = fmin(d.y + d.w, g.y + g.w) - fmax(d.y, g.y);
-    if (h <= 0) return 0.0;
-    const double i = w * h;
-    const double da = d.z * d.w;
-    const double u = crowd ? da : da + g.z * g.w - i;
-    return i / u;
-}
-
-// an order-preserving unsigned image of a float64 (-0.0 folded into +0.0; NaN is rejected by the host)
-__device__ __forceinline__ uint64_t score_key(double s) {
-    if (s == 0.0) s = 0.0;
-    const uint64_t b = (uint64_t)__double_as_longlong(s);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __global__ __launch_bounds__(EV_THREADS) void coco_match(CocoArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
