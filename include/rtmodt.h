@@ -639,6 +639,45 @@ int rtmodt_detection_errors(int device, const rtmodt_error_params *params, int K
                             int64_t *by_class, int64_t *by_size, int64_t *by_cell, int64_t *missed_uncovered, int64_t *cm,
                             int64_t *cm_dropped);
 
+/* ---- track stitching: the post-processing step the design document prescribes and never builds ---------------------- */
+/* TECHNICAL_DESIGN_DOCUMENT.md B.4 "IDF1 Optimization" item 4 ("post-process merging -- merge tracks with overlapping time
+ * windows and similar positions (< 20 px centroid distance)"), G.1 row 1 ("post-process merge tracks within 20 px and
+ * 30-frame gap") and G.2's correct_id_switches(tracks_history, max_gap=30, max_dist=20), whose body is `...`.  PARITY
+ * UNPINNED: the reference has no implementation and no third-party stitcher is installed anywhere this runs; the rules are
+ * stated in csrc/stitch.hip's header and DESIGN.md section 18, and tests/stitch_ref.py restates them in plain Python. */
+typedef struct rtmodt_stitch_params {
+    int32_t max_gap;         /* a link A -> B needs 1 <= first frame of B - last frame of A <= max_gap; 1..1<<20        (30) */
+    double max_dist;         /* ... and a squared centre distance < max_dist * max_dist (strict); finite, > 0        (20.0) */
+    int32_t velocity_window; /* >= 0; 0 = A's exit point is its last centre; w = extrapolated over the gap with the mean
+                              * velocity of A's last min(w, rows - 1) steps                                             (0) */
+    int32_t interpolate;     /* 0 / 1: emit linearly interpolated rows for the frames inside every linked gap            (0) */
+} rtmodt_stitch_params;
+/* A batch of sequences in a fixed number of launches.  seq_trk_start[n_seq + 1]: CSR into the tracklets (one per id, any
+ * order; indices below are positions in this list); trk_row_start[n_trk + 1]: CSR into the rows, every tracklet at least one
+ * row, frames strictly ascending (|frame| <= 2^53); row_box[n][4] x, y, w, h, float64.  The chosen links are one-to-one, the
+ * maximum number of admissible links and among those the minimum sum of d2 (lap.h, lexicographic costs): isolated candidate
+ * pairs directly, the contested remainder per connected component, all components of all sequences concurrently.  Candidate
+ * links are found by a binary-searched window over the tracklets ordered by first frame (work follows tracklets x window
+ * population) and kept as a CSR (memory follows the admissible links, at most 2^28 a call).  Outputs (host): per tracklet
+ * trk_succ (the tracklet it is linked to, -1 none), trk_root (the head of its chain: its rows take that tracklet's id) and
+ * trk_link_d2 (the cost of its link, 0 without one); per sequence seq_links and seq_cost (the sum of d2, added in tracklet
+ * order).  interpolate: for a link A -> B over a gap g the rows k = 1..g-1 at frame e_A + k with the box a + (b - a) * (k / g)
+ * come back as fill_trk (A), fill_frame, fill_box[.][4], ordered by (sequence, A, k); *n_fill is their number.  When they do
+ * not fit fill_cap the call returns RTMODT_E_CAPACITY, *n_fill holds the need, the per-tracklet and per-sequence outputs are
+ * complete, the first fill_cap rows are written and nothing past them.  n_cand != NULL also returns the admissible links in
+ * (A, first frame of B, B) order: cand_a, cand_b, cand_d2 and (when non-null) the exit point cand_p[.][2]; more than cand_cap
+ * is RTMODT_E_CAPACITY with the need in *n_cand and no other output valid.  A contested component of more than 256 rows, 256
+ * columns or 2048 links is RTMODT_E_CAPACITY naming the sequence and a tracklet of the component (its position within the
+ * sequence); no output is valid.  Every argument check runs before the first HIP call: RTMODT_E_INVALID, naming sequence and
+ * row, for a null pointer, a parameter out of range, a non-finite box, frames not strictly ascending inside a tracklet, a CSR
+ * that is not monotone.  n_seq = 0, or no tracklet at all, is success with nothing launched.  Device scratch is allocated and
+ * freed inside the call. */
+int rtmodt_stitch_tracks(int device, const rtmodt_stitch_params *params, int n_seq, const int32_t *seq_trk_start,
+                         const int32_t *trk_row_start, const int64_t *row_frame, const double *row_box, int32_t *trk_succ,
+                         int32_t *trk_root, double *trk_link_d2, int64_t *seq_links, double *seq_cost, int64_t fill_cap,
+                         int32_t *fill_trk, int64_t *fill_frame, double *fill_box, int64_t *n_fill, int64_t cand_cap, int32_t *cand_a,
+                         int32_t *cand_b, double *cand_d2, double *cand_p, int64_t *n_cand);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,9 @@ library being built):
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158)
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
-                            in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py)
+                            in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py); ``stitch_tracks`` /
+                            ``correct_id_switches``: fragmented tracks merged and their gaps filled on the GPU (the design
+                            document's B.4 / G.1 / G.2 post-processing step, which the reference does not implement)
 """
 import importlib as _importlib
 

@@ -158,6 +158,10 @@ class ErrorParams(C.Structure):                      # struct rtmodt_error_param
                 ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("reserved", C.c_int32)]
 
 
+class StitchParams(C.Structure):                     # struct rtmodt_stitch_params
+    _fields_ = [("max_gap", C.c_int32), ("max_dist", C.c_double), ("velocity_window", C.c_int32), ("interpolate", C.c_int32)]
+
+
 _lib = None
 
 
@@ -275,6 +279,8 @@ def lib() -> C.CDLL:
                                        vp, vp, vp, vp, vp, vp]),
         "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),
         "rtmodt_detection_errors": (C.c_int, [C.c_int, C.POINTER(ErrorParams), C.c_int, C.c_int] + [vp] * 20),
+        "rtmodt_stitch_tracks": (C.c_int, [C.c_int, C.POINTER(StitchParams), C.c_int] + [vp] * 9 + [i64, vp, vp, vp, C.POINTER(i64), i64, vp, vp, vp,
+                                                                                                 vp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError here == header/library drift
