@@ -678,6 +678,73 @@ int rtmodt_stitch_tracks(int device, const rtmodt_stitch_params *params, int n_s
                          int32_t *fill_trk, int64_t *fill_frame, double *fill_box, int64_t *n_fill, int64_t cand_cap, int32_t *cand_a,
                          int32_t *cand_b, double *cand_d2, double *cand_p, int64_t *n_cand);
 
+/* ---- ID-swap guard: ByteTrack identities verified by appearance, swaps reverted online --------------------------------- */
+/* TECHNICAL_DESIGN_DOCUMENT.md B.4 "Re-Identification Considerations" ("use appearance as a post-processing filter only on
+ * suspected ID swaps; keep a feature buffer per track, the average colour histogram of the last 5 frames; when two tracks swap
+ * within 3 frames, compare histograms and revert if similarity > 0.85"), B.4's failure table ("add appearance verification") and
+ * G.1 row 1 ("add lightweight appearance hash verification").  PARITY UNPINNED: the reference has no code for any of it; the
+ * rules are stated in csrc/swapguard.hip's header and DESIGN.md section 19, and tests/swapguard_ref.py restates them in plain
+ * Python, which the kernel equals exactly.  The document gives 5, 3 and 0.85; min_history, min_gain_pm and contact_iou are this
+ * project's additions, and no default has been validated on real footage.  The descriptor is csrc/appearance.hip's 192-bin int8
+ * colour histogram; all arithmetic is integer except the IoU (the tracker's, float32). */
+typedef struct rtmodt_swapguard rtmodt_swapguard;
+typedef struct rtmodt_swapguard_cfg {
+    int32_t history;            /* 1..8: descriptors kept per track id (B.4: 5)                                              */
+    int32_t min_history;        /* 1..history: a track with fewer stored descriptors is never part of a revert         (3) */
+    int32_t window;             /* >= 0: a revert needs frame_id - (last frame the two touched) <= window (B.4: 3)            */
+    int32_t min_similarity_pm;  /* 0..1000: both cross similarities must reach it, per mille (B.4: 850)                       */
+    int32_t min_gain_pm;        /* >= 0: ... and exceed the track's similarity to its own history by at least this     (1) */
+    float contact_iou;          /* two tracks touch when their IoU is > contact_iou (strict; not NaN)                   (0.0) */
+    int64_t max_gap_frames;     /* >= 0: a row not passed for more than this many frames is dropped (as the crossing counter) */
+    int32_t max_tracks;         /* 1..1024 tracks handed over per stream and frame; a ledger holds 2 x max_tracks rows        */
+    int32_t n_streams;          /* 1..64 independent ledgers                                                                  */
+    int32_t max_events;         /* 1..1<<20 events per stream and frame                                                       */
+    int32_t device;
+} rtmodt_swapguard_cfg;
+/* One reverted swap (B.4 step 3).  track_a < track_b: indices into the list handed over (the caller's, or the tracker's);
+ * id_a / id_b: their ids BEFORE the exchange; sims: per mille, a's descriptor against the history of id_a and of id_b, then b's
+ * against id_b's and id_a's (the revert needed sims[1] and sims[3] high, above sims[0] and sims[2]). */
+typedef struct rtmodt_swap_event {
+    int64_t frame_id, id_a, id_b;
+    int32_t track_a, track_b;
+    int32_t sims[4];
+} rtmodt_swap_event;
+/* B.4 step 2, the feature buffer: n_streams ledgers keyed by track id.  RTMODT_E_INVALID for a parameter outside the ranges
+ * above; nothing is launched.  PARITY UNPINNED. */
+int rtmodt_swapguard_create(const rtmodt_swapguard_cfg *cfg, rtmodt_swapguard **out);
+/* Ends B.4 step 2's buffers: waits for the work queued on the handle's own stream, then frees the ledgers and the handle; null
+ * is allowed.  PARITY UNPINNED. */
+void rtmodt_swapguard_destroy(rtmodt_swapguard *g);
+/* B.4 steps 1 and 3 on a caller-supplied list of one stream (any order, unique ids else RTMODT_E_INVALID, at most max_tracks
+ * else RTMODT_E_CAPACITY): every listed track is passed, described on `frame` (BGR24, h x w, row pitch stride_bytes, host or
+ * device memory by mem_kind).  ids_out[n] receives the ids after the reverts; the caller's tracker must adopt them, as the
+ * tracker form below does for ByteTrack -- otherwise the pair fires again while the window lasts.  Events in ascending track_a;
+ * `events` holds max_events records; a frame with more returns RTMODT_E_CAPACITY with the first max_events delivered and every
+ * revert applied.  A ledger that would pass 2 x max_tracks rows drops its idle rows and the stream stays in RTMODT_E_CAPACITY
+ * for good (as rtmodt_crossing_create describes); never a fault.  PARITY UNPINNED. */
+int rtmodt_swapguard_process(rtmodt_swapguard *g, int stream, const int64_t *track_ids, const float *xyxy, int n,
+                             const uint8_t *frame, int h, int w, int stride_bytes, int mem_kind, int64_t frame_id,
+                             int64_t *ids_out, rtmodt_swap_event *events, int32_t *n_events);
+/* G.1 row 1 on every stream of a ByteTrack handle at once, on its device-resident state and on the HIP stream its last update
+ * ran on: passed = time_since_update == report_tsu (1 = matched or spawned this frame, as rtmodt_crossing_process_tracker);
+ * frames[n_streams of the tracker] are the frames the detector read.  A revert exchanges the two ids inside the tracker's state
+ * and nothing else, so everything that reads that state afterwards sees the corrected identity.  More passed tracks than
+ * max_tracks in a stream is RTMODT_E_CAPACITY for that stream from then on.  events is [n_streams][max_events],
+ * n_events[n_streams].  The launch count is fixed: one gather, the two descriptor launches, one step.  PARITY UNPINNED. */
+int rtmodt_swapguard_process_tracker(rtmodt_swapguard *g, rtmodt_tracker *trk, const uint8_t *const *frames, int h, int w,
+                                     int stride_bytes, int mem_kind, int64_t frame_id, int report_tsu,
+                                     rtmodt_swap_event *events, int32_t *n_events);
+/* Ledger snapshot of one stream (B.4 step 2; the parity surface of tests/swapguard_ref.py), rows in ascending id: last passed
+ * frame, stored descriptors, the frame of the last contact and the id touched then (-1 none), and ring[row][history][192] with
+ * the stored descriptors oldest first (the rest zero).  Arrays sized 2 x max_tracks rows; any may be NULL.  PARITY UNPINNED. */
+int rtmodt_swapguard_state(rtmodt_swapguard *g, int stream, int64_t *ids, int64_t *last_frame, int32_t *count,
+                           int64_t *contact_frame, int64_t *contact_id, int8_t *ring, int32_t *n);
+/* Swaps reverted on one stream since creation (G.1 row 1's count of corrected switches).  PARITY UNPINNED. */
+int rtmodt_swapguard_counts(rtmodt_swapguard *g, int stream, int64_t *n_reverted);
+/* Device time of the last _process / _process_tracker call, from HIP events around its launches: the descriptor launches, then
+ * gather + step (B.4 calls the check "lightweight"; this is where that is measured).  PARITY UNPINNED. */
+int rtmodt_swapguard_last_ms(rtmodt_swapguard *g, float *describe_ms, float *step_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@ library being built):
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
 * ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
+* ``tracking.swapguard`` -- ``IdSwapGuard``: ByteTrack identities verified by appearance, ID swaps reverted online on the GPU (the
+                            design document's B.4 / G.1 appearance verification, which the reference does not implement)
 * ``tracking.reid``      -- ``ReidEmbedder``: the OSNet x0.25 re-identification network on the GPU (reference: config/default.yaml:60)
 * ``reid_weights``       -- its ``.rtreid`` weight file, synthetic weights, torchreid ``state_dict`` conversion
 * ``_ffi``               -- ctypes binding of ``include/rtmodt.h`` (librtmodt_hip.so)
@@ -41,6 +43,8 @@ _LAZY = {
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",
+    "IdSwapGuard": ".tracking.swapguard",
+    "SwapEvent": ".tracking.swapguard",
     "ZoneEventEngine": ".events.zone_engine",
     "CrossingCounter": ".events.crossing",
     "FrameReader": ".ingestion.reader",

@@ -162,6 +162,17 @@ class StitchParams(C.Structure):                     # struct rtmodt_stitch_para
     _fields_ = [("max_gap", C.c_int32), ("max_dist", C.c_double), ("velocity_window", C.c_int32), ("interpolate", C.c_int32)]
 
 
+class SwapGuardCfg(C.Structure):                     # struct rtmodt_swapguard_cfg
+    _fields_ = [("history", C.c_int32), ("min_history", C.c_int32), ("window", C.c_int32), ("min_similarity_pm", C.c_int32),
+                ("min_gain_pm", C.c_int32), ("contact_iou", C.c_float), ("max_gap_frames", C.c_int64), ("max_tracks", C.c_int32),
+                ("n_streams", C.c_int32), ("max_events", C.c_int32), ("device", C.c_int32)]
+
+
+class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
+    _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
+                ("sims", C.c_int32 * 4)]
+
+
 _lib = None
 
 
@@ -262,6 +273,13 @@ def lib() -> C.CDLL:
         "rtmodt_crossing_counts": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "rtmodt_crossing_reset_counts": (C.c_int, [vp]),
         "rtmodt_crossing_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_swapguard_create": (C.c_int, [C.POINTER(SwapGuardCfg), C.POINTER(vp)]),
+        "rtmodt_swapguard_destroy": (None, [vp]),
+        "rtmodt_swapguard_process": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp, vp, C.POINTER(i32)]),
+        "rtmodt_swapguard_process_tracker": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, C.c_int, vp, vp]),
+        "rtmodt_swapguard_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_swapguard_counts": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
+        "rtmodt_swapguard_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

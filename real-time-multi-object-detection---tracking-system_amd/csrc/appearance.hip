@@ -29,18 +29,6 @@ constexpr int APP_COORD_MAX = 1 << 20;
 
 __device__ __forceinline__ int app_coord(float v) { return (int)truncf(fminf(fmaxf(v, (float)-APP_COORD_MAX), (float)APP_COORD_MAX)); }
 
-// exact floor(sqrt(n)) of a non-negative 64-bit integer (bit-by-bit, no float)
-__host__ __device__ static inline long long isqrt64(long long n) {
-    unsigned long long x = (unsigned long long)n, r = 0, bit = 1ull << 62;
-    while (bit > x) bit >>= 2;
-    while (bit) {
-        if (x >= r + bit) { x -= r + bit; r = (r >> 1) + bit; }
-        else r >>= 1;
-        bit >>= 2;
-    }
-    return (long long)r;
-}
-
 constexpr int HIST_THREADS = 256;
 
 __global__ __launch_bounds__(HIST_THREADS) void appearance_hist(DescribeArgs a) {

@@ -196,7 +196,21 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         n_pass += tot;
     }
     if (tid == 0) ppre[n] = n_pass;
+    // a tracker's list ascends in id unless the swap guard (swapguard.hip) has exchanged two ids in its state: then a row's place among
+    // this frame's rows is counted, not read off its list position
     __syncthreads();
+    for (int i = tid + 1; i < n; i += CR_THREADS)
+        if (!(ids[i - 1] < ids[i])) s_err = -1;              // (every writer stores the same value)
+    __syncthreads();
+    const bool ascending = s_err != -1;
+    __syncthreads();
+    if (tid == 0 && !ascending) s_err = 0;
+    auto passed_below = [&](int64_t x) {                                       // passed tracks of the list with an id < x
+        if (ascending) return ppre[cr_lower_bound(ids, n, x)];
+        int c = 0;
+        for (int k = 0; k < n; ++k) c += ppre[k + 1] != ppre[k] && ids[k] < x ? 1 : 0;
+        return c;
+    };
     // each finds its old row; a matched row is no idle row, and one that has expired is not this track's row either
     for (int t = tid; t < n_pass; t += CR_THREADS) {
         const int64_t id = ids[p_idx[t]];
@@ -238,7 +252,8 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         if (tv) {
             i = p_idx[t]; j = oldpos[t];
             cr_centroid(box[i], c);
-            np = overflow ? t : t + ranks_below(cr_lower_bound(old_id, n_old, ids[i]));
+            const int tp = ascending ? t : passed_below(ids[i]);
+            np = overflow ? tp : tp + ranks_below(cr_lower_bound(old_id, n_old, ids[i]));
             if (sub < L) {
                 const int4 ab = line[sub];
                 const int sd = cr_side(ab.x, ab.y, ab.z, ab.w, c.x, c.y);
@@ -290,7 +305,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         for (int j = tid; j < n_old; j += CR_THREADS) {
             const int v = ret_pre[j];
             if (v < 0) continue;
-            const int np = v + ppre[cr_lower_bound(ids, n, old_id[j])];
+            const int np = v + passed_below(old_id[j]);
             n_id[np] = old_id[j];
             n_last[np] = o_last[j];
             n_prev[np] = o_prev[j];

@@ -260,6 +260,17 @@ struct DescribeArgs {
     int8_t *desc; int desc_stride;          // [stream][desc_stride][APP_DIM]
 };
 int launch_describe(const DescribeArgs &a, int n_streams, hipStream_t s);
+// exact floor(sqrt(n)) of a non-negative 64-bit integer (bit by bit, no float): the descriptor's norm, the swap guard's similarity
+__host__ __device__ static inline long long isqrt64(long long n) {
+    unsigned long long x = (unsigned long long)n, r = 0, bit = 1ull << 62;
+    while (bit > x) bit >>= 2;
+    while (bit) {
+        if (x >= r + bit) { x -= r + bit; r = (r >> 1) + bit; }
+        else r >>= 1;
+        bit >>= 2;
+    }
+    return (long long)r;
+}
 
 struct DsState {               // one stream; device pointers; double-buffered like TrackerState
     int64_t *ids[2]; float4 *dbox[2]; float *conf[2]; int32_t *cls[2];
@@ -291,6 +302,9 @@ int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, i
 // the tracker's most recent update was launched on
 struct TrackerDeviceView { const TrackerState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
 int tracker_device_view(rtmodt_tracker *trk, TrackerDeviceView *out);
+// its mutable counterpart, for the one consumer that writes the state: the swap guard (swapguard.hip) exchanges two track ids in place
+struct TrackerDeviceViewMut { TrackerState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+int tracker_device_view_mut(rtmodt_tracker *trk, TrackerDeviceViewMut *out);
 // the same of the DeepSORT tracker (deepsort.hip), consumed by the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, ...}
 struct DsDeviceView { const DsState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
 int deepsort_device_view(rtmodt_deepsort *ds, DsDeviceView *out);

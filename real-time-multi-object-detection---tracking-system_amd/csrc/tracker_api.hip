@@ -53,6 +53,11 @@ int tracker_device_view(rtmodt_tracker *t, TrackerDeviceView *out) {
     *out = TrackerDeviceView{t->d_states, t->d_meta, t->S, t->Mc, t->device, t->stream};
     return join_foreign(t);                                // the caller's work on t->stream is ordered behind every update
 }
+int tracker_device_view_mut(rtmodt_tracker *t, TrackerDeviceViewMut *out) {
+    RT_CHECK(t && out, RTMODT_E_INVALID, "null argument");
+    *out = TrackerDeviceViewMut{t->d_states, t->d_meta, t->S, t->Mc, t->device, t->stream};
+    return join_foreign(t);
+}
 }  // namespace rtmodt
 
 extern "C" {

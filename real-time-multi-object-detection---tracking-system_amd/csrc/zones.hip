@@ -130,6 +130,20 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
     for (int i = tid; i < n_old; i += ZN_THREADS) old_id[i] = o_id[i];
     for (int i = tid; i < a.zt.n_pts; i += ZN_THREADS) pts[i] = a.zt.pts[i];
     __syncthreads();
+    // a tracker's list ascends in id unless the swap guard (swapguard.hip) has exchanged two ids in its state: then a row's place among
+    // this frame's rows is counted, not read off its list position
+    for (int i = tid + 1; i < n; i += ZN_THREADS)
+        if (!(ids[i - 1] < ids[i])) s_err = -1;              // (every writer stores the same value)
+    __syncthreads();
+    const bool ascending = s_err != -1;
+    __syncthreads();
+    if (tid == 0 && !ascending) s_err = 0;
+    auto listed_below = [&](int64_t x) {                                       // list entries with an id < x
+        if (ascending) return lower_bound_i64(ids, n, x);
+        int c = 0;
+        for (int k = 0; k < n; ++k) c += ids[k] < x ? 1 : 0;
+        return c;
+    };
 
     int32_t *oldpos = a.oldpos + (size_t)sidx * cap;
     uint32_t *evmask = a.evmask + (size_t)sidx * cap;
@@ -168,7 +182,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
     for (int i = tid; i < n; i += ZN_THREADS) {
         const int j = oldpos[i];
         const bool active = tsu ? tsu[i] == a.report_tsu : true;
-        const int np = i + (overflow ? 0 : ranks_below(lower_bound_i64(old_id, n_old, ids[i])));
+        const int np = (ascending ? i : listed_below(ids[i])) + (overflow ? 0 : ranks_below(lower_bound_i64(old_id, n_old, ids[i])));
         uint32_t mask = j >= 0 ? o_mask[j] : 0u;
         uint32_t ev = 0u;
         double *nf = n_first + (size_t)np * Z, *na = n_alert + (size_t)np * Z;
@@ -210,7 +224,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
         for (int j = tid; j < n_old; j += ZN_THREADS) {
             const int v = ret_pre[j];
             if (v < 0) continue;
-            const int np = v + lower_bound_i64(ids, n, old_id[j]);
+            const int np = v + listed_below(old_id[j]);
             n_id[np] = old_id[j];
             n_seen[np] = o_seen[j];
             n_mask[np] = 0u;                                                            // idle == not passed == purged occupancy

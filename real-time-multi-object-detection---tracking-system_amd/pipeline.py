@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None) -> dict:
+        crossing_counter=None, swap_guard=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -84,10 +84,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
 
     ``crossing_counter``: an ``events.CrossingCounter``, called where the event engine is called, inside a ``crossings`` stage: on
     the tracker's device-resident state when the track list was not materialised (ByteTrack and DeepSORT alike), else on the list.
-    The summary then carries ``crossings``, the number of crossing events of stream 0."""
+    The summary then carries ``crossings``, the number of crossing events of stream 0.
+
+    ``swap_guard``: a ``tracking.IdSwapGuard``, called right after ``tracker.update`` and before events, crossings and rendering,
+    inside a ``swap_guard`` stage: it verifies the ByteTrack identities by appearance on the frame the detector read and exchanges
+    the ids of a swapped pair back inside the tracker's device-resident state, so every later stage reads the corrected identity
+    (a track list that was already materialised has its ids exchanged too).  The summary then carries ``id_swaps_reverted``."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
-    n_events = n_crossings = 0
+    n_events = n_crossings = n_reverted = 0
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
@@ -121,6 +126,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         else:
             tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
         profiler.tock("tracking")
+        if swap_guard is not None:
+            profiler.tick("swap_guard")
+            reverted = swap_guard.process_tracker(tracker, [frame], fid)[0]
+            if reverted and tracks:
+                from .tracking.swapguard import adopt
+                adopt(tracks, reverted)
+            n_reverted += len(reverted)
+            profiler.tock("swap_guard")
         if event_engine is not None:                       # tools/run_pipeline.py:141-146
             profiler.tick("events")
             if events_on_device:
@@ -154,4 +167,6 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     out["events"] = n_events
     if crossing_counter is not None:
         out["crossings"] = n_crossings
+    if swap_guard is not None:
+        out["id_swaps_reverted"] = n_reverted
     return out
