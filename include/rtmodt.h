@@ -220,7 +220,9 @@ int rtmodt_tracker_update_from_detector_batch(rtmodt_tracker *trk, rtmodt_detect
  * (the parity surface).  Arrays sized max_tracks; any may be NULL. */
 int rtmodt_tracker_state(rtmodt_tracker *trk, int stream, int64_t *ids, float *xyxy, float *conf,
                          int32_t *cls, int32_t *age, int32_t *tsu, int32_t *n, int64_t *next_id);
-int rtmodt_tracker_reset(rtmodt_tracker *trk, int stream);   /* stream < 0: all */
+/* Empties one stream -- no tracks, ids start again at 1, a sticky RTMODT_E_CAPACITY is cleared -- and leaves the others as they
+ * are.  ANY negative stream means all streams (-1 by convention); stream >= n_streams is RTMODT_E_INVALID. */
+int rtmodt_tracker_reset(rtmodt_tracker *trk, int stream);
 /* OPT-IN, no reference counterpart (the reference overwrites a matched track's box, tracker.py:99-104, and has no motion
  * model): ByteTrack's published 8-state constant-velocity Kalman filter over (cx, cy, a, h), batched inside the same
  * launch -- every track is predicted at the start of a frame, association runs on the predicted boxes, a matched track

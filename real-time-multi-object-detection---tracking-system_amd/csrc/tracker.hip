@@ -325,7 +325,7 @@ static size_t tracker_smem_bytes(int Mc, int Nc) {
 
 int launch_tracker_update(const TrackerArgs &a, hipStream_t s) {
     size_t smem = tracker_smem_bytes(a.max_tracks, a.max_dets) + (a.assign_mode == RTMODT_ASSIGN_LAPJV ? lap_smem_bytes(a.max_dets) + 8 : 0);
-    RT_CHECK(smem <= 150 * 1024, RTMODT_E_INVALID, "tracker: max_tracks %d / max_dets %d need %zu B of LDS (> 160 KiB)", a.max_tracks,
+    RT_CHECK(smem <= 150 * 1024, RTMODT_E_INVALID, "tracker: max_tracks %d / max_dets %d need %zu B of LDS (> 150 KiB)", a.max_tracks,
              a.max_dets, smem);
     static DynLdsSeen seen;                                // the attribute is per device
     RT_TRY(raise_dynamic_lds((const void *)tracker_update, smem, seen));
