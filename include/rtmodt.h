@@ -594,6 +594,30 @@ int rtmodt_mot_eval(int device, int n_seq, const int32_t *seq_frame_start, const
                     const int32_t *hyp_start, const int32_t *gt_oid, const double *gt_box, const int32_t *hyp_hid, const double *hyp_box,
                     const int32_t *seq_n_oid, const int32_t *seq_n_hid, rtmodt_mot_counts *out);
 
+/* HOTA (Luiten et al., IJCV 2021) beside CLEAR MOT and IDF1: csrc/hota.hip restates TrackEval's trackeval/metrics/hota.py.
+ * PARITY UNPINNED: TrackEval is installed nowhere this runs; the rules are in csrc/hota.hip's header and INTEGRATION.md
+ * section 17, tests/hota_ref.py restates them in plain Python / NumPy (its per-frame matching pinned to
+ * scipy.optimize.linear_sum_assignment, the solver TrackEval calls) and the GPU tests require bit identity with it.
+ * One sequence's sums at one alpha; DetA = tp / (tp + fn + fp), AssA = ass_a_sum / tp, LocA = loc_sum / tp,
+ * HOTA = sqrt(DetA * AssA) with TrackEval's guards are built by the caller. */
+typedef struct rtmodt_hota_counts {
+    int64_t tp, fn, fp;                 /* matches with S >= alpha - eps; GT rows - tp; hypothesis rows - tp              */
+    double loc_sum;                     /* sum of S over those matches, in ascending frame, then ascending GT row         */
+    double ass_a_sum, ass_re_sum, ass_pr_sum;   /* sums over the (o, h) with mc > 0, ascending (o, h), of
+                                                 * mc * (mc / (gtc + trc - mc)), mc * (mc / max(1, gtc)), mc * (mc / max(1, trc)) */
+} rtmodt_hota_counts;
+/* rtmodt_mot_eval's input (n_seq = 0 is an empty call) plus alphas[n_alpha]: ascending, used as given, n_alpha <= 32 (the
+ * Python side passes np.arange(0.05, 0.99, 0.05)).  out[n_seq][n_alpha].  Similarity S = the float64 IoU that mot_eval's
+ * distance is 1 - of; only pairs with S > 0 are stored and memory follows them, never |O| x |H|.  Pass 1 builds the global
+ * alignment score gas(o, h) of every co-occurring id pair, pass 2 matches every frame on its own (maximum weight of
+ * gas * S; lap.h's solver on the contested remainder), the finish runs on the host from the sparse (sequence, o, h, mc)
+ * table.  Limits: mot_eval's (1024 rows per frame and side, checked before launch; 2^28 stored pairs per call; a contested
+ * remainder above 256 rows / 256 columns / 2048 pairs fails with RTMODT_E_CAPACITY naming the sequence and frame, before
+ * anything is counted). */
+int rtmodt_hota_eval(int device, int n_seq, const int32_t *seq_frame_start, const int64_t *frame_id, const int32_t *gt_start,
+                     const int32_t *hyp_start, const int32_t *gt_oid, const double *gt_box, const int32_t *hyp_hid, const double *hyp_box,
+                     const int32_t *seq_n_oid, const int32_t *seq_n_hid, const double *alphas, int n_alpha, rtmodt_hota_counts *out);
+
 /* ---- detection error analysis: what the detector gets wrong ---------------------------------------------------- */
 /* TECHNICAL_DESIGN_DOCUMENT.md D.5 defines five error types (localization, classification, duplicate, background false
  * positive, missed) to be clustered by image region and object size, D.4 asks for the per-class breakdown and D.6 step 4

@@ -153,6 +153,10 @@ class MotCounts(C.Structure):                        # struct rtmodt_mot_counts
                                          "idfn")] + [("dist_sum", C.c_double)]
 
 
+class HotaCounts(C.Structure):                       # struct rtmodt_hota_counts
+    _fields_ = [(n, C.c_int64) for n in ("tp", "fn", "fp")] + [(n, C.c_double) for n in ("loc_sum", "ass_a_sum", "ass_re_sum", "ass_pr_sum")]
+
+
 class ErrorParams(C.Structure):                      # struct rtmodt_error_params
     _fields_ = [("conf_thr", C.c_double), ("iou_fg", C.c_double), ("iou_bg", C.c_double), ("cm_iou", C.c_double), ("max_det", C.c_int32),
                 ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("reserved", C.c_int32)]
@@ -296,6 +300,7 @@ def lib() -> C.CDLL:
         "rtmodt_coco_eval": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp]),
         "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),
+        "rtmodt_hota_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(HotaCounts)]),
         "rtmodt_detection_errors": (C.c_int, [C.c_int, C.POINTER(ErrorParams), C.c_int, C.c_int] + [vp] * 20),
         "rtmodt_stitch_tracks": (C.c_int, [C.c_int, C.POINTER(StitchParams), C.c_int] + [vp] * 9 + [i64, vp, vp, vp, C.POINTER(i64), i64, vp, vp, vp,
                                                                                                  vp, C.POINTER(i64)]),

@@ -43,28 +43,7 @@ namespace rtmodt {
 
 #pragma clang fp contract(off)
 
-constexpr int EV_THREADS = 256;
-constexpr int EV_WAVES = EV_THREADS / 64;
 constexpr int COCO_MAX_GT_CELL = 1024, COCO_MAX_DT_CELL = 4096, COCO_MAX_DETS = 1024, COCO_MAX_AT = 256;
-constexpr int MOT_MAX_ROWS = 1024;
-
-// inclusive scan over the workgroup in thread order; `wtot`: LDS T[EV_WAVES]; two barriers
-template <typename T, typename Op>
-__device__ __forceinline__ T block_scan(T v, Op op, T *wtot, T &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d);
-        if (lane >= d) v = op(o, v);
-    }
-    if (lane == 63) wtot[wave] = v;
-    __syncthreads();
-    T tot = wtot[0];
-    for (int w = 1; w < EV_WAVES; ++w) tot = op(tot, wtot[w]);
-    for (int w = 0; w < wave; ++w) v = op(wtot[w], v);
-    __syncthreads();
-    total = tot;
-    return v;
-}
 
 // ======================================================================================================================
 // COCO
@@ -340,16 +319,6 @@ struct MotArgs {
 };
 enum { MC_MATCH, MC_SWITCH, MC_MISS, MC_FP, MC_OBJ, MC_PRED, MC_MT, MC_ML, MC_ERR, MC_ERR_FRAME, MOT_NCOUNT };
 
-// motmetrics' boxiou in float64 (x, y, w, h)
-__device__ __forceinline__ double mot_dist(const double *a, const double *b) {
-    const double iw = fmax(fmin(a[0] + a[2], b[0] + b[2]) - fmax(a[0], b[0]), 0.0);
-    const double ih = fmax(fmin(a[1] + a[3], b[1] + b[3]) - fmax(a[1], b[1]), 0.0);
-    const double i = iw * ih;
-    const double u = (a[2] * a[3] + b[2] * b[3]) - i;
-    const double iou = i == 0.0 ? 0.0 : i / u;
-    return 1.0 - iou;
-}
-
 // WRITE = false: the count pass (pair_n only); WRITE = true: the same decisions again, compacted into the frame's CSR slice
 template <bool WRITE>
 __global__ __launch_bounds__(EV_THREADS) void mot_pairs(MotArgs a) {
@@ -622,24 +591,6 @@ static long long idtp_host(const IdEdge *edges, size_t n_edges, int n_oid, int n
                 if (ecol[e] == rm[o]) { w -= ecost[e]; break; }
     return w;
 }
-
-// device buffers of one call, freed on every return path
-struct DevBufs {
-    std::vector<void *> ptrs;
-    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return RTMODT_OK;
-    }
-    template <typename T> int up(T **out, const T *host, size_t n) {
-        RT_TRY(alloc(out, n));
-        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
-        return RTMODT_OK;
-    }
-};
 
 }  // namespace rtmodt
 

@@ -1,12 +1,48 @@
-// eval_dev.h -- the float64 device helpers shared by the evaluation kernels (eval.hip: coco_match; errors.hip: detection_errors).
-// Both translation units are built with -ffp-contract=off and IEEE division: every operation below rounds separately, as NumPy's do.
+// eval_dev.h -- the float64 device helpers shared by the evaluation kernels (eval.hip: coco_match, mot_pairs; errors.hip:
+// detection_errors; hota.hip), the workgroup scan and the per-call device buffers of eval.hip and hota.hip.
+// These translation units are built with -ffp-contract=off and IEEE division: every operation below rounds separately, as NumPy's do.
 #pragma once
 
 #include "common.h"
 
+#include <algorithm>
+#include <vector>
+
 namespace rtmodt {
 
 #pragma clang fp contract(off)
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_WAVES = EV_THREADS / 64;
+constexpr int MOT_MAX_ROWS = 1024;
+
+// inclusive scan over the workgroup in thread order; `wtot`: LDS T[EV_WAVES]; two barriers
+template <typename T, typename Op>
+__device__ __forceinline__ T block_scan(T v, Op op, T *wtot, T &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(v, d);
+        if (lane >= d) v = op(o, v);
+    }
+    if (lane == 63) wtot[wave] = v;
+    __syncthreads();
+    T tot = wtot[0];
+    for (int w = 1; w < EV_WAVES; ++w) tot = op(tot, wtot[w]);
+    for (int w = 0; w < wave; ++w) v = op(wtot[w], v);
+    __syncthreads();
+    total = tot;
+    return v;
+}
+
+// motmetrics' boxiou in float64 (x, y, w, h): the similarity S of hota.hip, and mot_eval's distance d = 1 - S
+__device__ __forceinline__ double mot_iou(const double *a, const double *b) {
+    const double iw = fmax(fmin(a[0] + a[2], b[0] + b[2]) - fmax(a[0], b[0]), 0.0);
+    const double ih = fmax(fmin(a[1] + a[3], b[1] + b[3]) - fmax(a[1], b[1]), 0.0);
+    const double i = iw * ih;
+    const double u = (a[2] * a[3] + b[2] * b[3]) - i;
+    return i == 0.0 ? 0.0 : i / u;
+}
+__device__ __forceinline__ double mot_dist(const double *a, const double *b) { return 1.0 - mot_iou(a, b); }
 
 // pycocotools' bbIou (maskApi.c): det d, GT g as x, y, w, h; the union of a crowd GT is the detection's area
 __device__ __forceinline__ double coco_iou(const double4 d, const double4 g, bool crowd) {
@@ -26,5 +62,23 @@ __device__ __forceinline__ uint64_t score_key(double s) {
     const uint64_t b = (uint64_t)__double_as_longlong(s);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
+
+// device buffers of one call, freed on every return path
+struct DevBufs {
+    std::vector<void *> ptrs;
+    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
+    template <typename T> int alloc(T **out, size_t n) {
+        void *p = nullptr;
+        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        *out = (T *)p;
+        return RTMODT_OK;
+    }
+    template <typename T> int up(T **out, const T *host, size_t n) {
+        RT_TRY(alloc(out, n));
+        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return RTMODT_OK;
+    }
+};
 
 }  // namespace rtmodt

@@ -1,11 +1,12 @@
 // lap.h -- the sparse shortest-augmenting-path assignment solver shared by the tracker's lapjv branch (tracker.hip:
 // assoc_lap) and the evaluator (eval.hip: the per-frame CLEAR MOT assignment on the device, the IDF1 identity pairing on
-// the host).
+// the host; hota.hip: the per-frame HOTA matching on the device).
 //
 // The problem: rows 0..nhr-1, each with a private dummy column of cost 0 (= stay unmatched) and real edges (CSR:
 // estart / ecol / ecost) of cost < 0.  lap_solve finds the minimum-cost assignment, row by row, with Jonker-Volgenant style
 // Dijkstra scans over the touched columns only.  The cost type C is any totally ordered additive group:
-//   double    the tracker (edge cost c_ij - cost_limit), unchanged from when this code lived in tracker.hip
+//   double    the tracker (edge cost c_ij - cost_limit), unchanged from when this code lived in tracker.hip; HOTA (edge
+//             cost -score: a maximum-weight matching)
 //   LexCost   (count, distance) compared lexicographically: edge cost (-1, d) makes the optimum "maximum cardinality, then
 //             minimum sum of d" exactly -- the count part is an integer, so no large constant is folded into d
 //   long long exact integer weights (edge cost -n): a maximum-weight matching
@@ -18,7 +19,7 @@
 namespace rtmodt {
 
 // Capacities of the arrays below, inclusive: a problem of <= 256 rows, <= 256 columns and <= 2048 edges is solved; the callers
-// that compact into them (assoc_sparse in track_dev.h, mot_accumulate in eval.hip) refuse one more of any with a capacity error.
+// that compact into them (assoc_sparse in track_dev.h, mot_accumulate in eval.hip, hota_match in hota.hip) refuse one more of any with a capacity error.
 constexpr int LAP_ROWS = 256, LAP_COLS = 256, LAP_EDGES = 2048;
 
 struct LexCost {

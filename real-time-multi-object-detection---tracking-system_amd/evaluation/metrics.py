@@ -6,6 +6,8 @@
   per-frame matching and the identity pairing.
 * ``build_confusion_matrix`` / ``measure_tracking_drift`` -- the reference's NumPy helpers, unchanged in behaviour.
 * ``coco_eval`` / ``mot_eval`` -- array-level entry points (custom IoU thresholds, many sequences per launch).
+* ``hota_eval`` / ``evaluate_tracking_hota`` -- HOTA (TrackEval's hota.py) on ``mot_eval``'s input: ``rtmodt_hota_eval`` in
+  ``csrc/hota.hip``, the final formulae in NumPy.
 * ``coco_results`` / ``mot_rows`` -- write the project's detections / tracks in COCO results / MOTChallenge form.
 
 PARITY UNPINNED: neither pycocotools nor motmetrics is installed anywhere this runs.  INTEGRATION.md section 9 states the
@@ -209,13 +211,8 @@ def _quiet_div(a, b) -> float:
         return float(np.float64(a) / np.float64(b))
 
 
-def mot_eval(sequences, *, device="cuda:0") -> list:
-    """CLEAR MOT + IDF1 of many sequences in one launch.  ``sequences``: ``(gt, hyp)`` pairs of ``(n, 6)`` arrays
-    ``frame, id, x, y, w, h`` (0-based boxes, as ``load_mot`` returns them).  Returns one record per sequence: every
-    count plus ``mota``, ``motp`` (1 - IoU) and ``idf1``."""
-    seqs = list(sequences)
-    if not seqs:
-        return []
+def _mot_arrays(seqs):
+    """``(gt, hyp)`` pairs -> the CSR arrays ``rtmodt_mot_eval`` and ``rtmodt_hota_eval`` share (``seqs`` is not empty)."""
     fstart, fids, gstart, hstart = [0], [], [0], [0]
     goid, gbox, hhid, hbox, n_oid, n_hid = [], [], [], [], [], []
     for gt, hyp in seqs:
@@ -244,6 +241,17 @@ def mot_eval(sequences, *, device="cuda:0") -> list:
     goid, hhid = i32(np.concatenate(goid)), i32(np.concatenate(hhid))
     gbox, hbox = f64(gbox), f64(hbox)
     n_oid, n_hid = i32(n_oid), i32(n_hid)
+    return fstart, fids, gstart, hstart, goid, gbox, hhid, hbox, n_oid, n_hid
+
+
+def mot_eval(sequences, *, device="cuda:0") -> list:
+    """CLEAR MOT + IDF1 of many sequences in one launch.  ``sequences``: ``(gt, hyp)`` pairs of ``(n, 6)`` arrays
+    ``frame, id, x, y, w, h`` (0-based boxes, as ``load_mot`` returns them).  Returns one record per sequence: every
+    count plus ``mota``, ``motp`` (1 - IoU) and ``idf1``."""
+    seqs = list(sequences)
+    if not seqs:
+        return []
+    fstart, fids, gstart, hstart, goid, gbox, hhid, hbox, n_oid, n_hid = _mot_arrays(seqs)
     out = (_ffi.MotCounts * len(seqs))()
     P = _ffi.ptr
     _ffi.check(_ffi.lib().rtmodt_mot_eval(_ffi.device_ordinal(device), len(seqs), P(fstart), P(fids), P(gstart), P(hstart), P(goid),
@@ -264,6 +272,87 @@ def evaluate_tracking(gt_mot_file: str, pred_mot_file: str, *, device="cuda:0") 
     r = mot_eval([(load_mot(gt_mot_file), load_mot(pred_mot_file))], device=device)[0]
     return {"idf1": r["idf1"], "mota": r["mota"], "motp": r["motp"], "num_switches": r["num_switches"],
             "mostly_tracked": r["mostly_tracked"], "mostly_lost": r["mostly_lost"]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# HOTA (TrackEval's trackeval/metrics/hota.py)
+# ---------------------------------------------------------------------------------------------------------------------
+HOTA_ALPHAS = np.arange(0.05, 0.99, 0.05)                  # TrackEval's array_labels: 19 values, used as built
+HOTA_FLOAT_FIELDS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+HOTA_COUNT_FIELDS = ("HOTA_TP", "HOTA_FN", "HOTA_FP")
+HOTA_SUM_FIELDS = ("loc_sum", "ass_a_sum", "ass_re_sum", "ass_pr_sum")
+
+
+def hota_record(tp, fn, fp, loc_sum, ass_a_sum, ass_re_sum, ass_pr_sum, alphas=None, *, combined=False) -> dict:
+    """The sums per alpha -> one HOTA record with TrackEval's formulae and guards.  Per alpha: the integer counts
+    ``HOTA_TP / HOTA_FN / HOTA_FP``, the four sums, and ``DetRe = TP / max(1, TP + FN)``, ``DetPr = TP / max(1, TP + FP)``,
+    ``DetA = TP / max(1, TP + FN + FP)``, ``AssA / AssRe / AssPr = sum / max(1, TP)``, ``HOTA = sqrt(DetA * AssA)``,
+    ``LocA = max(1e-10, loc_sum) / max(1e-10, TP)`` (1 where nothing matched).  ``combined``: TrackEval's
+    ``combine_sequences`` weights LocA by TP instead, ``loc_sum / max(1e-10, TP)`` (0 where nothing matched); every other
+    field of a combination is the same formula on the added sums.  ``mean``: each float field's mean over alpha;
+    ``HOTA(0)``, ``LocA(0)``, ``HOTALocA(0)``: the first alpha's values and their product."""
+    tp, fn, fp = (np.asarray(v, np.int64).reshape(-1) for v in (tp, fn, fp))
+    loc, aa, ar, ap = (np.asarray(v, np.float64).reshape(-1) for v in (loc_sum, ass_a_sum, ass_re_sum, ass_pr_sum))
+    r = {"alphas": HOTA_ALPHAS.copy() if alphas is None else np.asarray(alphas, np.float64).reshape(-1).copy(),
+         "HOTA_TP": tp, "HOTA_FN": fn, "HOTA_FP": fp, "loc_sum": loc, "ass_a_sum": aa, "ass_re_sum": ar, "ass_pr_sum": ap}
+    tpf = tp.astype(np.float64)
+    r["DetRe"] = tpf / np.maximum(1, tp + fn)
+    r["DetPr"] = tpf / np.maximum(1, tp + fp)
+    r["DetA"] = tpf / np.maximum(1, tp + fn + fp)
+    r["AssA"] = aa / np.maximum(1, tp)
+    r["AssRe"] = ar / np.maximum(1, tp)
+    r["AssPr"] = ap / np.maximum(1, tp)
+    r["HOTA"] = np.sqrt(r["DetA"] * r["AssA"])
+    r["LocA"] = loc / np.maximum(1e-10, tpf) if combined else np.maximum(1e-10, loc) / np.maximum(1e-10, tpf)
+    r["mean"] = {k: float(np.mean(r[k])) for k in HOTA_FLOAT_FIELDS}
+    r["HOTA(0)"] = float(r["HOTA"][0])
+    r["LocA(0)"] = float(r["LocA"][0])
+    r["HOTALocA(0)"] = r["HOTA(0)"] * r["LocA(0)"]
+    return r
+
+
+def hota_combine(records, alphas=None) -> dict:
+    """TrackEval's ``combine_sequences``: the counts summed and the association / localisation terms weighted by TP, which
+    with the sums kept in every record is adding the sums."""
+    records = list(records)
+    n = len(HOTA_ALPHAS if alphas is None else np.asarray(alphas).reshape(-1))
+    tot = {k: np.zeros(n, np.int64) for k in HOTA_COUNT_FIELDS}
+    tot.update({k: np.zeros(n, np.float64) for k in HOTA_SUM_FIELDS})
+    for r in records:
+        for k in tot:
+            tot[k] = tot[k] + r[k]
+    return hota_record(tot["HOTA_TP"], tot["HOTA_FN"], tot["HOTA_FP"], tot["loc_sum"], tot["ass_a_sum"], tot["ass_re_sum"],
+                       tot["ass_pr_sum"], alphas, combined=True)
+
+
+def hota_eval(sequences, *, alphas=None, device="cuda:0") -> dict:
+    """HOTA of many sequences in one call (``rtmodt_hota_eval``).  ``sequences``: ``mot_eval``'s input.  ``alphas``: an
+    ascending array of at most 32 thresholds, default ``np.arange(0.05, 0.99, 0.05)``.  Returns ``{"sequences": [one record
+    per sequence], "combined": the record of all of them, "alphas": the thresholds}``; a record is ``hota_record``'s.
+    PARITY UNPINNED against TrackEval."""
+    al = np.ascontiguousarray(HOTA_ALPHAS if alphas is None else np.asarray(alphas, np.float64).reshape(-1), np.float64)
+    if len(al) == 0:
+        raise ValueError("hota_eval needs at least one alpha")
+    seqs = list(sequences)
+    out = (_ffi.HotaCounts * (len(seqs) * len(al)))()
+    P = _ffi.ptr
+    if seqs:
+        fstart, fids, gstart, hstart, goid, gbox, hhid, hbox, n_oid, n_hid = _mot_arrays(seqs)
+        _ffi.check(_ffi.lib().rtmodt_hota_eval(_ffi.device_ordinal(device), len(seqs), P(fstart), P(fids), P(gstart), P(hstart), P(goid),
+                                               P(gbox), P(hhid), P(hbox), P(n_oid), P(n_hid), P(al), len(al), out))
+    else:
+        _ffi.check(_ffi.lib().rtmodt_hota_eval(_ffi.device_ordinal(device), 0, None, None, None, None, None, None, None, None, None, None,
+                                               P(al), len(al), out))
+    recs = []
+    for s in range(len(seqs)):
+        c = out[s * len(al):(s + 1) * len(al)]
+        recs.append(hota_record(*[[getattr(x, n) for x in c] for n, _ in _ffi.HotaCounts._fields_], al))
+    return {"sequences": recs, "combined": hota_combine(recs, al), "alphas": al.copy()}
+
+
+def evaluate_tracking_hota(gt_mot_file: str, pred_mot_file: str, *, device="cuda:0") -> dict:
+    """The HOTA record of one MOTChallenge sequence (``hota_eval`` on the two files)."""
+    return hota_eval([(load_mot(gt_mot_file), load_mot(pred_mot_file))], device=device)["sequences"][0]
 
 
 def _num(v: float) -> str:
