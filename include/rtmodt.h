@@ -43,6 +43,7 @@ typedef struct rtmodt_zones rtmodt_zones;
 typedef struct rtmodt_renderer rtmodt_renderer;
 typedef struct rtmodt_jpeg rtmodt_jpeg;
 typedef struct rtmodt_deepsort rtmodt_deepsort;
+typedef struct rtmodt_ocsort rtmodt_ocsort;
 typedef struct rtmodt_reid rtmodt_reid;
 
 /* ---- library / device ------------------------------------------------------------- */
@@ -312,6 +313,47 @@ int rtmodt_deepsort_state(rtmodt_deepsort *ds, int stream, int64_t *ids, int32_t
 /* Device time (ms, HIP events) of the last update's three parts: descriptors (0 with caller descriptors), distance, update. */
 int rtmodt_deepsort_last_ms(rtmodt_deepsort *ds, float *describe_ms, float *distance_ms, float *update_ms);
 
+/* ---- OC-SORT: the motion-only tracker of TECHNICAL_DESIGN_DOCUMENT.md H.2 (row 4, "Req. Re-ID Model: No") ---- */
+/* Observation-Centric SORT (Cao et al., CVPR 2023) with the state resident on the device: csrc/ocsort.hip states the rules (split,
+ * SORT's 7-state filter, direction-consistent first association, BYTE stage, recovery on the last observation, re-update across
+ * an occlusion), tests/ocsort_ref.py restates them and the kernel equals that restatement bit for bit.  PARITY UNPINNED: ocsort,
+ * boxmot and filterpy are installed nowhere this runs.  Class-agnostic, as published: a track carries the class of its last matched
+ * detection.  One launch per call whatever the counts.  Limits: 256 tracks and 1024 detections per stream, 64 streams, delta_t <= 8,
+ * and the contested-pair limits of rtmodt_assign_lapjv; beyond them RTMODT_E_CAPACITY, never a fault. */
+typedef struct rtmodt_ocsort_cfg {
+    float det_thresh;           /* 0.6: high detections have conf > det_thresh (float32, strict)                                 */
+    float low_thresh;           /* 0.1: low detections have low_thresh < conf < det_thresh; used only with use_byte              */
+    float iou_threshold;        /* 0.3: a pair is admissible when iou >= iou_threshold (float32).  Must exceed inertia / 2 (our
+                                 * rule, RTMODT_E_INVALID otherwise): it makes every admissible pair's gain positive             */
+    double inertia;             /* 0.2: weight of the direction-consistency term of the first association; 0 turns it off        */
+    int32_t max_age;            /* 30: an unmatched track dies when time_since_update > max_age                                  */
+    int32_t min_hits;           /* 3: a matched track is returned once hit_streak >= min_hits (or while frame_count <= min_hits) */
+    int32_t delta_t;            /* 3: frames back to the reference observation of a track's direction; 1..8 (8 is our limit)     */
+    int32_t use_byte;           /* 0: non-zero adds the BYTE stage on the low detections                                         */
+    int32_t max_tracks, max_dets, n_streams, device;
+} rtmodt_ocsort_cfg;
+int rtmodt_ocsort_create(const rtmodt_ocsort_cfg *cfg, rtmodt_ocsort **out);
+void rtmodt_ocsort_destroy(rtmodt_ocsort *oc);
+int rtmodt_ocsort_reset(rtmodt_ocsort *oc, int stream);       /* stream < 0: all */
+/* One frame for every stream: xyxy[n_streams][max_dets][4], conf / cls[n_streams][max_dets], n[n_streams].
+ * n_returned_out[n_streams] (may be NULL) = the tracks returned this frame (what update() returns). */
+int rtmodt_ocsort_update_batch(rtmodt_ocsort *oc, const float *xyxy, const float *conf, const int32_t *cls, const int32_t *n,
+                               int32_t *n_returned_out);
+/* The same on the device-resident detections of det's last enqueue_batch (stream i <- frame i), queued on det's HIP stream behind
+ * its NMS: asynchronous, the detections never visit the host (rtmodt_ocsort_state, rtmodt_ocsort_last_ms and rtmodt_synchronize
+ * wait for it). */
+int rtmodt_ocsort_update_from_detector(rtmodt_ocsort *oc, rtmodt_detector *det);
+/* A stream's tracks in list order (creation order, deletions compacted); arrays sized max_tracks, any may be NULL.  xyxy / conf /
+ * cls: the last observation (before a track's first match: its birth detection; hits > 0 <=> it has an observation);
+ * mean[n][8] = (x, y, s, r, vx, vy, vs, 0), cov[n][12] as rtmodt_tracker_kalman_state; direction[n][2] = the stored unit direction
+ * (dy, dx), zero when none.  A track is returned this frame when tsu == 0 and (hit_streak >= min_hits or frame_count <= min_hits).
+ * On a stream in (sticky) error the outputs are still filled in before RTMODT_E_CAPACITY is returned. */
+int rtmodt_ocsort_state(rtmodt_ocsort *oc, int stream, int64_t *ids, int32_t *hits, int32_t *hit_streak, int32_t *age, int32_t *tsu,
+                        float *xyxy, float *conf, int32_t *cls, float *mean, float *cov, float *direction, int32_t *n,
+                        int64_t *next_id, int64_t *frame_count);
+/* Device time (ms, HIP events) of the last update's single launch. */
+int rtmodt_ocsort_last_ms(rtmodt_ocsort *oc, float *update_ms);
+
 /* ---- the embedder of default.yaml:60 (`tracking.deepsort.embedder: "weights/osnet_x0_25.onnx"`): OSNet x0.25 on the GPU ---- */
 /* csrc/reid.hip states the crop rule, the rounding contract and the launches; tests/reid_ref.py restates them.  PINNED: the crop
  * and the int8 quantiser exactly, the network within a measured fp16 bound of float64 (profiles/reid/README.md).  PARITY
@@ -444,7 +486,7 @@ typedef struct rtmodt_crossing_event {
  * row is kept as it is.  A ledger holds 2 x max_tracks rows: the frame that needs more returns RTMODT_E_CAPACITY, the idle rows are
  * dropped to make room, and the stream stays in error for good (every later _process*, and _state, of that stream returns
  * RTMODT_E_CAPACITY; the counts remain readable, and passed tracks that cross keep entering them).  Destroy the handle and create a larger
- * one.  Track ids are taken to name one object for the handle's lifetime: after rtmodt_tracker_reset / rtmodt_deepsort_reset, or with a new
+ * one.  Track ids are taken to name one object for the handle's lifetime: after rtmodt_tracker_reset / rtmodt_deepsort_reset / rtmodt_ocsort_reset, or with a new
  * tracker handle, ids start again at 1, so create a new counter with it (rows kept within the gap would be taken for the new tracks). */
 int rtmodt_crossing_create(int device, const rtmodt_line_cfg *lines, int n_lines, const rtmodt_gate_cfg *gates, int n_gates,
                            int n_classes, int n_streams, int max_tracks, int max_events, int64_t max_gap_frames,
@@ -465,6 +507,10 @@ int rtmodt_crossing_process_tracker(rtmodt_crossing *c, rtmodt_tracker *trk, int
  * time_since_update == report_tsu (0 = matched this frame); the box is the matched detection's (rtmodt_deepsort_state: xyxy). */
 int rtmodt_crossing_process_deepsort(rtmodt_crossing *c, rtmodt_deepsort *ds, int64_t frame_id, int report_tsu,
                                      rtmodt_crossing_event *events, int32_t *n_events);
+/* The same on an OC-SORT handle: passed = the tracks that handle returns this frame (rtmodt_ocsort_state); the box is the matched
+ * detection's. */
+int rtmodt_crossing_process_ocsort(rtmodt_crossing *c, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events,
+                                   int32_t *n_events);
 /* One stream's counts since creation or the last reset (default.yaml:73-77): line_total [n_lines][2] (pos, neg),
  * line_class [n_lines][2][n_classes], gate_total [n_gates], gate_class [n_gates][n_classes]; any pointer may be null. */
 int rtmodt_crossing_counts(rtmodt_crossing *c, int stream, int64_t *line_total, int64_t *line_class, int64_t *gate_total,

@@ -11,6 +11,7 @@ library being built):
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
 * ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
+* ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
 * ``tracking.swapguard`` -- ``IdSwapGuard``: ByteTrack identities verified by appearance, ID swaps reverted online on the GPU (the
                             design document's B.4 / G.1 appearance verification, which the reference does not implement)
 * ``tracking.reid``      -- ``ReidEmbedder``: the OSNet x0.25 re-identification network on the GPU (reference: config/default.yaml:60)
@@ -35,7 +36,7 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker"]
+__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
@@ -43,6 +44,7 @@ _LAZY = {
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",
+    "OcSortTracker": ".tracking.ocsort",
     "IdSwapGuard": ".tracking.swapguard",
     "SwapEvent": ".tracking.swapguard",
     "ZoneEventEngine": ".events.zone_engine",

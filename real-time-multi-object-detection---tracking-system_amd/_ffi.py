@@ -143,6 +143,12 @@ class DeepSortCfg(C.Structure):                     # struct rtmodt_deepsort_cfg
                 ("max_dets", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
 
 
+class OcSortCfg(C.Structure):                       # struct rtmodt_ocsort_cfg
+    _fields_ = [("det_thresh", C.c_float), ("low_thresh", C.c_float), ("iou_threshold", C.c_float), ("inertia", C.c_double),
+                ("max_age", C.c_int32), ("min_hits", C.c_int32), ("delta_t", C.c_int32), ("use_byte", C.c_int32), ("max_tracks", C.c_int32),
+                ("max_dets", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
+
+
 class ReidCfg(C.Structure):                         # struct rtmodt_reid_cfg
     _fields_ = [("weight_path", C.c_char_p), ("device", C.c_int32), ("max_frames", C.c_int32), ("max_boxes", C.c_int32)]
 
@@ -257,6 +263,13 @@ def lib() -> C.CDLL:
         "rtmodt_deepsort_update_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtmodt_deepsort_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i64)]),
         "rtmodt_deepsort_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_ocsort_create": (C.c_int, [C.POINTER(OcSortCfg), C.POINTER(vp)]),
+        "rtmodt_ocsort_destroy": (None, [vp]),
+        "rtmodt_ocsort_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_ocsort_update_batch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        "rtmodt_ocsort_update_from_detector": (C.c_int, [vp, vp]),
+        "rtmodt_ocsort_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
+        "rtmodt_ocsort_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_reid_create": (C.c_int, [C.POINTER(ReidCfg), C.POINTER(vp)]),
         "rtmodt_reid_destroy": (None, [vp]),
         "rtmodt_reid_embed": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
@@ -274,6 +287,7 @@ def lib() -> C.CDLL:
         "rtmodt_crossing_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, i64, vp, C.POINTER(i32)]),
         "rtmodt_crossing_process_tracker": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
         "rtmodt_crossing_process_deepsort": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
+        "rtmodt_crossing_process_ocsort": (C.c_int, [vp, vp, i64, vp, vp]),
         "rtmodt_crossing_counts": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "rtmodt_crossing_reset_counts": (C.c_int, [vp]),
         "rtmodt_crossing_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),

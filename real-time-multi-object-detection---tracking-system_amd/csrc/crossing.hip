@@ -1,7 +1,7 @@
 // crossing.hip -- directional line (tripwire) and gate crossing counts on the GPU: the meaning the reference's config gives a
 // `trigger: "crossing"` zone with a `direction` (config/default.yaml:73-77) and its engine never implements (zone_engine.py:150
 // parses the direction and nothing reads it).  ONE launch per frame, one 256-thread workgroup per video stream, run on a track
-// list the host hands over or straight on the device-resident state of the ByteTrack or the DeepSORT tracker.
+// list the host hands over or straight on the device-resident state of the ByteTrack, the DeepSORT or the OC-SORT tracker.
 //
 // tests/crossing_ref.py states the rules ("Crossing counter"); the kernel equals it exactly.  Everything after the
 // centroid is integer arithmetic: coordinates are held to +-2^20, so every cross product is below 2^43.
@@ -52,6 +52,8 @@ struct CrossArgs {
     const int64_t *s_ids; const float4 *s_box; const int32_t *s_cls; const int32_t *s_order, *s_inv; const int32_t *s_n; int s_stride;
     // source B / C: the ByteTrack / DeepSORT tracker's device state; passed tracks are those with tsu == report_tsu (C: and flag == 2)
     const TrackerState *t_states; const DsState *d_states; const int64_t *t_meta; int report_tsu;
+    // source D: the OC-SORT tracker's device state; passed = returned: tsu == 0 and (hit_streak >= o_min_hits or frame_count <= o_min_hits)
+    const OcState *o_states; int o_min_hits;
     // per-stream scratch [n_streams][cap]
     int32_t *p_idx, *oldpos; uint64_t *evmask;
     // events [n_streams][max_events]; ev_n = the number that fired (may exceed max_events)
@@ -147,7 +149,8 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
 
     // ---- this frame's list (ids ascending in all three sources) ----
     const int64_t *ids; const float4 *box; const int32_t *cls;
-    const int32_t *tsu = nullptr, *flag = nullptr, *order = nullptr, *inv = nullptr;
+    const int32_t *tsu = nullptr, *flag = nullptr, *streak = nullptr, *order = nullptr, *inv = nullptr;
+    bool early = false;                                    // OC-SORT: the first min_hits frames return every matched track
     int n;
     if (a.s_ids) {
         const size_t o = (size_t)sidx * a.s_stride;
@@ -157,6 +160,13 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         const int64_t *tm = a.t_meta + (size_t)sidx * 8;
         const int tc = (int)tm[0] & 1;
         ids = st->ids[tc]; box = st->box[tc]; cls = st->cls[tc]; tsu = st->tsu[tc];
+        n = (int)tm[1];
+    } else if (a.o_states) {
+        const OcState *st = a.o_states + sidx;
+        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
+        const int tc = (int)tm[0] & 1;
+        ids = st->ids[tc]; box = st->obox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; streak = st->streak[tc];
+        early = tm[5] <= (int64_t)a.o_min_hits;
         n = (int)tm[1];
     } else {
         const DsState *st = a.d_states + sidx;
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         bool f = false;
         if (i < n) {
             int2 c;
-            f = (!tsu || tsu[i] == a.report_tsu) && (!flag || flag[i] == 2) && cr_centroid(box[i], c);
+            f = (!tsu || tsu[i] == a.report_tsu) && (!flag || flag[i] == 2) && (!streak || early || streak[i] >= a.o_min_hits) && cr_centroid(box[i], c);
         }
         int tot;
         const int pos = n_pass + cr_block_scan(f ? 1 : 0, wsum, tot);
@@ -643,6 +653,22 @@ int rtmodt_crossing_process_deepsort(rtmodt_crossing *z, rtmodt_deepsort *ds, in
     RT_HIP(hipSetDevice(z->device));
     CrossArgs a = cr_args(z, frame_id);
     a.d_states = v.states; a.t_meta = v.meta; a.report_tsu = report_tsu;
+    RT_TRY(cr_launch(z, a, v.n_streams, v.stream));
+    CrEvHost h;
+    RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
+    return cr_deliver(z, h, 0, v.n_streams, false, events, n_events);
+}
+
+int rtmodt_crossing_process_ocsort(rtmodt_crossing *z, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
+    RT_CHECK(z && oc && n_events, RTMODT_E_INVALID, "bad argument");
+    OcDeviceView v;
+    RT_TRY(ocsort_device_view(oc, &v));
+    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
+    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
+             v.n_streams, v.max_tracks, z->S, z->Mc);
+    RT_HIP(hipSetDevice(z->device));
+    CrossArgs a = cr_args(z, frame_id);
+    a.o_states = v.states; a.o_min_hits = v.min_hits; a.t_meta = v.meta; a.report_tsu = 0;
     RT_TRY(cr_launch(z, a, v.n_streams, v.stream));
     CrEvHost h;
     RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));

@@ -309,6 +309,19 @@ int tracker_device_view_mut(rtmodt_tracker *trk, TrackerDeviceViewMut *out);
 struct DsDeviceView { const DsState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
 int deepsort_device_view(rtmodt_deepsort *ds, DsDeviceView *out);
 
+// OC-SORT (ocsort.hip): one stream's state; device pointers; double-buffered like DsState
+constexpr int OC_MAX_TRACKS = 256, OC_MAX_DETS = 1024, OC_MAX_STREAMS = 64, OC_RING = 8;      // OC_RING = the largest delta_t (a power of two)
+struct OcState {
+    int64_t *ids[2]; float4 *obox[2]; float *conf[2]; int32_t *cls[2];       // obox / conf / cls: the last observation (the birth detection before the first)
+    int32_t *hits[2], *streak[2], *age[2], *tsu[2];
+    float2 *dir[2];                                     // stored direction (dy, dx)
+    float4 *kf[2], *saved[2];                           // [5][max_tracks] as TrackerState::kf; saved = the state at the first missed frame
+    float4 *ring[2]; int32_t *ring_age[2];              // [OC_RING][max_tracks]: observation at age a in slot a % OC_RING, with its age (-1 none)
+};
+// its view for the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, n_returned, next_id, frame_count, ...}
+struct OcDeviceView { const OcState *states; const int64_t *meta; int n_streams, max_tracks, min_hits, device; hipStream_t stream; };
+int ocsort_device_view(rtmodt_ocsort *oc, OcDeviceView *out);
+
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };
 int detector_outputs(rtmodt_detector *det, DetOutputs *out);

@@ -1,6 +1,6 @@
-// track_dev.h -- device functions shared by the two trackers (tracker.hip: ByteTrack, deepsort.hip: DeepSORT): the bit-exact
-// IoU, the block-diagonal 8-state Kalman filter and the workgroup scan (moved here unchanged from tracker.hip), and the sparse
-// exact assignment both use (assoc_sparse; include lap.h first).
+// track_dev.h -- device functions shared by the trackers (tracker.hip: ByteTrack, deepsort.hip: DeepSORT, ocsort.hip: OC-SORT): the
+// bit-exact IoU, the block-diagonal 8-state Kalman filter and the workgroup scan (moved here unchanged from tracker.hip), the sparse
+// exact assignment all use (assoc_sparse; include lap.h first), and OC-SORT's fixed-sequence acos.
 // Include from a translation unit built with -ffp-contract=off and correctly rounded division (Makefile: EXACT), inside
 // namespace rtmodt.
 #pragma once
@@ -215,3 +215,43 @@ __device__ __forceinline__ void assoc_sparse(F edge, int n_rows, int n_cols, int
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------------------
+// acos of a float32 in [-1, 1] as a fixed sequence of float64 additions, multiplications and divisions -- each correctly rounded,
+// none contracted (fp contract off) -- so that the value is the same wherever it is built: no libm call, no float64 square root.
+// tests/ocsort_ref.py (acos_fixed) restates it operation for operation; its largest error against libm's acos is recorded in
+// DESIGN.md section 21.  asin(x) = x + x * z * P(z), z = x * x, P = the Taylor coefficients (2k)! / (4^k k!^2 (2k + 1)), k = 1..22.
+//   |x| <= 0.5   pi/2 - asin(x)
+//   |x| >  0.5   t = (1 - |x|) * 0.5 (exact), s = sqrt(t) by two Newton steps y = 0.5 * (y + t / y) from the correctly rounded
+//                float32 square root of float32(t); 2 * asin(s), reflected to pi - that for x < 0
+// ---------------------------------------------------------------------------------------
+constexpr double ACOS_PI = 0x1.921fb54442d18p+1, ACOS_HALF_PI = 0x1.921fb54442d18p+0;
+__device__ __forceinline__ double asin_poly(const double z) {
+    constexpr double C[22] = {0x1.5555555555555p-3, 0x1.3333333333333p-4, 0x1.6db6db6db6db7p-5, 0x1.f1c71c71c71c7p-6, 0x1.6e8ba2e8ba2e9p-6,
+                              0x1.1c4ec4ec4ec4fp-6, 0x1.c99999999999ap-7, 0x1.7a87878787878p-7, 0x1.3fde50d79435ep-7, 0x1.12ef3cf3cf3cfp-7,
+                              0x1.df3bd37a6f4dfp-8, 0x1.a6863d70a3d71p-8, 0x1.782dda12f684cp-8, 0x1.51ba308d3dcb1p-8, 0x1.31683bdef7bdfp-8,
+                              0x1.15ee9d45d1746p-8, 0x1.fcaf8fb6db6dbp-9, 0x1.d3d2a8e0dd67dp-9, 0x1.b026f57b13b14p-9, 0x1.90cb77f60c7cep-9,
+                              0x1.750de64d7d05fp-9, 0x1.5c5f56efaaaabp-9};
+    double p = C[21];
+#pragma unroll
+    for (int k = 20; k >= 0; --k) p = C[k] + z * p;
+    return p;
+}
+__device__ __forceinline__ double acos_fixed(const float c) {
+    const double x = (double)c;
+    const double a = x < 0.0 ? -x : x;
+    if (a <= 0.5) {
+        const double z = x * x;
+        return ACOS_HALF_PI - (x + x * (z * asin_poly(z)));
+    }
+    const double t = (1.0 - a) * 0.5;
+    double s = 0.0;
+    if (t != 0.0) {
+        double y = (double)__builtin_sqrtf((float)t);
+        y = 0.5 * (y + t / y);
+        y = 0.5 * (y + t / y);
+        s = y;
+    }
+    const double r = s + s * (t * asin_poly(t));
+    const double ac = 2.0 * r;
+    return x < 0.0 ? ACOS_PI - ac : ac;
+}

@@ -13,7 +13,8 @@ plain tripwires -- beside the zone engine, which stays bit-identical to the refe
 The per-frame work -- ledger upkeep, side tests, point-in-polygon, counts, event order -- runs in ``csrc/crossing.hip``
 (one launch per frame for all streams); there is no CPU implementation here.  ``tests/crossing_ref.py`` states the rules.
 Three ways in: ``process(tracks, frame_id)`` on a host list, and ``process_tracker(tracker, frame_id)`` straight on the
-device-resident state of a ``MultiObjectTracker`` / ``_ByteTrackCore`` or of a ``DeepSortTracker`` / ``_DeepSortCore``.
+device-resident state of a ``MultiObjectTracker`` / ``_ByteTrackCore``, a ``DeepSortTracker`` / ``_DeepSortCore`` or an
+``OcSortTracker`` / ``_OcSortCore``.
 """
 from __future__ import annotations
 
@@ -138,8 +139,10 @@ class CrossingCounter:
     def process_tracker(self, tracker, frame_id: int, class_names=None) -> list:
         """All streams of ``tracker`` at once, on its device-resident state.  Returns one event list per stream.  A
         ``MultiObjectTracker`` / ``_ByteTrackCore`` passes the tracks ``tracker.report`` names (``"matched"``: matched or spawned
-        this frame); a ``DeepSortTracker`` / ``_DeepSortCore`` its confirmed tracks matched this frame."""
+        this frame); a ``DeepSortTracker`` / ``_DeepSortCore`` its confirmed tracks matched this frame; an ``OcSortTracker`` /
+        ``_OcSortCore`` the tracks it returns this frame."""
         from ..tracking.deepsort import _DeepSortCore
+        from ..tracking.ocsort import _OcSortCore
         from ..tracking.tracker import _ByteTrackCore
         core = getattr(tracker, "_core", tracker)
         ev, n = C.cast(self._ev, C.c_void_p), _ffi.ptr(self._n)
@@ -148,8 +151,10 @@ class CrossingCounter:
             rc = _ffi.lib().rtmodt_crossing_process_tracker(self._h, core._h, int(frame_id), 1 if report == "matched" else 0, ev, n)
         elif isinstance(core, _DeepSortCore):
             rc = _ffi.lib().rtmodt_crossing_process_deepsort(self._h, core._h, int(frame_id), 0, ev, n)
+        elif isinstance(core, _OcSortCore):
+            rc = _ffi.lib().rtmodt_crossing_process_ocsort(self._h, core._h, int(frame_id), ev, n)
         else:
-            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack or the DeepSORT tracker; hand the tracks of a "
+            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT or the OC-SORT tracker; hand the tracks of a "
                             f"{type(tracker).__name__} over as a list: process(tracks, frame_id)")
         out = []
         if rc in (_ffi.OK, _ffi.E_CAPACITY):

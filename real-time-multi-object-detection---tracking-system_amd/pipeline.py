@@ -83,7 +83,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``visualization.MjpegRecorder`` encodes it on the GPU and appends it to an AVI.
 
     ``crossing_counter``: an ``events.CrossingCounter``, called where the event engine is called, inside a ``crossings`` stage: on
-    the tracker's device-resident state when the track list was not materialised (ByteTrack and DeepSORT alike), else on the list.
+    the tracker's device-resident state when the track list was not materialised (ByteTrack, DeepSORT and OC-SORT alike), else on the list.
     The summary then carries ``crossings``, the number of crossing events of stream 0.
 
     ``swap_guard``: a ``tracking.IdSwapGuard``, called right after ``tracker.update`` and before events, crossings and rendering,
@@ -112,9 +112,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         handoff = device_handoff and hasattr(tracker, "update_from_detector") and hasattr(detector, "model")
         # the track list stays on the device only when the event stage can read it there; an engine with the reference's
         # host API alone (`process(tracks, fid)`) must be handed the materialised list, trails included
-        # (and only a ByteTrack handle can be read there: the DeepSORT tracker hands its tracks over as a list, through process())
+        # (and only a ByteTrack handle can be read there: the DeepSORT and OC-SORT trackers hand their tracks over as a list, through
+        # process(); OcSortTracker says so with zone_events_on_device = False, DeepSortTracker by asking for the frame)
         needs_frame = bool(getattr(tracker, "needs_frame", False))
-        events_on_device = (handoff and not needs_frame and renderer is None and event_engine is not None
+        events_on_device = (handoff and not needs_frame and getattr(tracker, "zone_events_on_device", True) and renderer is None and event_engine is not None
                             and hasattr(event_engine, "process_tracker"))
         # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
         crossings_on_device = events_on_device

@@ -1,6 +1,7 @@
 from .deepsort import DeepSortTracker
+from .ocsort import OcSortTracker
 from .reid import ReidEmbedder
 from .swapguard import IdSwapGuard, SwapEvent
 from .tracker import MultiObjectTracker, Track
 
-__all__ = ["DeepSortTracker", "IdSwapGuard", "MultiObjectTracker", "ReidEmbedder", "SwapEvent", "Track"]
+__all__ = ["DeepSortTracker", "IdSwapGuard", "MultiObjectTracker", "OcSortTracker", "ReidEmbedder", "SwapEvent", "Track"]
