@@ -22,8 +22,11 @@
 
 #include "kernels.h"
 #include "polygon.h"
+#include "track_layout.h"
 
 namespace rtmodt {
+
+#include "wg_dev.h"
 
 constexpr int CR_THREADS = 256, CR_WAVES = CR_THREADS / 64;
 constexpr int CR_MAX_LINES = 32, CR_MAX_GATES = 32, CR_MAX_POINTS = 2048, CR_MAX_CLASSES = 256;
@@ -60,42 +63,9 @@ struct CrossArgs {
     rtmodt_crossing_event *ev; int32_t *ev_n;
 };
 
-__device__ __forceinline__ int cr_lower_bound(const int64_t *a, int n, int64_t x) {     // first index with a[i] >= x
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// exclusive prefix of a per-thread count over the workgroup; two barriers
-__device__ __forceinline__ int cr_block_scan(int v, int *wsum, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < CR_WAVES; ++w) {
-        const int s = wsum[w];
-        if (w < wave) off += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return off + incl - v;
-}
-
-__device__ __forceinline__ bool cr_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 // the zone engine's centroid (zones.hip), clamped to +-2^20; false: a coordinate is not finite, the track is not passed
 __device__ __forceinline__ bool cr_centroid(const float4 b, int2 &c) {
-    if (!(cr_finite(b.x) && cr_finite(b.y) && cr_finite(b.z) && cr_finite(b.w))) return false;
+    if (!(finite_bits(b.x) && finite_bits(b.y) && finite_bits(b.z) && finite_bits(b.w))) return false;
     float fx = (b.x + b.z) / 2.0f, fy = (b.y + b.w) / 2.0f;
     fx = fminf(fmaxf(fx, -(float)CR_LIMIT), (float)CR_LIMIT);
     fy = fminf(fmaxf(fy, -(float)CR_LIMIT), (float)CR_LIMIT);
@@ -200,7 +170,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
             f = (!tsu || tsu[i] == a.report_tsu) && (!flag || flag[i] == 2) && (!streak || early || streak[i] >= a.o_min_hits) && cr_centroid(box[i], c);
         }
         int tot;
-        const int pos = n_pass + cr_block_scan(f ? 1 : 0, wsum, tot);
+        const int pos = n_pass + block_scan_count<CR_WAVES>(f ? 1 : 0, wsum, tot);
         if (i < n) ppre[i] = pos;
         if (f) p_idx[pos] = i;
         n_pass += tot;
@@ -216,7 +186,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     __syncthreads();
     if (tid == 0 && !ascending) s_err = 0;
     auto passed_below = [&](int64_t x) {                                       // passed tracks of the list with an id < x
-        if (ascending) return ppre[cr_lower_bound(ids, n, x)];
+        if (ascending) return ppre[lower_bound_i64(ids, n, x)];
         int c = 0;
         for (int k = 0; k < n; ++k) c += ppre[k + 1] != ppre[k] && ids[k] < x ? 1 : 0;
         return c;
@@ -224,7 +194,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     // each finds its old row; a matched row is no idle row, and one that has expired is not this track's row either
     for (int t = tid; t < n_pass; t += CR_THREADS) {
         const int64_t id = ids[p_idx[t]];
-        const int j = cr_lower_bound(old_id, n_old, id);
+        const int j = lower_bound_i64(old_id, n_old, id);
         const bool hit = j < n_old && old_id[j] == id;
         oldpos[t] = hit && ret_pre[j] ? j : -1;
         if (hit) ret_pre[j] = 0;
@@ -235,7 +205,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         const int j = base + tid;
         const int f = j < n_old ? ret_pre[j] : 0;
         int tot;
-        const int pos = cr_block_scan(f, wsum, tot);
+        const int pos = block_scan_count<CR_WAVES>(f, wsum, tot);
         if (j < n_old) ret_pre[j] = f ? n_ret + pos : -(n_ret + pos) - 1;       // retained: rank; dropped: -(rank of next retained) - 1
         n_ret += tot;
     }
@@ -263,7 +233,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
             i = p_idx[t]; j = oldpos[t];
             cr_centroid(box[i], c);
             const int tp = ascending ? t : passed_below(ids[i]);
-            np = overflow ? tp : tp + ranks_below(cr_lower_bound(old_id, n_old, ids[i]));
+            np = overflow ? tp : tp + ranks_below(lower_bound_i64(old_id, n_old, ids[i]));
             if (sub < L) {
                 const int4 ab = line[sub];
                 const int sd = cr_side(ab.x, ab.y, ab.z, ab.w, c.x, c.y);
@@ -336,7 +306,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
             if (ppre[i + 1] != ppre[i]) { t = ppre[i]; ev = evmask[t]; }
         }
         int tot;
-        int pos = n_ev + cr_block_scan(__popcll(ev), wsum, tot);
+        int pos = n_ev + block_scan_count<CR_WAVES>(__popcll(ev), wsum, tot);
         if (ev) {
             const int j = oldpos[t];                                          // a crossing or an exit always has an old row
             const float4 b = box[i];
@@ -401,19 +371,9 @@ struct rtmodt_crossing {
 
 namespace {
 
-struct CrCarver {
-    char *base; size_t off = 0;
-    template <typename T> T *take(size_t count) {
-        off = align_up(off, 16);
-        T *p = base ? (T *)(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 // lays out every device array; base == nullptr -> size only
 size_t cr_carve(rtmodt_crossing *z, char *base) {
-    CrCarver c{base};
+    Carver c{base};
     const size_t S = z->S, cap = z->cap, L = z->L, G = z->G, E = z->max_events, Gs = std::max(z->G, 1);
     const int4 *line = c.take<int4>(std::max(z->L, 1));
     const int32_t *dir = c.take<int32_t>(std::max<size_t>(L + G, 1));
@@ -509,6 +469,22 @@ int cr_sync_own(rtmodt_crossing *z) {
     RT_HIP(hipSetDevice(z->device));
     RT_HIP(hipStreamSynchronize(z->stream));
     return RTMODT_OK;
+}
+
+// one frame on a tracker's device-resident state: `fill` sets the source's own fields of CrossArgs
+template <typename F> int cr_process_view(rtmodt_crossing *z, const TrackViewBase &v, int64_t frame_id, rtmodt_crossing_event *events,
+                                                 int32_t *n_events, F fill) {
+    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
+    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
+             v.n_streams, v.max_tracks, z->S, z->Mc);
+    RT_HIP(hipSetDevice(z->device));
+    CrossArgs a = cr_args(z, frame_id);
+    a.t_meta = v.meta;
+    fill(a);
+    RT_TRY(cr_launch(z, a, v.n_streams, v.stream));         // the stream the tracker's last update ran on: ordered after it
+    CrEvHost h;
+    RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
+    return cr_deliver(z, h, 0, v.n_streams, false, events, n_events);
 }
 
 }  // namespace
@@ -630,16 +606,7 @@ int rtmodt_crossing_process_tracker(rtmodt_crossing *z, rtmodt_tracker *trk, int
     RT_CHECK(z && trk && n_events, RTMODT_E_INVALID, "bad argument");
     TrackerDeviceView v;
     RT_TRY(tracker_device_view(trk, &v));
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
-    RT_HIP(hipSetDevice(z->device));
-    CrossArgs a = cr_args(z, frame_id);
-    a.t_states = v.states; a.t_meta = v.meta; a.report_tsu = report_tsu;
-    RT_TRY(cr_launch(z, a, v.n_streams, v.stream));         // the stream the tracker's last update ran on: ordered after it
-    CrEvHost h;
-    RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
-    return cr_deliver(z, h, 0, v.n_streams, false, events, n_events);
+    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.t_states = v.states; a.report_tsu = report_tsu; });
 }
 
 int rtmodt_crossing_process_deepsort(rtmodt_crossing *z, rtmodt_deepsort *ds, int64_t frame_id, int report_tsu, rtmodt_crossing_event *events,
@@ -647,32 +614,14 @@ int rtmodt_crossing_process_deepsort(rtmodt_crossing *z, rtmodt_deepsort *ds, in
     RT_CHECK(z && ds && n_events, RTMODT_E_INVALID, "bad argument");
     DsDeviceView v;
     RT_TRY(deepsort_device_view(ds, &v));
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
-    RT_HIP(hipSetDevice(z->device));
-    CrossArgs a = cr_args(z, frame_id);
-    a.d_states = v.states; a.t_meta = v.meta; a.report_tsu = report_tsu;
-    RT_TRY(cr_launch(z, a, v.n_streams, v.stream));
-    CrEvHost h;
-    RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
-    return cr_deliver(z, h, 0, v.n_streams, false, events, n_events);
+    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.d_states = v.states; a.report_tsu = report_tsu; });
 }
 
 int rtmodt_crossing_process_ocsort(rtmodt_crossing *z, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
     RT_CHECK(z && oc && n_events, RTMODT_E_INVALID, "bad argument");
     OcDeviceView v;
     RT_TRY(ocsort_device_view(oc, &v));
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
-    RT_HIP(hipSetDevice(z->device));
-    CrossArgs a = cr_args(z, frame_id);
-    a.o_states = v.states; a.o_min_hits = v.min_hits; a.t_meta = v.meta; a.report_tsu = 0;
-    RT_TRY(cr_launch(z, a, v.n_streams, v.stream));
-    CrEvHost h;
-    RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
-    return cr_deliver(z, h, 0, v.n_streams, false, events, n_events);
+    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.o_states = v.states; a.o_min_hits = v.min_hits; a.report_tsu = 0; });
 }
 
 int rtmodt_crossing_counts(rtmodt_crossing *z, int stream, int64_t *line_total, int64_t *line_class, int64_t *gate_total, int64_t *gate_class) {

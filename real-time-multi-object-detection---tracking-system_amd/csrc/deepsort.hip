@@ -25,7 +25,7 @@
 // contested-pair limits (256 rows / 256 columns / 2048 pairs) raise the sticky error 2.
 #include <vector>
 
-#include "kernels.h"
+#include "track_host.h"
 #include "lap.h"
 
 #include <climits>
@@ -47,21 +47,6 @@ struct DsArgs {
 
 constexpr float DS_GATE = 9.4877f;           // chi-square 0.95 quantile, 4 degrees of freedom (deep_sort kalman_filter.chi2inv95[4])
 constexpr long long DS_DOT_ONE = 16129;      // 127 * 127
-
-// compacts the indices i < n with flag(i) into list (ascending); returns their number.  Ends with a barrier.
-template <typename F> __device__ __forceinline__ int ds_compact(F flag, int n, int *list, int *wsum) {
-    int cnt = 0;
-    for (int base = 0; base < n; base += TRK_THREADS) {
-        const int i = base + threadIdx.x;
-        const bool f = i < n && flag(i);
-        int tot;
-        const int pos = block_scan_flag(f, wsum, tot);
-        if (f) list[cnt + pos] = i;
-        cnt += tot;
-    }
-    __syncthreads();
-    return cnt;
-}
 
 __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -129,7 +114,7 @@ __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
     }
     // ---- confidence filter, input order kept ----
     const float min_conf = a.min_conf;
-    const int nd = ds_compact([&](int i) { return gc[i] >= min_conf; }, n, draw, wsum);
+    const int nd = block_compact([&](int i) { return gc[i] >= min_conf; }, n, draw, wsum);
     for (int j = tid; j < nd; j += TRK_THREADS) {
         const float4 b = gb[draw[j]];
         dbox[j] = b;
@@ -157,9 +142,9 @@ __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
     };
     const int maxlv = min(a.max_age, s_maxlv);
     for (int lv = 1; lv <= maxlv; ++lv) {
-        const int nr = ds_compact([&](int i) { return t_flag[i] == 2 && t_tsu[i] == lv; }, M, rows, wsum);
+        const int nr = block_compact([&](int i) { return t_flag[i] == 2 && t_tsu[i] == lv; }, M, rows, wsum);
         if (nr == 0) continue;
-        const int nc = ds_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum);
+        const int nc = block_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum);
         if (nc == 0) break;
         assoc_sparse<long long>(edge_app, nr, nc, row_best, col_winner, rowcand, Li, wsum, &lap_err);
         for (int r = tid; r < nr; r += TRK_THREADS) {
@@ -179,8 +164,8 @@ __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
             cost = cd - limit;
             return true;
         };
-        const int nr = ds_compact([&](int i) { return t_match[i] < 0 && (t_flag[i] == 1 || t_tsu[i] == 1); }, M, rows, wsum);
-        const int nc = nr ? ds_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum) : 0;
+        const int nr = block_compact([&](int i) { return t_match[i] < 0 && (t_flag[i] == 1 || t_tsu[i] == 1); }, M, rows, wsum);
+        const int nc = nr ? block_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum) : 0;
         if (nr > 0 && nc > 0) {
             assoc_sparse<double>(edge_iou, nr, nc, row_best, col_winner, rowcand, Ld, wsum, &lap_err);
             for (int r = tid; r < nr; r += TRK_THREADS) {
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
         }
     }
     __syncthreads();
-    const int kept = ds_compact([&](int i) { return t_match[i] >= 0 || (t_flag[i] == 2 && t_tsu[i] <= a.max_age); }, M, rows, wsum);
+    const int kept = block_compact([&](int i) { return t_match[i] >= 0 || (t_flag[i] == 2 && t_tsu[i] <= a.max_age); }, M, rows, wsum);
     for (int i = tid; i < M; i += TRK_THREADS) t_new[i] = -1;
     __syncthreads();
     for (int o = tid; o < kept; o += TRK_THREADS) t_new[rows[o]] = o;
@@ -232,10 +217,10 @@ __global__ __launch_bounds__(TRK_THREADS) void deepsort_update(DsArgs a) {
     }
     __syncthreads();                                       // slot_used is final for the old tracks
     // ---- new tentative tracks, detection order ----
-    int nsp = ds_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum);
+    int nsp = block_compact([&](int j) { return d_match[j] < 0; }, nd, cols, wsum);
     int err = 0;
     if (kept + nsp > Mc) { err = 1; nsp = Mc - kept; }
-    const int nfree = ds_compact([&](int q) { return st.slot_used[q] == 0; }, Mc, rows, wsum);
+    const int nfree = block_compact([&](int q) { return st.slot_used[q] == 0; }, Mc, rows, wsum);
     if (nsp > nfree) { err = 1; nsp = nfree; }             // (cannot happen: free slots = Mc - kept)
     for (int k = tid; k < nsp; k += TRK_THREADS) {
         const int j = cols[k], o = kept + k, q = rows[k];
@@ -278,79 +263,41 @@ static int launch_deepsort_update(const DsArgs &a, int n_streams, hipStream_t s)
 
 using namespace rtmodt;
 
-struct rtmodt_deepsort {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t foreign_done = nullptr;       // as rtmodt_tracker: an update fed from a detector runs on that detector's stream
-    bool foreign_pending = false;
+struct rtmodt_deepsort : TrackHandleBase {
     hipEvent_t ev[4] = {};                   // describe | distance | update boundaries of the last call
     bool timed = false, described = false;
-    int S = 1, Mc = 0, Nc = 0, budget = 0, dim = APP_DIM;
+    int budget = 0, dim = APP_DIM;
     float min_conf = 0.3f; double max_dist = 0.2, max_iou = 0.7; long long thr = 0; int max_age = 70, n_init = 3;
-    char *pool = nullptr; int8_t *gallery = nullptr;
+    char *pool = nullptr; int8_t *gallery = nullptr;      // pool: all state arrays (track_layout.h: carve_deepsort)
     DsState *d_states = nullptr; std::vector<DsState> h_states;
-    int64_t *d_meta = nullptr, *h_meta = nullptr;
-    float4 *d_box = nullptr; float *d_conf = nullptr; int32_t *d_cls = nullptr, *d_n = nullptr, *h_n = nullptr;
     int8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_dotmax = nullptr;
     uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
     rtmodt_reid *reid = nullptr;             // embedder = a .rtreid file: the network of reid.hip describes the boxes instead of the histogram
 };
 
-static const int64_t ds_init_meta[8] = {0, 0, 0, 0, 1, 0, 0, 0};
 static size_t ds_gallery_stream_bytes(const rtmodt_deepsort *t) { return (size_t)t->Mc * t->budget * t->dim; }
-
-static int ds_join(rtmodt_deepsort *t) {
-    if (t->foreign_pending) {
-        RT_HIP(hipStreamWaitEvent(t->stream, t->foreign_done, 0));
-        t->foreign_pending = false;
-    }
-    return RTMODT_OK;
-}
 
 namespace rtmodt {
 int deepsort_device_view(rtmodt_deepsort *t, DsDeviceView *out) {
     RT_CHECK(t && out, RTMODT_E_INVALID, "null argument");
-    *out = DsDeviceView{t->d_states, t->d_meta, t->S, t->Mc, t->device, t->stream};
-    return ds_join(t);                                     // the caller's work on t->stream is ordered behind every update
+    out->states = t->d_states;
+    return track_view(t, out);
 }
 }  // namespace rtmodt
 
 static int ds_create_impl(rtmodt_deepsort *t) {
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    RT_HIP(hipEventCreateWithFlags(&t->foreign_done, hipEventDisableTiming));
+    RT_TRY(track_open(t));
     for (auto &e : t->ev) RT_HIP(hipEventCreate(&e));
-    const size_t M = (size_t)t->Mc;
-    auto a16 = [](size_t v) { return align_up(v, 16); };   // every sub-array starts on a 16-byte boundary, whatever max_tracks is
-    const size_t per_buf = a16(M * 80) + a16(M * 16) + a16(M * 8) + 8 * a16(M * 4), per_stream = per_buf * 2 + a16(M * 4);
-    RT_HIP(hipMalloc((void **)&t->pool, per_stream * t->S));
-    RT_HIP(hipMemset(t->pool, 0, per_stream * t->S));
-    t->h_states.resize(t->S);
-    char *p = t->pool;
-    for (int s = 0; s < t->S; ++s) {
-        DsState &st = t->h_states[s];
-        for (int b = 0; b < 2; ++b) {
-            st.kf[b] = (float4 *)p; p += a16(M * 80);
-            st.dbox[b] = (float4 *)p; p += a16(M * 16);
-            st.ids[b] = (int64_t *)p; p += a16(M * 8);
-            st.conf[b] = (float *)p; p += a16(M * 4);
-            int32_t **f[] = {&st.cls[b], &st.flag[b], &st.hits[b], &st.age[b], &st.tsu[b], &st.slot[b], &st.gcount[b]};
-            for (auto q : f) { *q = (int32_t *)p; p += a16(M * 4); }
-        }
-        st.slot_used = (int32_t *)p; p += a16(M * 4);
-    }
+    t->h_states.assign(t->S, DsState{});
+    const size_t total = carve_deepsort(t->h_states.data(), t->S, t->Mc, nullptr);
+    RT_HIP(hipMalloc((void **)&t->pool, total));
+    RT_HIP(hipMemset(t->pool, 0, total));
+    carve_deepsort(t->h_states.data(), t->S, t->Mc, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(DsState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(DsState) * t->S, hipMemcpyHostToDevice));
     RT_HIP(hipMalloc((void **)&t->gallery, ds_gallery_stream_bytes(t) * t->S));
     RT_HIP(hipMemset(t->gallery, 0, ds_gallery_stream_bytes(t) * t->S));
-    RT_HIP(hipMalloc((void **)&t->d_meta, sizeof(int64_t) * 8 * t->S));
-    RT_HIP(hipHostMalloc((void **)&t->h_meta, sizeof(int64_t) * 8 * t->S, hipHostMallocDefault));
-    RT_HIP(hipHostMalloc((void **)&t->h_n, sizeof(int32_t) * t->S, hipHostMallocDefault));
-    for (int s = 0; s < t->S; ++s) memcpy(t->h_meta + 8 * s, ds_init_meta, sizeof(ds_init_meta));
-    RT_HIP(hipMemcpy(t->d_meta, t->h_meta, sizeof(int64_t) * 8 * t->S, hipMemcpyHostToDevice));
     const size_t SN = (size_t)t->S * t->Nc;
-    RT_HIP(hipMalloc((void **)&t->d_box, SN * 16)); RT_HIP(hipMalloc((void **)&t->d_conf, SN * 4)); RT_HIP(hipMalloc((void **)&t->d_cls, SN * 4));
-    RT_HIP(hipMalloc((void **)&t->d_n, (size_t)t->S * 4)); RT_HIP(hipMemset(t->d_n, 0, (size_t)t->S * 4));
     RT_HIP(hipMalloc((void **)&t->d_desc, SN * t->dim)); RT_HIP(hipMemset(t->d_desc, 0, SN * t->dim));
     RT_HIP(hipMalloc((void **)&t->d_counts, SN * APP_DIM * 4));
     RT_HIP(hipMalloc((void **)&t->d_dotmax, (size_t)t->S * t->Mc * t->Nc * 4));
@@ -395,12 +342,7 @@ static DsArgs ds_args(rtmodt_deepsort *t) {
     return a;
 }
 
-static int ds_check_sticky(rtmodt_deepsort *t, int s, int64_t err) {
-    RT_CHECK(err != 1, RTMODT_E_CAPACITY, "stream %d: more than max_tracks=%d live tracks", s, t->Mc);
-    RT_CHECK(err != 2, RTMODT_E_CAPACITY, "stream %d: assignment too dense (more than 256 contested rows/columns or 2048 contested pairs)", s);
-    RT_CHECK(err == 0, RTMODT_E_INVALID, "stream %d: tracker error %lld", s, (long long)err);
-    return RTMODT_OK;
-}
+static int ds_check_sticky(rtmodt_deepsort *t, int s, int64_t err) { return track_check_sticky(t, s, err, "assignment"); }
 
 // frames of a call -> device pointers (host frames are staged on stream q)
 static int ds_frames(rtmodt_deepsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
@@ -430,17 +372,12 @@ extern "C" {
 
 void rtmodt_deepsort_destroy(rtmodt_deepsort *t) {
     if (!t) return;
-    hipSetDevice(t->device);
-    if (t->foreign_done) hipEventSynchronize(t->foreign_done);
-    if (t->stream) hipStreamSynchronize(t->stream);
-    if (t->foreign_done) hipEventDestroy(t->foreign_done);
-    for (auto &e : t->ev) if (e) hipEventDestroy(e);
-    hipFree(t->pool); hipFree(t->gallery); hipFree(t->d_states); hipFree(t->d_meta);
-    hipFree(t->d_box); hipFree(t->d_conf); hipFree(t->d_cls); hipFree(t->d_n); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dotmax);
-    hipFree(t->d_frames);
-    reid_close(t->reid);
-    hipHostFree(t->h_meta); hipHostFree(t->h_n);
-    if (t->stream) hipStreamDestroy(t->stream);
+    track_close(t, [t] {
+        for (auto &e : t->ev) if (e) hipEventDestroy(e);
+        hipFree(t->pool); hipFree(t->gallery); hipFree(t->d_states); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dotmax);
+        hipFree(t->d_frames);
+        reid_close(t->reid);
+    });
     delete t;
 }
 
@@ -469,57 +406,31 @@ int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out
     t->thr = (long long)std::floor(cfg->max_dist * 16129.0);
     int rc = net ? reid_open(cfg->embedder, cfg->device, cfg->n_streams, cfg->max_dets, false, &t->reid) : RTMODT_OK;     // the file is checked before the device is touched
     if (rc == RTMODT_OK) rc = ds_create_impl(t);
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_deepsort_destroy(t);
-        last_error() = keep;
-        return rc;
-    }
-    *out = t;
-    return RTMODT_OK;
+    return track_created(rc, t, rtmodt_deepsort_destroy, out);
 }
 
 int rtmodt_deepsort_reset(rtmodt_deepsort *t, int stream) {
-    RT_CHECK(t && stream < t->S, RTMODT_E_INVALID, "bad argument");
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipDeviceSynchronize());
-    t->foreign_pending = false;
+    RT_TRY(track_reset_meta(t, stream));
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->S : stream + 1;
-    for (int s = s0; s < s1; ++s) {
-        RT_HIP(hipMemcpy(t->d_meta + 8 * s, ds_init_meta, sizeof(ds_init_meta), hipMemcpyHostToDevice));
-        RT_HIP(hipMemset(t->h_states[s].slot_used, 0, (size_t)t->Mc * 4));
-    }
+    for (int s = s0; s < s1; ++s) RT_HIP(hipMemset(t->h_states[s].slot_used, 0, (size_t)t->Mc * 4));
     return RTMODT_OK;
 }
 
 int rtmodt_deepsort_update_batch(rtmodt_deepsort *t, const float *xyxy, const float *conf, const int32_t *cls, const int32_t *n,
                                  const uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind, const int8_t *desc,
                                  int32_t *n_returned_out) {
-    RT_CHECK(t && n, RTMODT_E_INVALID, "null argument");
     bool any = false;
-    for (int s = 0; s < t->S; ++s) {
-        RT_CHECK(n[s] >= 0, RTMODT_E_INVALID, "stream %d: %d detections", s, n[s]);
-        RT_CHECK(n[s] <= t->Nc, RTMODT_E_CAPACITY, "stream %d: %d detections > max_dets %d", s, n[s], t->Nc);
-        any |= n[s] > 0;
-    }
-    RT_CHECK(!any || (xyxy && conf && cls), RTMODT_E_INVALID, "null detections");
+    RT_TRY(track_batch_check(t, xyxy, conf, cls, n, &any));
     RT_CHECK(!(frames && desc), RTMODT_E_INVALID, "give frames or descriptors, not both");
     RT_CHECK(!(t->reid && desc), RTMODT_E_INVALID, "this handle computes its descriptors with its embedder network: give frames, not descriptors");
     RT_CHECK(!any || frames || desc, RTMODT_E_INVALID, "detections need frames (built-in descriptor) or caller descriptors");
     RT_HIP(hipSetDevice(t->device));
-    RT_TRY(ds_join(t));
+    RT_TRY(track_join(t));
     hipStream_t q = t->stream;
     AppFrames fp{};
     if (frames && any) RT_TRY(ds_frames(t, frames, t->S, h, w, stride_bytes, mem_kind, q, &fp));
-    const size_t SN = (size_t)t->S * t->Nc;
-    for (int s = 0; s < t->S; ++s) t->h_n[s] = n[s];
-    if (any) {
-        RT_HIP(hipMemcpyAsync(t->d_box, xyxy, SN * 16, hipMemcpyHostToDevice, q));
-        RT_HIP(hipMemcpyAsync(t->d_conf, conf, SN * 4, hipMemcpyHostToDevice, q));
-        RT_HIP(hipMemcpyAsync(t->d_cls, cls, SN * 4, hipMemcpyHostToDevice, q));
-        if (desc) RT_HIP(hipMemcpyAsync(t->d_desc, desc, SN * t->dim, hipMemcpyHostToDevice, q));
-    }
-    RT_HIP(hipMemcpyAsync(t->d_n, t->h_n, (size_t)t->S * 4, hipMemcpyHostToDevice, q));
+    RT_TRY(track_batch_stage(t, xyxy, conf, cls, n, any));
+    if (any && desc) RT_HIP(hipMemcpyAsync(t->d_desc, desc, (size_t)t->S * t->Nc * t->dim, hipMemcpyHostToDevice, q));
     RT_TRY(ds_run(t, ds_args(t), t->S, frames && any ? &fp : nullptr, h, w, stride_bytes, q));
     RT_HIP(hipMemcpyAsync(t->h_meta, t->d_meta, sizeof(int64_t) * 8 * t->S, hipMemcpyDeviceToHost, q));
     RT_HIP(hipStreamSynchronize(q));
@@ -534,27 +445,22 @@ int rtmodt_deepsort_update_from_detector(rtmodt_deepsort *t, rtmodt_detector *de
                                          int stride_bytes, int mem_kind) {
     RT_CHECK(t && det && frames, RTMODT_E_INVALID, "null argument");
     DetOutputs o;
-    RT_TRY(detector_outputs(det, &o));
-    RT_CHECK(o.device == t->device, RTMODT_E_INVALID, "tracker on device %d, detector on device %d", t->device, o.device);
+    RT_TRY(track_detector_outputs(t, det, &o));
     RT_CHECK(n_frames == o.count, RTMODT_E_INVALID, "%d frames for the detector's batch of %d", n_frames, o.count);
-    RT_CHECK(o.count >= 1 && o.count <= t->S, RTMODT_E_INVALID, "%d frames > tracker streams %d", o.count, t->S);
-    RT_CHECK(o.stride <= t->Nc, RTMODT_E_CAPACITY, "detector max_det %d > tracker max_dets %d", o.stride, t->Nc);
-    RT_HIP(hipSetDevice(t->device));
+    RT_TRY(track_detector_fits(t, o, o.count));
     AppFrames fp{};
     RT_TRY(ds_frames(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
     DsArgs a = ds_args(t);
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
     RT_TRY(ds_run(t, a, o.count, &fp, h, w, stride_bytes, o.stream));
-    RT_HIP(hipEventRecord(t->foreign_done, o.stream));
-    t->foreign_pending = true;
-    return RTMODT_OK;
+    return track_detector_done(t, o.stream);
 }
 
 int rtmodt_deepsort_state(rtmodt_deepsort *t, int stream, int64_t *ids, int32_t *state, int32_t *hits, int32_t *age, int32_t *tsu, float *xyxy,
                           float *conf, int32_t *cls, float *mean, float *cov, int32_t *gallery_count, int8_t *gallery, int32_t *n, int64_t *next_id) {
     RT_CHECK(t && stream >= 0 && stream < t->S, RTMODT_E_INVALID, "bad argument");
     RT_HIP(hipSetDevice(t->device));
-    RT_TRY(ds_join(t));
+    RT_TRY(track_join(t));
     RT_HIP(hipStreamSynchronize(t->stream));
     int64_t m[8];
     RT_HIP(hipMemcpy(m, t->d_meta + 8 * stream, sizeof(m), hipMemcpyDeviceToHost));
@@ -576,15 +482,7 @@ int rtmodt_deepsort_state(rtmodt_deepsort *t, int stream, int64_t *ids, int32_t 
     if (mean || cov) {
         std::vector<float4> buf((size_t)5 * t->Mc);
         RT_HIP(hipMemcpy(buf.data(), st.kf[cur], buf.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (int i = 0; i < cnt; ++i) {
-            const float4 pos = buf[i], vel = buf[t->Mc + i], pa = buf[2 * (size_t)t->Mc + i], pb = buf[3 * (size_t)t->Mc + i], pc = buf[4 * (size_t)t->Mc + i];
-            if (mean) { float *o = mean + 8 * (size_t)i; o[0] = pos.x; o[1] = pos.y; o[2] = pos.z; o[3] = pos.w; o[4] = vel.x; o[5] = vel.y; o[6] = vel.z; o[7] = vel.w; }
-            if (cov) {
-                float *o = cov + 12 * (size_t)i;
-                o[0] = pa.x; o[1] = pb.x; o[2] = pc.x; o[3] = pa.y; o[4] = pb.y; o[5] = pc.y;
-                o[6] = pa.z; o[7] = pb.z; o[8] = pc.z; o[9] = pa.w; o[10] = pb.w; o[11] = pc.w;
-            }
-        }
+        kalman_unpack(&buf[0].x, t->Mc, cnt, mean, cov);
     }
     if (gallery_count || gallery) {
         std::vector<int32_t> slot(c), total(c);

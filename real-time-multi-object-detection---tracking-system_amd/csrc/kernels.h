@@ -297,16 +297,18 @@ void reid_close(rtmodt_reid *e);
 int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, int pitch, const float4 *box, const int32_t *box_n, int box_stride,
              int launch_mb, int8_t *desc, int desc_stride, hipStream_t q);
 
-// the tracker's device-resident state (tracker_api.hip), consumed by the zone engine (zones.hip):
-// states[n_streams], meta[n_streams][8] = {cur, n_tracks, err, n_active, next_id, ...}; `stream` is the HIP stream
-// the tracker's most recent update was launched on
-struct TrackerDeviceView { const TrackerState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+// A tracker's device-resident state as its consumers see it.  The part all three trackers share (track_host.h fills it):
+// meta[n_streams][8] = {cur, n_tracks, err, n_active, next_id, ...}; `stream` is the HIP stream the tracker's most recent update
+// was launched on
+struct TrackViewBase { const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+// ByteTrack (tracker_api.hip), consumed by the zone engine (zones.hip) and the crossing counter (crossing.hip): states[n_streams]
+struct TrackerDeviceView : TrackViewBase { const TrackerState *states; };
 int tracker_device_view(rtmodt_tracker *trk, TrackerDeviceView *out);
 // its mutable counterpart, for the one consumer that writes the state: the swap guard (swapguard.hip) exchanges two track ids in place
-struct TrackerDeviceViewMut { TrackerState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+struct TrackerDeviceViewMut : TrackViewBase { TrackerState *states; };
 int tracker_device_view_mut(rtmodt_tracker *trk, TrackerDeviceViewMut *out);
 // the same of the DeepSORT tracker (deepsort.hip), consumed by the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, ...}
-struct DsDeviceView { const DsState *states; const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
+struct DsDeviceView : TrackViewBase { const DsState *states; };
 int deepsort_device_view(rtmodt_deepsort *ds, DsDeviceView *out);
 
 // OC-SORT (ocsort.hip): one stream's state; device pointers; double-buffered like DsState
@@ -319,7 +321,7 @@ struct OcState {
     float4 *ring[2]; int32_t *ring_age[2];              // [OC_RING][max_tracks]: observation at age a in slot a % OC_RING, with its age (-1 none)
 };
 // its view for the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, n_returned, next_id, frame_count, ...}
-struct OcDeviceView { const OcState *states; const int64_t *meta; int n_streams, max_tracks, min_hits, device; hipStream_t stream; };
+struct OcDeviceView : TrackViewBase { const OcState *states; int min_hits; };
 int ocsort_device_view(rtmodt_ocsort *oc, OcDeviceView *out);
 
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker

@@ -37,7 +37,7 @@
 // pairs below the threshold afterwards.  lap.h's contested-pair limits (256 rows / 256 columns / 2048 pairs) raise the sticky error 2.
 #include <vector>
 
-#include "kernels.h"
+#include "track_host.h"
 #include "lap.h"
 
 #include <climits>
@@ -46,6 +46,7 @@
 namespace rtmodt {
 
 #include "track_dev.h"
+#include "wg_dev.h"
 
 struct OcArgs {
     int max_tracks, max_dets;
@@ -54,22 +55,6 @@ struct OcArgs {
     const float4 *det_box; const float *det_conf; const int32_t *det_cls; const int32_t *det_n; int det_stride;
 };
 
-// compacts the indices i < n with flag(i) into list (ascending); returns their number.  Ends with a barrier.
-template <typename F> __device__ __forceinline__ int oc_compact(F flag, int n, int *list, int *wsum) {
-    int cnt = 0;
-    for (int base = 0; base < n; base += TRK_THREADS) {
-        const int i = base + threadIdx.x;
-        const bool f = i < n && flag(i);
-        int tot;
-        const int pos = block_scan_flag(f, wsum, tot);
-        if (f) list[cnt + pos] = i;
-        cnt += tot;
-    }
-    __syncthreads();
-    return cnt;
-}
-
-__device__ __forceinline__ bool oc_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ void oc_predict(Kf &k) {
     kf_predict1(k.pos.x, k.vel.x, k.pa.x, k.pb.x, k.pc.x, 1.0f, 1e-2f);
     kf_predict1(k.pos.y, k.vel.y, k.pa.y, k.pb.y, k.pc.y, 1.0f, 1e-2f);
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
         }
         tref[i] = oc_centre(ref);
         tdir[i] = c_dir[i];
-        const bool alive = oc_finite(pb.x) && oc_finite(pb.y) && oc_finite(pb.z) && oc_finite(pb.w);
+        const bool alive = finite_bits(pb.x) && finite_bits(pb.y) && finite_bits(pb.z) && finite_bits(pb.w);
         t_flag[i] = (alive ? OC_ALIVE : 0) | (c_hits[i] > 0 ? OC_HAS_OBS : 0);
         t_match[i] = -1;
     }
@@ -218,8 +203,8 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
             cost = -g;
             return true;
         };
-        const int nr = oc_compact([&](int i) { return (t_flag[i] & OC_ALIVE) != 0; }, M, rows, wsum);
-        const int nc = nr ? oc_compact(is_high, n, cols, wsum) : 0;
+        const int nr = block_compact([&](int i) { return (t_flag[i] & OC_ALIVE) != 0; }, M, rows, wsum);
+        const int nc = nr ? block_compact(is_high, n, cols, wsum) : 0;
         if (nr > 0 && nc > 0) {
             assoc_sparse<double>(edge, nr, nc, row_best, col_winner, rowcand, L, wsum, &shared[0]);
             take(nr);
@@ -233,8 +218,8 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
         return true;
     };
     if (a.use_byte) {
-        const int nr = oc_compact([&](int i) { return (t_flag[i] & OC_ALIVE) && t_match[i] < 0; }, M, rows, wsum);
-        const int nc = nr ? oc_compact(is_low, n, cols, wsum) : 0;
+        const int nr = block_compact([&](int i) { return (t_flag[i] & OC_ALIVE) && t_match[i] < 0; }, M, rows, wsum);
+        const int nc = nr ? block_compact(is_low, n, cols, wsum) : 0;
         if (nr > 0 && nc > 0) {
             assoc_sparse<double>(edge_pred, nr, nc, row_best, col_winner, rowcand, L, wsum, &shared[0]);
             take(nr);
@@ -248,8 +233,8 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
             cost = -(double)v;
             return true;
         };
-        const int nr = oc_compact([&](int i) { return t_flag[i] == (OC_ALIVE | OC_HAS_OBS) && t_match[i] < 0; }, M, rows, wsum);
-        const int nc = nr ? oc_compact([&](int j) { return is_high(j) && !d_used[j]; }, n, cols, wsum) : 0;
+        const int nr = block_compact([&](int i) { return t_flag[i] == (OC_ALIVE | OC_HAS_OBS) && t_match[i] < 0; }, M, rows, wsum);
+        const int nc = nr ? block_compact([&](int j) { return is_high(j) && !d_used[j]; }, n, cols, wsum) : 0;
         if (nr > 0 && nc > 0) {
             assoc_sparse<double>(edge_last, nr, nc, row_best, col_winner, rowcand, L, wsum, &shared[0]);
             take(nr);
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
     }
 
     // ---- update, deaths, compaction into the other buffer ----
-    const int kept = oc_compact([&](int i) { return (t_flag[i] & OC_ALIVE) && (t_match[i] >= 0 || t_tsu[i] <= a.max_age); }, M, rows, wsum);
+    const int kept = block_compact([&](int i) { return (t_flag[i] & OC_ALIVE) && (t_match[i] >= 0 || t_tsu[i] <= a.max_age); }, M, rows, wsum);
     for (int i = tid; i < M; i += TRK_THREADS) t_new[i] = -1;
     __syncthreads();
     for (int o = tid; o < kept; o += TRK_THREADS) t_new[rows[o]] = o;
@@ -314,7 +299,7 @@ __global__ __launch_bounds__(TRK_THREADS) void ocsort_update(OcArgs a) {
         kf_store(n_saved, Mc, o, sv);
     }
     // ---- births, detection order ----
-    int nsp = oc_compact([&](int j) { return is_high(j) && !d_used[j]; }, n, cols, wsum);
+    int nsp = block_compact([&](int j) { return is_high(j) && !d_used[j]; }, n, cols, wsum);
     int err = 0;
     if (kept + nsp > Mc) { err = 1; nsp = Mc - kept; }
     for (int q = tid; q < nsp; q += TRK_THREADS) {
@@ -360,77 +345,32 @@ static int launch_ocsort_update(const OcArgs &a, int n_streams, hipStream_t s) {
 
 using namespace rtmodt;
 
-struct rtmodt_ocsort {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t foreign_done = nullptr;       // as rtmodt_deepsort: an update fed from a detector runs on that detector's stream
-    bool foreign_pending = false;
+struct rtmodt_ocsort : TrackHandleBase {
     hipEvent_t ev[2] = {};
     bool timed = false;
-    int S = 1, Mc = 0, Nc = 0;
     rtmodt_ocsort_cfg cfg = {};
-    char *pool = nullptr;
+    char *pool = nullptr;                    // all state arrays (track_layout.h: carve_ocsort)
     OcState *d_states = nullptr; std::vector<OcState> h_states;
-    int64_t *d_meta = nullptr, *h_meta = nullptr;
-    float4 *d_box = nullptr; float *d_conf = nullptr; int32_t *d_cls = nullptr, *d_n = nullptr, *h_n = nullptr;
 };
-
-static const int64_t oc_init_meta[8] = {0, 0, 0, 0, 1, 0, 0, 0};
-
-static int oc_join(rtmodt_ocsort *t) {
-    if (t->foreign_pending) {
-        RT_HIP(hipStreamWaitEvent(t->stream, t->foreign_done, 0));
-        t->foreign_pending = false;
-    }
-    return RTMODT_OK;
-}
 
 namespace rtmodt {
 int ocsort_device_view(rtmodt_ocsort *t, OcDeviceView *out) {
     RT_CHECK(t && out, RTMODT_E_INVALID, "null argument");
-    *out = OcDeviceView{t->d_states, t->d_meta, t->S, t->Mc, t->cfg.min_hits, t->device, t->stream};
-    return oc_join(t);                                     // the caller's work on t->stream is ordered behind every update
+    out->states = t->d_states; out->min_hits = t->cfg.min_hits;
+    return track_view(t, out);
 }
 }  // namespace rtmodt
 
 static int oc_create_impl(rtmodt_ocsort *t) {
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    RT_HIP(hipEventCreateWithFlags(&t->foreign_done, hipEventDisableTiming));
+    RT_TRY(track_open(t));
     for (auto &e : t->ev) RT_HIP(hipEventCreate(&e));
-    const size_t M = (size_t)t->Mc;
-    auto a16 = [](size_t v) { return align_up(v, 16); };   // every sub-array starts on a 16-byte boundary, whatever max_tracks is
-    const size_t per_buf = 2 * a16(M * 80) + a16(M * 16 * OC_RING) + a16(M * 4 * OC_RING) + a16(M * 16) + 2 * a16(M * 8) + 6 * a16(M * 4);
-    const size_t per_stream = per_buf * 2;
-    RT_HIP(hipMalloc((void **)&t->pool, per_stream * t->S));
-    RT_HIP(hipMemset(t->pool, 0, per_stream * t->S));
-    t->h_states.resize(t->S);
-    char *p = t->pool;
-    for (int s = 0; s < t->S; ++s) {
-        OcState &st = t->h_states[s];
-        for (int b = 0; b < 2; ++b) {
-            st.kf[b] = (float4 *)p; p += a16(M * 80);
-            st.saved[b] = (float4 *)p; p += a16(M * 80);
-            st.ring[b] = (float4 *)p; p += a16(M * 16 * OC_RING);
-            st.ring_age[b] = (int32_t *)p; p += a16(M * 4 * OC_RING);
-            st.obox[b] = (float4 *)p; p += a16(M * 16);
-            st.ids[b] = (int64_t *)p; p += a16(M * 8);
-            st.dir[b] = (float2 *)p; p += a16(M * 8);
-            st.conf[b] = (float *)p; p += a16(M * 4);
-            int32_t **f[] = {&st.cls[b], &st.hits[b], &st.streak[b], &st.age[b], &st.tsu[b]};
-            for (auto q : f) { *q = (int32_t *)p; p += a16(M * 4); }
-        }
-    }
+    t->h_states.assign(t->S, OcState{});
+    const size_t total = carve_ocsort(t->h_states.data(), t->S, t->Mc, OC_RING, nullptr);
+    RT_HIP(hipMalloc((void **)&t->pool, total));
+    RT_HIP(hipMemset(t->pool, 0, total));
+    carve_ocsort(t->h_states.data(), t->S, t->Mc, OC_RING, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(OcState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(OcState) * t->S, hipMemcpyHostToDevice));
-    RT_HIP(hipMalloc((void **)&t->d_meta, sizeof(int64_t) * 8 * t->S));
-    RT_HIP(hipHostMalloc((void **)&t->h_meta, sizeof(int64_t) * 8 * t->S, hipHostMallocDefault));
-    RT_HIP(hipHostMalloc((void **)&t->h_n, sizeof(int32_t) * t->S, hipHostMallocDefault));
-    for (int s = 0; s < t->S; ++s) memcpy(t->h_meta + 8 * s, oc_init_meta, sizeof(oc_init_meta));
-    RT_HIP(hipMemcpy(t->d_meta, t->h_meta, sizeof(int64_t) * 8 * t->S, hipMemcpyHostToDevice));
-    const size_t SN = (size_t)t->S * t->Nc;
-    RT_HIP(hipMalloc((void **)&t->d_box, SN * 16)); RT_HIP(hipMalloc((void **)&t->d_conf, SN * 4)); RT_HIP(hipMalloc((void **)&t->d_cls, SN * 4));
-    RT_HIP(hipMalloc((void **)&t->d_n, (size_t)t->S * 4)); RT_HIP(hipMemset(t->d_n, 0, (size_t)t->S * 4));
     return RTMODT_OK;
 }
 
@@ -452,26 +392,16 @@ static int oc_run(rtmodt_ocsort *t, const OcArgs &a, int count, hipStream_t q) {
     return RTMODT_OK;
 }
 
-static int oc_check_sticky(rtmodt_ocsort *t, int s, int64_t err) {
-    RT_CHECK(err != 1, RTMODT_E_CAPACITY, "stream %d: more than max_tracks=%d live tracks", s, t->Mc);
-    RT_CHECK(err != 2, RTMODT_E_CAPACITY, "stream %d: assignment too dense (more than 256 contested rows/columns or 2048 contested pairs)", s);
-    RT_CHECK(err == 0, RTMODT_E_INVALID, "stream %d: tracker error %lld", s, (long long)err);
-    return RTMODT_OK;
-}
+static int oc_check_sticky(rtmodt_ocsort *t, int s, int64_t err) { return track_check_sticky(t, s, err, "assignment"); }
 
 extern "C" {
 
 void rtmodt_ocsort_destroy(rtmodt_ocsort *t) {
     if (!t) return;
-    hipSetDevice(t->device);
-    if (t->foreign_done) hipEventSynchronize(t->foreign_done);
-    if (t->stream) hipStreamSynchronize(t->stream);
-    if (t->foreign_done) hipEventDestroy(t->foreign_done);
-    for (auto &e : t->ev) if (e) hipEventDestroy(e);
-    hipFree(t->pool); hipFree(t->d_states); hipFree(t->d_meta);
-    hipFree(t->d_box); hipFree(t->d_conf); hipFree(t->d_cls); hipFree(t->d_n);
-    hipHostFree(t->h_meta); hipHostFree(t->h_n);
-    if (t->stream) hipStreamDestroy(t->stream);
+    track_close(t, [t] {
+        for (auto &e : t->ev) if (e) hipEventDestroy(e);
+        hipFree(t->pool); hipFree(t->d_states);
+    });
     delete t;
 }
 
@@ -493,47 +423,18 @@ int rtmodt_ocsort_create(const rtmodt_ocsort_cfg *cfg, rtmodt_ocsort **out) {
     rtmodt_ocsort *t = new rtmodt_ocsort();
     t->cfg = *cfg;
     t->device = cfg->device; t->S = cfg->n_streams; t->Mc = cfg->max_tracks; t->Nc = cfg->max_dets;
-    const int rc = oc_create_impl(t);
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_ocsort_destroy(t);
-        last_error() = keep;
-        return rc;
-    }
-    *out = t;
-    return RTMODT_OK;
+    return track_created(oc_create_impl(t), t, rtmodt_ocsort_destroy, out);
 }
 
-int rtmodt_ocsort_reset(rtmodt_ocsort *t, int stream) {
-    RT_CHECK(t && stream < t->S, RTMODT_E_INVALID, "bad argument");
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipDeviceSynchronize());
-    t->foreign_pending = false;
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->S : stream + 1;
-    for (int s = s0; s < s1; ++s) RT_HIP(hipMemcpy(t->d_meta + 8 * s, oc_init_meta, sizeof(oc_init_meta), hipMemcpyHostToDevice));
-    return RTMODT_OK;
-}
+int rtmodt_ocsort_reset(rtmodt_ocsort *t, int stream) { return track_reset_meta(t, stream); }
 
 int rtmodt_ocsort_update_batch(rtmodt_ocsort *t, const float *xyxy, const float *conf, const int32_t *cls, const int32_t *n, int32_t *n_returned_out) {
-    RT_CHECK(t && n, RTMODT_E_INVALID, "null argument");
     bool any = false;
-    for (int s = 0; s < t->S; ++s) {
-        RT_CHECK(n[s] >= 0, RTMODT_E_INVALID, "stream %d: %d detections", s, n[s]);
-        RT_CHECK(n[s] <= t->Nc, RTMODT_E_CAPACITY, "stream %d: %d detections > max_dets %d", s, n[s], t->Nc);
-        any |= n[s] > 0;
-    }
-    RT_CHECK(!any || (xyxy && conf && cls), RTMODT_E_INVALID, "null detections");
+    RT_TRY(track_batch_check(t, xyxy, conf, cls, n, &any));
     RT_HIP(hipSetDevice(t->device));
-    RT_TRY(oc_join(t));
+    RT_TRY(track_join(t));
     hipStream_t q = t->stream;
-    const size_t SN = (size_t)t->S * t->Nc;
-    for (int s = 0; s < t->S; ++s) t->h_n[s] = n[s];
-    if (any) {
-        RT_HIP(hipMemcpyAsync(t->d_box, xyxy, SN * 16, hipMemcpyHostToDevice, q));
-        RT_HIP(hipMemcpyAsync(t->d_conf, conf, SN * 4, hipMemcpyHostToDevice, q));
-        RT_HIP(hipMemcpyAsync(t->d_cls, cls, SN * 4, hipMemcpyHostToDevice, q));
-    }
-    RT_HIP(hipMemcpyAsync(t->d_n, t->h_n, (size_t)t->S * 4, hipMemcpyHostToDevice, q));
+    RT_TRY(track_batch_stage(t, xyxy, conf, cls, n, any));
     RT_TRY(oc_run(t, oc_args(t), t->S, q));
     RT_HIP(hipMemcpyAsync(t->h_meta, t->d_meta, sizeof(int64_t) * 8 * t->S, hipMemcpyDeviceToHost, q));
     RT_HIP(hipStreamSynchronize(q));
@@ -546,24 +447,19 @@ int rtmodt_ocsort_update_batch(rtmodt_ocsort *t, const float *xyxy, const float 
 int rtmodt_ocsort_update_from_detector(rtmodt_ocsort *t, rtmodt_detector *det) {
     RT_CHECK(t && det, RTMODT_E_INVALID, "null argument");
     DetOutputs o;
-    RT_TRY(detector_outputs(det, &o));
-    RT_CHECK(o.device == t->device, RTMODT_E_INVALID, "tracker on device %d, detector on device %d", t->device, o.device);
-    RT_CHECK(o.count >= 1 && o.count <= t->S, RTMODT_E_INVALID, "%d frames > tracker streams %d", o.count, t->S);
-    RT_CHECK(o.stride <= t->Nc, RTMODT_E_CAPACITY, "detector max_det %d > tracker max_dets %d", o.stride, t->Nc);
-    RT_HIP(hipSetDevice(t->device));
+    RT_TRY(track_detector_outputs(t, det, &o));
+    RT_TRY(track_detector_fits(t, o, o.count));
     OcArgs a = oc_args(t);
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
     RT_TRY(oc_run(t, a, o.count, o.stream));
-    RT_HIP(hipEventRecord(t->foreign_done, o.stream));
-    t->foreign_pending = true;
-    return RTMODT_OK;
+    return track_detector_done(t, o.stream);
 }
 
 int rtmodt_ocsort_state(rtmodt_ocsort *t, int stream, int64_t *ids, int32_t *hits, int32_t *hit_streak, int32_t *age, int32_t *tsu, float *xyxy,
                         float *conf, int32_t *cls, float *mean, float *cov, float *direction, int32_t *n, int64_t *next_id, int64_t *frame_count) {
     RT_CHECK(t && stream >= 0 && stream < t->S, RTMODT_E_INVALID, "bad argument");
     RT_HIP(hipSetDevice(t->device));
-    RT_TRY(oc_join(t));
+    RT_TRY(track_join(t));
     RT_HIP(hipStreamSynchronize(t->stream));
     int64_t m[8];
     RT_HIP(hipMemcpy(m, t->d_meta + 8 * stream, sizeof(m), hipMemcpyDeviceToHost));
@@ -587,15 +483,7 @@ int rtmodt_ocsort_state(rtmodt_ocsort *t, int stream, int64_t *ids, int32_t *hit
         if (mean || cov) {
             std::vector<float4> buf((size_t)5 * t->Mc);
             RT_HIP(hipMemcpy(buf.data(), st.kf[cur], buf.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            for (int i = 0; i < cnt; ++i) {
-                const float4 pos = buf[i], vel = buf[t->Mc + i], pa = buf[2 * (size_t)t->Mc + i], pb = buf[3 * (size_t)t->Mc + i], pc = buf[4 * (size_t)t->Mc + i];
-                if (mean) { float *o = mean + 8 * (size_t)i; o[0] = pos.x; o[1] = pos.y; o[2] = pos.z; o[3] = pos.w; o[4] = vel.x; o[5] = vel.y; o[6] = vel.z; o[7] = vel.w; }
-                if (cov) {
-                    float *o = cov + 12 * (size_t)i;
-                    o[0] = pa.x; o[1] = pb.x; o[2] = pc.x; o[3] = pa.y; o[4] = pb.y; o[5] = pc.y;
-                    o[6] = pa.z; o[7] = pb.z; o[8] = pc.z; o[9] = pa.w; o[10] = pb.w; o[11] = pc.w;
-                }
-            }
+            kalman_unpack(&buf[0].x, t->Mc, cnt, mean, cov);
         }
     }
     return oc_check_sticky(t, stream, m[2]);               // after the copies: a stream in error stays readable

@@ -34,10 +34,12 @@
 
 #include "kernels.h"
 #include "lap.h"
+#include "track_layout.h"
 
 namespace rtmodt {
 
 #include "track_dev.h"
+#include "wg_dev.h"
 
 constexpr int SG_THREADS = 256, SG_WAVES = SG_THREADS / 64;
 constexpr int SG_MAX_TRACKS = 1024, SG_MAX_HISTORY = 8, SG_MAX_STREAMS = DS_MAX_STREAMS;
@@ -71,38 +73,6 @@ struct SgGatherArgs {
     float4 *box; int32_t *src; int32_t *n; int64_t *meta;
 };
 
-__device__ __forceinline__ int sg_lower_bound(const int64_t *a, int n, int64_t x) {     // first index with a[i] >= x
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// exclusive prefix of a per-thread count over the workgroup; two barriers
-__device__ __forceinline__ int sg_block_scan(int v, int *wsum, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SG_WAVES; ++w) {
-        const int s = wsum[w];
-        if (w < wave) off += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return off + incl - v;
-}
-
 __device__ __forceinline__ int sg_wave_sum(int v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_gather(SgGatherArgs a) {
         const int i = base + tid;
         const bool f = i < n && tsu[i] == a.report_tsu;
         int tot;
-        const int pos = n_pass + sg_block_scan(f ? 1 : 0, wsum, tot);
+        const int pos = n_pass + block_scan_count<SG_WAVES>(f ? 1 : 0, wsum, tot);
         if (f && pos < a.Mc) { a.box[po + pos] = box[i]; a.src[po + pos] = i; }
         n_pass += tot;
     }
@@ -206,7 +176,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
     __syncthreads();
     for (int t = tid; t < np; t += SG_THREADS) {
         const int64_t id = pid[t];
-        const int j = sg_lower_bound(old_id, n_old, id);
+        const int j = lower_bound_i64(old_id, n_old, id);
         const bool hit = j < n_old && old_id[j] == id;
         slot[t] = hit && keep[j] ? o_slot[j] : -1;          // a row that has expired is not this track's row either
         if (hit) keep[j] = 0;                              // a matched row is no idle row
@@ -285,7 +255,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         const int t = base + tid;
         const int u = t < np ? cand[t] : -1;
         int tot;
-        const int pos = n_rev + sg_block_scan(u >= 0 ? 1 : 0, wsum, tot);
+        const int pos = n_rev + block_scan_count<SG_WAVES>(u >= 0 ? 1 : 0, wsum, tot);
         if (u >= 0) {                                      // t and u are in no other pair: nobody else touches their cells
             const int64_t A = pid[t], B = pid[u];
             const int st = slot[t], su = slot[u];
@@ -316,7 +286,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         const int j = base + tid;
         const int f = j < n_old ? keep[j] : 0;
         int tot;
-        const int pos = sg_block_scan(f, wsum, tot);
+        const int pos = block_scan_count<SG_WAVES>(f, wsum, tot);
         if (j < n_old) keep[j] = f ? n_ret + pos : -(n_ret + pos) - 1;         // stays: its rank; dropped: -(rank of the next that stays) - 1
         n_ret += tot;
     }
@@ -335,7 +305,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         const int k = base + tid;
         const int f = k < cap && !used[k] ? 1 : 0;
         int tot;
-        const int pos = n_free + sg_block_scan(f, wsum, tot);
+        const int pos = n_free + block_scan_count<SG_WAVES>(f, wsum, tot);
         if (f) used[pos] = k;
         n_free += tot;
     }
@@ -345,7 +315,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         const int t = base + tid;
         const bool f = t < np && slot[t] < 0;
         int tot;
-        const int pos = n_new + sg_block_scan(f ? 1 : 0, wsum, tot);
+        const int pos = n_new + block_scan_count<SG_WAVES>(f ? 1 : 0, wsum, tot);
         if (f && pos < n_free) { slot[t] = used[pos]; flags[t] |= SG_NEW; }   // (pos < n_free always: rows after the frame <= cap)
         n_new += tot;
     }
@@ -356,7 +326,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         if (s >= 0) {
             const int64_t id = pid[t];
             int below = 0;
-            if (!overflow) { const int v = keep[sg_lower_bound(old_id, n_old, id)]; below = v >= 0 ? v : -v - 1; }
+            if (!overflow) { const int v = keep[lower_bound_i64(old_id, n_old, id)]; below = v >= 0 ? v : -v - 1; }
             const int at = rank[t] + below;
             n_sid[at] = id; n_slot[at] = s;
             int cnt = r_count[s], head = r_head[s];
@@ -378,7 +348,7 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
         for (int j = tid; j < n_old; j += SG_THREADS) {                       // idle rows: the index entry moves, the row stays in its slot
             const int v = keep[j];
             if (v < 0) continue;
-            const int at = v + sg_lower_bound(spid, np, old_id[j]);
+            const int at = v + lower_bound_i64(spid, np, old_id[j]);
             n_sid[at] = old_id[j]; n_slot[at] = o_slot[j];
         }
     __syncthreads();
@@ -425,19 +395,9 @@ struct rtmodt_swapguard {
 
 namespace {
 
-struct SgCarver {
-    char *base; size_t off = 0;
-    template <typename T> T *take(size_t count) {
-        off = align_up(off, 16);
-        T *p = base ? (T *)(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 // lays out every device array; base == nullptr -> size only
 size_t sg_carve(rtmodt_swapguard *g, char *base) {
-    SgCarver c{base};
+    Carver c{base};
     const size_t S = g->S, cap = g->cap, Mc = g->Mc, E = g->max_events, H = g->H;
     g->d_ledgers = c.take<SgLedger>(S);
     g->d_meta = c.take<int64_t>(S * 4);

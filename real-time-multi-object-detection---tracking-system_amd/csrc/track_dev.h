@@ -1,5 +1,5 @@
 // track_dev.h -- device functions shared by the trackers (tracker.hip: ByteTrack, deepsort.hip: DeepSORT, ocsort.hip: OC-SORT): the
-// bit-exact IoU, the block-diagonal 8-state Kalman filter and the workgroup scan (moved here unchanged from tracker.hip), the sparse
+// bit-exact IoU, the block-diagonal 8-state Kalman filter, the workgroup scan and the compaction built on it, the sparse
 // exact assignment all use (assoc_sparse; include lap.h first), and OC-SORT's fixed-sequence acos.
 // Include from a translation unit built with -ffp-contract=off and correctly rounded division (Makefile: EXACT), inside
 // namespace rtmodt.
@@ -107,6 +107,21 @@ __device__ __forceinline__ int block_scan_flag(bool flag, int *wsum, int &total)
     __syncthreads();
     total = tot;
     return off + within;
+}
+
+// compacts the indices i < n with flag(i) into list (ascending); returns their number.  Ends with a barrier.
+template <typename F> __device__ __forceinline__ int block_compact(F flag, int n, int *list, int *wsum) {
+    int cnt = 0;
+    for (int base = 0; base < n; base += TRK_THREADS) {
+        const int i = base + threadIdx.x;
+        const bool f = i < n && flag(i);
+        int tot;
+        const int pos = block_scan_flag(f, wsum, tot);
+        if (f) list[cnt + pos] = i;
+        cnt += tot;
+    }
+    __syncthreads();
+    return cnt;
 }
 
 // The exact maximum-gain matching of a sparse bipartite graph, for any cost type of lap.h (the comment at tracker.hip's assoc_lap

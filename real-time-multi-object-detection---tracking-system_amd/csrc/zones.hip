@@ -23,8 +23,11 @@
 
 #include "kernels.h"
 #include "polygon.h"
+#include "track_layout.h"
 
 namespace rtmodt {
+
+#include "wg_dev.h"
 
 constexpr int ZN_THREADS = 256, ZN_WAVES = ZN_THREADS / 64;
 constexpr int ZN_MAX_ZONES = 32, ZN_MAX_POINTS = 2048;
@@ -57,38 +60,6 @@ struct ZoneArgs {
     // events [n_streams][max_events]
     int64_t *ev_id; int32_t *ev_track; int32_t *ev_zone; double *ev_dwell; float4 *ev_box; int2 *ev_c; int32_t *ev_cls; int32_t *ev_n;
 };
-
-__device__ __forceinline__ int lower_bound_i64(const int64_t *a, int n, int64_t x) {     // first index with a[i] >= x
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// exclusive prefix of a per-thread count over the workgroup; two barriers
-__device__ __forceinline__ int zn_block_scan(int v, int *wsum, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < ZN_WAVES; ++w) {
-        const int s = wsum[w];
-        if (w < wave) off += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return off + incl - v;
-}
 
 #pragma clang fp contract(off)
 
@@ -168,7 +139,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
         const int j = base + tid;
         const int f = j < n_old ? ret_pre[j] : 0;
         int tot;
-        const int pos = zn_block_scan(f, wsum, tot);
+        const int pos = block_scan_count<ZN_WAVES>(f, wsum, tot);
         if (j < n_old) ret_pre[j] = f ? n_ret + pos : -(n_ret + pos) - 1;       // retained: rank; dropped: -(rank of next retained) - 1
         n_ret += tot;
     }
@@ -239,7 +210,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
         const int i = base + tid;
         const uint32_t ev = i < n ? evmask[i] : 0u;
         int tot;
-        int pos = n_ev + zn_block_scan(__popc(ev), wsum, tot);
+        int pos = n_ev + block_scan_count<ZN_WAVES>(__popc(ev), wsum, tot);
         if (ev) {
             const float4 b = box[i];
             for (int z = 0; z < Z; ++z)
@@ -292,16 +263,6 @@ struct rtmodt_zones {
 };
 
 namespace {
-
-struct Carver {
-    char *base; size_t off = 0;
-    template <typename T> T *take(size_t count) {
-        off = align_up(off, 16);
-        T *p = base ? (T *)(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
 
 // lays out every device array; base == nullptr -> size only
 size_t carve(rtmodt_zones *z, char *base) {

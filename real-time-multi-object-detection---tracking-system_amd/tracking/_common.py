@@ -1,0 +1,42 @@
+"""What the DeepSORT and OC-SORT front ends share: the padding of one frame's detections to a single-stream batch, and the trails."""
+from __future__ import annotations
+
+from collections import defaultdict
+
+import numpy as np
+
+from .. import _ffi
+
+
+def pad_single_stream(xyxy, confidence, class_id, max_dets: int):
+    """One frame's detections as the ``[1, max_dets(, 4)]`` arrays ``update_batch`` takes: ``(bx, cf, cl, n)``."""
+    xyxy = np.asarray(xyxy, np.float32).reshape(-1, 4)
+    n = len(xyxy)
+    if n > max_dets:
+        raise _ffi.RtmodtError(_ffi.E_CAPACITY, f"{n} detections > max_dets {max_dets}")
+    bx = np.zeros((1, max_dets, 4), np.float32); bx[0, :n] = xyxy
+    cf = np.zeros((1, max_dets), np.float32); cf[0, :n] = np.asarray(confidence, np.float32).reshape(-1)
+    cl = np.zeros((1, max_dets), np.int32); cl[0, :n] = np.asarray(class_id, np.int32).reshape(-1)
+    return bx, cf, cl, n
+
+
+class TrailKeeper:
+    """The last ``maxlen`` centroids of every live track, as ``MultiObjectTracker`` draws them."""
+
+    def __init__(self, maxlen: int = 30) -> None:
+        self._map = defaultdict(list)
+        self._maxlen = maxlen
+
+    def drop_dead(self, ids) -> None:
+        """ids are never reused: a dead track's trail is dead weight"""
+        alive = set(int(i) for i in ids)
+        for tid in [t for t in self._map if t not in alive]:
+            del self._map[tid]
+
+    def push(self, tid: int, b) -> list:
+        """Appends the centroid of box ``b`` (float32 arithmetic, truncation) to ``tid``'s trail; returns a copy of the trail."""
+        trail = self._map[tid]
+        trail.append((int((b[0] + b[2]) / 2), int((b[1] + b[3]) / 2)))
+        if len(trail) > self._maxlen:
+            trail.pop(0)
+        return list(trail)

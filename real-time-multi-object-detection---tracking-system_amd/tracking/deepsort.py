@@ -12,11 +12,11 @@ runs elsewhere come in through ``embeddings=``.
 from __future__ import annotations
 
 import ctypes as C
-from collections import defaultdict
 
 import numpy as np
 
 from .. import _ffi
+from ._common import TrailKeeper, pad_single_stream
 from ..reid_weights import FEAT_DIM, SUFFIX
 from .reid import check_weights_path
 from .tracker import Track
@@ -81,13 +81,7 @@ class _DeepSortCore:
         """One frame of a single-stream tracker."""
         if self.n_streams != 1 or stream != 0:
             raise ValueError("update() drives a single-stream tracker; use update_batch for several streams")
-        xyxy = np.asarray(xyxy, np.float32).reshape(-1, 4)
-        n = len(xyxy)
-        if n > self.max_dets:
-            raise _ffi.RtmodtError(_ffi.E_CAPACITY, f"{n} detections > max_dets {self.max_dets}")
-        bx = np.zeros((1, self.max_dets, 4), np.float32); bx[0, :n] = xyxy
-        cf = np.zeros((1, self.max_dets), np.float32); cf[0, :n] = np.asarray(confidence, np.float32).reshape(-1)
-        cl = np.zeros((1, self.max_dets), np.int32); cl[0, :n] = np.asarray(class_id, np.int32).reshape(-1)
+        bx, cf, cl, n = pad_single_stream(xyxy, confidence, class_id, self.max_dets)
         emb = None
         if embeddings is not None:
             emb = np.zeros((1, self.max_dets, self.dim), np.int8)
@@ -175,8 +169,7 @@ class DeepSortTracker:
         self.embedder = embedder
         self._core = _DeepSortCore(max_dist, min_confidence, max_iou_distance, max_age, n_init, nn_budget, embedder, dim=embedding_dim,
                                    device=device, max_tracks=max_tracks, max_dets=max_dets)
-        self._trail_map = defaultdict(list)
-        self._trail_maxlen = 30
+        self._trails = TrailKeeper()
 
     @classmethod
     def from_config(cls, tracking_cfg: dict, **extra) -> "DeepSortTracker":
@@ -212,20 +205,12 @@ class DeepSortTracker:
     def _tracks_out(self) -> list:
         st = self._core.snapshot(0, gallery=False)
         boxes = _xyah_to_xyxy(st["mean"][:, :4])
-        alive = set(int(i) for i in st["ids"])
-        for tid in [t for t in self._trail_map if t not in alive]:      # ids are never reused: a dead track's trail is dead weight
-            del self._trail_map[tid]
+        self._trails.drop_dead(st["ids"])
         out = []
         for i in np.nonzero((st["state"] == CONFIRMED) & (st["tsu"] == 0))[0]:
             tid, b = int(st["ids"][i]), boxes[i]
-            cx = int((b[0] + b[2]) / 2)
-            cy = int((b[1] + b[3]) / 2)
-            trail = self._trail_map[tid]
-            trail.append((cx, cy))
-            if len(trail) > self._trail_maxlen:
-                trail.pop(0)
             out.append(Track(track_id=tid, xyxy=b, confidence=float(st["conf"][i]), class_id=int(st["cls"][i]), age=int(st["age"][i]),
-                             time_since_update=0, trail=list(trail)))
+                             time_since_update=0, trail=self._trails.push(tid, b)))
         return out
 
     def close(self) -> None:

@@ -298,6 +298,33 @@ def test_ragged_streams_batch_and_single_updates_interleaved(pkg):
         core.close()
 
 
+# ------------------------------------------------------------------ K: the smallest handle, odd capacities
+@pytest.mark.parametrize("assign", ["greedy", "lapjv"])
+@pytest.mark.parametrize("kalman", [False, True], ids=["plain", "kalman"])
+def test_small_odd_handle_equals_oracle_every_frame(pkg, kalman, assign):
+    """7 tracks x 5 detections x 3 streams: no state array's size is a multiple of 16 bytes, so every array after the first
+    depends on the pool's alignment rule.  Births, misses, a second-pass match and expiries (track_buffer = 2) in every stream; the
+    full state -- with the Kalman model on, the filter state too -- equals the oracle's bit for bit after every frame."""
+    S, N = TC.SMALL_STREAMS, TC.SMALL_DETS
+    mode = pkg._ffi.ASSIGN_LAPJV if assign == "lapjv" else pkg._ffi.ASSIGN_GREEDY
+    core = make_core(pkg, track_buffer=TC.SMALL_BUFFER, n_streams=S, max_tracks=TC.SMALL_TRACKS, max_dets=N, assign_mode=mode, kalman=kalman)
+    orcs = [oracle_for(kalman, track_buffer=TC.SMALL_BUFFER, assign=assign) for _ in range(S)]
+    seqs = [TC.small_handle_frames(s) for s in range(S)]
+    try:
+        for f in range(TC.SMALL_FRAMES):
+            xy, cf, cl, cnt = np.zeros((S, N, 4), np.float32), np.zeros((S, N), np.float32), np.zeros((S, N), np.int32), np.zeros(S, np.int32)
+            for s in range(S):
+                b, c, k = seqs[s][f]
+                xy[s, :len(b)], cf[s, :len(b)], cl[s, :len(b)], cnt[s] = b, c, k, len(b)
+                orcs[s].update(b, c, k)
+            core.update_batch(xy, cf, cl, cnt)
+            for s in range(S):
+                same_state(core, orcs[s], stream=s, tag=(f, s))
+        assert all(o.next_id - 1 > len(o.ids) for o in orcs)              # tracks expired in every stream
+    finally:
+        core.close()
+
+
 # ------------------------------------------------------------------ L: LDS budget
 # The kernel carves max_tracks * 28 + max_dets * 40 + 132 bytes (boxes 16 + three int lists 12 per track; box 16 + confidence,
 # class, three index lists and the column winners 24 per detection; 17 scan words + 64) and launch_tracker_update accepts at

@@ -131,3 +131,22 @@ def test_big_frames_exceed_1024_highs_and_lows():
     counts = run(orc, frames)
     assert counts[0] > 1024 and max(counts) <= 2048 and counts[-1] > counts[0]      # later frames spawn too, and all of it fits
     assert (orc.age[:counts[0]] > 1).any()
+
+
+@pytest.mark.parametrize("make", [T.TrackerOracle, K.TrackerOracleKalman])
+@pytest.mark.parametrize("assign", ["greedy", "lapjv"])
+def test_small_handle_frames_have_births_misses_and_an_expiry(make, assign):
+    for s in range(TC.SMALL_STREAMS):
+        frames = TC.small_handle_frames(s)
+        assert len(frames) == TC.SMALL_FRAMES and max(len(c) for _, c, _ in frames) <= TC.SMALL_DETS
+        assert any((c < np.float32(TC.TRACK_THRESH)).any() for _, c, _ in frames)         # the second pass has a detection
+        orc = make(track_buffer=TC.SMALL_BUFFER, assign=assign)
+        births = misses = expired = 0
+        for f, (b, c, k) in enumerate(frames):
+            before, next_before = orc.ids.copy(), orc.next_id
+            orc.update(b, c, k)
+            births += f > 0 and orc.next_id > next_before
+            misses += int((orc.tsu > 1).sum())
+            expired += int((~np.isin(before, orc.ids)).sum())
+            assert len(orc.ids) <= TC.SMALL_TRACKS
+        assert births >= 2 and misses >= 2 and expired >= 2, (s, births, misses, expired)

@@ -150,3 +150,32 @@ def tie_rng(m, low_share=0.0):
     if low_share:
         return np.random.default_rng(2 if m == 30 else 0)
     return np.random.default_rng(1 if m == 60 else 0)
+
+
+# the smallest handle of the suite: odd capacities, so no state array's size is a multiple of 16 bytes
+SMALL_TRACKS, SMALL_DETS, SMALL_STREAMS, SMALL_FRAMES, SMALL_BUFFER = 7, 5, 3, 12, 2
+
+
+def small_handle_frames(stream):
+    """SMALL_FRAMES frames of stream ``stream`` for a SMALL_TRACKS x SMALL_DETS handle with track_buffer = SMALL_BUFFER: 40 x 60
+    boxes moving right by 1 + stream px a frame, events shifted by ``stream`` frames.  A is there throughout; a second detection one
+    pixel beside it in one frame makes a contested row, then a contested column, and a track that expires; B misses one frame (re-matched
+    at 1 or 2 px a frame, lost and born again at 3) and comes in below the confidence threshold once (second pass); C leaves for
+    good (expiry); D is born after that.  At most 4 detections a frame and 4 live tracks."""
+    v, t0 = 1.0 + stream, stream
+    frames = []
+    for f in range(SMALL_FRAMES):
+        e = f - t0                                               # the event clock of this stream
+        x = 16.0 + v * f
+        dets = [((x, 16.0 + 80 * stream), 0.9, 1)]                                   # A
+        if e == 2:
+            dets.append(((x + 1.0, 16.0 + 80 * stream), 0.625, 1))                     # beside A
+        if e != 4:
+            dets.append(((x + 96.0, 24.0), 0.375 if e == 7 else 0.875, 2))              # B
+        if e < 6:
+            dets.append(((x + 192.0, 32.0), 0.75, 3))                                # C
+        if e >= 8:
+            dets.append(((x + 288.0, 40.0), 0.8125, 4))                              # D
+        b = np.asarray([[px, py, px + 40.0, py + 60.0] for (px, py), _, _ in dets], F32)
+        frames.append((b, np.asarray([c for _, c, _ in dets], F32), np.asarray([k for _, _, k in dets], np.int32)))
+    return frames
