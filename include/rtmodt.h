@@ -44,6 +44,7 @@ typedef struct rtmodt_renderer rtmodt_renderer;
 typedef struct rtmodt_jpeg rtmodt_jpeg;
 typedef struct rtmodt_deepsort rtmodt_deepsort;
 typedef struct rtmodt_ocsort rtmodt_ocsort;
+typedef struct rtmodt_botsort rtmodt_botsort;
 typedef struct rtmodt_reid rtmodt_reid;
 
 /* ---- library / device ------------------------------------------------------------- */
@@ -354,6 +355,61 @@ int rtmodt_ocsort_state(rtmodt_ocsort *oc, int stream, int64_t *ids, int32_t *hi
 /* Device time (ms, HIP events) of the last update's single launch. */
 int rtmodt_ocsort_last_ms(rtmodt_ocsort *oc, float *update_ms);
 
+/* ---- BoT-SORT: the tracker TECHNICAL_DESIGN_DOCUMENT.md H.2 ranks best (row 3, IDF1 0.83, 38 switches, "Req. Re-ID Model: Yes") ---- */
+/* BoT-SORT (Aharon et al., 2022) with the state resident on the device: csrc/botsort.hip states the rules (split, the 8-state filter
+ * on width and height with its two 4x4 covariance blocks, camera-motion compensation by a caller-supplied warp, IoU fused with the
+ * detection score and with appearance, the second association on the low detections, new / tracked / lost life cycle, duplicate
+ * removal), tests/botsort_ref.py restates them and the kernel equals that restatement bit for bit.  PARITY UNPINNED: BoT-SORT and
+ * boxmot are installed nowhere this runs.  Class-agnostic.  A fixed number of launches per call whatever the counts.  Limits: 256
+ * tracks and 1024 detections per stream, 64 streams, descriptors of at most 512 values, and the contested-pair limits of
+ * rtmodt_assign_lapjv; beyond them RTMODT_E_CAPACITY, never a fault.  Estimating the warp from pixels is not part of this library:
+ * it comes from whoever has it (PTZ telemetry, an estimator elsewhere). */
+typedef struct rtmodt_botsort_cfg {
+    float track_high_thresh;    /* H.2 row 3  0.6: high detections have conf > track_high_thresh (float32, strict)               */
+    float track_low_thresh;     /* 0.1: low detections have track_low_thresh < conf < track_high_thresh                          */
+    float new_track_thresh;     /* 0.7: an unmatched high detection becomes a track when conf >= new_track_thresh                */
+    int32_t track_buffer;       /* 30: a lost track dies when frame_count - last_frame > track_buffer                            */
+    double match_thresh;        /* 0.8: the first association admits a pair when its cost <= match_thresh                        */
+    double proximity_thresh;    /* 0.5: appearance is ignored for a pair with 1 - iou > proximity_thresh                         */
+    double appearance_thresh;   /* 0.25: ... and when (1 - cos) / 2 > appearance_thresh                                          */
+    int32_t fuse_score;         /* 1: the IoU cost is 1 - iou * conf (the published `not mot20`)                                 */
+    const char *embedder;       /* NULL, "" or "none" = motion only; "colorhist" = the built-in descriptor (or, with dim != 192,
+                                 * caller descriptors); a path ending in ".rtreid" = the OSNet x0.25 network of rtmodt_reid_*;
+                                 * anything else is RTMODT_E_UNSUPPORTED, as rtmodt_deepsort_create words it                     */
+    int32_t dim;                /* descriptor dimension: 0 = 192 (built-in) or 512 (network); 64..512 in multiples of 64 for caller
+                                 * descriptors; must be 0 without an embedder                                                    */
+    int32_t max_tracks, max_dets, n_streams, device;
+} rtmodt_botsort_cfg;
+int rtmodt_botsort_create(const rtmodt_botsort_cfg *cfg, rtmodt_botsort **out);                    /* H.2 row 3 */
+void rtmodt_botsort_destroy(rtmodt_botsort *bot);
+int rtmodt_botsort_reset(rtmodt_botsort *bot, int stream);    /* stream < 0: all */
+/* Host only, no device needed: RTMODT_OK for warp[n_streams][6] (row-major 2x3 [R | t] per stream, NULL = identity) whose entries
+ * are all finite and whose |det R| >= 1e-6, RTMODT_E_INVALID otherwise.  The update calls apply it before anything is launched. */
+int rtmodt_botsort_check_warp(const float *warp, int n_streams);
+/* One frame for every stream (H.2 row 3): detections as rtmodt_ocsort_update_batch takes them, then frames + geometry OR desc as
+ * rtmodt_deepsort_update_batch takes them (neither on a motion-only handle), then warp[n_streams][6] (host; row-major 2x3 per stream,
+ * the image motion from the previous frame to this one; NULL = identity).  n_returned_out[n_streams] (may be NULL) = the tracks
+ * with flag 2 after the frame. */
+int rtmodt_botsort_update_batch(rtmodt_botsort *bot, const float *xyxy, const float *conf, const int32_t *cls, const int32_t *n,
+                                const uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind, const int8_t *desc,
+                                const float *warp, int32_t *n_returned_out);
+/* The same on the device-resident detections of det's last enqueue_batch (H.2 row 3; stream i <- frame i), queued on det's HIP
+ * stream behind its NMS as rtmodt_deepsort_update_from_detector is; frames = NULL on a motion-only handle.  warp[n_frames][6]
+ * travels in the kernel's arguments: it is read before the call returns and never blocks that stream. */
+int rtmodt_botsort_update_from_detector(rtmodt_botsort *bot, rtmodt_detector *det, const uint8_t *const *frames, int n_frames, int h,
+                                        int w, int stride_bytes, int mem_kind, const float *warp);
+/* A stream's tracks in list order (H.2 row 3; creation order, deletions compacted); arrays sized max_tracks, any may be NULL.
+ * flag: 1 new, 2 tracked, 3 lost; xyxy / conf / cls: the last matched detection; mean[n][8] = (cx, cy, w, h, vx, vy, vw, vh);
+ * cov[n][20] = the upper triangle, row-major ((0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)), of the covariance block
+ * of (cx, cy, vx, vy), then that of (w, h, vw, vh); feat16[n][dim] / feat8[n][dim] = the smoothed feature at norm 16256 / 127
+ * (untouched on a motion-only handle).  A track is returned when flag == 2.  On a stream in (sticky) error the outputs are still
+ * filled in before RTMODT_E_CAPACITY is returned. */
+int rtmodt_botsort_state(rtmodt_botsort *bot, int stream, int64_t *ids, int32_t *flag, int32_t *age, int32_t *tsu, int32_t *start_frame,
+                         int32_t *last_frame, float *xyxy, float *conf, int32_t *cls, float *mean, float *cov, int16_t *feat16,
+                         int8_t *feat8, int32_t *n, int64_t *next_id, int64_t *frame_count);
+/* Device time (ms, HIP events) of the last update's three parts (H.2 row 3): descriptors (0 without frames), distance, update. */
+int rtmodt_botsort_last_ms(rtmodt_botsort *bot, float *describe_ms, float *distance_ms, float *update_ms);
+
 /* ---- the embedder of default.yaml:60 (`tracking.deepsort.embedder: "weights/osnet_x0_25.onnx"`): OSNet x0.25 on the GPU ---- */
 /* csrc/reid.hip states the crop rule, the rounding contract and the launches; tests/reid_ref.py restates them.  PINNED: the crop
  * and the int8 quantiser exactly, the network within a measured fp16 bound of float64 (profiles/reid/README.md).  PARITY
@@ -511,6 +567,10 @@ int rtmodt_crossing_process_deepsort(rtmodt_crossing *c, rtmodt_deepsort *ds, in
  * detection's. */
 int rtmodt_crossing_process_ocsort(rtmodt_crossing *c, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events,
                                    int32_t *n_events);
+/* The same on a BoT-SORT handle (H.2 row 3): passed = the returned tracks (flag 2) matched this frame (tsu == 0); the box is the
+ * matched detection's. */
+int rtmodt_crossing_process_botsort(rtmodt_crossing *c, rtmodt_botsort *bot, int64_t frame_id, rtmodt_crossing_event *events,
+                                    int32_t *n_events);
 /* One stream's counts since creation or the last reset (default.yaml:73-77): line_total [n_lines][2] (pos, neg),
  * line_class [n_lines][2][n_classes], gate_total [n_gates], gate_class [n_gates][n_classes]; any pointer may be null. */
 int rtmodt_crossing_counts(rtmodt_crossing *c, int stream, int64_t *line_total, int64_t *line_class, int64_t *gate_total,

@@ -12,6 +12,7 @@ library being built):
 * ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
+* ``tracking.botsort``   -- ``BotSortTracker``: BoT-SORT, the comparison's best row (Re-ID fusion, camera-motion compensation), on the GPU
 * ``tracking.swapguard`` -- ``IdSwapGuard``: ByteTrack identities verified by appearance, ID swaps reverted online on the GPU (the
                             design document's B.4 / G.1 appearance verification, which the reference does not implement)
 * ``tracking.reid``      -- ``ReidEmbedder``: the OSNet x0.25 re-identification network on the GPU (reference: config/default.yaml:60)
@@ -36,7 +37,7 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker"]
+__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
@@ -45,6 +46,7 @@ _LAZY = {
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",
     "OcSortTracker": ".tracking.ocsort",
+    "BotSortTracker": ".tracking.botsort",
     "IdSwapGuard": ".tracking.swapguard",
     "SwapEvent": ".tracking.swapguard",
     "ZoneEventEngine": ".events.zone_engine",

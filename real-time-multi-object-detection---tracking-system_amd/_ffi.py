@@ -149,6 +149,13 @@ class OcSortCfg(C.Structure):                       # struct rtmodt_ocsort_cfg
                 ("max_dets", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
 
 
+class BotSortCfg(C.Structure):                      # struct rtmodt_botsort_cfg
+    _fields_ = [("track_high_thresh", C.c_float), ("track_low_thresh", C.c_float), ("new_track_thresh", C.c_float), ("track_buffer", C.c_int32),
+                ("match_thresh", C.c_double), ("proximity_thresh", C.c_double), ("appearance_thresh", C.c_double), ("fuse_score", C.c_int32),
+                ("embedder", C.c_char_p), ("dim", C.c_int32), ("max_tracks", C.c_int32), ("max_dets", C.c_int32), ("n_streams", C.c_int32),
+                ("device", C.c_int32)]
+
+
 class ReidCfg(C.Structure):                         # struct rtmodt_reid_cfg
     _fields_ = [("weight_path", C.c_char_p), ("device", C.c_int32), ("max_frames", C.c_int32), ("max_boxes", C.c_int32)]
 
@@ -270,6 +277,14 @@ def lib() -> C.CDLL:
         "rtmodt_ocsort_update_from_detector": (C.c_int, [vp, vp]),
         "rtmodt_ocsort_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
         "rtmodt_ocsort_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_botsort_create": (C.c_int, [C.POINTER(BotSortCfg), C.POINTER(vp)]),
+        "rtmodt_botsort_destroy": (None, [vp]),
+        "rtmodt_botsort_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_botsort_check_warp": (C.c_int, [vp, C.c_int]),
+        "rtmodt_botsort_update_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "rtmodt_botsort_update_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_botsort_state": (C.c_int, [vp, C.c_int] + [vp] * 13 + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
+        "rtmodt_botsort_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
         "rtmodt_reid_create": (C.c_int, [C.POINTER(ReidCfg), C.POINTER(vp)]),
         "rtmodt_reid_destroy": (None, [vp]),
         "rtmodt_reid_embed": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
@@ -288,6 +303,7 @@ def lib() -> C.CDLL:
         "rtmodt_crossing_process_tracker": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
         "rtmodt_crossing_process_deepsort": (C.c_int, [vp, vp, i64, C.c_int, vp, vp]),
         "rtmodt_crossing_process_ocsort": (C.c_int, [vp, vp, i64, vp, vp]),
+        "rtmodt_crossing_process_botsort": (C.c_int, [vp, vp, i64, vp, vp]),
         "rtmodt_crossing_counts": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "rtmodt_crossing_reset_counts": (C.c_int, [vp]),
         "rtmodt_crossing_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),

@@ -93,7 +93,7 @@ typedef int intx4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void appearance_dotmax(DotmaxArgs a) {
     const int t = blockIdx.x, s = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int T = a.states ? (int)a.meta[(size_t)s * 8 + 1] : a.n_tracks;
+    const int T = a.states || a.meta_rows ? (int)a.meta[(size_t)s * 8 + 1] : a.n_tracks;
     const int N = a.n_dets_dev ? min(a.n_dets_dev[s], a.max_dets) : a.n_dets;
     const int col0 = blockIdx.y * 64 + wave * 16;
     if (t >= T || col0 >= N) return;                       // wave-uniform
@@ -103,6 +103,8 @@ __global__ __launch_bounds__(256) void appearance_dotmax(DotmaxArgs a) {
         const DsState &st = a.states[s];
         slot = (cur ? st.slot[1] : st.slot[0])[t];
         cnt = (cur ? st.gcount[1] : st.gcount[0])[t];
+    } else if (a.meta_rows) {
+        cnt = 1;
     } else {
         cnt = a.counts[t];
     }
@@ -118,6 +120,7 @@ __global__ __launch_bounds__(256) void appearance_dotmax(DotmaxArgs a) {
         if (k < KC && col < N) bf[k] = *(const intx4_t *)(dp + 64 * k);
     }
     const int8_t *gp = a.gallery + ((size_t)s * a.gallery_stream_stride + (size_t)slot * a.budget * a.dim);
+    if (a.meta_rows) gp += (size_t)(a.meta[(size_t)s * 8] & 1) * a.gallery_cur_stride;
     int best = INT_MIN;
     for (int r0 = 0; r0 < cnt; r0 += 16) {
         const int row = r0 + (lane & 15);

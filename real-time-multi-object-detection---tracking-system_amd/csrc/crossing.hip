@@ -57,6 +57,8 @@ struct CrossArgs {
     const TrackerState *t_states; const DsState *d_states; const int64_t *t_meta; int report_tsu;
     // source D: the OC-SORT tracker's device state; passed = returned: tsu == 0 and (hit_streak >= o_min_hits or frame_count <= o_min_hits)
     const OcState *o_states; int o_min_hits;
+    // source E: the BoT-SORT tracker's device state; passed = returned (flag == 2) and matched this frame (tsu == 0)
+    const BotState *b_states;
     // per-stream scratch [n_streams][cap]
     int32_t *p_idx, *oldpos; uint64_t *evmask;
     // events [n_streams][max_events]; ev_n = the number that fired (may exceed max_events)
@@ -137,6 +139,12 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         const int tc = (int)tm[0] & 1;
         ids = st->ids[tc]; box = st->obox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; streak = st->streak[tc];
         early = tm[5] <= (int64_t)a.o_min_hits;
+        n = (int)tm[1];
+    } else if (a.b_states) {
+        const BotState *st = a.b_states + sidx;
+        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
+        const int tc = (int)tm[0] & 1;
+        ids = st->ids[tc]; box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
         n = (int)tm[1];
     } else {
         const DsState *st = a.d_states + sidx;
@@ -615,6 +623,13 @@ int rtmodt_crossing_process_deepsort(rtmodt_crossing *z, rtmodt_deepsort *ds, in
     DsDeviceView v;
     RT_TRY(deepsort_device_view(ds, &v));
     return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.d_states = v.states; a.report_tsu = report_tsu; });
+}
+
+int rtmodt_crossing_process_botsort(rtmodt_crossing *z, rtmodt_botsort *bot, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
+    RT_CHECK(z && bot && n_events, RTMODT_E_INVALID, "bad argument");
+    BotDeviceView v;
+    RT_TRY(botsort_device_view(bot, &v));
+    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.b_states = v.states; a.report_tsu = 0; });
 }
 
 int rtmodt_crossing_process_ocsort(rtmodt_crossing *z, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {

@@ -283,6 +283,8 @@ struct DotmaxArgs {
     const int8_t *gallery; size_t gallery_stream_stride;        // [stream][slot][budget][dim]
     const int32_t *counts;                                      // standalone: samples per track (slot == track)
     const DsState *states; const int64_t *meta;                 // tracker: slot / gcount / track count come from the state
+    int meta_rows; size_t gallery_cur_stride;                   // meta_rows (states == nullptr): one row per track, slot == track, the track count from
+                                                                // meta, the rows of buffer meta[0] & 1 at gallery + cur * gallery_cur_stride (botsort.hip)
     int budget, dim;
     const int8_t *dets; int det_stride;                         // [stream][det_stride][dim]
     int n_tracks, n_dets; const int32_t *n_dets_dev; int max_dets;
@@ -297,7 +299,7 @@ void reid_close(rtmodt_reid *e);
 int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, int pitch, const float4 *box, const int32_t *box_n, int box_stride,
              int launch_mb, int8_t *desc, int desc_stride, hipStream_t q);
 
-// A tracker's device-resident state as its consumers see it.  The part all three trackers share (track_host.h fills it):
+// A tracker's device-resident state as its consumers see it.  The part all four trackers share (track_host.h fills it):
 // meta[n_streams][8] = {cur, n_tracks, err, n_active, next_id, ...}; `stream` is the HIP stream the tracker's most recent update
 // was launched on
 struct TrackViewBase { const int64_t *meta; int n_streams, max_tracks, device; hipStream_t stream; };
@@ -323,6 +325,18 @@ struct OcState {
 // its view for the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, n_returned, next_id, frame_count, ...}
 struct OcDeviceView : TrackViewBase { const OcState *states; int min_hits; };
 int ocsort_device_view(rtmodt_ocsort *oc, OcDeviceView *out);
+
+// BoT-SORT (botsort.hip): one stream's state; device pointers; double-buffered like DsState.  The features live beside it
+// ([stream][2][max_tracks][dim] int16 and int8), so that appearance_dotmax reads the int8 rows as a gallery of one row per track
+constexpr int BOT_MAX_TRACKS = 256, BOT_MAX_DETS = 1024, BOT_MAX_STREAMS = 64;
+struct BotState {
+    int64_t *ids[2]; float4 *dbox[2]; float *conf[2]; int32_t *cls[2];      // dbox / conf / cls: the last matched detection
+    int32_t *flag[2], *age[2], *tsu[2], *start[2], *last[2];                // flag: 1 new, 2 tracked, 3 lost; start / last: frame numbers
+    float4 *kf[2];                                      // [7][max_tracks]: mean (cx, cy, w, h), velocities, the covariance's 20 entries
+};
+// its view for the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, n_returned, next_id, frame_count, ...}
+struct BotDeviceView : TrackViewBase { const BotState *states; };
+int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
 
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };

@@ -1,4 +1,4 @@
-// track_dev.h -- device functions shared by the trackers (tracker.hip: ByteTrack, deepsort.hip: DeepSORT, ocsort.hip: OC-SORT): the
+// track_dev.h -- device functions shared by the trackers (tracker.hip: ByteTrack, deepsort.hip: DeepSORT, ocsort.hip: OC-SORT, botsort.hip: BoT-SORT): the
 // bit-exact IoU, the block-diagonal 8-state Kalman filter, the workgroup scan and the compaction built on it, the sparse
 // exact assignment all use (assoc_sparse; include lap.h first), and OC-SORT's fixed-sequence acos.
 // Include from a translation unit built with -ffp-contract=off and correctly rounded division (Makefile: EXACT), inside

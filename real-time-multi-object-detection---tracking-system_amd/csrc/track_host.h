@@ -1,4 +1,4 @@
-// track_host.h -- the host skeleton the three tracker handles share (tracker_api.hip: ByteTrack, deepsort.hip, ocsort.hip): stream
+// track_host.h -- the host skeleton the four tracker handles share (tracker_api.hip: ByteTrack, deepsort.hip, ocsort.hip, botsort.hip): stream
 // and event, the meta rows, the detection staging, and the calls every one of them makes around its own launches.
 #pragma once
 

@@ -1,9 +1,9 @@
-// track_layout.h -- the pure host pieces the trackers and their consumers share: the pool carver, the state layouts of the three
+// track_layout.h -- the pure host pieces the trackers and their consumers share: the pool carver, the state layouts of the four
 // trackers, and the read-back of a Kalman block.  No HIP header: a plain C++ compiler builds it (tests/native/track_layout_check.cpp).
 //
 // A pool is laid out by ONE function that is run twice -- base == nullptr measures, a real base assigns -- so a size can never
 // disagree with the layout it was computed for.  Every array starts on a 16-byte boundary whatever max_tracks is.  The layouts are
-// templates over the state struct (kernels.h: TrackerState, DsState, OcState): an array's element type is its field's.
+// templates over the state struct (kernels.h: TrackerState, DsState, OcState, BotState): an array's element type is its field's.
 #pragma once
 
 #include <cstddef>
@@ -66,6 +66,18 @@ template <typename St> size_t carve_ocsort(St *states, size_t S, size_t M, size_
     return c.size();
 }
 
+// BoT-SORT (botsort.hip)
+template <typename St> size_t carve_botsort(St *states, size_t S, size_t M, char *base) {
+    Carver c{base};
+    for (size_t s = 0; s < S; ++s)
+        for (int b = 0; b < 2; ++b) {
+            St &st = states[s];
+            c.take(st.kf[b], 7 * M); c.take(st.dbox[b], M); c.take(st.ids[b], M); c.take(st.conf[b], M); c.take(st.cls[b], M);
+            c.take(st.flag[b], M); c.take(st.age[b], M); c.take(st.tsu[b], M); c.take(st.start[b], M); c.take(st.last[b], M);
+        }
+    return c.size();
+}
+
 // A Kalman block ([5][Mc] float4 = mean, velocities, and the a / b / c entries of the four 2x2 covariance blocks; here as 4 floats
 // each) -> mean[cnt][8] = (mean, velocities) and cov[cnt][12] = per coordinate (a, b, c) of [[a, b], [b, c]].  Either may be null.
 inline void kalman_unpack(const float *block, size_t Mc, int cnt, float *mean, float *cov) {
@@ -76,6 +88,18 @@ inline void kalman_unpack(const float *block, size_t Mc, int cnt, float *mean, f
             if (cov) { cov[12 * i + 3 * k] = pa[k]; cov[12 * i + 3 * k + 1] = pb[k]; cov[12 * i + 3 * k + 2] = pc[k]; }
         }
     }
+}
+
+// BoT-SORT's block ([7][Mc] float4 = mean, velocities, 5 x 4 covariance entries) -> mean[cnt][8] and cov[cnt][20] = the upper triangles,
+// row-major, of the (cx, cy, vx, vy) block and of the (w, h, vw, vh) block.  Either may be null.
+inline void botsort_unpack(const float *block, size_t Mc, int cnt, float *mean, float *cov) {
+    for (size_t i = 0; i < (size_t)cnt; ++i)
+        for (int q = 0; q < 7; ++q)
+            for (int k = 0; k < 4; ++k) {
+                const float v = block[4 * (q * Mc + i) + k];
+                if (q < 2) { if (mean) mean[8 * i + 4 * q + k] = v; }
+                else if (cov) cov[20 * i + 4 * (q - 2) + k] = v;
+            }
 }
 
 }  // namespace rtmodt

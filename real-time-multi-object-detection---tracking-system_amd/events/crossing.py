@@ -140,7 +140,9 @@ class CrossingCounter:
         """All streams of ``tracker`` at once, on its device-resident state.  Returns one event list per stream.  A
         ``MultiObjectTracker`` / ``_ByteTrackCore`` passes the tracks ``tracker.report`` names (``"matched"``: matched or spawned
         this frame); a ``DeepSortTracker`` / ``_DeepSortCore`` its confirmed tracks matched this frame; an ``OcSortTracker`` /
-        ``_OcSortCore`` the tracks it returns this frame."""
+        ``_OcSortCore`` the tracks it returns this frame; a ``BotSortTracker`` / ``_BotSortCore`` its returned tracks matched this
+        frame."""
+        from ..tracking.botsort import _BotSortCore
         from ..tracking.deepsort import _DeepSortCore
         from ..tracking.ocsort import _OcSortCore
         from ..tracking.tracker import _ByteTrackCore
@@ -153,8 +155,10 @@ class CrossingCounter:
             rc = _ffi.lib().rtmodt_crossing_process_deepsort(self._h, core._h, int(frame_id), 0, ev, n)
         elif isinstance(core, _OcSortCore):
             rc = _ffi.lib().rtmodt_crossing_process_ocsort(self._h, core._h, int(frame_id), ev, n)
+        elif isinstance(core, _BotSortCore):
+            rc = _ffi.lib().rtmodt_crossing_process_botsort(self._h, core._h, int(frame_id), ev, n)
         else:
-            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT or the OC-SORT tracker; hand the tracks of a "
+            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; hand the tracks of a "
                             f"{type(tracker).__name__} over as a list: process(tracks, frame_id)")
         out = []
         if rc in (_ffi.OK, _ffi.E_CAPACITY):
