@@ -45,6 +45,7 @@ typedef struct rtmodt_jpeg rtmodt_jpeg;
 typedef struct rtmodt_deepsort rtmodt_deepsort;
 typedef struct rtmodt_ocsort rtmodt_ocsort;
 typedef struct rtmodt_botsort rtmodt_botsort;
+typedef struct rtmodt_gmc rtmodt_gmc;
 typedef struct rtmodt_reid rtmodt_reid;
 
 /* ---- library / device ------------------------------------------------------------- */
@@ -362,8 +363,8 @@ int rtmodt_ocsort_last_ms(rtmodt_ocsort *oc, float *update_ms);
  * removal), tests/botsort_ref.py restates them and the kernel equals that restatement bit for bit.  PARITY UNPINNED: BoT-SORT and
  * boxmot are installed nowhere this runs.  Class-agnostic.  A fixed number of launches per call whatever the counts.  Limits: 256
  * tracks and 1024 detections per stream, 64 streams, descriptors of at most 512 values, and the contested-pair limits of
- * rtmodt_assign_lapjv; beyond them RTMODT_E_CAPACITY, never a fault.  Estimating the warp from pixels is not part of this library:
- * it comes from whoever has it (PTZ telemetry, an estimator elsewhere). */
+ * rtmodt_assign_lapjv; beyond them RTMODT_E_CAPACITY, never a fault.  The warp comes from whoever has it (PTZ telemetry) or from
+ * the estimator below (rtmodt_gmc_*), which computes it from the frames themselves. */
 typedef struct rtmodt_botsort_cfg {
     float track_high_thresh;    /* H.2 row 3  0.6: high detections have conf > track_high_thresh (float32, strict)               */
     float track_low_thresh;     /* 0.1: low detections have track_low_thresh < conf < track_high_thresh                          */
@@ -409,6 +410,69 @@ int rtmodt_botsort_state(rtmodt_botsort *bot, int stream, int64_t *ids, int32_t 
                          int8_t *feat8, int32_t *n, int64_t *next_id, int64_t *frame_count);
 /* Device time (ms, HIP events) of the last update's three parts (H.2 row 3): descriptors (0 without frames), distance, update. */
 int rtmodt_botsort_last_ms(rtmodt_botsort *bot, float *describe_ms, float *distance_ms, float *update_ms);
+
+/* ---- camera-motion estimation for BoT-SORT: the warp of rtmodt_botsort_update_*, computed from two consecutive frames on the device ---- */
+/* csrc/gmc.hip states the rules (integer luma pyramid, coarse translation by SAD on level 1, 16 x 16 block matching on level 0 with a
+ * parabolic sub-pixel step, a fixed sequence of two-point hypotheses, a similarity refitted twice from exact integer sums),
+ * tests/gmc_ref.py restates them and the kernels equal that restatement bit for bit.  PARITY UNPINNED: OpenCV and BoT-SORT's GMC
+ * (sparse optical flow / ORB / ECC + estimateAffinePartial2D) are installed nowhere this runs; DESIGN.md section 23 lists the deliberate
+ * differences.  Six launches per call whatever the counts.  Limits: 64 streams, 4096 blocks per stream, frames up to 3840 x 2160,
+ * 1024 mask boxes per stream; beyond them RTMODT_E_CAPACITY, never a fault.  The smallest frame accepted has a level 1 of
+ * (2 coarse_search + 4) pixels each way, i.e. w, h >= 4 downscale (2 coarse_search + 4); below that RTMODT_E_INVALID.  BGR24 only. */
+typedef struct rtmodt_gmc_cfg {
+    int32_t downscale;        /* 4: level 0 is the d x d box average of the luma, d in {1, 2, 4, 8}                                  */
+    int32_t coarse_search;    /* 8: the coarse translation is searched over |dx|, |dy| <= coarse_search level-1 pixels, 0..16: it
+                               * reaches 4 downscale coarse_search pixels a frame                                                     */
+    int32_t search;           /* 4: a block is searched over |dx|, |dy| <= search level-0 pixels around the coarse shift, 1..8        */
+    int32_t min_texture;      /* 256: both gradient sums of a 16 x 16 block must reach it                                            */
+    int32_t max_sad;          /* 4096: the best SAD of a block must not exceed it                                                    */
+    float mask_conf;          /* 0.1: a box with conf >= mask_conf masks the blocks it meets                                         */
+    int32_t n_hyp;            /* 128: two-point hypotheses drawn, 1..256                                                             */
+    uint32_t seed;            /* 1: of the stated generator; the same inputs give the same warp, call after call                     */
+    float min_sep;            /* 32: a hypothesis whose two block centres are closer than this (pixels) is rejected                   */
+    float inlier_px;          /* 1.5: a correspondence within this residual (pixels) of the model is an inlier                        */
+    int32_t min_blocks;       /* 16: fewer valid blocks give the identity (status 2), >= 2                                           */
+    int32_t min_inliers;      /* 12: fewer inliers give the identity (status 3), >= 2                                                */
+    int32_t max_boxes;        /* mask boxes per stream of rtmodt_gmc_estimate_batch, 0..1024                                         */
+    int32_t n_streams, device;
+} rtmodt_gmc_cfg;
+/* Host only: the defaults above, max_boxes 1024, one stream, device 0.  PARITY UNPINNED (no OpenCV / GMC here). */
+void rtmodt_gmc_default_cfg(rtmodt_gmc_cfg *cfg);
+/* PARITY UNPINNED (no OpenCV / GMC here).  The pyramid buffers are carved at the first estimate, for its frame size. */
+int rtmodt_gmc_create(const rtmodt_gmc_cfg *cfg, rtmodt_gmc **out);
+void rtmodt_gmc_destroy(rtmodt_gmc *gmc);
+/* Forgets the previous frame of a stream (stream < 0: all): its next frame returns the identity with status 1.  Once every stream is
+ * reset the frame size may change. */
+int rtmodt_gmc_reset(rtmodt_gmc *gmc, int stream);
+/* One BGR24 frame for every stream, as rtmodt_deepsort_update_batch takes frames (PARITY UNPINNED).  mask_xyxy[n_streams][max_boxes][4],
+ * mask_conf[n_streams][max_boxes], mask_n[n_streams]: host arrays, all may be NULL (no mask).  warp_out[n_streams][6]: row-major 2x3
+ * [a, -b, tx; b, a, ty], previous frame to this one, full-resolution pixels; status_out[n_streams]: 0 estimated, 1 first frame,
+ * 2 too few valid blocks, 3 too few inliers, 4 scale outside [0.5, 2]; with a status other than 0 the warp is exactly the identity,
+ * so the output always passes rtmodt_botsort_check_warp.  A frame size other than the previous call's without a reset of every
+ * stream, or a frame below the smallest accepted, is RTMODT_E_INVALID; beyond a limit RTMODT_E_CAPACITY; both before any launch. */
+int rtmodt_gmc_estimate_batch(rtmodt_gmc *gmc, const uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind,
+                              const float *mask_xyxy, const float *mask_conf, const int32_t *mask_n, float *warp_out, int32_t *status_out);
+/* The same for the frames of det's last enqueue_batch (stream i <- frame i), masked with its device-resident detections, queued on
+ * det's HIP stream behind its NMS: no copy of the detections, no wait (PARITY UNPINNED).  rtmodt_gmc_result fetches. */
+int rtmodt_gmc_estimate_from_detector(rtmodt_gmc *gmc, rtmodt_detector *det, const uint8_t *const *frames, int n_frames, int h, int w,
+                                      int stride_bytes, int mem_kind);
+/* Waits for the last estimate and copies warp_out[n_streams][6] / status_out[n_streams] (either may be NULL). */
+int rtmodt_gmc_result(rtmodt_gmc *gmc, float *warp_out, int32_t *status_out);
+/* Every intermediate of a stream's last frame the tests compare with tests/gmc_ref.py; any pointer may be NULL.  With W0 = w / d,
+ * H0 = h / d, W1 = W0 / 4, H1 = H0 / 4, nb = (W0 / 16) (H0 / 16): l0[H0][W0], l1[H1][W1] of the current frame; coarse_table[1089]
+ * ((2 cs + 1)^2 entries used, [dy + cs][dx + cs]); coarse_shift[2] = (dx, dy); blk[6][nb] = reason, dx, dy, offx, offy, sad;
+ * order[nb] (n_valid used); hyp_score[256] (-1: rejected or not drawn); best_k; inliers[2][nb] (bytes, compacted order, both rounds);
+ * sums[2][8] = N, SPx, SPy, SQx, SQy, S(P.Q), S(PxQ), S|P|^2; model[3][4] = a, b, tx, ty (1/16 pixel) of the winning hypothesis and
+ * of both refits.  After a first frame only l0 and l1 are defined.  Stages not reached leave zeros (best_k -1). */
+int rtmodt_gmc_debug(rtmodt_gmc *gmc, int stream, uint8_t *l0, uint8_t *l1, int32_t *coarse_table, int32_t *coarse_shift, int32_t *blk,
+                     int32_t *order, int32_t *n_valid, int32_t *hyp_score, int32_t *best_k, uint8_t *inliers, int64_t *sums, double *model);
+/* Device time (ms, HIP events) of the last estimate's six launches. */
+int rtmodt_gmc_last_ms(rtmodt_gmc *gmc, float *estimate_ms);
+/* rtmodt_botsort_update_from_detector with the warp estimated by gmc from the same frames (PARITY UNPINNED): the estimate and the
+ * update are queued on det's stream, botsort_update reads the six floats of stream s from the estimator's device buffer, nothing
+ * crosses the host.  frames are required (the estimator reads them; a handle with an embedder describes the detections on them). */
+int rtmodt_botsort_update_from_detector_gmc(rtmodt_botsort *bot, rtmodt_detector *det, rtmodt_gmc *gmc, const uint8_t *const *frames,
+                                            int n_frames, int h, int w, int stride_bytes, int mem_kind);
 
 /* ---- the embedder of default.yaml:60 (`tracking.deepsort.embedder: "weights/osnet_x0_25.onnx"`): OSNet x0.25 on the GPU ---- */
 /* csrc/reid.hip states the crop rule, the rounding contract and the launches; tests/reid_ref.py restates them.  PINNED: the crop

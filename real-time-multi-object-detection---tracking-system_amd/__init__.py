@@ -13,6 +13,7 @@ library being built):
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
 * ``tracking.botsort``   -- ``BotSortTracker``: BoT-SORT, the comparison's best row (Re-ID fusion, camera-motion compensation), on the GPU
+* ``tracking.gmc``       -- ``CameraMotionEstimator``: the camera-motion warp BoT-SORT compensates with, estimated from the frames on the GPU
 * ``tracking.swapguard`` -- ``IdSwapGuard``: ByteTrack identities verified by appearance, ID swaps reverted online on the GPU (the
                             design document's B.4 / G.1 appearance verification, which the reference does not implement)
 * ``tracking.reid``      -- ``ReidEmbedder``: the OSNet x0.25 re-identification network on the GPU (reference: config/default.yaml:60)
@@ -47,6 +48,7 @@ _LAZY = {
     "DeepSortTracker": ".tracking.deepsort",
     "OcSortTracker": ".tracking.ocsort",
     "BotSortTracker": ".tracking.botsort",
+    "CameraMotionEstimator": ".tracking.gmc",
     "IdSwapGuard": ".tracking.swapguard",
     "SwapEvent": ".tracking.swapguard",
     "ZoneEventEngine": ".events.zone_engine",

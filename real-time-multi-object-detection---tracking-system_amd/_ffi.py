@@ -156,6 +156,12 @@ class BotSortCfg(C.Structure):                      # struct rtmodt_botsort_cfg
                 ("device", C.c_int32)]
 
 
+class GmcCfg(C.Structure):                          # struct rtmodt_gmc_cfg
+    _fields_ = [("downscale", C.c_int32), ("coarse_search", C.c_int32), ("search", C.c_int32), ("min_texture", C.c_int32), ("max_sad", C.c_int32),
+                ("mask_conf", C.c_float), ("n_hyp", C.c_int32), ("seed", C.c_uint32), ("min_sep", C.c_float), ("inlier_px", C.c_float),
+                ("min_blocks", C.c_int32), ("min_inliers", C.c_int32), ("max_boxes", C.c_int32), ("n_streams", C.c_int32), ("device", C.c_int32)]
+
+
 class ReidCfg(C.Structure):                         # struct rtmodt_reid_cfg
     _fields_ = [("weight_path", C.c_char_p), ("device", C.c_int32), ("max_frames", C.c_int32), ("max_boxes", C.c_int32)]
 
@@ -285,6 +291,16 @@ def lib() -> C.CDLL:
         "rtmodt_botsort_update_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "rtmodt_botsort_state": (C.c_int, [vp, C.c_int] + [vp] * 13 + [C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]),
         "rtmodt_botsort_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_botsort_update_from_detector_gmc": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_gmc_default_cfg": (None, [C.POINTER(GmcCfg)]),
+        "rtmodt_gmc_create": (C.c_int, [C.POINTER(GmcCfg), C.POINTER(vp)]),
+        "rtmodt_gmc_destroy": (None, [vp]),
+        "rtmodt_gmc_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_gmc_estimate_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+        "rtmodt_gmc_estimate_from_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_gmc_result": (C.c_int, [vp, vp, vp]),
+        "rtmodt_gmc_debug": (C.c_int, [vp, C.c_int] + [vp] * 12),
+        "rtmodt_gmc_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_reid_create": (C.c_int, [C.POINTER(ReidCfg), C.POINTER(vp)]),
         "rtmodt_reid_destroy": (None, [vp]),
         "rtmodt_reid_embed": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),

@@ -22,7 +22,8 @@
 //   predict   tracked and lost tracks (a lost track's vw, vh are zeroed first); new tracks are not predicted; age += 1, tsu += 1
 //   warp      the caller's 2x3 affine [R | t] of the stream, after predict, on every track: each pair (cx, cy), (w, h), (vx, vy),
 //             (vw, vh) times R, t added to (cx, cy), each block M P M' with M = diag(R, R) as T = R X, then T R' per 2x2 part.  No
-//             warp, or exactly the identity: the step is skipped and the state keeps its bits
+//             warp, or exactly the identity: the step is skipped and the state keeps its bits.  The six floats come by value in
+//             the kernel arguments, or (warp_dev) from the device buffer the estimator of gmc.hip wrote them to
 //   split     high: conf > track_high_thresh; low: track_low_thresh < conf < track_high_thresh (both strict), input order kept
 //   feature   int8 descriptor rows f; a track holds s16[dim] (int16, norm 16256 = 127 * 128) and s8[dim] (the int8 row the matrix
 //             cores read).  On a match v = 9 s16 + 128 f (a birth: v = 128 f) in int32, r = isqrt64(sum v^2), s16 = sign(v) ((16256 |v|
@@ -68,6 +69,7 @@ struct BotArgs {
     const int32_t *dot;                                      // [stream][max_tracks][max_dets], columns = detection index
     int16_t *feat16; int8_t *feat8;                          // [stream][2][max_tracks][dim]
     int has_warp; BotWarps warp;
+    const float *warp_dev;                                   // not null: [stream][6] on the device (gmc.hip), read instead of `warp`
 };
 
 constexpr float BOT_WP = 0.05f, BOT_WV = 0.00625f;
@@ -257,9 +259,10 @@ __global__ __launch_bounds__(TRK_THREADS) void botsort_update(BotArgs a) {
     const int32_t *gk = a.det_cls + (size_t)s * a.det_stride;
     const int8_t *desc = a.desc + (size_t)s * a.desc_stride * D;
     const int32_t *dm = a.dot + (size_t)s * Mc * Nc;
-    const float4 R = float4{a.warp.m[s][0], a.warp.m[s][1], a.warp.m[s][3], a.warp.m[s][4]};
-    const float wtx = a.warp.m[s][2], wty = a.warp.m[s][5];
-    const bool warped = a.has_warp && !(R.x == 1.0f && R.y == 0.0f && R.z == 0.0f && R.w == 1.0f && wtx == 0.0f && wty == 0.0f);
+    const float *wm = a.warp_dev ? a.warp_dev + 6 * s : a.warp.m[s];
+    const float4 R = float4{wm[0], wm[1], wm[3], wm[4]};
+    const float wtx = wm[2], wty = wm[5];
+    const bool warped = (a.has_warp || a.warp_dev) && !(R.x == 1.0f && R.y == 0.0f && R.z == 0.0f && R.w == 1.0f && wtx == 0.0f && wty == 0.0f);
 
     // ---- predict, warp ----
     for (int i = tid; i < M; i += TRK_THREADS) {
@@ -682,6 +685,25 @@ int rtmodt_botsort_update_from_detector(rtmodt_botsort *t, rtmodt_detector *det,
     BotArgs a = bot_args(t, warp, o.count);                // the warp travels in the kernel arguments: nothing to copy, nothing to wait for
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
     RT_TRY(bot_run(t, a, o.count, frames ? &fp : nullptr, h, w, stride_bytes, o.stream));
+    return track_detector_done(t, o.stream);
+}
+
+int rtmodt_botsort_update_from_detector_gmc(rtmodt_botsort *t, rtmodt_detector *det, rtmodt_gmc *gmc, const uint8_t *const *frames, int n_frames, int h,
+                                            int w, int stride_bytes, int mem_kind) {
+    RT_CHECK(t && det && gmc && frames, RTMODT_E_INVALID, "null argument");
+    RT_CHECK(!t->dim || t->reid || t->dim == APP_DIM, RTMODT_E_INVALID, "a handle for caller descriptors cannot describe a detector's boxes");
+    DetOutputs o;
+    RT_TRY(track_detector_outputs(t, det, &o));
+    RT_CHECK(n_frames == o.count, RTMODT_E_INVALID, "%d frames for the detector's batch of %d", n_frames, o.count);
+    RT_TRY(track_detector_fits(t, o, o.count));
+    const float *warp_dev = nullptr;
+    RT_TRY(gmc_enqueue_detector(gmc, o, frames, n_frames, h, w, stride_bytes, mem_kind, &warp_dev));      // first: refused before anything of this call is queued
+    AppFrames fp{};
+    if (t->dim) RT_TRY(bot_frames(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
+    BotArgs a = bot_args(t, nullptr, o.count);
+    a.warp_dev = warp_dev;
+    a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
+    RT_TRY(bot_run(t, a, o.count, t->dim ? &fp : nullptr, h, w, stride_bytes, o.stream));
     return track_detector_done(t, o.stream);
 }
 

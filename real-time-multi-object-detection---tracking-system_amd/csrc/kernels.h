@@ -341,5 +341,8 @@ int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };
 int detector_outputs(rtmodt_detector *det, DetOutputs *out);
+// gmc.hip: the camera-motion estimate of the detector's batch, queued on its stream; *warp_dev = the estimator's [stream][6] device buffer
+int gmc_enqueue_detector(rtmodt_gmc *g, const DetOutputs &o, const uint8_t *const *frames, int n_frames, int h, int w, int pitch, int mem_kind,
+                         const float **warp_dev);
 
 }  // namespace rtmodt

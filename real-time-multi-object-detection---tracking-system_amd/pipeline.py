@@ -122,7 +122,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         if crossing_counter is not None and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
         profiler.tick("tracking")
-        if needs_frame:                                    # a tracker that describes its detections on the frame (DeepSortTracker)
+        if needs_frame:                                    # a tracker that describes its detections on the frame (DeepSortTracker) or estimates the camera motion from it (BotSortTracker(gmc=))
             tracks = tracker.update_from_detector(detector, frame=frame, materialize=not events_on_device) if handoff else tracker.update(detections, frame=frame)
         else:
             tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)

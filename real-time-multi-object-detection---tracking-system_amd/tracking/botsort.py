@@ -6,8 +6,8 @@ The algorithm is the published one (Aharon et al., "BoT-SORT: Robust Association
 reads it, with the state resident on the GPU behind ``rtmodt_botsort_*`` (``include/rtmodt.h``, ``csrc/botsort.hip``): the Kalman
 states are compensated for camera motion by a warp the caller supplies, and IoU is fused with the detection score and with
 appearance.  PINNED: the kernel equals the plain-Python restatement ``tests/botsort_ref.py`` bit for bit.  PARITY UNPINNED:
-``BoT-SORT`` and ``boxmot`` are installed nowhere this runs.  Estimating the warp from pixels is not done here: it comes from whoever
-has it (PTZ telemetry, an estimator elsewhere).
+``BoT-SORT`` and ``boxmot`` are installed nowhere this runs.  The warp comes from whoever has it (PTZ telemetry) or, with ``gmc=``, from
+``tracking.gmc.CameraMotionEstimator``, which computes it from the frames on the GPU.
 """
 from __future__ import annotations
 
@@ -122,6 +122,16 @@ class _BotSortCore:
         if keep:                                         # pageable host frames: the copy has been issued from them; wait before they may go
             _ffi.check(_ffi.lib().rtmodt_synchronize(self._device))
 
+    def update_from_detector_gmc(self, detector, gmc, frames, *, mem_kind=_ffi.MEM_HOST, height=0, width=0, stride=0) -> None:
+        """:meth:`update_from_detector` with the warp estimated by ``gmc`` (a ``CameraMotionEstimator``) from the same frames: the
+        estimate and the update are queued on the detector's stream and the warp never leaves the device."""
+        fp, keep, height, width, stride = _ffi.frame_pointers(frames, mem_kind, height, width, stride)
+        _ffi.check(_ffi.lib().rtmodt_botsort_update_from_detector_gmc(self._h, detector.model.handle, gmc.handle, fp, len(frames), int(height),
+                                                                      int(width), int(stride), int(mem_kind)))
+        gmc._geom = (int(height), int(width))
+        if keep:
+            _ffi.check(_ffi.lib().rtmodt_synchronize(self._device))
+
     def snapshot(self, stream: int = 0, allow_capacity: bool = False, features: bool = True) -> dict:
         """The parity surface (``rtmodt_botsort_state``), list order.  ``allow_capacity``: a stream in sticky ``E_CAPACITY`` error is
         still read (the call fills its outputs before it reports the error) and the dict carries ``"error"``."""
@@ -179,8 +189,9 @@ class BotSortTracker:
     published; ``xyxy`` = the box of the filter's mean, ``time_since_update`` tells the two apart; trails as ``MultiObjectTracker``
     keeps them.  ``embedder``: ``"none"`` (motion only), ``"colorhist"`` (the built-in descriptor, computed from ``frame``; or with
     ``embedding_dim`` caller descriptors through ``embeddings=``) or an ``.rtreid`` file (the OSNet x0.25 network).  ``warp``: the
-    2x3 image motion from the previous frame to this one; a caller with a moving camera drives the tracker itself, ``pipeline.run``
-    passes none.  Class-agnostic: a track carries the class of its last matched detection."""
+    2x3 image motion from the previous frame to this one.  ``gmc``: a ``CameraMotionEstimator``; with one, ``update`` estimates the
+    warp from ``frame`` (masking with the frame's detections) when no ``warp`` is passed, ``update_from_detector`` keeps estimate and
+    update on the device, and ``pipeline.run`` hands the frame over; passing both ``gmc`` and an explicit ``warp`` raises.  Class-agnostic: a track carries the class of its last matched detection."""
 
     #: the zone engine reads only a ByteTrack handle on the device: ``pipeline.run`` hands it this tracker's materialised list
     zone_events_on_device = False
@@ -188,7 +199,10 @@ class BotSortTracker:
     def __init__(self, track_high_thresh: float = 0.6, track_low_thresh: float = 0.1, new_track_thresh: float = 0.7, track_buffer: int = 30,
                  match_thresh: float = 0.8, proximity_thresh: float = 0.5, appearance_thresh: float = 0.25, fuse_score: bool = True,
                  embedder: str = NO_EMBEDDER, *, embedding_dim: int = 0, device=0, max_tracks: int = DEFAULT_MAX_TRACKS,
-                 max_dets: int | None = None) -> None:
+                 max_dets: int | None = None, gmc=None) -> None:
+        if gmc is not None and gmc.n_streams != 1:
+            raise ValueError("BotSortTracker drives one stream: its estimator must have n_streams == 1")
+        self.gmc = gmc
         if embedder in (None, ""):
             embedder = NO_EMBEDDER
         if str(embedder).endswith(SUFFIX):
@@ -209,7 +223,8 @@ class BotSortTracker:
         self._core = _BotSortCore(track_high_thresh, track_low_thresh, new_track_thresh, track_buffer, match_thresh, proximity_thresh,
                                   appearance_thresh, fuse_score, embedder, dim=embedding_dim, device=device, max_tracks=max_tracks, max_dets=max_dets)
         #: ``pipeline.run`` hands the frame to a tracker that describes its detections on it
-        self.needs_frame = str(embedder).endswith(SUFFIX) or (embedder == BUILTIN_EMBEDDER and self._core.dim == BUILTIN_DIM)
+        self._describes = str(embedder).endswith(SUFFIX) or (embedder == BUILTIN_EMBEDDER and self._core.dim == BUILTIN_DIM)
+        self.needs_frame = self._describes or gmc is not None
         self._trails = TrailKeeper()
 
     @classmethod
@@ -222,8 +237,18 @@ class BotSortTracker:
                  "appearance_thresh", "fuse_score", "embedder", "embedding_dim", "device", "max_tracks", "max_dets")
         return cls(**{k: v for k, v in p.items() if k in known})
 
+    def _estimate(self, detections, frame, warp):
+        if self.gmc is None:
+            return warp
+        if warp is not None:
+            raise ValueError("this tracker estimates the warp itself (gmc=): pass no warp")
+        if frame is None:
+            raise ValueError("a tracker with an estimator (gmc=) needs the frame")
+        return self.gmc.estimate([frame], [detections])[0]
+
     def update(self, detections, frame=None, warp=None, embeddings=None) -> list:
         n = len(detections.confidence)
+        warp = self._estimate(detections, frame, warp)
         if self.embedder == NO_EMBEDDER:
             frame = None                                        # motion only: the frame pipeline.run may offer is not used
             if embeddings is not None:
@@ -242,7 +267,12 @@ class BotSortTracker:
         """:meth:`update` fed from ``detector``'s device-resident detections of its last ``detect`` on ``frame``."""
         if self.needs_frame and frame is None:
             raise ValueError("update_from_detector() needs the frame the detector ran on")
-        self._core.update_from_detector(detector, [frame] if self.needs_frame else None, check_warp(warp))
+        if self.gmc is not None:
+            if warp is not None:
+                raise ValueError("this tracker estimates the warp itself (gmc=): pass no warp")
+            self._core.update_from_detector_gmc(detector, self.gmc, [frame])
+        else:
+            self._core.update_from_detector(detector, [frame] if self._describes else None, check_warp(warp))
         return self._tracks_out() if materialize else []
 
     def _tracks_out(self) -> list:
