@@ -42,6 +42,7 @@ typedef struct rtmodt_tracker rtmodt_tracker;
 typedef struct rtmodt_zones rtmodt_zones;
 typedef struct rtmodt_renderer rtmodt_renderer;
 typedef struct rtmodt_jpeg rtmodt_jpeg;
+typedef struct rtmodt_jpegdec rtmodt_jpegdec;
 typedef struct rtmodt_deepsort rtmodt_deepsort;
 typedef struct rtmodt_ocsort rtmodt_ocsort;
 typedef struct rtmodt_botsort rtmodt_botsort;
@@ -720,6 +721,55 @@ int rtmodt_jpeg_last_ms(rtmodt_jpeg *j, float *kernel_ms);
 /* Host only, no device needed: everything from SOI up to and including the SOS header of an h x w file at `quality` (1..100).
  * *needed = its size; written to out when out_bytes >= *needed. */
 int rtmodt_jpeg_header(int quality, int h, int w, uint8_t *out, size_t out_bytes, size_t *needed);
+
+/* ---- JPEG / Motion-JPEG decoder: replaces `cap.read()` of src/ingestion/rtsp_reader.py (cv2.VideoCapture on an MJPEG camera) and
+ * the image upload of web/server.py (cv2.imdecode) ---------------------------------------------------------------------------- */
+/* Baseline JPEG files (SOF0, 8 bit, 1 or 3 components, one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0 / gray, any Huffman tables, any
+ * DRI; files without DHT use the Annex K tables) become BGR24 frames (csrc/jpeg_dec.hip; the stream rules are in
+ * csrc/jpeg_dec_core.h; tests/jpeg_dec_ref.py restates both).  The arithmetic is libjpeg's (islow IDCT, fancy upsampling):
+ * PARITY PINNED -- the pixels equal libjpeg-turbo 3.1's default decoder's (Pillow) byte for byte on accepted streams.  UNPINNED: parity
+ * with cv2's / cameras' decoders, and everything about damaged streams (statuses below; libjpeg's concealment is not reproduced). */
+#define RTMODT_JPEG_OK 0
+#define RTMODT_JPEG_UNSUPPORTED 1    /* progressive, extended, lossless, arithmetic, 12 bit, several scans, 4 components, other sampling */
+#define RTMODT_JPEG_CORRUPT 2        /* broken structure; a restart marker missing, surplus or misnumbered; an impossible code        */
+#define RTMODT_JPEG_TRUNCATED 3      /* the file ends inside the header, or a restart interval ends before its last MCU               */
+#define RTMODT_JPEG_SIZE_MISMATCH 4  /* a sound file whose h x w is not the call's                                                    */
+typedef struct rtmodt_jpeg_info {
+    int32_t status;                  /* RTMODT_JPEG_*; the other fields are valid as far as the header was read                       */
+    int32_t h, w, components;
+    int32_t h_samp, v_samp;          /* luminance sampling factors: 1x1 (4:4:4, gray), 2x1 (4:2:2), 2x2 (4:2:0)                       */
+    int32_t restart_interval;        /* MCUs, 0: none -- such a stream is decoded by ONE GPU lane per frame (slow)                    */
+    int32_t reserved;
+    char message[96];                /* what is unsupported / wrong, "" when OK                                                       */
+} rtmodt_jpeg_info;
+/* What `cap.read()` / cv2.imdecode would be asked to decode: reads the header of file[0, bytes) up to and including SOS.  Host only,
+ * no device.  Returns RTMODT_OK whenever info was filled (whatever info->status says); RTMODT_E_INVALID for null pointers. */
+int rtmodt_jpeg_probe(const uint8_t *file, size_t bytes, rtmodt_jpeg_info *info);
+typedef struct rtmodt_jpegdec_cfg {
+    int32_t max_h, max_w;            /* largest frame the handle accepts (<= 8192 each)                                               */
+    int32_t max_batch;               /* files per call                                                                                */
+    int64_t max_file_bytes;          /* largest file; 0 = max_h * max_w * 3 / 4 + 65536.  Page-locked staging: max_batch x this        */
+} rtmodt_jpegdec_cfg;
+/* The handle behind an MJPEG `cap.read()` (rtsp_reader.py) / the web server's image upload.  Device scratch grows with the calls:
+ * 192 bytes per 8x8 block (coefficients + planes) and 4 bytes per restart interval. */
+int rtmodt_jpegdec_create(int device, const rtmodt_jpegdec_cfg *cfg, rtmodt_jpegdec **out);
+void rtmodt_jpegdec_destroy(rtmodt_jpegdec *dec);
+/* `ok, frame = cap.read()` (rtsp_reader.py) / cv2.imdecode of an upload (web/server.py) for n files: files[i][0, sizes[i]) (host
+ * memory) is decoded into frames[i], n frames of h x w BGR24 with row pitch stride_bytes >= 3w; only the 3w bytes of a row are
+ * written.  mem_kind as in rtmodt_render_batch: RTMODT_MEM_DEVICE frames are device pointers -- directly what
+ * rtmodt_detector_enqueue_batch(..., RTMODT_MEM_DEVICE) and rtmodt_render_batch take; RTMODT_MEM_HOST frames are copied back.
+ * status[i] (host) = RTMODT_JPEG_*; a frame whose status is not OK has unspecified pixels inside its own rows (here: untouched).
+ * The call succeeds when individual files fail.  RTMODT_E_CAPACITY, nothing launched, when n, h, w or a file's size exceeds the
+ * handle; RTMODT_E_INVALID for null pointers, stride_bytes < 3w or a bad mem_kind; n = 0: success, nothing launched.  Four
+ * launches per call whatever n is; returns when the frames are final. */
+int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *dec, const uint8_t *const *files, const size_t *sizes, int n, uint8_t *const *frames,
+                                int h, int w, int stride_bytes, int mem_kind, int32_t *status);
+/* Device time (ms, HIP events) of the last decode_batch's kernels (the `cap.read()` cost that moved to the GPU). */
+int rtmodt_jpegdec_last_ms(rtmodt_jpegdec *dec, float *kernel_ms);
+/* Diagnostics of `cap.read()`'s replacement: the entropy decoder's output for one component of one frame of the last decode_batch,
+ * int16 [rows][cols][64] in natural order, not dequantised (whole MCUs).  *rows / *cols are always set; out is written when
+ * out_elems >= rows * cols * 64. */
+int rtmodt_jpegdec_coefficients(rtmodt_jpegdec *dec, int frame, int component, int16_t *out, size_t out_elems, int *rows, int *cols);
 
 /* ---- offline evaluation: replaces src/evaluation/metrics.py's pycocotools / motmetrics calls --------------------- */
 /* PARITY UNPINNED: neither library is installed anywhere this runs.  The rules are restated in csrc/eval.hip's header and

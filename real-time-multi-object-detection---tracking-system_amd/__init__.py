@@ -30,7 +30,8 @@ library being built):
                             (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
                             frames as JPEG / Motion-JPEG, encoded on the GPU (reference: tools/run_pipeline.py:112-117,160-161)
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
-                            decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158)
+                            decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158); ``JpegDecoder`` /
+                            ``MjpegCapture``: JPEG / Motion-JPEG files, AVI and multipart streams decoded on the GPU
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
                             in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py); ``stitch_tracks`` /
                             ``correct_id_switches``: fragmented tracks merged and their gaps filled on the GPU (the design
@@ -55,6 +56,8 @@ _LAZY = {
     "CrossingCounter": ".events.crossing",
     "FrameReader": ".ingestion.reader",
     "RTSPReader": ".ingestion.reader",
+    "JpegDecoder": ".ingestion.jpeg_decode",
+    "MjpegCapture": ".ingestion.mjpeg",
     "FrameRenderer": ".visualization.renderer",
     "JpegEncoder": ".visualization.jpeg",
     "MjpegWriter": ".visualization.jpeg",

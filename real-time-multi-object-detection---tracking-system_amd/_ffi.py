@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rtmodt.h")
 OK, E_INVALID, E_IO, E_HIP, E_CAPACITY, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 MEM_HOST, MEM_DEVICE = 0, 1
 PIX_BGR24, PIX_NV12, PIX_I420 = 0, 1, 2
+JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_TRUNCATED, JPEG_SIZE_MISMATCH = 0, 1, 2, 3, 4
 PIXEL_FORMATS = {"bgr24": PIX_BGR24, "nv12": PIX_NV12, "i420": PIX_I420, "yuv420p": PIX_I420}
 ASSIGN_GREEDY, ASSIGN_LAPJV = 0, 1
 
@@ -135,6 +136,15 @@ class RenderList(C.Structure):                       # struct rtmodt_render_list
 
 class JpegCfg(C.Structure):                          # struct rtmodt_jpeg_cfg
     _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("max_h", C.c_int32), ("max_w", C.c_int32), ("max_batch", C.c_int32)]
+
+
+class JpegInfo(C.Structure):                         # struct rtmodt_jpeg_info
+    _fields_ = [("status", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32),
+                ("v_samp", C.c_int32), ("restart_interval", C.c_int32), ("reserved", C.c_int32), ("message", C.c_char * 96)]
+
+
+class JpegDecCfg(C.Structure):                       # struct rtmodt_jpegdec_cfg
+    _fields_ = [("max_h", C.c_int32), ("max_w", C.c_int32), ("max_batch", C.c_int32), ("max_file_bytes", C.c_int64)]
 
 
 class DeepSortCfg(C.Structure):                     # struct rtmodt_deepsort_cfg
@@ -343,6 +353,12 @@ def lib() -> C.CDLL:
         "rtmodt_jpeg_encode_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]),
         "rtmodt_jpeg_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rtmodt_jpeg_probe": (C.c_int, [vp, C.c_size_t, C.POINTER(JpegInfo)]),
+        "rtmodt_jpegdec_create": (C.c_int, [C.c_int, C.POINTER(JpegDecCfg), C.POINTER(vp)]),
+        "rtmodt_jpegdec_destroy": (None, [vp]),
+        "rtmodt_jpegdec_decode_batch": (C.c_int, [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_jpegdec_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_jpegdec_coefficients": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "rtmodt_coco_eval": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp]),
         "rtmodt_mot_eval": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(MotCounts)]),
