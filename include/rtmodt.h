@@ -991,6 +991,81 @@ int rtmodt_swapguard_counts(rtmodt_swapguard *g, int stream, int64_t *n_reverted
  * gather + step (B.4 calls the check "lightweight"; this is where that is measured).  PARITY UNPINNED. */
 int rtmodt_swapguard_last_ms(rtmodt_swapguard *g, float *describe_ms, float *step_ms);
 
+/* ---- sliced inference: the cure for config/default.yaml:24-26, 34 (1920 x 1080 frames into a 640 x 640 detector) --------------- */
+/* The reference shrinks every object three times before the network sees it; its design document lists "Missed small objects"
+ * (B.4's failure table, mitigation "lower track_thresh or use YOLOv8m") and marks conf 0.40 "Misses small objects" (B.3's
+ * threshold table).  The standard cure that keeps the model is the SAHI scheme: cut the frame into overlapping tiles at native
+ * resolution, detect in every tile plus one down-scaled overview, merge the boxes back in frame coordinates.  Here the cut and
+ * the merge run on the GPU around an ordinary detector handle (csrc/slice.hip states the rules, DESIGN.md section 25 the
+ * layouts).  PINNED against tests/slice_ref.py, bit for bit: the tile bytes, the per-image detections, the merge.  PARITY
+ * UNPINNED: the `sahi` package is installed nowhere this runs.  UNPINNED as well: any accuracy gain on real footage -- no trained
+ * checkpoint exists offline, so the small-object claim rests on the published method, not on a measurement here.
+ *
+ * Grid: along an axis of length L with tile t and overlap o (0 <= o < t): te = min(t, L), step = te - o (one position, 0, when
+ * step <= 0), p_k = min(k * step, L - te) up to and including the first with p_k + te >= L -- every tile is full size, the last
+ * one shifted inward.  Tiles are ordered row-major (y outer, x inner); at most 64 per frame, else RTMODT_E_CAPACITY.  With T
+ * tiles and the overview on, a frame is I = T + 1 images; a batch of n frames is n * I images of te_w x te_h BGR24 with pitch
+ * 3 * te_w, frame-major (image f * I + j; j == T is the overview: the whole frame letterboxed with 114 padding). */
+#define RTMODT_SLICE_MERGE_NMM 0   /* greedy non-maximum merging: a keeper absorbs its matches into a min / max union box */
+#define RTMODT_SLICE_MERGE_NMS 1   /* a keeper drops its matches                                                          */
+#define RTMODT_SLICE_METRIC_IOS 0  /* inter / min(area_a, area_b)                                                         */
+#define RTMODT_SLICE_METRIC_IOU 1  /* inter / (area_a + area_b - inter)                                                   */
+typedef struct rtmodt_slicer rtmodt_slicer;
+typedef struct rtmodt_slice_cfg {
+    int32_t device;
+    int32_t frame_w, frame_h;     /* the source frames (config/default.yaml:24-26: 1920 x 1080)                              */
+    int32_t tile_w, tile_h;       /* requested tile = the detector's input (config/default.yaml:34: 640); effective min(t, L) */
+    int32_t overlap_w, overlap_h; /* pixels, 0 <= overlap < tile                                                            */
+    int32_t overview;             /* 1: one more image per frame, the whole frame letterboxed into the effective tile       */
+    int32_t merge;                /* RTMODT_SLICE_MERGE_*  (SAHI's default: NMM)                                            */
+    int32_t metric;               /* RTMODT_SLICE_METRIC_* (SAHI's default: IoS)                                            */
+    float match_thresh;           /* a pair matches when the metric is > match_thresh (strict, float32; SAHI's default 0.5)  */
+    int32_t agnostic;             /* 0: only boxes of one class match                                                       */
+    int32_t max_out;              /* merged detections kept per frame (1..4096), the first in (conf, image, slot) order     */
+    int32_t max_frames;           /* frames per sliced batch; max_frames * I <= 64 (a detector batch)                       */
+} rtmodt_slice_cfg;
+/* The grid alone, host only (no device is touched): xs / ys[64] (may be NULL) receive the tile origins, *n_tiles their count,
+ * *te_w / *te_h the effective tile.  RTMODT_E_INVALID for a bad argument, RTMODT_E_CAPACITY for more than 64 tiles. */
+int rtmodt_slice_grid(int frame_w, int frame_h, int tile_w, int tile_h, int overlap_w, int overlap_h, int32_t *xs, int32_t *ys,
+                      int32_t *n_tiles, int32_t *te_w, int32_t *te_h);
+/* A slicer for detectors built with `max_det` detections per image.  The merge sorts a frame's candidates in LDS: I * max_det
+ * above 8192 is RTMODT_E_CAPACITY, as is max_frames * I above 64; bad arguments (overlap >= tile among them) are
+ * RTMODT_E_INVALID; nothing is allocated in either case. */
+int rtmodt_slicer_create(const rtmodt_slice_cfg *cfg, int max_det, rtmodt_slicer **out);
+/* Waits for the work queued on behalf of the handle (its own stream, the merges on a detector's stream), then frees it; null is
+ * allowed.  Destroy the slicer before the detector it was last used with. */
+void rtmodt_slicer_destroy(rtmodt_slicer *s);
+int rtmodt_slicer_info(rtmodt_slicer *s, int32_t *n_tiles, int32_t *images_per_frame, int32_t *te_w, int32_t *te_h);
+/* slice_gather alone: n frames (frame_h x frame_w BGR24, row pitch >= 3 * frame_w, host or device memory by mem_kind) are cut in
+ * ONE launch and the n * I images copied out to tiles_out_host.  Not while a sliced batch is in flight (RTMODT_E_INVALID). */
+int rtmodt_slicer_gather(rtmodt_slicer *s, const uint8_t *const *frames, int n, int pitch, int mem_kind, uint8_t *tiles_out_host);
+/* slice_merge alone on caller-supplied per-image detections (host arrays, the layout rtmodt_detector_fetch hands out for a batch of
+ * n_frames * I images: det_xyxy[n_frames * I][max_det][4] in image coordinates, det_conf / det_cls[n_frames * I][max_det],
+ * det_n[n_frames * I]); cfg->device and cfg->max_frames are not used.  One workgroup per frame.  Outputs (host):
+ * xyxy[n_frames][max_out][4], conf / cls / n_merged[n_frames][max_out] (n_merged: boxes the keeper absorbed or dropped),
+ * n_out[n_frames]; *kernel_ms (may be NULL) the launch's device time from HIP events. */
+int rtmodt_slice_merge(int device, const rtmodt_slice_cfg *cfg, int max_det, int n_frames, const float *det_xyxy, const float *det_conf,
+                       const int32_t *det_cls, const int32_t *det_n, float *xyxy, float *conf, int32_t *cls, int32_t *n_merged,
+                       int32_t *n_out, float *kernel_ms);
+/* One sliced batch, asynchronous: slice_gather on the slicer's stream (host frames are staged by the handle; the stream is idle
+ * before the detector sees the tile pointers), rtmodt_detector_enqueue_batch on the n * I images as device frames, slice_merge on
+ * the detector's post-processing stream behind its NMS -- no host round trip.  det must be on the same device, built with the
+ * slicer's max_det (else RTMODT_E_INVALID), with batch >= n * I and max_src >= the effective tile (else RTMODT_E_CAPACITY), and
+ * must have no batch in flight that is not this slicer's.  Two sliced batches may be in flight (enqueue t+1, then fetch t); a
+ * third is RTMODT_E_INVALID.  A refusal launches nothing. */
+int rtmodt_slicer_enqueue(rtmodt_slicer *s, rtmodt_detector *det, const uint8_t *const *frames, int n, int pitch, int mem_kind);
+/* The OLDEST sliced batch in flight: drains det's oldest batch through rtmodt_detector_fetch (its in-flight accounting stays
+ * right) and hands out the merged detections, xyxy[n][max_out][4], conf / cls / n_merged[n][max_out], n_out[n]; any but n_out may
+ * be NULL.  tile_xyxy[n * I][max_det][4], tile_conf / tile_cls[n * I][max_det], tile_n[n * I] (each may be NULL) receive the
+ * per-image detections they were merged from, in image coordinates. */
+int rtmodt_slicer_fetch(rtmodt_slicer *s, rtmodt_detector *det, float *xyxy, float *conf, int32_t *cls, int32_t *n_merged, int32_t *n_out,
+                        float *tile_xyxy, float *tile_conf, int32_t *tile_cls, int32_t *tile_n);
+/* Device time (ms, HIP events) of slice_gather of the last enqueue / gather and of slice_merge of the last fetched batch. */
+int rtmodt_slicer_last_ms(rtmodt_slicer *s, float *gather_ms, float *merge_ms);
+/* rtmodt_tracker_update_from_detector on the MERGED detections of the slicer's newest batch (stream i <- frame i), queued on the
+ * same HIP stream behind slice_merge; the tracker needs max_dets >= max_out. */
+int rtmodt_tracker_update_from_slicer(rtmodt_tracker *trk, rtmodt_slicer *s);
+
 #ifdef __cplusplus
 }
 #endif

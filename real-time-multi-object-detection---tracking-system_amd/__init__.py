@@ -9,7 +9,9 @@ Sub-modules (imported lazily so that ``synth``/``weights`` work without the HIP
 library being built):
 
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
-* ``tracking.tracker``   -- ``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
+* ``detection.sliced``   -- ``SlicedDetector``: overlapping tiles plus an overview per frame, cut and merged on the GPU (the SAHI
+                            scheme; the cure for the design document's "Missed small objects", B.4)
+* ``tracking.tracker``   --``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
 * ``tracking.botsort``   -- ``BotSortTracker``: BoT-SORT, the comparison's best row (Re-ID fusion, camera-motion compensation), on the GPU
@@ -39,11 +41,12 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
+__all__ = ["Detector", "Detections", "SlicedDetector", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
     "Detections": ".detection.detector",
+    "SlicedDetector": ".detection.sliced",
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",

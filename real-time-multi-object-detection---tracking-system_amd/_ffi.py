@@ -21,6 +21,8 @@ PIX_BGR24, PIX_NV12, PIX_I420 = 0, 1, 2
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_TRUNCATED, JPEG_SIZE_MISMATCH = 0, 1, 2, 3, 4
 PIXEL_FORMATS = {"bgr24": PIX_BGR24, "nv12": PIX_NV12, "i420": PIX_I420, "yuv420p": PIX_I420}
 ASSIGN_GREEDY, ASSIGN_LAPJV = 0, 1
+SLICE_MERGE_NMM, SLICE_MERGE_NMS = 0, 1
+SLICE_METRIC_IOS, SLICE_METRIC_IOU = 0, 1
 
 
 class RtmodtError(RuntimeError):
@@ -201,6 +203,12 @@ class SwapGuardCfg(C.Structure):                     # struct rtmodt_swapguard_c
                 ("n_streams", C.c_int32), ("max_events", C.c_int32), ("device", C.c_int32)]
 
 
+class SliceCfg(C.Structure):                        # struct rtmodt_slice_cfg
+    _fields_ = [("device", C.c_int32), ("frame_w", C.c_int32), ("frame_h", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32),
+                ("overlap_w", C.c_int32), ("overlap_h", C.c_int32), ("overview", C.c_int32), ("merge", C.c_int32), ("metric", C.c_int32),
+                ("match_thresh", C.c_float), ("agnostic", C.c_int32), ("max_out", C.c_int32), ("max_frames", C.c_int32)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -340,6 +348,16 @@ def lib() -> C.CDLL:
         "rtmodt_swapguard_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_swapguard_counts": (C.c_int, [vp, C.c_int, C.POINTER(i64)]),
         "rtmodt_swapguard_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_slice_grid": (C.c_int, [C.c_int] * 6 + [vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "rtmodt_slicer_create": (C.c_int, [C.POINTER(SliceCfg), C.c_int, C.POINTER(vp)]),
+        "rtmodt_slicer_destroy": (None, [vp]),
+        "rtmodt_slicer_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "rtmodt_slicer_gather": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_slice_merge": (C.c_int, [C.c_int, C.POINTER(SliceCfg), C.c_int, C.c_int] + [vp] * 9 + [C.POINTER(f32)]),
+        "rtmodt_slicer_enqueue": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_slicer_fetch": (C.c_int, [vp, vp] + [vp] * 9),
+        "rtmodt_slicer_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
+        "rtmodt_tracker_update_from_slicer": (C.c_int, [vp, vp]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -1509,6 +1509,12 @@ int detector_outputs(rtmodt_detector *d, DetOutputs *o) {
     return RTMODT_OK;
 }
 
+int detector_limits(rtmodt_detector *d, DetLimits *o) {
+    RT_CHECK(d && o, RTMODT_E_INVALID, "null argument");
+    *o = DetLimits{d->B, d->cfg.max_det, d->cfg.max_src_w, d->cfg.max_src_h, d->device, d->n_pending};
+    return RTMODT_OK;
+}
+
 }  // namespace rtmodt
 
 // =====================================================================================

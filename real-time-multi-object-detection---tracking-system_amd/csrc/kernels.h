@@ -341,6 +341,12 @@ int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };
 int detector_outputs(rtmodt_detector *det, DetOutputs *out);
+// what a detector handle was built for, as the slicer (slice.hip) checks it before handing it a batch of tile images
+struct DetLimits { int batch, max_det, max_src_w, max_src_h, device, pending; };
+int detector_limits(rtmodt_detector *det, DetLimits *out);
+// slice.hip: the merged detections of a slicer's newest batch behind the same seam (stride = max_out, count = frames, stream = the
+// detector's post-processing stream the merge was queued on)
+int slicer_outputs(rtmodt_slicer *s, DetOutputs *out);
 // gmc.hip: the camera-motion estimate of the detector's batch, queued on its stream; *warp_dev = the estimator's [stream][6] device buffer
 int gmc_enqueue_detector(rtmodt_gmc *g, const DetOutputs &o, const uint8_t *const *frames, int n_frames, int h, int w, int pitch, int mem_kind,
                          const float **warp_dev);

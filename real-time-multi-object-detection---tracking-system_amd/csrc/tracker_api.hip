@@ -131,10 +131,8 @@ int rtmodt_tracker_update_batch(rtmodt_tracker *t, const float *xyxy, const floa
     return finish(t, 0, t->S, n_active_out);
 }
 
-static int update_from_detector_slice(rtmodt_tracker *t, rtmodt_detector *det, int first, int count, int frames = 1) {
-    RT_CHECK(t && det, RTMODT_E_INVALID, "null argument");
-    DetOutputs o;
-    RT_TRY(track_detector_outputs(t, det, &o));
+// frames [first, first + count * frames) of device-resident detections `o` (a detector's, or a slicer's merged ones), on o.stream
+static int update_from_outputs(rtmodt_tracker *t, const DetOutputs &o, int first, int count, int frames) {
     if (count < 0) count = o.count - first;
     RT_CHECK(frames >= 1, RTMODT_E_INVALID, "n_frames %d", frames);
     RT_CHECK(first >= 0 && count >= 1 && (long)first + (long)count * frames <= o.count, RTMODT_E_INVALID, "frames [%d, %ld) outside the detector's batch of %d", first,
@@ -148,6 +146,21 @@ static int update_from_detector_slice(rtmodt_tracker *t, rtmodt_detector *det, i
     // (host-fed updates are synchronous -- finish() waits for them -- so the detector's stream needs no event from ours)
     RT_TRY(launch_tracker_update(a, o.stream));          // same HIP stream as the detector's NMS: ordered, no host sync
     return track_detector_done(t, o.stream);
+}
+
+static int update_from_detector_slice(rtmodt_tracker *t, rtmodt_detector *det, int first, int count, int frames = 1) {
+    RT_CHECK(t && det, RTMODT_E_INVALID, "null argument");
+    DetOutputs o;
+    RT_TRY(track_detector_outputs(t, det, &o));
+    return update_from_outputs(t, o, first, count, frames);
+}
+
+int rtmodt_tracker_update_from_slicer(rtmodt_tracker *t, rtmodt_slicer *s) {
+    RT_CHECK(t && s, RTMODT_E_INVALID, "null argument");
+    DetOutputs o;
+    RT_TRY(slicer_outputs(s, &o));
+    RT_CHECK(o.device == t->device, RTMODT_E_INVALID, "tracker on device %d, slicer on device %d", t->device, o.device);
+    return update_from_outputs(t, o, 0, -1, 1);
 }
 
 int rtmodt_tracker_update_from_detector(rtmodt_tracker *t, rtmodt_detector *det) { return update_from_detector_slice(t, det, 0, -1); }

@@ -1,3 +1,4 @@
 from .detector import Detections, Detector
+from .sliced import SlicedDetector
 
-__all__ = ["Detector", "Detections"]
+__all__ = ["Detector", "Detections", "SlicedDetector"]

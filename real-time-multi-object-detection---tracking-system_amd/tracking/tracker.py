@@ -100,6 +100,11 @@ class _ByteTrackCore:
             _ffi.check(_ffi.lib().rtmodt_tracker_update_from_detector_frames(self._h, detector.model.handle, int(first_frame),
                                                                              int(self.n_streams if n_frames < 0 else n_frames)))
 
+    def update_from_sliced(self, sliced) -> None:
+        """Consume the MERGED detections of a ``SlicedDetector``'s newest batch (stream i <- frame i), device-resident, queued
+        behind the merge kernel (``rtmodt_tracker_update_from_slicer``); needs ``max_dets >= sliced.max_out``."""
+        _ffi.check(_ffi.lib().rtmodt_tracker_update_from_slicer(self._h, sliced._h))
+
     # -- parity surface ----------------------------------------------------------------
     def snapshot(self, stream: int = 0) -> dict:
         M = self.max_tracks
@@ -190,6 +195,14 @@ class MultiObjectTracker:
         self._core.update_from_detector(detector)
         if not materialize or self.report != "matched":
             return []                                     # reference mode: tracks with tsu == 0 after ageing -- none (tracker.py:141,146)
+        return self._tracks_out([])
+
+    def update_from_sliced(self, sliced, materialize: bool = True) -> list:
+        """:meth:`update_from_detector` for a ``SlicedDetector``: the tracker consumes the merged, frame-coordinate detections of
+        its last ``detect`` / ``enqueue`` on the device."""
+        self._core.update_from_sliced(sliced)
+        if not materialize or self.report != "matched":
+            return []
         return self._tracks_out([])
 
     def update(self, detections) -> list:
