@@ -4,12 +4,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/rtmodt.h"
 
@@ -73,6 +75,24 @@ static inline const char *rt_diag(const char *name) { return rt_env(name); }
 #else
 static inline const char *rt_diag(const char *) { return nullptr; }
 #endif
+
+// device buffers of one call, freed on every return path
+struct DevBufs {
+    std::vector<void *> ptrs;
+    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
+    template <typename T> int alloc(T **out, size_t n) {
+        void *p = nullptr;
+        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(p);
+        *out = (T *)p;
+        return RTMODT_OK;
+    }
+    template <typename T> int up(T **out, const T *host, size_t n) {
+        RT_TRY(alloc(out, n));
+        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return RTMODT_OK;
+    }
+};
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

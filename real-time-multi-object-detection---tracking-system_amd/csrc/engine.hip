@@ -111,44 +111,6 @@ static int read_weight_file(const char *path, WeightFile &wf) {
     return RTMODT_OK;
 }
 
-// ------------------------------------------------------------------ letterbox geometry (ultralytics LetterBox, App. B.1)
-static inline int round_half_even(double v) { return (int)std::nearbyint(v); }   // == Python round()
-
-struct LbHost { int new_w, new_h, top, left, resize; double gain; int pad_x, pad_y; };
-
-// rect: LetterBox(auto=True) -- new_shape is the SQUARE S x S (S = the longer side of the rectangle the
-// engine was built for), the pads are whatever is left of the rectangle (== the square's pads mod 32)
-static LbHost letterbox_geometry(int h, int w, int in_h, int in_w, bool rect = false) {
-    LbHost g;
-    const int S = std::max(in_h, in_w);
-    double r = rect ? std::min((double)S / h, (double)S / w) : std::min((double)in_h / h, (double)in_w / w);
-    g.new_w = round_half_even(w * r); g.new_h = round_half_even(h * r);
-    double dw = (in_w - g.new_w) / 2.0, dh = (in_h - g.new_h) / 2.0;
-    g.top = round_half_even(dh - 0.1); g.left = round_half_even(dw - 0.1);
-    g.resize = (g.new_w != w) || (g.new_h != h);
-    // scale_boxes (App. B.4)
-    g.gain = std::min((double)in_h / h, (double)in_w / w);
-    g.pad_x = round_half_even((in_w - w * g.gain) / 2 - 0.1);
-    g.pad_y = round_half_even((in_h - h * g.gain) / 2 - 0.1);
-    return g;
-}
-
-// cv::resize INTER_LINEAR 8-bit tables (same arithmetic as oracle/yolo_oracle.py:_resize_coeffs)
-static void build_resize_tables(int dst, int src, std::vector<int32_t> &ofs, std::vector<int32_t> &c0, std::vector<int32_t> &c1) {
-    ofs.resize(dst); c0.resize(dst); c1.resize(dst);
-    double scale = 1.0 / ((double)dst / src);
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f = f - (float)s;
-        if (s < 0) { s = 0; f = 0.f; }
-        if (s >= src - 1) { s = src - 1; f = 0.f; }
-        ofs[d] = s;
-        c0[d] = (int)std::nearbyint((1.0f - f) * 2048.0f);
-        c1[d] = (int)std::nearbyint(f * 2048.0f);
-    }
-}
-
 // ------------------------------------------------------------------ graph description
 struct Tensor { f16 *ptr = nullptr; int H, W, C, pad; size_t per_image; };
 
@@ -1443,7 +1405,7 @@ static int forward_chains(rtmodt_detector *d, rtmodt_detector::Slot &sl, bool ho
     return RTMODT_OK;
 }
 
-static int run_nms(rtmodt_detector *d, const LbHost &g, int h, int w, rtmodt_detector::Slot &sl) {
+static int run_nms(rtmodt_detector *d, const Letterbox &g, int h, int w, rtmodt_detector::Slot &sl) {
     NmsArgs a{};
     a.B = d->B; a.n_anchors = d->n_anchors; a.max_det = d->cfg.max_det; a.agnostic = d->cfg.agnostic; a.iou = d->cfg.iou;
     const rtmodt_detector::Dense &dn = d->dense[d->cur_dense];
@@ -1497,6 +1459,37 @@ static int resolve_frame_format(int h, int w, const rtmodt_frame_format *fmt, Fr
     o.pitch = (int)pitch;
     o.l.u_off = uo; o.l.v_off = vo; o.l.pitch = (int)pitch; o.l.chroma_pitch = (int)cp; o.l.nv12 = nv12;
     o.span = (size_t)span;
+    return RTMODT_OK;
+}
+
+// The stand-alone preprocess entry points (rtmodt_preprocess, rtmodt_preprocess_yuv420): one host frame of `bytes` staged bytes
+// -> the in_h x in_w letterboxed image as 3 halves per pixel.  launch(frame pointers, geometry, tables, image tensor) runs the kernel.
+template <typename Launch>
+static int preprocess_one(int device, const uint8_t *frame, size_t bytes, int h, int w, int in_w, int in_h, uint16_t *out_f16, Launch launch) {
+    RT_HIP(hipSetDevice(device));
+    DevBufs bufs;
+    uint8_t *dimg; f16 *dout;
+    const size_t per = (size_t)(in_h + 2) * (in_w + 2) * 4;
+    RT_TRY(bufs.up(&dimg, frame, bytes));
+    RT_TRY(bufs.alloc(&dout, per));
+    RT_HIP(hipMemset(dout, 0, per * 2));
+    FramePtrs fp{};
+    fp.p[0] = dimg;
+    const LetterboxGeom g = letterbox_geometry(h, w, in_h, in_w).g;
+    ResizeTables tabs{};
+    if (g.resize) {
+        int32_t *dtab;
+        RT_TRY(bufs.alloc(&dtab, (size_t)(g.new_w + g.new_h) * 3));
+        RT_TRY(upload_resize_tables(g, dtab, &tabs));
+    }
+    TensorView img; img.base = dout; img.H = in_h; img.W = in_w; img.C = 4; img.pad = 1; img.c = 4;
+    RT_TRY(launch(fp, g, tabs, img));
+    RT_HIP(hipDeviceSynchronize());
+    std::vector<uint16_t> tmp(per);
+    RT_HIP(hipMemcpy(tmp.data(), dout, per * 2, hipMemcpyDeviceToHost));
+    for (int y = 0; y < in_h; ++y)
+        for (int x = 0; x < in_w; ++x)
+            memcpy(out_f16 + ((size_t)y * in_w + x) * 3, &tmp[((size_t)(y + 1) * (in_w + 2) + x + 1) * 4], 6);
     return RTMODT_OK;
 }
 
@@ -1735,7 +1728,8 @@ static int enqueue_impl(rtmodt_detector *d, const uint8_t *const *frames, int n,
              d->n_pending);
     RT_HIP(hipSetDevice(d->device));
     rtmodt_detector::Slot &sl = d->slots[d->head];
-    LbHost g = letterbox_geometry(h, w, d->in_h, d->in_w, d->rect);
+    const Letterbox lb = letterbox_geometry(h, w, d->in_h, d->in_w, d->rect);
+    const LetterboxGeom &g = lb.g;
     RT_CHECK(g.new_w <= d->in_w && g.new_h <= d->in_h, RTMODT_E_INVALID, "a %dx%d frame does not fit the %dx%d rectangle this detector was built for", w, h, d->in_w, d->in_h);
     // Opt-in (RTMODT_ZERO_COPY=1): page-locked frames the device can address (rtmodt_host_alloc / hipHostMalloc) that need no
     // resize are not copied -- the stem conv reads their bytes in place, over PCIe, once.  The caller keeps such frames
@@ -1798,25 +1792,14 @@ static int enqueue_impl(rtmodt_detector *d, const uint8_t *const *frames, int n,
     }
     for (int i = n; i < d->B; ++i) d->fptrs.p[i] = d->fptrs.p[0];
     if (g.resize && (h != d->tab_h || w != d->tab_w)) {
-        std::vector<int32_t> xo, x0, x1, yo, y0, y1;
-        build_resize_tables(g.new_w, w, xo, x0, x1);
-        build_resize_tables(g.new_h, h, yo, y0, y1);
         RT_CHECK((size_t)(g.new_w + g.new_h) * 3 <= d->tab_cap, RTMODT_E_INVALID, "resize table overflow");
         RT_HIP(hipStreamSynchronize(d->stream));
-        int32_t *p = d->d_tab;
-        const std::vector<int32_t> *src[6] = {&xo, &x0, &x1, &yo, &y0, &y1};
-        const int32_t *dst[6];
-        for (int k = 0; k < 6; ++k) {
-            RT_HIP(hipMemcpy(p, src[k]->data(), src[k]->size() * 4, hipMemcpyHostToDevice));
-            dst[k] = p; p += src[k]->size();
-        }
-        d->tabs = ResizeTables{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5]};
+        RT_TRY(upload_resize_tables(g, d->d_tab, &d->tabs));
         d->tab_h = h; d->tab_w = w;
     }
-    LetterboxGeom lg{h, w, g.new_w, g.new_h, g.top, g.left, g.resize};
     TensorView img; img.base = d->tensors[d->img_t].ptr; img.H = d->in_h; img.W = d->in_w; img.C = 4; img.pad = 1; img.c = 4;
     d->cur_dense = d->head;                            // ring slot == dense set
-    d->last_lg = lg; d->last_pitch = stride_bytes;
+    d->last_lg = g; d->last_pitch = stride_bytes;
     d->last_fused = d->stem_fuse && !g.resize && !fl.yuv;
     const bool graphs = (!d->graph_execs.empty() || (d->pipe && d->pipe_exec[0][0][0])) && !d->want_pred;
     const bool chained = graphs && d->n_chains > 1;
@@ -1834,8 +1817,8 @@ static int enqueue_impl(rtmodt_detector *d, const uint8_t *const *frames, int n,
     RT_HIP(hipEventRecord(sl.ev0, d->stream));
     if (!d->last_fused) {
         if (graphs && d->pipe) img.base = (f16 *)((char *)img.base + (size_t)(d->batch_no % d->n_stages) * d->arena_stride);
-        if (fl.yuv) RT_TRY(launch_letterbox_yuv420(d->fptrs, fl.l, lg, d->tabs, img, d->B, d->stream));
-        else RT_TRY(launch_letterbox(d->fptrs, stride_bytes, lg, d->tabs, img, d->B, d->stream));
+        if (fl.yuv) RT_TRY(launch_letterbox_yuv420(d->fptrs, fl.l, g, d->tabs, img, d->B, d->stream));
+        else RT_TRY(launch_letterbox(d->fptrs, stride_bytes, g, d->tabs, img, d->B, d->stream));
         if (chained) RT_HIP(hipEventRecord(sl.evp, d->stream));
     }
     sl.chained = chained; sl.joined = false;
@@ -1873,7 +1856,7 @@ static int enqueue_impl(rtmodt_detector *d, const uint8_t *const *frames, int n,
     // underneath the next batch's forward pass instead of in front of it
     RT_HIP(hipStreamWaitEvent(d->post_stream, sl.decoded, 0));
     if (chained && !sl.joined) for (int c = 1; c < d->n_chains; ++c) RT_HIP(hipStreamWaitEvent(d->post_stream, sl.chain_done[c], 0));
-    RT_TRY(run_nms(d, g, h, w, sl));
+    RT_TRY(run_nms(d, lb, h, w, sl));
     RT_HIP(hipEventRecord(sl.ev2, d->post_stream));
     if (d->clock_on) {                                    // one wave, ~20 us, behind the NMS of this batch (the forward pass of the next ones is running)
         hipLaunchKernelGGL(clock_sample_kernel, dim3(1), dim3(64), 0, d->post_stream, d->d_clock + 4 * (d->clock_n % rtmodt_detector::CLOCK_SLOTS), 2000u);
@@ -2230,21 +2213,16 @@ int rtmodt_nms_pred(int device, const float *pred, int nc, int A, float conf, fl
         for (int i = 0; i < n_classes; ++i)
             if (classes[i] >= 0 && classes[i] < 128) mask[classes[i] >> 6] |= 1ull << (classes[i] & 63);
     }
-    struct Bufs {
-        std::vector<void *> p;
-        ~Bufs() { for (void *q : p) hipFree(q); }
-        int get(size_t bytes, void **o) { RT_HIP(hipMalloc(o, bytes)); p.push_back(*o); return RTMODT_OK; }
-    } bufs;
+    DevBufs bufs;
     float *dpred; float4 *box, *sbox; float *score; int32_t *dcls, *sidx; uint64_t *keys;
     float *oxy, *ocf; int32_t *ocl, *oan, *on;
-    RT_TRY(bufs.get((size_t)(4 + nc) * A * 4, (void **)&dpred));
-    RT_TRY(bufs.get((size_t)A * 16, (void **)&box)); RT_TRY(bufs.get((size_t)A * 16, (void **)&sbox));
-    RT_TRY(bufs.get((size_t)A * 4, (void **)&score)); RT_TRY(bufs.get((size_t)A * 4, (void **)&dcls));
-    RT_TRY(bufs.get((size_t)A * 4, (void **)&sidx)); RT_TRY(bufs.get((size_t)A * 8, (void **)&keys));
-    RT_TRY(bufs.get((size_t)max_det * 16, (void **)&oxy)); RT_TRY(bufs.get((size_t)max_det * 4, (void **)&ocf));
-    RT_TRY(bufs.get((size_t)max_det * 4, (void **)&ocl)); RT_TRY(bufs.get((size_t)max_det * 4, (void **)&oan));
-    RT_TRY(bufs.get(4, (void **)&on));
-    RT_HIP(hipMemcpy(dpred, pred, (size_t)(4 + nc) * A * 4, hipMemcpyHostToDevice));
+    RT_TRY(bufs.up(&dpred, pred, (size_t)(4 + nc) * A));
+    RT_TRY(bufs.alloc(&box, A)); RT_TRY(bufs.alloc(&sbox, A));
+    RT_TRY(bufs.alloc(&score, A)); RT_TRY(bufs.alloc(&dcls, A));
+    RT_TRY(bufs.alloc(&sidx, A)); RT_TRY(bufs.alloc(&keys, A));
+    RT_TRY(bufs.alloc(&oxy, (size_t)max_det * 4)); RT_TRY(bufs.alloc(&ocf, max_det));
+    RT_TRY(bufs.alloc(&ocl, max_det)); RT_TRY(bufs.alloc(&oan, max_det));
+    RT_TRY(bufs.alloc(&on, 1));
     RT_TRY(launch_pred_candidates(dpred, nc, A, conf, mask, box, score, dcls, nullptr));
     NmsArgs a{};
     a.B = 1; a.n_anchors = A; a.max_det = max_det; a.agnostic = agnostic; a.iou = iou;
@@ -2265,44 +2243,10 @@ int rtmodt_nms_pred(int device, const float *pred, int nc, int A, float conf, fl
 
 int rtmodt_preprocess(int device, const uint8_t *bgr, int h, int w, int stride_bytes, int in_w, int in_h, uint16_t *out_f16) {
     RT_CHECK(bgr && out_f16 && h >= 1 && w >= 1 && stride_bytes >= 3 * w && in_w >= 1 && in_h >= 1, RTMODT_E_INVALID, "bad argument");
-    RT_HIP(hipSetDevice(device));
-    struct Bufs {
-        std::vector<void *> p;
-        ~Bufs() { for (void *q : p) hipFree(q); }
-        int get(size_t bytes, void **o) { RT_HIP(hipMalloc(o, bytes)); p.push_back(*o); return RTMODT_OK; }
-    } bufs;
-    uint8_t *dimg; f16 *dout; int32_t *dtab;
-    size_t per = (size_t)(in_h + 2) * (in_w + 2) * 4;
-    RT_TRY(bufs.get((size_t)h * stride_bytes, (void **)&dimg));
-    RT_TRY(bufs.get(per * 2, (void **)&dout));
-    RT_HIP(hipMemset(dout, 0, per * 2));
-    RT_HIP(hipMemcpy(dimg, bgr, (size_t)h * stride_bytes, hipMemcpyHostToDevice));
-    FramePtrs fp{};
-    fp.p[0] = dimg;
-    LbHost g = letterbox_geometry(h, w, in_h, in_w);
-    ResizeTables tabs{};
-    if (g.resize) {
-        std::vector<int32_t> t[6];
-        build_resize_tables(g.new_w, w, t[0], t[1], t[2]);
-        build_resize_tables(g.new_h, h, t[3], t[4], t[5]);
-        RT_TRY(bufs.get((size_t)(g.new_w + g.new_h) * 3 * 4, (void **)&dtab));
-        const int32_t *dst[6]; int32_t *p = dtab;
-        for (int k = 0; k < 6; ++k) {
-            RT_HIP(hipMemcpy(p, t[k].data(), t[k].size() * 4, hipMemcpyHostToDevice));
-            dst[k] = p; p += t[k].size();
-        }
-        tabs = ResizeTables{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5]};
-    }
-    LetterboxGeom lg{h, w, g.new_w, g.new_h, g.top, g.left, g.resize};
-    TensorView img; img.base = dout; img.H = in_h; img.W = in_w; img.C = 4; img.pad = 1; img.c = 4;
-    RT_TRY(launch_letterbox(fp, stride_bytes, lg, tabs, img, 1, nullptr));
-    RT_HIP(hipDeviceSynchronize());
-    std::vector<uint16_t> tmp(per);
-    RT_HIP(hipMemcpy(tmp.data(), dout, per * 2, hipMemcpyDeviceToHost));
-    for (int y = 0; y < in_h; ++y)
-        for (int x = 0; x < in_w; ++x)
-            memcpy(out_f16 + ((size_t)y * in_w + x) * 3, &tmp[((size_t)(y + 1) * (in_w + 2) + x + 1) * 4], 6);
-    return RTMODT_OK;
+    return preprocess_one(device, bgr, (size_t)h * stride_bytes, h, w, in_w, in_h, out_f16,
+                          [&](const FramePtrs &fp, const LetterboxGeom &g, const ResizeTables &tabs, const TensorView &img) {
+                              return launch_letterbox(fp, stride_bytes, g, tabs, img, 1, nullptr);
+                          });
 }
 
 int rtmodt_preprocess_yuv420(int device, const uint8_t *frame, int h, int w, const rtmodt_frame_format *fmt, int in_w, int in_h,
@@ -2312,44 +2256,10 @@ int rtmodt_preprocess_yuv420(int device, const uint8_t *frame, int h, int w, con
              "preprocess_yuv420: pixel format %d is not a 4:2:0 format", fmt->pixel_format);
     FrameLayout fl;
     RT_TRY(resolve_frame_format(h, w, fmt, fl));
-    RT_HIP(hipSetDevice(device));
-    struct Bufs {
-        std::vector<void *> p;
-        ~Bufs() { for (void *q : p) hipFree(q); }
-        int get(size_t bytes, void **o) { RT_HIP(hipMalloc(o, bytes)); p.push_back(*o); return RTMODT_OK; }
-    } bufs;
-    uint8_t *dimg; f16 *dout; int32_t *dtab;
-    size_t per = (size_t)(in_h + 2) * (in_w + 2) * 4;
-    RT_TRY(bufs.get(fl.span, (void **)&dimg));
-    RT_TRY(bufs.get(per * 2, (void **)&dout));
-    RT_HIP(hipMemset(dout, 0, per * 2));
-    RT_HIP(hipMemcpy(dimg, frame, fl.span, hipMemcpyHostToDevice));
-    FramePtrs fp{};
-    fp.p[0] = dimg;
-    LbHost g = letterbox_geometry(h, w, in_h, in_w);
-    ResizeTables tabs{};
-    if (g.resize) {
-        std::vector<int32_t> t[6];
-        build_resize_tables(g.new_w, w, t[0], t[1], t[2]);
-        build_resize_tables(g.new_h, h, t[3], t[4], t[5]);
-        RT_TRY(bufs.get((size_t)(g.new_w + g.new_h) * 3 * 4, (void **)&dtab));
-        const int32_t *dst[6]; int32_t *p = dtab;
-        for (int k = 0; k < 6; ++k) {
-            RT_HIP(hipMemcpy(p, t[k].data(), t[k].size() * 4, hipMemcpyHostToDevice));
-            dst[k] = p; p += t[k].size();
-        }
-        tabs = ResizeTables{dst[0], dst[1], dst[2], dst[3], dst[4], dst[5]};
-    }
-    LetterboxGeom lg{h, w, g.new_w, g.new_h, g.top, g.left, g.resize};
-    TensorView img; img.base = dout; img.H = in_h; img.W = in_w; img.C = 4; img.pad = 1; img.c = 4;
-    RT_TRY(launch_letterbox_yuv420(fp, fl.l, lg, tabs, img, 1, nullptr));
-    RT_HIP(hipDeviceSynchronize());
-    std::vector<uint16_t> tmp(per);
-    RT_HIP(hipMemcpy(tmp.data(), dout, per * 2, hipMemcpyDeviceToHost));
-    for (int y = 0; y < in_h; ++y)
-        for (int x = 0; x < in_w; ++x)
-            memcpy(out_f16 + ((size_t)y * in_w + x) * 3, &tmp[((size_t)(y + 1) * (in_w + 2) + x + 1) * 4], 6);
-    return RTMODT_OK;
+    return preprocess_one(device, frame, fl.span, h, w, in_w, in_h, out_f16,
+                          [&](const FramePtrs &fp, const LetterboxGeom &g, const ResizeTables &tabs, const TensorView &img) {
+                              return launch_letterbox_yuv420(fp, fl.l, g, tabs, img, 1, nullptr);
+                          });
 }
 
 }  // extern "C"

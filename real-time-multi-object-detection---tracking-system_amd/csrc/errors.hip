@@ -310,29 +310,6 @@ __global__ __launch_bounds__(ER_THREADS) void detection_errors(ErrArgs a) {
         if (S.size_hist[i]) atomicAdd(&a.by_size[i], (unsigned long long)S.size_hist[i]);
 }
 
-// device buffers of one call, freed on every return path
-struct ErrBufs {
-    std::vector<void *> ptrs;
-    ~ErrBufs() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return RTMODT_OK;
-    }
-    template <typename T> int up(T **out, const T *host, size_t n) {
-        RT_TRY(alloc(out, n));
-        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
-        return RTMODT_OK;
-    }
-    template <typename T> int zeros(T **out, size_t n) {
-        RT_TRY(alloc(out, n));
-        RT_HIP(hipMemset(*out, 0, std::max<size_t>(n, 1) * sizeof(T)));
-        return RTMODT_OK;
-    }
-};
-
 }  // namespace rtmodt
 
 using namespace rtmodt;
@@ -391,7 +368,7 @@ extern "C" int rtmodt_detection_errors(int device, const rtmodt_error_params *pa
     const size_t n_class = (size_t)K * ER_NCOL, n_size = 3 * ER_NCOL, n_cell = (size_t)p.grid_x * p.grid_y * ER_NCOL, n_cm = ((size_t)K + 1) * (K + 1);
 
     RT_HIP(hipSetDevice(device));
-    ErrBufs B;
+    DevBufs B;
     ErrArgs ea{};
     ea.conf_thr = p.conf_thr;
     ea.iou_fg = std::fmin(p.iou_fg, 1.0 - 1e-10); ea.iou_bg = std::fmin(p.iou_bg, 1.0 - 1e-10); ea.cm_iou = std::fmin(p.cm_iou, 1.0 - 1e-10);
@@ -410,7 +387,8 @@ extern "C" int rtmodt_detection_errors(int device, const rtmodt_error_params *pa
     // one zeroed block for every histogram: by_class, by_size, by_cell, missed_uncovered, cm, cm_dropped
     unsigned long long *d_hist;
     const size_t n_hist = n_class + n_size + n_cell + (size_t)K + n_cm + (size_t)K;
-    RT_TRY(B.zeros(&d_hist, n_hist));
+    RT_TRY(B.alloc(&d_hist, n_hist));
+    RT_HIP(hipMemset(d_hist, 0, n_hist * sizeof(*d_hist)));
     ea.by_class = d_hist; ea.by_size = ea.by_class + n_class; ea.by_cell = ea.by_size + n_size; ea.missed_uncovered = ea.by_cell + n_cell;
     ea.cm = ea.missed_uncovered + K; ea.cm_dropped = ea.cm + n_cm;
     if (n_img) {

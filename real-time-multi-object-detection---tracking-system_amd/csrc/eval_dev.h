@@ -1,5 +1,5 @@
 // eval_dev.h -- the float64 device helpers shared by the evaluation kernels (eval.hip: coco_match, mot_pairs; errors.hip:
-// detection_errors; hota.hip), the workgroup scan and the per-call device buffers of eval.hip and hota.hip.
+// detection_errors; hota.hip) and the workgroup scan.
 // These translation units are built with -ffp-contract=off and IEEE division: every operation below rounds separately, as NumPy's do.
 #pragma once
 
@@ -62,23 +62,5 @@ __device__ __forceinline__ uint64_t score_key(double s) {
     const uint64_t b = (uint64_t)__double_as_longlong(s);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-
-// device buffers of one call, freed on every return path
-struct DevBufs {
-    std::vector<void *> ptrs;
-    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return RTMODT_OK;
-    }
-    template <typename T> int up(T **out, const T *host, size_t n) {
-        RT_TRY(alloc(out, n));
-        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
-        return RTMODT_OK;
-    }
-};
 
 }  // namespace rtmodt

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "letterbox.h"
 
 namespace rtmodt {
 
@@ -119,8 +120,7 @@ int launch_bottleneck32_tail(const BottleneckLaunch &l, hipStream_t s);
 int launch_stem(const TensorView &img4, const TensorView &out, const f16 *wm, const float *bias, int B,
                 int cout, hipStream_t s);
 // the same conv reading the BGR uint8 frames themselves (letterbox folded in); only for frames that need no
-// resize.  lut: 256 fp16 values c/255.  Frames frame0 .. frame0+B-1 of `frames`.
-struct LetterboxGeom { int src_h, src_w, new_w, new_h, top, left, resize; };
+// resize.  lut: 256 fp16 values c/255.  Frames frame0 .. frame0+B-1 of `frames`.  (LetterboxGeom: letterbox.h)
 // frames: up to 64 device pointers to BGR uint8 images with row pitch `pitch`, passed by value in
 // the kernel arguments (no pointer table to upload, nothing to race with launch-ahead)
 struct FramePtrs { const uint8_t *p[64]; };
@@ -149,9 +149,13 @@ int launch_upsample2(const TensorView &in, const TensorView &out, int B, hipStre
 // ---------------------------------------------------------------------------------------
 // preprocess (preprocess.hip)
 // ---------------------------------------------------------------------------------------
-struct ResizeTables {          // device arrays, cv::resize INTER_LINEAR fixed-point tables
-    const int32_t *xofs, *xa0, *xa1, *yofs, *yb0, *yb1;
-};
+// the resize tables of `g` (letterbox.h) built and copied to d_tab, 3 * (new_w + new_h) int32, in one blocking copy
+static inline int upload_resize_tables(const LetterboxGeom &g, int32_t *d_tab, ResizeTables *out) {
+    const std::vector<int32_t> t = resize_tables(g);
+    RT_HIP(hipMemcpy(d_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    *out = resize_tables_at(d_tab, g);
+    return RTMODT_OK;
+}
 int launch_letterbox(const FramePtrs &frames, int pitch, const LetterboxGeom &g, const ResizeTables &t,
                      const TensorView &img4, int B, hipStream_t s);
 // 4:2:0 frames (NV12 / I420, BT.601 limited range as cv::cvtColor converts it) -> the same image tensor.  Byte offsets from

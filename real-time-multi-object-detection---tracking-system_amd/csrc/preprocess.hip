@@ -6,11 +6,10 @@
 // .half().  Output goes straight into the engine's input tensor: fp16 NHWC with 4 channels
 // (R, G, B, 0) and the 1-pixel zero border the stem conv reads as its padding.
 //
-// The resize is OpenCV's 8-bit fixed-point bilinear, restated bit for bit (11-bit
-// coefficients; horizontal pass x2048 in int32; vertical pass
-// (((b0*(r0>>4))>>16) + ((b1*(r1>>4))>>16) + 2) >> 2); the coefficient tables are built on the
-// host (engine.hip: build_resize_tables) exactly as oracle/yolo_oracle.py:_resize_coeffs does.
-#include "kernels.h"
+// The resize is OpenCV's 8-bit fixed-point bilinear, restated bit for bit: the pixel is
+// letterbox_dev.h's letterbox_pixel, and the coefficient tables are built on the host
+// (letterbox.h: resize_table) exactly as oracle/yolo_oracle.py:_resize_coeffs does.
+#include "letterbox_dev.h"
 
 namespace rtmodt {
 
@@ -24,30 +23,8 @@ __global__ __launch_bounds__(256) void letterbox_kernel(FramePtrs frames, int pi
     long r = gid / in_w;
     int y = (int)(r % in_h);
     int b = (int)(r / in_h);
-    int sy = y - g.top, sx = x - g.left;
-    int c0 = 114, c1 = 114, c2 = 114;                       // B, G, R
-    if (sy >= 0 && sy < g.new_h && sx >= 0 && sx < g.new_w) {
-        const uint8_t *f = frames.p[b];
-        if (!g.resize) {
-            const uint8_t *p = f + (long)sy * pitch + sx * 3;
-            c0 = p[0]; c1 = p[1]; c2 = p[2];
-        } else {
-            int xi = t.xofs[sx], a0 = t.xa0[sx], a1 = t.xa1[sx];
-            int yi = t.yofs[sy], b0 = t.yb0[sy], b1 = t.yb1[sy];
-            int xj = min(xi + 1, g.src_w - 1), yj = min(yi + 1, g.src_h - 1);
-            const uint8_t *p00 = f + (long)yi * pitch + xi * 3, *p01 = f + (long)yi * pitch + xj * 3;
-            const uint8_t *p10 = f + (long)yj * pitch + xi * 3, *p11 = f + (long)yj * pitch + xj * 3;
-            int v[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                int h0 = p00[c] * a0 + p01[c] * a1;
-                int h1 = p10[c] * a0 + p11[c] * a1;
-                int o = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                v[c] = min(max(o, 0), 255);
-            }
-            c0 = v[0]; c1 = v[1]; c2 = v[2];
-        }
-    }
+    int c0, c1, c2;                                         // B, G, R
+    letterbox_pixel(x, y, g, t, Bgr24Source{frames.p[b], pitch}, c0, c1, c2);
     half4 o = {(f16)((float)c2 / 255.0f), (f16)((float)c1 / 255.0f), (f16)((float)c0 / 255.0f), (f16)0.0f};
     *(half4 *)(out + (((long)b * (in_h + 2) + y + 1) * (in_w + 2) + x + 1) * 4) = o;
 }
@@ -100,32 +77,9 @@ __global__ __launch_bounds__(256) void letterbox_yuv420_kernel(FramePtrs frames,
     long r = gid / in_w;
     int y = (int)(r % in_h);
     int b = (int)(r / in_h);
-    int sy = y - g.top, sx = x - g.left;
-    int c0 = 114, c1 = 114, c2 = 114;                       // B, G, R
-    if (sy >= 0 && sy < g.new_h && sx >= 0 && sx < g.new_w) {
-        const uint8_t *f = frames.p[b];
-        if (!g.resize) {
-            yuv420_bgr(f, l, sx, sy, c0, c1, c2);
-        } else {
-            int xi = t.xofs[sx], a0 = t.xa0[sx], a1 = t.xa1[sx];
-            int yi = t.yofs[sy], b0 = t.yb0[sy], b1 = t.yb1[sy];
-            int xj = min(xi + 1, g.src_w - 1), yj = min(yi + 1, g.src_h - 1);
-            int p00[3], p01[3], p10[3], p11[3];
-            yuv420_bgr(f, l, xi, yi, p00[0], p00[1], p00[2]);
-            yuv420_bgr(f, l, xj, yi, p01[0], p01[1], p01[2]);
-            yuv420_bgr(f, l, xi, yj, p10[0], p10[1], p10[2]);
-            yuv420_bgr(f, l, xj, yj, p11[0], p11[1], p11[2]);
-            int v[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                int h0 = p00[c] * a0 + p01[c] * a1;
-                int h1 = p10[c] * a0 + p11[c] * a1;
-                int o = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                v[c] = min(max(o, 0), 255);
-            }
-            c0 = v[0]; c1 = v[1]; c2 = v[2];
-        }
-    }
+    int c0, c1, c2;                                         // B, G, R
+    const uint8_t *f = frames.p[b];
+    letterbox_pixel(x, y, g, t, [&](int sx, int sy, int &cb, int &cg, int &cr) { yuv420_bgr(f, l, sx, sy, cb, cg, cr); }, c0, c1, c2);
     half4 o = {(f16)((float)c2 / 255.0f), (f16)((float)c1 / 255.0f), (f16)((float)c0 / 255.0f), (f16)0.0f};
     *(half4 *)(out + (((long)b * (in_h + 2) + y + 1) * (in_w + 2) + x + 1) * 4) = o;
 }

@@ -8,8 +8,8 @@
 // installed nowhere this runs; tests/slice_ref.py restates the rules below and the kernels equal it bit for bit.
 //
 // slice_gather: ONE launch; image f * I + j of the batch is tile j of frame f (a byte copy of the te_w x te_h window at
-//   (x_j, y_j)) or, for j == T, the whole frame letterboxed into te_w x te_h with the cv2.resize INTER_LINEAR fixed-point
-//   arithmetic of preprocess.hip and 114 padding.  Images are BGR24 with pitch 3 * te_w.  A window starts 3 * x_j bytes into a
+//   (x_j, y_j)) or, for j == T, the whole frame letterboxed into te_w x te_h by the detector's own letterbox (letterbox.h's
+//   geometry and tables, letterbox_dev.h's pixel: cv2.resize INTER_LINEAR fixed point, 114 padding).  Images are BGR24 with pitch 3 * te_w.  A window starts 3 * x_j bytes into a
 //   row, so nothing is known about its alignment: a row is copied as a byte head up to the first 16-byte boundary of the
 //   DESTINATION, 16-byte stores fed by one 16-byte load, four 4-byte loads or sixteen byte loads -- whichever the source
 //   address of that row allows -- and a byte tail.  No byte outside the window is read, none outside the row is written.
@@ -26,7 +26,7 @@
 //   Capacities: 64 tiles per frame, I x max_det <= 8192 candidates per frame (the LDS sort), max_frames x I <= 64 (a detector batch).
 #include <vector>
 
-#include "kernels.h"
+#include "letterbox_dev.h"
 #include "slice_grid.h"
 
 using namespace rtmodt;
@@ -42,34 +42,6 @@ struct SliceGatherArgs {
     LetterboxGeom lb; ResizeTables t;        // the overview
     uint8_t *out;                            // [n * I][te_h][3 * te_w]
 };
-
-__device__ __forceinline__ void overview_pixel(const uint8_t *__restrict__ f, int pitch, const LetterboxGeom &g, const ResizeTables &t, int x, int y,
-                                               uint8_t *px) {
-    const int sy = y - g.top, sx = x - g.left;
-    int c0 = 114, c1 = 114, c2 = 114;
-    if (sy >= 0 && sy < g.new_h && sx >= 0 && sx < g.new_w) {
-        if (!g.resize) {
-            const uint8_t *p = f + (long)sy * pitch + sx * 3;
-            c0 = p[0]; c1 = p[1]; c2 = p[2];
-        } else {
-            const int xi = t.xofs[sx], a0 = t.xa0[sx], a1 = t.xa1[sx];
-            const int yi = t.yofs[sy], b0 = t.yb0[sy], b1 = t.yb1[sy];
-            const int xj = min(xi + 1, g.src_w - 1), yj = min(yi + 1, g.src_h - 1);
-            const uint8_t *p00 = f + (long)yi * pitch + xi * 3, *p01 = f + (long)yi * pitch + xj * 3;
-            const uint8_t *p10 = f + (long)yj * pitch + xi * 3, *p11 = f + (long)yj * pitch + xj * 3;
-            int v[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int h0 = p00[c] * a0 + p01[c] * a1;
-                const int h1 = p10[c] * a0 + p11[c] * a1;
-                const int o = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-                v[c] = min(max(o, 0), 255);
-            }
-            c0 = v[0]; c1 = v[1]; c2 = v[2];
-        }
-    }
-    px[0] = (uint8_t)c0; px[1] = (uint8_t)c1; px[2] = (uint8_t)c2;
-}
 
 __global__ __launch_bounds__(256) void slice_gather_kernel(SliceGatherArgs a) {
     const SliceGeom &g = a.g;
@@ -87,7 +59,11 @@ __global__ __launch_bounds__(256) void slice_gather_kernel(SliceGatherArgs a) {
             uint8_t b[12];
             const int cnt = (int)min(4L, npx - p0);
             for (int k = 0; k < 4; ++k)
-                if (k < cnt) overview_pixel(src, a.pitch, a.lb, a.t, (int)((p0 + k) % g.te_w), (int)((p0 + k) / g.te_w), b + 3 * k);
+                if (k < cnt) {
+                    int c0, c1, c2;
+                    letterbox_pixel((int)((p0 + k) % g.te_w), (int)((p0 + k) / g.te_w), a.lb, a.t, Bgr24Source{src, a.pitch}, c0, c1, c2);
+                    b[3 * k] = (uint8_t)c0; b[3 * k + 1] = (uint8_t)c1; b[3 * k + 2] = (uint8_t)c2;
+                }
             uint8_t *d = dimg + p0 * 3;
             if (aligned && cnt == 4) {
                 uint32_t *d4 = (uint32_t *)d;
@@ -319,7 +295,7 @@ static int launch_slice_merge(const SliceMergeArgs &a, int frames, hipStream_t s
 
 // ---------------------------------------------------------------------------------------------------------------- host
 struct SlicePlan {                           // everything a cfg decides, computed before the device is touched
-    SliceGrid grid; SliceGeom geom{}; SliceLetterbox lb{};
+    SliceGrid grid; SliceGeom geom{}; Letterbox lb{};        // lb: the overview (letterbox.h)
     int T = 0, I = 0, cap = 0;
     size_t img_bytes = 0;
 };
@@ -345,14 +321,14 @@ static int slice_plan(const rtmodt_slice_cfg *c, int max_det, SlicePlan *p) {
     SliceGeom &g = p->geom;
     g.W = c->frame_w; g.H = c->frame_h; g.te_w = p->grid.te_w; g.te_h = p->grid.te_h; g.T = p->T; g.I = p->I;
     for (int j = 0; j < p->T; ++j) { g.tx[j] = p->grid.x[j]; g.ty[j] = p->grid.y[j]; }
-    p->lb = slice_letterbox(c->frame_h, c->frame_w, g.te_h, g.te_w);
+    p->lb = letterbox_geometry(c->frame_h, c->frame_w, g.te_h, g.te_w);
     p->img_bytes = (size_t)3 * g.te_w * g.te_h;
     return RTMODT_OK;
 }
 
 static SliceMergeArgs merge_args(const rtmodt_slice_cfg &c, const SlicePlan &p, int max_det) {
     SliceMergeArgs a{};
-    a.g = p.geom; a.gain = p.lb.gain; a.pad_x = p.lb.pad_x; a.pad_y = p.lb.pad_y;
+    a.g = p.geom; a.gain = (float)p.lb.gain; a.pad_x = (float)p.lb.pad_x; a.pad_y = (float)p.lb.pad_y;
     a.nms = c.merge == RTMODT_SLICE_MERGE_NMS; a.iou = c.metric == RTMODT_SLICE_METRIC_IOU; a.agnostic = c.agnostic != 0; a.max_out = c.max_out;
     a.thresh = c.match_thresh; a.stride = max_det; a.cap = p.cap;
     return a;
@@ -402,8 +378,7 @@ static int slicer_run_gather(rtmodt_slicer *s, const uint8_t *const *frames, int
     const rtmodt_slice_cfg &c = s->cfg;
     SliceGatherArgs a{};
     a.g = s->plan.geom;
-    const SliceLetterbox &lb = s->plan.lb;
-    a.lb = LetterboxGeom{c.frame_h, c.frame_w, lb.new_w, lb.new_h, lb.top, lb.left, lb.resize};
+    a.lb = s->plan.lb.g;
     a.t = s->tabs;
     a.out = s->d_tiles[buf];
     if (mem_kind == RTMODT_MEM_HOST) {
@@ -481,15 +456,9 @@ static int slicer_create_impl(rtmodt_slicer *s) {
     RT_HIP(hipMalloc((void **)&s->d_stage, (size_t)c.max_frames * c.frame_h * c.frame_w * 3));
     const size_t batch_bytes = (size_t)c.max_frames * p.I * p.img_bytes;
     for (int b = 0; b < 2; ++b) RT_HIP(hipMalloc((void **)&s->d_tiles[b], batch_bytes + 256));      // (slack: a reader may take the last row in wide loads)
-    if (c.overview && p.lb.resize) {
-        std::vector<int32_t> t((size_t)3 * (p.lb.new_w + p.lb.new_h));
-        int32_t *x = t.data(), *y = x + 3 * p.lb.new_w;
-        slice_resize_table(p.lb.new_w, c.frame_w, x, x + p.lb.new_w, x + 2 * p.lb.new_w);
-        slice_resize_table(p.lb.new_h, c.frame_h, y, y + p.lb.new_h, y + 2 * p.lb.new_h);
-        RT_HIP(hipMalloc((void **)&s->d_tab, t.size() * 4));
-        RT_HIP(hipMemcpy(s->d_tab, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-        const int32_t *dx = s->d_tab, *dy = dx + 3 * p.lb.new_w;
-        s->tabs = ResizeTables{dx, dx + p.lb.new_w, dx + 2 * p.lb.new_w, dy, dy + p.lb.new_h, dy + 2 * p.lb.new_h};
+    if (c.overview && p.lb.g.resize) {
+        RT_HIP(hipMalloc((void **)&s->d_tab, (size_t)3 * (p.lb.g.new_w + p.lb.g.new_h) * 4));
+        RT_TRY(upload_resize_tables(p.lb.g, s->d_tab, &s->tabs));
     }
     RT_HIP(hipMalloc((void **)&s->d_sbox, (size_t)c.max_frames * p.cap * 16));
     RT_HIP(hipMalloc((void **)&s->d_scls, (size_t)c.max_frames * p.cap * 4));

@@ -1,6 +1,7 @@
-// slice_grid.h -- the host arithmetic of sliced inference (slice.hip): where the tiles of a frame lie, how the overview image is
-// letterboxed, how its boxes travel back.  Plain C++, no HIP: tests/native/slice_grid_check.cpp compiles it on the host under the
-// address and UB sanitizers, and tests/slice_ref.py restates it.
+// slice_grid.h -- the host arithmetic of sliced inference (slice.hip): where the tiles of a frame lie.  How the overview image is
+// letterboxed and how its boxes travel back is the detector's own letterbox (letterbox.h, included here for slice.hip and the
+// native check).  Plain C++, no HIP: tests/native/slice_grid_check.cpp compiles it on the host under the address and UB
+// sanitizers, and tests/slice_ref.py restates it.
 //
 // The grid (SAHI's get_slice_bboxes with the last tile shifted inward): along an axis of length L with tile t and overlap o,
 // 0 <= o < t:  te = min(t, L);  step = te - o (one position, 0, when step <= 0);  p_k = min(k * step, L - te) for k = 0, 1, ...
@@ -8,9 +9,9 @@
 #pragma once
 
 #include <algorithm>
-#include <cmath>
-#include <cstdint>
 #include <vector>
+
+#include "letterbox.h"
 
 namespace rtmodt {
 
@@ -51,41 +52,6 @@ inline int slice_grid(int W, int H, int tw, int th, int ow, int oh, SliceGrid *g
     for (int py : ay.pos)
         for (int px : ax.pos) { g->x.push_back(px); g->y.push_back(py); }
     return 0;
-}
-
-// The overview: the whole h x w frame letterboxed into in_h x in_w (ultralytics LetterBox, oracle/yolo_oracle.py:295-308) and the way
-// back for its boxes (scale_boxes, oracle/yolo_oracle.py:457-468: pad and gain in double, handed to the kernel as float32)
-struct SliceLetterbox { int new_w, new_h, top, left, resize; float gain, pad_x, pad_y; };
-
-inline int slice_round_half_even(double v) { return (int)std::nearbyint(v); }      // == Python round()
-
-inline SliceLetterbox slice_letterbox(int h, int w, int in_h, int in_w) {
-    SliceLetterbox g;
-    const double r = std::min((double)in_h / h, (double)in_w / w);
-    g.new_w = slice_round_half_even(w * r); g.new_h = slice_round_half_even(h * r);
-    const double dw = (in_w - g.new_w) / 2.0, dh = (in_h - g.new_h) / 2.0;
-    g.top = slice_round_half_even(dh - 0.1); g.left = slice_round_half_even(dw - 0.1);
-    g.resize = (g.new_w != w) || (g.new_h != h);
-    g.gain = (float)r;
-    g.pad_x = (float)slice_round_half_even((in_w - w * r) / 2 - 0.1);
-    g.pad_y = (float)slice_round_half_even((in_h - h * r) / 2 - 0.1);
-    return g;
-}
-
-// cv::resize INTER_LINEAR 8-bit tables for one axis (oracle/yolo_oracle.py:311-330, _resize_coeffs): source index and the two
-// 11-bit weights per destination position
-inline void slice_resize_table(int dst, int src, int32_t *ofs, int32_t *c0, int32_t *c1) {
-    const double scale = 1.0 / ((double)dst / src);
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)std::floor(f);
-        f = f - (float)s;
-        if (s < 0) { s = 0; f = 0.f; }
-        if (s >= src - 1) { s = src - 1; f = 0.f; }
-        ofs[d] = s;
-        c0[d] = (int)std::nearbyint((1.0f - f) * 2048.0f);
-        c1[d] = (int)std::nearbyint(f * 2048.0f);
-    }
 }
 
 }  // namespace rtmodt

@@ -306,24 +306,6 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_fill(StitchArgs a) {
     for (int q = 0; q < 4; ++q) a.fill_box[4 * f + q] = pa[q] + (pb[q] - pa[q]) * tt;
 }
 
-// device buffers of one call, freed on every return path
-struct StitchBufs {
-    std::vector<void *> ptrs;
-    ~StitchBufs() { for (void *p : ptrs) (void)hipFree(p); }
-    template <typename T> int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        RT_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return RTMODT_OK;
-    }
-    template <typename T> int up(T **out, const T *host, size_t n) {
-        RT_TRY(alloc(out, n));
-        if (n) RT_HIP(hipMemcpy(*out, host, n * sizeof(T), hipMemcpyHostToDevice));
-        return RTMODT_OK;
-    }
-};
-
 constexpr int64_t ST_MAX_FRAME = (int64_t)1 << 53;         // frames come from float64 files: exact, and e + max_gap cannot overflow
 
 }  // namespace
@@ -396,7 +378,7 @@ int rtmodt_stitch_tracks(int device, const rtmodt_stitch_params *params, int n_s
     for (int t = 0; t < n_trk; ++t) order_start[t] = row_frame[trk_row_start[order[t]]];
 
     RT_HIP(hipSetDevice(device));
-    StitchBufs B;
+    DevBufs B;
     StitchArgs a{};
     a.n_trk = n_trk; a.max_gap = params->max_gap; a.vwin = params->velocity_window; a.interpolate = params->interpolate;
     a.max_d2 = params->max_dist * params->max_dist;

@@ -1,5 +1,6 @@
-// slice_grid_check.cpp -- csrc/slice_grid.h on the host (no HIP): the worked grid values, coverage and containment over a sweep,
-// the tile-count limit, the resize tables' index bounds (what the overview kernel dereferences) and the letterbox geometry.
+// slice_grid_check.cpp -- csrc/slice_grid.h and the csrc/letterbox.h it includes on the host (no HIP): the worked grid values,
+// coverage and containment over a sweep, the tile-count limit, the resize tables' index bounds (what the overview kernel
+// dereferences) and the letterbox geometry of the overview.
 // Built plain and with the address / undefined-behaviour sanitizers by tests/test_slice_cpu.py; runs by itself.
 #include <cstdio>
 #include <vector>
@@ -65,7 +66,7 @@ int main() {
     for (int src = 1; src <= 200; src += 3)
         for (int dst = 1; dst <= 70; dst += 2) {
             std::vector<int32_t> t((size_t)3 * dst);
-            slice_resize_table(dst, src, t.data(), t.data() + dst, t.data() + 2 * dst);
+            resize_table(dst, src, t.data(), t.data() + dst, t.data() + 2 * dst);
             for (int d = 0; d < dst; ++d) {
                 CHECK(t[(size_t)d] >= 0 && t[(size_t)d] <= src - 1, "table %d <- %d: index %d at %d", dst, src, t[(size_t)d], d);
                 CHECK(t[(size_t)dst + d] + t[(size_t)2 * dst + d] == 2048, "table %d <- %d: weights at %d", dst, src, d);
@@ -78,13 +79,14 @@ int main() {
         for (int w = 1; w <= 320; w += 11)
             for (int t : {32, 50, 64}) {
                 const int in_w = std::min(t, w), in_h = std::min(t, h);
-                const SliceLetterbox lb = slice_letterbox(h, w, in_h, in_w);
-                CHECK(lb.new_w >= 0 && lb.new_h >= 0 && lb.new_w <= in_w && lb.new_h <= in_h, "letterbox %dx%d -> %dx%d: %dx%d", w, h, in_w, in_h, lb.new_w, lb.new_h);
-                CHECK(lb.left >= 0 && lb.top >= 0 && lb.left + lb.new_w <= in_w && lb.top + lb.new_h <= in_h, "letterbox %dx%d -> %dx%d: pads", w, h, in_w, in_h);
-                CHECK(lb.gain > 0.f, "letterbox gain");
+                const Letterbox lb = letterbox_geometry(h, w, in_h, in_w);
+                const LetterboxGeom &g = lb.g;
+                CHECK(g.new_w >= 0 && g.new_h >= 0 && g.new_w <= in_w && g.new_h <= in_h, "letterbox %dx%d -> %dx%d: %dx%d", w, h, in_w, in_h, g.new_w, g.new_h);
+                CHECK(g.left >= 0 && g.top >= 0 && g.left + g.new_w <= in_w && g.top + g.new_h <= in_h, "letterbox %dx%d -> %dx%d: pads", w, h, in_w, in_h);
+                CHECK((float)lb.gain > 0.f, "letterbox gain");
             }
-    const SliceLetterbox hd = slice_letterbox(1080, 1920, 640, 640);
-    CHECK(hd.new_w == 640 && hd.new_h == 360 && hd.top == 140 && hd.left == 0 && hd.resize == 1 && hd.pad_x == 0.f && hd.pad_y == 140.f, "1080p overview");
+    const Letterbox hd = letterbox_geometry(1080, 1920, 640, 640);
+    CHECK(hd.g.new_w == 640 && hd.g.new_h == 360 && hd.g.top == 140 && hd.g.left == 0 && hd.g.resize == 1 && hd.pad_x == 0 && hd.pad_y == 140, "1080p overview");
     printf("ok letterbox\n");
 
     if (failures) { printf("FAIL %d checks\n", failures); return 1; }
