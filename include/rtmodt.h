@@ -1066,6 +1066,89 @@ int rtmodt_slicer_last_ms(rtmodt_slicer *s, float *gather_ms, float *merge_ms);
  * same HIP stream behind slice_merge; the tracker needs max_dets >= max_out. */
 int rtmodt_tracker_update_from_slicer(rtmodt_tracker *trk, rtmodt_slicer *s);
 
+/* ---- privacy masking: people, objects and fixed privacy zones redacted before a frame leaves the box ------------------------ */
+/* The reference records and streams every frame in the clear; it has no code for redaction (PARITY UNPINNED throughout: no
+ * counterpart in the reference, no OpenCV to run cv2.blur / GaussianBlur against, no camera's privacy mask to compare with).
+ * PINNED, byte for byte, against tests/privacy_ref.py: the regions, the mask and the three modes.  csrc/privacy_regions.h states
+ * how a box becomes a rectangle (truncated corners clamped to +-2^20, BOX or HEAD rows, expansion, clip, class filter),
+ * csrc/privacy.hip's header the paint rules; all of it is integer arithmetic.  A pixel is masked when it lies in a region
+ * rectangle of its frame or inside or on a privacy polygon (the zone engine's test).  Unmasked pixels and the bytes past 3w of a
+ * row are never written.  Frames as in rtmodt_render_batch: BGR24, h x w, row pitch stride_bytes >= 3w, host or device memory
+ * by mem_kind.  At most 32 polygons / 2048 points / 65536 regions per frame, else RTMODT_E_CAPACITY with nothing launched. */
+#define RTMODT_PRIVACY_FILL 0       /* masked pixels become fill_bgr                                                            */
+#define RTMODT_PRIVACY_PIXELATE 1   /* ... the rounded mean (sum + n/2) / n of their cell x cell cell, grid anchored at (0, 0)    */
+#define RTMODT_PRIVACY_BLUR 2       /* ... `passes` box filters of (2 radius + 1)^2, each rounded to u8, windows clipped to the frame */
+#define RTMODT_PRIVACY_REGION_BOX 0   /* the whole box                                                                          */
+#define RTMODT_PRIVACY_REGION_HEAD 1  /* its top max(1, (H * head_pm + 999) / 1000) rows                                        */
+typedef struct rtmodt_privacy rtmodt_privacy;
+typedef struct rtmodt_privacy_cfg {
+    int32_t mode;               /* RTMODT_PRIVACY_*                                                                             */
+    uint8_t fill_bgr[4];        /* FILL's colour, B G R (the fourth byte is ignored)                                            */
+    int32_t cell;               /* 2..64                                                                                        */
+    int32_t radius;             /* 1..16                                                                                        */
+    int32_t passes;             /* 1..3                                                                                         */
+    int32_t region;             /* RTMODT_PRIVACY_REGION_*                                                                      */
+    int32_t head_pm;            /* 1..1000 per mille of the box height                                                          */
+    int32_t expand_px;          /* 0..256 pixels added on all four sides                                                        */
+    const int32_t *classes;     /* NULL: every class; else only boxes of these n_classes (0..256) class ids yield a region      */
+    int32_t n_classes;
+    int32_t max_regions;        /* 1..65536 regions per frame the handle accepts                                                */
+    int32_t device;
+} rtmodt_privacy_cfg;
+/* Host only: pixelate, black fill colour, cell 16, radius 8, passes 2, whole boxes, head_pm 300, no expansion, every class,
+ * 65536 regions, device 0.  PARITY UNPINNED. */
+void rtmodt_privacy_default_cfg(rtmodt_privacy_cfg *cfg);
+/* Every parameter is checked whatever the mode: one outside its range is RTMODT_E_INVALID and nothing is launched or
+ * allocated.  The class list is copied.  PARITY UNPINNED. */
+int rtmodt_privacy_create(const rtmodt_privacy_cfg *cfg, rtmodt_privacy **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_privacy_destroy(rtmodt_privacy *p);
+/* The fixed privacy zones (a camera's "privacy masks"), int32 polygons as rtmodt_renderer_set_zones takes them, uploaded once and
+ * cached by the handle; n = 0 clears them.  More than 32 polygons or 2048 points is RTMODT_E_CAPACITY.  PARITY UNPINNED. */
+int rtmodt_privacy_set_polygons(rtmodt_privacy *p, const int32_t *const *polygons_xy, const int32_t *n_points, int n);
+/* Host only, no device needed: the rectangles (x0, y0, x1, y1 inclusive, in box order, skipped boxes left out) that n_boxes
+ * boxes xyxy[n_boxes][4] of classes cls[n_boxes] (may be NULL without a class list) yield in an h x w frame under cfg's region
+ * kind, head_pm, expand_px and classes.  *needed = their count; written to rects when cap_rects >= *needed (the two-call
+ * protocol of rtmodt_render_pack).  A NaN or infinite coordinate is RTMODT_E_INVALID.  The parity surface of
+ * csrc/privacy_regions.h.  PARITY UNPINNED. */
+int rtmodt_privacy_regions(const rtmodt_privacy_cfg *cfg, const float *xyxy, const int32_t *cls, int n_boxes, int h, int w,
+                           int32_t *rects, int cap_rects, int32_t *needed);
+/* Masks n frames with the boxes handed over: xyxy[i] points at n_boxes[i] boxes of frame i (4 floats each), cls[i] at their
+ * classes (cls, or cls[i], may be NULL without a class list).  dst_frames == NULL: in place.  Otherwise dst_frames[i] receives
+ * the whole masked frame (its bytes past 3w of a row stay as they are) and src_frames[i] is left untouched; dst_frames[i] must
+ * equal src_frames[i] (that frame is masked in place) or not overlap it, else RTMODT_E_INVALID.  A NaN or infinite coordinate is
+ * RTMODT_E_INVALID, more regions in a frame than max_regions RTMODT_E_CAPACITY; a refusal launches nothing and leaves every
+ * frame untouched.  Every output is a function of the frame as it was before the call: in-place BLUR goes through a scratch
+ * buffer of the handle.  At most three launches, whatever the number of regions.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_privacy_apply(rtmodt_privacy *p, uint8_t *const *src_frames, uint8_t *const *dst_frames, int n, int h, int w,
+                         int stride_bytes, int mem_kind, const float *const *xyxy, const int32_t *const *cls,
+                         const int32_t *n_boxes);
+/* Masks, in place, frames[n_streams of the tracker] with the ByteTrack handle's device-resident tracks, on the HIP stream its
+ * last update ran on: exactly the tracks rtmodt_crossing_process_tracker passes (time_since_update == report_tsu, finite box;
+ * a non-finite box is skipped).  No box crosses to the host.  The tracker's max_tracks must not exceed max_regions
+ * (RTMODT_E_CAPACITY).  PARITY UNPINNED. */
+int rtmodt_privacy_apply_tracker(rtmodt_privacy *p, rtmodt_tracker *trk, uint8_t *const *frames, int h, int w, int stride_bytes,
+                                 int mem_kind, int report_tsu);
+/* The same on a DeepSORT handle: the tracks rtmodt_crossing_process_deepsort passes (confirmed, time_since_update ==
+ * report_tsu).  PARITY UNPINNED. */
+int rtmodt_privacy_apply_deepsort(rtmodt_privacy *p, rtmodt_deepsort *ds, uint8_t *const *frames, int h, int w, int stride_bytes,
+                                  int mem_kind, int report_tsu);
+/* The same on an OC-SORT handle: the tracks rtmodt_crossing_process_ocsort passes (the returned ones).  PARITY UNPINNED. */
+int rtmodt_privacy_apply_ocsort(rtmodt_privacy *p, rtmodt_ocsort *oc, uint8_t *const *frames, int h, int w, int stride_bytes,
+                                int mem_kind);
+/* The same on a BoT-SORT handle: the tracks rtmodt_crossing_process_botsort passes (tracked and matched this frame).  PARITY
+ * UNPINNED. */
+int rtmodt_privacy_apply_botsort(rtmodt_privacy *p, rtmodt_botsort *bot, uint8_t *const *frames, int h, int w, int stride_bytes,
+                                 int mem_kind);
+/* Masks, in place, the first n frames of the detector's newest batch with EVERY detection of that batch, read from its
+ * device-resident outputs on its post-processing stream behind the NMS (a tracker reports an object only once it is confirmed;
+ * masking the detections closes that gap).  n above the batch's frame count is RTMODT_E_INVALID, the detector's max_det above
+ * max_regions RTMODT_E_CAPACITY.  PARITY UNPINNED. */
+int rtmodt_privacy_apply_detector(rtmodt_privacy *p, rtmodt_detector *det, uint8_t *const *frames, int n, int h, int w,
+                                  int stride_bytes, int mem_kind);
+/* Device time (ms, HIP events around the launches) of the last apply call that launched.  PARITY UNPINNED. */
+int rtmodt_privacy_last_ms(rtmodt_privacy *p, float *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,9 @@ library being built):
 * ``pipeline``           -- the reference's per-frame loop (tools/run_pipeline.py:121-158) around the native classes
 * ``visualization``      -- ``FrameRenderer``: boxes, labels, trails, zones and HUD drawn into frames on the GPU
                             (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
-                            frames as JPEG / Motion-JPEG, encoded on the GPU (reference: tools/run_pipeline.py:112-117,160-161)
+                            frames as JPEG / Motion-JPEG, encoded on the GPU (reference: tools/run_pipeline.py:112-117,160-161);
+                            ``PrivacyMask``: tracked objects and fixed privacy zones filled, pixelated or blurred on the GPU before a
+                            frame is recorded or served (the reference has no redaction)
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158); ``JpegDecoder`` /
                             ``MjpegCapture``: JPEG / Motion-JPEG files, AVI and multipart streams decoded on the GPU
@@ -62,6 +64,7 @@ _LAZY = {
     "JpegDecoder": ".ingestion.jpeg_decode",
     "MjpegCapture": ".ingestion.mjpeg",
     "FrameRenderer": ".visualization.renderer",
+    "PrivacyMask": ".visualization.privacy",
     "JpegEncoder": ".visualization.jpeg",
     "MjpegWriter": ".visualization.jpeg",
     "MjpegRecorder": ".visualization.jpeg",

@@ -209,6 +209,12 @@ class SliceCfg(C.Structure):                        # struct rtmodt_slice_cfg
                 ("match_thresh", C.c_float), ("agnostic", C.c_int32), ("max_out", C.c_int32), ("max_frames", C.c_int32)]
 
 
+class PrivacyCfg(C.Structure):                      # struct rtmodt_privacy_cfg
+    _fields_ = [("mode", C.c_int32), ("fill_bgr", C.c_uint8 * 4), ("cell", C.c_int32), ("radius", C.c_int32), ("passes", C.c_int32),
+                ("region", C.c_int32), ("head_pm", C.c_int32), ("expand_px", C.c_int32), ("classes", C.POINTER(C.c_int32)),
+                ("n_classes", C.c_int32), ("max_regions", C.c_int32), ("device", C.c_int32)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -358,6 +364,18 @@ def lib() -> C.CDLL:
         "rtmodt_slicer_fetch": (C.c_int, [vp, vp] + [vp] * 9),
         "rtmodt_slicer_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
         "rtmodt_tracker_update_from_slicer": (C.c_int, [vp, vp]),
+        "rtmodt_privacy_default_cfg": (None, [C.POINTER(PrivacyCfg)]),
+        "rtmodt_privacy_create": (C.c_int, [C.POINTER(PrivacyCfg), C.POINTER(vp)]),
+        "rtmodt_privacy_destroy": (None, [vp]),
+        "rtmodt_privacy_set_polygons": (C.c_int, [vp, vp, vp, C.c_int]),
+        "rtmodt_privacy_regions": (C.c_int, [C.POINTER(PrivacyCfg), vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(i32)]),
+        "rtmodt_privacy_apply": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "rtmodt_privacy_apply_tracker": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_privacy_apply_deepsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_privacy_apply_ocsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_privacy_apply_botsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_privacy_apply_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_privacy_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -89,10 +89,19 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``swap_guard``: a ``tracking.IdSwapGuard``, called right after ``tracker.update`` and before events, crossings and rendering,
     inside a ``swap_guard`` stage: it verifies the ByteTrack identities by appearance on the frame the detector read and exchanges
     the ids of a swapped pair back inside the tracker's device-resident state, so every later stage reads the corrected identity
-    (a track list that was already materialised has its ids exchanged too).  The summary then carries ``id_swaps_reverted``."""
+    (a track list that was already materialised has its ids exchanged too).  The summary then carries ``id_swaps_reverted``.
+
+    ``privacy``: a ``visualization.PrivacyMask``, called inside a ``privacy`` stage after the swap guard, the events and the crossings
+    and directly before ``visualization``: the masker is the last reader of the clean pixels, and labels and boxes are drawn on top
+    of the mask.  It masks the materialised track list when there is one, else the tracker's device-resident tracks (no box crosses
+    to the host); the recorder then receives the masked frame.  ``None``: the stage table and every output are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
+    if privacy is not None and "privacy" not in profiler.STAGE_ORDER:          # this profiler's table gains the row (the class's order stays)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("visualization"), "privacy")
+        profiler.STAGE_ORDER = order
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
@@ -149,6 +158,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_crossings += len(crossing_counter.process(tracks, fid))
             profiler.tock("crossings")
+        if privacy is not None:
+            profiler.tick("privacy")
+            if tracks is None or events_on_device:
+                privacy.apply_tracker(tracker, [frame])
+            else:
+                privacy.apply(frame, tracks)
+            profiler.tock("privacy")
         if renderer is not None:                           # tools/run_pipeline.py:149-156
             profiler.tick("visualization")
             zones = event_engine.get_zone_polygons() if event_engine is not None else None

@@ -1,4 +1,5 @@
 from .jpeg import JpegEncoder, MjpegRecorder, MjpegWriter, multipart_chunk
+from .privacy import PrivacyMask
 from .renderer import FrameRenderer
 
-__all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk"]
+__all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk", "PrivacyMask"]
