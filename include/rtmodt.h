@@ -1149,6 +1149,94 @@ int rtmodt_privacy_apply_detector(rtmodt_privacy *p, rtmodt_detector *det, uint8
 /* Device time (ms, HIP events around the launches) of the last apply call that launched.  PARITY UNPINNED. */
 int rtmodt_privacy_last_ms(rtmodt_privacy *p, float *kernel_ms);
 
+/* ---- occupancy heatmaps: where objects have been, accumulated from boxes or device-resident tracks ------------------------- */
+/* The reference has nothing that accumulates presence over time (its heat-map plot is the confusion matrix); PARITY UNPINNED
+ * throughout: no counterpart in the reference, no Ultralytics Heatmap solution, no cv2 colormap or addWeighted to compare with, no
+ * default tuned on real footage.  PINNED, exactly, against tests/heatmap_ref.py: the footprints, decay, saturation, the overlay and
+ * the zone sums.  csrc/heatmap_stamp.h states which cells a box stamps, csrc/heatmap.hip's header the other rules; all of it is
+ * integer arithmetic.  A handle holds one uint32 grid of ceil(height / cell) x ceil(width / cell) cells per stream, zero at
+ * creation, edge cells clipped to the frame.  At most 65536 boxes per frame, 32 polygons / 2048 points, else RTMODT_E_CAPACITY
+ * with nothing launched; a refused call leaves the grid and the frames as they were. */
+#define RTMODT_HEATMAP_BOX 0        /* every cell the box's rectangle (clipped to the frame) touches                             */
+#define RTMODT_HEATMAP_DISC 1       /* of those, the cells whose centre lies within min(W, H) / 2 of the box centre, and the centre pixel's */
+#define RTMODT_HEATMAP_FOOT 2       /* the cells within foot_radius of the bottom-centre (ground contact) pixel, and that pixel's  */
+typedef struct rtmodt_heatmap rtmodt_heatmap;
+typedef struct rtmodt_heatmap_cfg {
+    int32_t n_streams;          /* 1..1024 grids                                                                                */
+    int32_t height, width;      /* the frame size, 1..32768 each; n_streams * cells at most 2^30                                */
+    int32_t cell;               /* 1, 2, 4, 8 or 16 pixels per cell side                                                        */
+    int32_t footprint;          /* RTMODT_HEATMAP_*                                                                             */
+    int32_t foot_radius;        /* 0..256 pixels (FOOT)                                                                         */
+    int32_t weight;             /* 1..1024 added per footprint covering a cell                                                  */
+    int32_t decay_shift;        /* 0: no decay; 1..16: heat -= heat >> decay_shift ...                                          */
+    int32_t decay_every;        /* ... in every decay_every-th accumulate call (1..65536)                                       */
+    const int32_t *classes;     /* NULL: every class; else only boxes of these n_classes (0..256) class ids leave a footprint   */
+    int32_t n_classes;
+    int32_t device;
+} rtmodt_heatmap_cfg;
+/* Host only: 1 stream, height and width 0 (the caller sets them), cell 4, DISC, foot_radius 0, weight 1, no decay (shift 0, every
+ * 1), every class, device 0.  PARITY UNPINNED. */
+void rtmodt_heatmap_default_cfg(rtmodt_heatmap_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range is RTMODT_E_INVALID.  The class list is copied;
+ * the colour table starts as the closed-form jet (rtmodt_heatmap_set_colormap).  PARITY UNPINNED. */
+int rtmodt_heatmap_create(const rtmodt_heatmap_cfg *cfg, rtmodt_heatmap **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_heatmap_destroy(rtmodt_heatmap *h);
+/* Host only, no device needed: the cells (cx, cy pairs, row by row) the one box xyxy[4] of class cls stamps on the grid of cfg's
+ * height x width frame under cfg's cell, footprint, foot_radius and classes.  *needed = their count; written to cells_xy when
+ * cap_cells >= *needed (the two-call protocol of rtmodt_privacy_regions).  A NaN or infinite coordinate is RTMODT_E_INVALID.  The
+ * parity surface of csrc/heatmap_stamp.h.  PARITY UNPINNED. */
+int rtmodt_heatmap_footprint(const rtmodt_heatmap_cfg *cfg, const float *xyxy, int32_t cls, int32_t *cells_xy, int cap_cells,
+                             int32_t *needed);
+/* One frame of every stream: xyxy[s] points at n_boxes[s] boxes of stream s (4 floats each), cls[s] at their classes (cls, or
+ * cls[s], may be NULL without a class list).  Calls are numbered from 1 per handle (refused calls are not counted): if decay_shift
+ * != 0 and call % decay_every == 0 every cell first becomes heat - (heat >> decay_shift); then heat = min(heat + weight * count,
+ * 2^32 - 1) with count the number of this frame's footprints covering the cell.  No atomics: saturation is exact, the order of
+ * the boxes does not matter.  A NaN or infinite coordinate is RTMODT_E_INVALID, more than 65536 boxes in a frame
+ * RTMODT_E_CAPACITY.  One launch, whatever the number of boxes.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_heatmap_accumulate(rtmodt_heatmap *h, const float *const *xyxy, const int32_t *const *cls, const int32_t *n_boxes);
+/* The same with the ByteTrack handle's device-resident tracks (stream s of the tracker -> grid s), on the HIP stream its last
+ * update ran on: exactly the tracks rtmodt_privacy_apply_tracker masks (time_since_update == report_tsu, finite box; a non-finite
+ * box is skipped).  No box crosses to the host; two launches.  A stream count other than the handle's is RTMODT_E_INVALID.  PARITY
+ * UNPINNED. */
+int rtmodt_heatmap_accumulate_tracker(rtmodt_heatmap *h, rtmodt_tracker *trk, int report_tsu);
+/* The same on a DeepSORT handle: confirmed tracks with time_since_update == report_tsu.  PARITY UNPINNED. */
+int rtmodt_heatmap_accumulate_deepsort(rtmodt_heatmap *h, rtmodt_deepsort *ds, int report_tsu);
+/* The same on an OC-SORT handle: the returned tracks.  PARITY UNPINNED. */
+int rtmodt_heatmap_accumulate_ocsort(rtmodt_heatmap *h, rtmodt_ocsort *oc);
+/* The same on a BoT-SORT handle: tracked and matched this frame.  PARITY UNPINNED. */
+int rtmodt_heatmap_accumulate_botsort(rtmodt_heatmap *h, rtmodt_botsort *bot);
+/* The same with EVERY detection of the detector's newest batch (frame i -> grid i), read from its device-resident outputs on its
+ * post-processing stream behind the NMS.  A batch whose frame count is not the handle's stream count is RTMODT_E_INVALID.  PARITY
+ * UNPINNED. */
+int rtmodt_heatmap_accumulate_detector(rtmodt_heatmap *h, rtmodt_detector *det);
+/* Blends the heat onto n BGR24 frames in place (height x width as created, else RTMODT_E_INVALID; row pitch stride_bytes >= 3w;
+ * host or device memory by mem_kind).  Frame i shows grid streams[i]; streams == NULL: grid i, and n must be the stream count.
+ * m = scale_max (colours stable over time), or with scale_max == 0 the grid's maximum now; m == 0 leaves the frame untouched.
+ * Level v = min(255, (heat * 255 + m / 2) / m); pixel (x, y) reads cell (x / cell, y / cell) (nearest sampling); v < min_level
+ * (1..255): the pixel keeps its bytes; else each channel becomes (p * (256 - alpha) + lut[v][c] * alpha + 128) >> 8, alpha
+ * 0..256.  The bytes past 3w of a row are never written.  Two launches at most.  Synchronous.  PARITY UNPINNED (cv2.addWeighted,
+ * cv2.applyColorMap). */
+int rtmodt_heatmap_overlay(rtmodt_heatmap *h, uint8_t *const *frames, const int32_t *streams, int n, int height, int width,
+                           int stride_bytes, int mem_kind, int alpha, int min_level, uint32_t scale_max);
+/* The colour table, 256 x 3 bytes B G R, copied.  NULL restores the default, a closed-form jet: channel = clamp(max(0, 765 -
+ * |8v - 510k|) >> 1, 0, 255) with k = 3, 2, 1 for R, G, B; its parity with cv2.COLORMAP_JET is UNPINNED.  PARITY UNPINNED. */
+int rtmodt_heatmap_set_colormap(rtmodt_heatmap *h, const uint8_t *lut_bgr);
+/* sums[z] = the sum of heat over the cells of polygon z (int32 polygons as rtmodt_renderer_set_zones takes them) of one stream's
+ * grid; a cell belongs to a polygon when its centre pixel (min(cx * cell + cell / 2, width - 1), likewise y) is inside or on it
+ * (the zone engine's test).  With weight 1 and FOOT radius 0 that is the object-frames spent in the zone.  More than 32 polygons
+ * or 2048 points is RTMODT_E_CAPACITY.  One launch.  PARITY UNPINNED. */
+int rtmodt_heatmap_zone_sums(rtmodt_heatmap *h, int stream, const int32_t *const *polygons_xy, const int32_t *n_points, int n,
+                             uint64_t *sums);
+/* One stream's grid to host memory, uint32[gh][gw].  PARITY UNPINNED. */
+int rtmodt_heatmap_read(rtmodt_heatmap *h, int stream, uint32_t *out);
+/* Replaces one stream's grid with a saved one (uint32[gh][gw]), so that a map survives a restart.  PARITY UNPINNED. */
+int rtmodt_heatmap_load(rtmodt_heatmap *h, int stream, const uint32_t *in);
+/* Zeroes one stream's grid, or every grid with stream == -1; the call numbering goes on.  PARITY UNPINNED. */
+int rtmodt_heatmap_reset(rtmodt_heatmap *h, int stream);
+/* Device time (ms, HIP events around the launches) of the last accumulate or overlay call that launched.  PARITY UNPINNED. */
+int rtmodt_heatmap_last_ms(rtmodt_heatmap *h, float *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,9 @@ library being built):
                             (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
                             frames as JPEG / Motion-JPEG, encoded on the GPU (reference: tools/run_pipeline.py:112-117,160-161);
                             ``PrivacyMask``: tracked objects and fixed privacy zones filled, pixelated or blurred on the GPU before a
-                            frame is recorded or served (the reference has no redaction)
+                            frame is recorded or served (the reference has no redaction); ``Heatmap``: occupancy heatmaps
+                            accumulated from boxes or device-resident tracks, blended onto frames and summed per zone on the GPU
+                            (the reference accumulates nothing over time)
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158); ``JpegDecoder`` /
                             ``MjpegCapture``: JPEG / Motion-JPEG files, AVI and multipart streams decoded on the GPU
@@ -65,6 +67,7 @@ _LAZY = {
     "MjpegCapture": ".ingestion.mjpeg",
     "FrameRenderer": ".visualization.renderer",
     "PrivacyMask": ".visualization.privacy",
+    "Heatmap": ".visualization.heatmap",
     "JpegEncoder": ".visualization.jpeg",
     "MjpegWriter": ".visualization.jpeg",
     "MjpegRecorder": ".visualization.jpeg",

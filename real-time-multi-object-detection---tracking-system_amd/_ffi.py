@@ -215,6 +215,12 @@ class PrivacyCfg(C.Structure):                      # struct rtmodt_privacy_cfg
                 ("n_classes", C.c_int32), ("max_regions", C.c_int32), ("device", C.c_int32)]
 
 
+class HeatmapCfg(C.Structure):                      # struct rtmodt_heatmap_cfg
+    _fields_ = [("n_streams", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("cell", C.c_int32), ("footprint", C.c_int32),
+                ("foot_radius", C.c_int32), ("weight", C.c_int32), ("decay_shift", C.c_int32), ("decay_every", C.c_int32),
+                ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32), ("device", C.c_int32)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -376,6 +382,23 @@ def lib() -> C.CDLL:
         "rtmodt_privacy_apply_botsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtmodt_privacy_apply_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtmodt_privacy_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_heatmap_default_cfg": (None, [C.POINTER(HeatmapCfg)]),
+        "rtmodt_heatmap_create": (C.c_int, [C.POINTER(HeatmapCfg), C.POINTER(vp)]),
+        "rtmodt_heatmap_destroy": (None, [vp]),
+        "rtmodt_heatmap_footprint": (C.c_int, [C.POINTER(HeatmapCfg), vp, i32, vp, C.c_int, C.POINTER(i32)]),
+        "rtmodt_heatmap_accumulate": (C.c_int, [vp, vp, vp, vp]),
+        "rtmodt_heatmap_accumulate_tracker": (C.c_int, [vp, vp, C.c_int]),
+        "rtmodt_heatmap_accumulate_deepsort": (C.c_int, [vp, vp, C.c_int]),
+        "rtmodt_heatmap_accumulate_ocsort": (C.c_int, [vp, vp]),
+        "rtmodt_heatmap_accumulate_botsort": (C.c_int, [vp, vp]),
+        "rtmodt_heatmap_accumulate_detector": (C.c_int, [vp, vp]),
+        "rtmodt_heatmap_overlay": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32]),
+        "rtmodt_heatmap_set_colormap": (C.c_int, [vp, vp]),
+        "rtmodt_heatmap_zone_sums": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp]),
+        "rtmodt_heatmap_read": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_heatmap_load": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_heatmap_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_heatmap_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -94,13 +94,22 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``privacy``: a ``visualization.PrivacyMask``, called inside a ``privacy`` stage after the swap guard, the events and the crossings
     and directly before ``visualization``: the masker is the last reader of the clean pixels, and labels and boxes are drawn on top
     of the mask.  It masks the materialised track list when there is one, else the tracker's device-resident tracks (no box crosses
-    to the host); the recorder then receives the masked frame.  ``None``: the stage table and every output are unchanged."""
+    to the host); the recorder then receives the masked frame.  ``None``: the stage table and every output are unchanged.
+
+    ``heatmap``: a one-stream ``visualization.Heatmap`` of the frames' size, called inside a ``heatmap`` stage after ``privacy`` and
+    directly before ``visualization``, so that boxes and labels are drawn over the heat.  Every frame is accumulated -- the
+    materialised track list when there is one, else the tracker's device-resident tracks -- and the heat is blended onto the frame
+    only if the object's ``overlay_enabled`` is set.  ``None``: the stage table and every output are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
     if privacy is not None and "privacy" not in profiler.STAGE_ORDER:          # this profiler's table gains the row (the class's order stays)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("visualization"), "privacy")
+        profiler.STAGE_ORDER = order
+    if heatmap is not None and "heatmap" not in profiler.STAGE_ORDER:          # likewise, between privacy and visualization
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("visualization"), "heatmap")
         profiler.STAGE_ORDER = order
     for _ in range(max_frames):
         profiler.tick("decode")
@@ -165,6 +174,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 privacy.apply(frame, tracks)
             profiler.tock("privacy")
+        if heatmap is not None:
+            profiler.tick("heatmap")
+            if tracks is None or events_on_device:
+                heatmap.accumulate_tracker(tracker)
+            else:
+                heatmap.accumulate([tracks])
+            if heatmap.overlay_enabled:
+                heatmap.overlay([frame])
+            profiler.tock("heatmap")
         if renderer is not None:                           # tools/run_pipeline.py:149-156
             profiler.tick("visualization")
             zones = event_engine.get_zone_polygons() if event_engine is not None else None

@@ -1,5 +1,6 @@
+from .heatmap import Heatmap
 from .jpeg import JpegEncoder, MjpegRecorder, MjpegWriter, multipart_chunk
 from .privacy import PrivacyMask
 from .renderer import FrameRenderer
 
-__all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk", "PrivacyMask"]
+__all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk", "PrivacyMask", "Heatmap"]
