@@ -555,19 +555,58 @@ def frame_pointers(frames, mem_kind: int, height: int = 0, width: int = 0, strid
     stride) is refused: a silent copy would change the pitch under the caller's feet."""
     if mem_kind == MEM_DEVICE:
         return (C.c_void_p * len(frames))(*[int(p) for p in frames]), [], int(height), int(width), int(stride)
-    keep = []
+    keep = list(frames)
+    h, w, pitch = _host_frames(keep, writable=False)
+    return (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep]), keep, h, w, pitch
+
+
+def _host_frames(frames, writable: bool, one_row_any_pitch: bool = False):
+    """The one check of a list of host frames -> their common (height, width, row pitch); (0, 0, 0) for an empty list.
+    ``one_row_any_pitch`` (the JPEG encoder): the pitch NumPy reports for a single row means nothing and is read as at least 3w."""
+    geo = (0, 0, 0)
     for i, f in enumerate(frames):
-        if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.strides[2] != 1 or f.strides[1] != 3 \
-                or f.strides[0] < 3 * f.shape[1]:
+        ok = isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3 and f.strides[2] == 1 and f.strides[1] == 3
+        pitch = 0 if not ok else max(f.strides[0], 3 * f.shape[1]) if one_row_any_pitch and f.shape[0] == 1 else f.strides[0]
+        if not ok or pitch < 3 * f.shape[1]:
             raise ValueError(f"frame {i}: a host frame is an (h, w, 3) uint8 array with packed pixels and a row pitch >= 3w "
                              f"(got {getattr(f, 'dtype', type(f))}, shape {getattr(f, 'shape', None)}, strides {getattr(f, 'strides', None)})")
-        keep.append(f)
-    if not keep:
-        return (C.c_void_p * 0)(), keep, 0, 0, 0
-    h, w, pitch = keep[0].shape[0], keep[0].shape[1], keep[0].strides[0]
-    if any(k.shape[:2] != (h, w) or k.strides[0] != pitch for k in keep):
-        raise ValueError("the frames of one call share their size and row pitch")
-    return (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep]), keep, h, w, pitch
+        if writable and not f.flags.writeable:
+            raise ValueError(f"frame {i} is read-only; it is written in place")
+        g = (f.shape[0], f.shape[1], pitch)
+        if i and g != geo:
+            raise ValueError("the frames of one call share their size and row pitch")
+        geo = g
+    return geo
+
+
+def batch_frames(frames, n: int | None = None, *, height: int | None = None, width: int | None = None, stride: int | None = None,
+                 offset: int = 0, writable: bool = True, strict: bool = False):
+    """The frame argument block of the batched calls: ``frames`` -> ``(addresses, height, width, row stride, mem_kind, n)``.
+
+    ``frames`` is a list of ``n`` host arrays (``(h, w, 3)`` uint8, packed pixels, rows may be padded, one shape and row stride; writable
+    when ``writable``), whose geometry is read from the arrays, or a ``DeviceBuffer`` that holds the frames one after another: frame i at
+    ``offset + i * height * stride`` (``stride`` defaults to ``3 * width``), checked against the buffer's size to its last byte.
+    ``n`` None: ``len(frames)``, or as many frames as fit behind ``offset``.  ``strict``: an empty frame or a device stride below
+    ``3 * width`` is refused here; otherwise the library refuses it.  Anything else than these two forms is refused: a silent copy would
+    change the pitch under the caller's feet."""
+    if isinstance(frames, DeviceBuffer):
+        if height is None or width is None:
+            raise ValueError("device frames need height and width")
+        h, w = int(height), int(width)
+        st = 3 * w if stride is None else int(stride)
+        if (strict or n is None) and (h < 1 or w < 1 or st < 3 * w):
+            raise ValueError(f"bad frame geometry {w}x{h}, stride {st}")
+        n = (frames.nbytes - offset + st - 3 * w) // (h * st) if n is None else int(n)
+        if ((strict or n) and offset < 0) or n < 0 or (n and offset + (n - 1) * h * st + (h - 1) * st + 3 * w > frames.nbytes):
+            raise ValueError(f"{n} frames of {w}x{h} (stride {st}) from offset {offset} overrun the {frames.nbytes}-byte buffer")
+        return [frames.ptr + offset + i * h * st for i in range(n)], h, w, st, MEM_DEVICE, n
+    frames = list(frames)
+    if n is not None and len(frames) != n:
+        raise ValueError(f"{len(frames)} frames, {n} expected")
+    h, w, st = _host_frames(frames, writable, one_row_any_pitch=strict and not writable)
+    if strict and frames and (h < 1 or w < 1):
+        raise ValueError(f"empty frames {h}x{w}")
+    return [f.ctypes.data for f in frames], h, w, st, MEM_HOST, len(frames)
 
 
 def appearance_describe(frames, boxes, *, height: int = 0, width: int = 0, stride: int = 0, mem_kind: int = MEM_HOST, device: int = 0,

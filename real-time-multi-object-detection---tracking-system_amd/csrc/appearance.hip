@@ -19,6 +19,7 @@
 // for row / column l & 15 -- both operands take the same k from the same lane group, and integer accumulation is exact, so
 // the sum does not depend on the order inside a group.  C: column l & 15, rows 4 * (l >> 4) + reg.
 #include "kernels.h"
+#include "frame_stage.h"
 
 #include <climits>
 #include <cmath>
@@ -178,8 +179,7 @@ int rtmodt_appearance_describe(int device, const uint8_t *const *frames, int n_f
     RT_CHECK(n_frames >= 0 && n_frames <= 64, RTMODT_E_CAPACITY, "%d frames: at most 64 per call", n_frames);
     if (n_frames == 0) return RTMODT_OK;
     RT_CHECK(frames && xyxy && n_boxes && desc, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(h >= 1 && w >= 1 && h <= 16384 && w <= 16384 && stride_bytes >= 3 * w, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", w, h, stride_bytes);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
+    RT_TRY(check_frame_block(n_frames, h, w, stride_bytes, mem_kind, kAppFrames));
     RT_CHECK(max_boxes >= 1 && max_boxes <= 1024, RTMODT_E_CAPACITY, "max_boxes %d: 1..1024", max_boxes);
     for (int i = 0; i < n_frames; ++i) {
         RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
@@ -187,19 +187,13 @@ int rtmodt_appearance_describe(int device, const uint8_t *const *frames, int n_f
         RT_CHECK(n_boxes[i] <= max_boxes, RTMODT_E_CAPACITY, "frame %d: %d boxes > max_boxes %d", i, n_boxes[i], max_boxes);
     }
     RT_HIP(hipSetDevice(device));
-    const size_t fbytes = (size_t)h * stride_bytes, nb = (size_t)n_frames * max_boxes;
-    uint8_t *d_frames = nullptr; float4 *d_box = nullptr; int32_t *d_n = nullptr, *d_counts = nullptr; int8_t *d_desc = nullptr;
+    const size_t nb = (size_t)n_frames * max_boxes;
+    FrameStage stage;                                       // of this call alone
+    float4 *d_box = nullptr; int32_t *d_n = nullptr, *d_counts = nullptr; int8_t *d_desc = nullptr;
     auto body = [&]() -> int {
         DescribeArgs a{};
-        if (mem_kind == RTMODT_MEM_HOST) {
-            RT_HIP(hipMalloc((void **)&d_frames, fbytes * n_frames));
-            for (int i = 0; i < n_frames; ++i) {
-                RT_HIP(hipMemcpy(d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice));
-                a.frames.p[i] = d_frames + fbytes * i;
-            }
-        } else {
-            for (int i = 0; i < n_frames; ++i) a.frames.p[i] = frames[i];
-        }
+        RT_TRY(stage.in(frames, n_frames, h, w, stride_bytes, mem_kind, nullptr, FRAMES_AS_GIVEN));
+        for (int i = 0; i < n_frames; ++i) a.frames.p[i] = stage.at(frames, i);
         RT_HIP(hipMalloc((void **)&d_box, nb * 16)); RT_HIP(hipMalloc((void **)&d_n, (size_t)n_frames * 4));
         RT_HIP(hipMalloc((void **)&d_counts, nb * APP_DIM * 4)); RT_HIP(hipMalloc((void **)&d_desc, nb * APP_DIM));
         RT_HIP(hipMemset(d_counts, 0, nb * APP_DIM * 4)); RT_HIP(hipMemset(d_desc, 0, nb * APP_DIM));
@@ -214,7 +208,7 @@ int rtmodt_appearance_describe(int device, const uint8_t *const *frames, int n_f
         return RTMODT_OK;
     };
     const int rc = body();
-    hipFree(d_frames); hipFree(d_box); hipFree(d_n); hipFree(d_counts); hipFree(d_desc);
+    stage.release(); hipFree(d_box); hipFree(d_n); hipFree(d_counts); hipFree(d_desc);
     return rc;
 }
 

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "track_host.h"
+#include "frame_stage.h"
 #include "lap.h"
 
 #include <climits>
@@ -483,7 +484,7 @@ struct rtmodt_botsort : TrackHandleBase {
     BotState *d_states = nullptr; std::vector<BotState> h_states;
     int16_t *d_feat16 = nullptr; int8_t *d_feat8 = nullptr;        // [S][2][Mc][dim]
     int8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_dot = nullptr;
-    uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
+    FrameStage stage;                        // host frames
     rtmodt_reid *reid = nullptr;             // embedder = a .rtreid file
 };
 
@@ -561,26 +562,11 @@ static int bot_run(rtmodt_botsort *t, const BotArgs &a, int count, const AppFram
 static int bot_check_sticky(rtmodt_botsort *t, int s, int64_t err) { return track_check_sticky(t, s, err, "assignment"); }
 
 // frames of a call -> device pointers (host frames are staged on stream q), as DeepSORT takes them
-static int bot_frames(rtmodt_botsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
+static int bot_stage(rtmodt_botsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
     RT_CHECK(t->reid || t->dim == APP_DIM, RTMODT_E_INVALID, "this handle takes caller descriptors of dimension %d; the built-in descriptor has %d", t->dim, APP_DIM);
-    RT_CHECK(fh >= 1 && fw >= 1 && fh <= 16384 && fw <= 16384 && pitch >= 3 * fw, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", fw, fh, pitch);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    for (int i = 0; i < count; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-    const size_t fbytes = (size_t)fh * pitch;
-    if (mem_kind == RTMODT_MEM_HOST) {
-        if (t->d_frames_bytes < fbytes * count) {
-            RT_HIP(hipStreamSynchronize(q));
-            hipFree(t->d_frames); t->d_frames = nullptr; t->d_frames_bytes = 0;
-            RT_HIP(hipMalloc((void **)&t->d_frames, fbytes * count));
-            t->d_frames_bytes = fbytes * count;
-        }
-        for (int i = 0; i < count; ++i) {
-            RT_HIP(hipMemcpyAsync(t->d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice, q));
-            out->p[i] = t->d_frames + fbytes * i;
-        }
-    } else {
-        for (int i = 0; i < count; ++i) out->p[i] = frames[i];
-    }
+    RT_TRY(check_frames(frames, count, fh, fw, pitch, mem_kind, kAppFrames));
+    RT_TRY(t->stage.in(frames, count, fh, fw, pitch, mem_kind, q, FRAMES_AS_GIVEN));
+    for (int i = 0; i < count; ++i) out->p[i] = t->stage.at(frames, i);
     return RTMODT_OK;
 }
 
@@ -603,7 +589,7 @@ void rtmodt_botsort_destroy(rtmodt_botsort *t) {
     track_close(t, [t] {
         for (auto &e : t->ev) if (e) hipEventDestroy(e);
         hipFree(t->pool); hipFree(t->d_states); hipFree(t->d_feat16); hipFree(t->d_feat8); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dot);
-        hipFree(t->d_frames);
+        t->stage.release();
         reid_close(t->reid);
     });
     delete t;
@@ -657,7 +643,7 @@ int rtmodt_botsort_update_batch(rtmodt_botsort *t, const float *xyxy, const floa
     RT_TRY(track_join(t));
     hipStream_t q = t->stream;
     AppFrames fp{};
-    if (frames && any) RT_TRY(bot_frames(t, frames, t->S, h, w, stride_bytes, mem_kind, q, &fp));
+    if (frames && any) RT_TRY(bot_stage(t, frames, t->S, h, w, stride_bytes, mem_kind, q, &fp));
     RT_TRY(track_batch_stage(t, xyxy, conf, cls, n, any));
     if (any && desc) RT_HIP(hipMemcpyAsync(t->d_desc, desc, (size_t)t->S * t->Nc * t->dim, hipMemcpyHostToDevice, q));
     RT_TRY(bot_run(t, bot_args(t, warp, t->S), t->S, frames && any ? &fp : nullptr, h, w, stride_bytes, q));
@@ -681,7 +667,7 @@ int rtmodt_botsort_update_from_detector(rtmodt_botsort *t, rtmodt_detector *det,
     RT_TRY(rtmodt_botsort_check_warp(warp, o.count >= 1 && o.count <= BOT_MAX_STREAMS ? o.count : 1));
     RT_TRY(track_detector_fits(t, o, o.count));
     AppFrames fp{};
-    if (frames) RT_TRY(bot_frames(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
+    if (frames) RT_TRY(bot_stage(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
     BotArgs a = bot_args(t, warp, o.count);                // the warp travels in the kernel arguments: nothing to copy, nothing to wait for
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
     RT_TRY(bot_run(t, a, o.count, frames ? &fp : nullptr, h, w, stride_bytes, o.stream));
@@ -699,7 +685,7 @@ int rtmodt_botsort_update_from_detector_gmc(rtmodt_botsort *t, rtmodt_detector *
     const float *warp_dev = nullptr;
     RT_TRY(gmc_enqueue_detector(gmc, o, frames, n_frames, h, w, stride_bytes, mem_kind, &warp_dev));      // first: refused before anything of this call is queued
     AppFrames fp{};
-    if (t->dim) RT_TRY(bot_frames(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
+    if (t->dim) RT_TRY(bot_stage(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
     BotArgs a = bot_args(t, nullptr, o.count);
     a.warp_dev = warp_dev;
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;

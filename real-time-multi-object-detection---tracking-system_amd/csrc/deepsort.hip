@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "track_host.h"
+#include "frame_stage.h"
 #include "lap.h"
 
 #include <climits>
@@ -271,7 +272,7 @@ struct rtmodt_deepsort : TrackHandleBase {
     char *pool = nullptr; int8_t *gallery = nullptr;      // pool: all state arrays (track_layout.h: carve_deepsort)
     DsState *d_states = nullptr; std::vector<DsState> h_states;
     int8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_dotmax = nullptr;
-    uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
+    FrameStage stage;                        // host frames
     rtmodt_reid *reid = nullptr;             // embedder = a .rtreid file: the network of reid.hip describes the boxes instead of the histogram
 };
 
@@ -345,26 +346,11 @@ static DsArgs ds_args(rtmodt_deepsort *t) {
 static int ds_check_sticky(rtmodt_deepsort *t, int s, int64_t err) { return track_check_sticky(t, s, err, "assignment"); }
 
 // frames of a call -> device pointers (host frames are staged on stream q)
-static int ds_frames(rtmodt_deepsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
+static int ds_stage(rtmodt_deepsort *t, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
     RT_CHECK(t->reid || t->dim == APP_DIM, RTMODT_E_INVALID, "this handle takes caller descriptors of dimension %d; the built-in descriptor has %d", t->dim, APP_DIM);
-    RT_CHECK(fh >= 1 && fw >= 1 && fh <= 16384 && fw <= 16384 && pitch >= 3 * fw, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", fw, fh, pitch);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    for (int i = 0; i < count; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-    const size_t fbytes = (size_t)fh * pitch;
-    if (mem_kind == RTMODT_MEM_HOST) {
-        if (t->d_frames_bytes < fbytes * count) {
-            RT_HIP(hipStreamSynchronize(q));
-            hipFree(t->d_frames); t->d_frames = nullptr; t->d_frames_bytes = 0;
-            RT_HIP(hipMalloc((void **)&t->d_frames, fbytes * count));
-            t->d_frames_bytes = fbytes * count;
-        }
-        for (int i = 0; i < count; ++i) {
-            RT_HIP(hipMemcpyAsync(t->d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice, q));
-            out->p[i] = t->d_frames + fbytes * i;
-        }
-    } else {
-        for (int i = 0; i < count; ++i) out->p[i] = frames[i];
-    }
+    RT_TRY(check_frames(frames, count, fh, fw, pitch, mem_kind, kAppFrames));
+    RT_TRY(t->stage.in(frames, count, fh, fw, pitch, mem_kind, q, FRAMES_AS_GIVEN));
+    for (int i = 0; i < count; ++i) out->p[i] = t->stage.at(frames, i);
     return RTMODT_OK;
 }
 
@@ -375,7 +361,7 @@ void rtmodt_deepsort_destroy(rtmodt_deepsort *t) {
     track_close(t, [t] {
         for (auto &e : t->ev) if (e) hipEventDestroy(e);
         hipFree(t->pool); hipFree(t->gallery); hipFree(t->d_states); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dotmax);
-        hipFree(t->d_frames);
+        t->stage.release();
         reid_close(t->reid);
     });
     delete t;
@@ -428,7 +414,7 @@ int rtmodt_deepsort_update_batch(rtmodt_deepsort *t, const float *xyxy, const fl
     RT_TRY(track_join(t));
     hipStream_t q = t->stream;
     AppFrames fp{};
-    if (frames && any) RT_TRY(ds_frames(t, frames, t->S, h, w, stride_bytes, mem_kind, q, &fp));
+    if (frames && any) RT_TRY(ds_stage(t, frames, t->S, h, w, stride_bytes, mem_kind, q, &fp));
     RT_TRY(track_batch_stage(t, xyxy, conf, cls, n, any));
     if (any && desc) RT_HIP(hipMemcpyAsync(t->d_desc, desc, (size_t)t->S * t->Nc * t->dim, hipMemcpyHostToDevice, q));
     RT_TRY(ds_run(t, ds_args(t), t->S, frames && any ? &fp : nullptr, h, w, stride_bytes, q));
@@ -449,7 +435,7 @@ int rtmodt_deepsort_update_from_detector(rtmodt_deepsort *t, rtmodt_detector *de
     RT_CHECK(n_frames == o.count, RTMODT_E_INVALID, "%d frames for the detector's batch of %d", n_frames, o.count);
     RT_TRY(track_detector_fits(t, o, o.count));
     AppFrames fp{};
-    RT_TRY(ds_frames(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
+    RT_TRY(ds_stage(t, frames, o.count, h, w, stride_bytes, mem_kind, o.stream, &fp));
     DsArgs a = ds_args(t);
     a.det_box = o.box; a.det_conf = o.conf; a.det_cls = o.cls; a.det_n = o.n; a.det_stride = o.stride;
     RT_TRY(ds_run(t, a, o.count, &fp, h, w, stride_bytes, o.stream));

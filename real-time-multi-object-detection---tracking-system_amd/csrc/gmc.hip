@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "track_host.h"
+#include "frame_stage.h"
 
 #include <cmath>
 
@@ -454,7 +455,7 @@ struct rtmodt_gmc {
     int64_t *d_sums = nullptr; double *d_model = nullptr;
     float *d_warp = nullptr, *h_warp = nullptr; int32_t *d_status = nullptr, *h_status = nullptr;        // h_*: pinned
     float4 *d_mbox = nullptr; float *d_mconf = nullptr; int32_t *d_mn = nullptr, *h_mn = nullptr;
-    uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
+    FrameStage stage;                                        // host frames
 };
 
 static void gmc_free_geometry(rtmodt_gmc *g) {
@@ -473,8 +474,7 @@ static int gmc_join(rtmodt_gmc *g) {
 
 // everything a call is refused for, before anything is launched or allocated
 static int gmc_check_geometry(const rtmodt_gmc *g, int h, int w, int pitch, int mem_kind) {
-    RT_CHECK(h >= 1 && w >= 1 && pitch >= 3 * w, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", w, h, pitch);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
+    RT_TRY(check_frame_block(g->S, h, w, pitch, mem_kind, kGmcFrames));      // (the size limits are the estimator's own, below)
     RT_CHECK(w <= GMC_MAX_W && h <= GMC_MAX_H, RTMODT_E_CAPACITY, "frame %dx%d: at most %dx%d", w, h, GMC_MAX_W, GMC_MAX_H);
     const int d = g->cfg.downscale, W0 = w / d, H0 = h / d;
     RT_CHECK((W0 / 16) * (H0 / 16) <= GMC_MAX_BLOCKS, RTMODT_E_CAPACITY, "frame %dx%d at downscale %d has %d blocks: at most %d", w, h, d, (W0 / 16) * (H0 / 16),
@@ -506,22 +506,9 @@ static int gmc_set_geometry(rtmodt_gmc *g, int h, int w) {
 }
 
 // frames of a call -> device pointers (host frames are staged on stream q)
-static int gmc_frames(rtmodt_gmc *g, const uint8_t *const *frames, int count, int h, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
-    const size_t fbytes = (size_t)h * pitch;
-    if (mem_kind == RTMODT_MEM_HOST) {
-        if (g->d_frames_bytes < fbytes * count) {
-            RT_HIP(hipDeviceSynchronize());
-            hipFree(g->d_frames); g->d_frames = nullptr; g->d_frames_bytes = 0;
-            RT_HIP(hipMalloc((void **)&g->d_frames, fbytes * count));
-            g->d_frames_bytes = fbytes * count;
-        }
-        for (int i = 0; i < count; ++i) {
-            RT_HIP(hipMemcpyAsync(g->d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice, q));
-            out->p[i] = g->d_frames + fbytes * i;
-        }
-    } else {
-        for (int i = 0; i < count; ++i) out->p[i] = frames[i];
-    }
+static int gmc_stage(rtmodt_gmc *g, const uint8_t *const *frames, int count, int h, int w, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
+    RT_TRY(g->stage.in(frames, count, h, w, pitch, mem_kind, q, FRAMES_AS_GIVEN));
+    for (int i = 0; i < count; ++i) out->p[i] = g->stage.at(frames, i);
     return RTMODT_OK;
 }
 
@@ -567,12 +554,12 @@ int gmc_enqueue_detector(rtmodt_gmc *g, const DetOutputs &o, const uint8_t *cons
     RT_CHECK(n_frames == o.count, RTMODT_E_INVALID, "%d frames for the detector's batch of %d", n_frames, o.count);
     RT_CHECK(o.count >= 1 && o.count <= g->S, RTMODT_E_INVALID, "%d frames > estimator streams %d", o.count, g->S);
     RT_CHECK(o.stride <= GMC_MAX_BOXES, RTMODT_E_CAPACITY, "detector max_det %d > %d mask boxes", o.stride, GMC_MAX_BOXES);
-    for (int i = 0; i < n_frames; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
+    RT_TRY(check_frame_ptrs(frames, n_frames));
     RT_TRY(gmc_check_geometry(g, h, w, pitch, mem_kind));
     RT_HIP(hipSetDevice(g->device));
     RT_TRY(gmc_set_geometry(g, h, w));
     AppFrames fp{};
-    RT_TRY(gmc_frames(g, frames, o.count, h, pitch, mem_kind, o.stream, &fp));
+    RT_TRY(gmc_stage(g, frames, o.count, h, w, pitch, mem_kind, o.stream, &fp));
     RT_TRY(gmc_run(g, fp, o.count, h, w, pitch, o.box, o.conf, o.n, o.stride, o.stream));
     RT_HIP(hipEventRecord(g->foreign_done, o.stream));
     g->foreign_pending = true;
@@ -600,7 +587,7 @@ void rtmodt_gmc_destroy(rtmodt_gmc *g) {
     for (auto &e : g->ev) if (e) hipEventDestroy(e);
     gmc_free_geometry(g);
     hipFree(g->d_table); hipFree(g->d_coarse); hipFree(g->d_nvalid); hipFree(g->d_scores); hipFree(g->d_bestk); hipFree(g->d_sums); hipFree(g->d_model);
-    hipFree(g->d_warp); hipFree(g->d_status); hipFree(g->d_mbox); hipFree(g->d_mconf); hipFree(g->d_mn); hipFree(g->d_frames);
+    hipFree(g->d_warp); hipFree(g->d_status); hipFree(g->d_mbox); hipFree(g->d_mconf); hipFree(g->d_mn); g->stage.release();
     hipHostFree(g->h_warp); hipHostFree(g->h_status); hipHostFree(g->h_mn);
     if (g->stream) hipStreamDestroy(g->stream);
     delete g;
@@ -665,7 +652,7 @@ int rtmodt_gmc_reset(rtmodt_gmc *g, int stream) {
 int rtmodt_gmc_estimate_batch(rtmodt_gmc *g, const uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind, const float *mask_xyxy,
                               const float *mask_conf, const int32_t *mask_n, float *warp_out, int32_t *status_out) {
     RT_CHECK(g && frames, RTMODT_E_INVALID, "null argument");
-    for (int i = 0; i < g->S; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
+    RT_TRY(check_frame_ptrs(frames, g->S));
     RT_TRY(gmc_check_geometry(g, h, w, stride_bytes, mem_kind));
     bool any = false;
     if (mask_n)
@@ -680,7 +667,7 @@ int rtmodt_gmc_estimate_batch(rtmodt_gmc *g, const uint8_t *const *frames, int h
     RT_TRY(gmc_set_geometry(g, h, w));
     hipStream_t q = g->stream;
     AppFrames fp{};
-    RT_TRY(gmc_frames(g, frames, g->S, h, stride_bytes, mem_kind, q, &fp));
+    RT_TRY(gmc_stage(g, frames, g->S, h, w, stride_bytes, mem_kind, q, &fp));
     const size_t SM = (size_t)g->S * g->cfg.max_boxes;
     for (int s = 0; s < g->S; ++s) g->h_mn[s] = mask_n ? mask_n[s] : 0;
     if (any) {

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "frame_stage.h"
 #include "polygon.h"
 
 #define PV_HD __host__ __device__
@@ -317,12 +318,10 @@ struct rtmodt_heatmap {
     uint32_t *d_grid = nullptr, *d_maxpart = nullptr;
     unsigned long long *d_part = nullptr, *h_part = nullptr;
     uint8_t *d_lut = nullptr;
-    char *h_cmd = nullptr, *d_cmd = nullptr;
-    size_t cmd_cap = 0;
-    uint8_t *d_stage = nullptr;
-    size_t stage_cap = 0;
+    CmdBuf cmd;                         // (every call ends with a synchronize: the pinned half is idle when the next one writes it)
+    FrameStage stage;
     HmStamp *d_gather = nullptr; int32_t *d_gn = nullptr;
-    size_t gather_cap = 0;
+    size_t gather_bytes = 0;
 };
 
 namespace {
@@ -367,20 +366,6 @@ int hm_pack_boxes(const HmStampCfg &sc, const float *xyxy, const int32_t *cls, i
     return RTMODT_OK;
 }
 
-// the pinned / device command buffer pair holds at least `bytes` (every call ends with a synchronize: the pinned buffer is idle)
-int hm_cmd(rtmodt_heatmap *p, hipStream_t q, size_t bytes) {
-    if (bytes <= p->cmd_cap) return RTMODT_OK;
-    const size_t cap = std::max(bytes, 2 * p->cmd_cap);
-    RT_HIP(hipStreamSynchronize(q));
-    if (p->h_cmd) { hipHostFree(p->h_cmd); p->h_cmd = nullptr; }
-    if (p->d_cmd) { hipFree(p->d_cmd); p->d_cmd = nullptr; }
-    p->cmd_cap = 0;
-    RT_HIP(hipHostMalloc((void **)&p->h_cmd, cap, hipHostMallocDefault));
-    RT_HIP(hipMalloc((void **)&p->d_cmd, cap));
-    p->cmd_cap = cap;
-    return RTMODT_OK;
-}
-
 // Everything after the argument checks of an accumulate call: [gather] + accumulate on stream q, then the call is counted.
 // host_stamps: one list per stream (host form); g: the gather launch (device forms).
 int hm_accumulate(rtmodt_heatmap *p, hipStream_t q, const std::vector<std::vector<HmStamp>> *host_stamps, HmGatherArgs *g) {
@@ -397,9 +382,9 @@ int hm_accumulate(rtmodt_heatmap *p, hipStream_t q, const std::vector<std::vecto
         size_t n_stamps = 0;
         for (const auto &v : *host_stamps) n_stamps += v.size();
         const size_t off_stamps = align_up((size_t)S * sizeof(HmStream), 16), bytes = off_stamps + std::max<size_t>(n_stamps, 1) * sizeof(HmStamp);
-        RT_TRY(hm_cmd(p, q, bytes));
-        HmStream *hs = (HmStream *)p->h_cmd;
-        HmStamp *st = (HmStamp *)(p->h_cmd + off_stamps);
+        RT_TRY(p->cmd.reserve(bytes));
+        HmStream *hs = (HmStream *)p->cmd.h;
+        HmStamp *st = (HmStamp *)(p->cmd.h + off_stamps);
         size_t so = 0;
         for (int s = 0; s < S; ++s) {
             const auto &v = (*host_stamps)[s];
@@ -407,8 +392,8 @@ int hm_accumulate(rtmodt_heatmap *p, hipStream_t q, const std::vector<std::vecto
             if (!v.empty()) memcpy(st + so, v.data(), v.size() * sizeof(HmStamp));
             so += v.size();
         }
-        RT_HIP(hipMemcpyAsync(p->d_cmd, p->h_cmd, bytes, hipMemcpyHostToDevice, q));
-        a.streams = (const HmStream *)p->d_cmd; a.stamps = (const HmStamp *)(p->d_cmd + off_stamps);
+        RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, bytes, hipMemcpyHostToDevice, q));
+        a.streams = (const HmStream *)p->cmd.d; a.stamps = (const HmStamp *)(p->cmd.d + off_stamps);
     } else {
         a.stamps = g->out; a.n_dev = g->n_out; a.cap = g->cap;
     }
@@ -430,13 +415,7 @@ template <typename F> int hm_accumulate_view(rtmodt_heatmap *p, int src_device, 
     RT_CHECK(n == p->cfg.n_streams, RTMODT_E_INVALID, "%s has %d streams, the heatmap %d", what, n, p->cfg.n_streams);
     RT_CHECK(cap >= 1 && cap <= HM_MAX_BOXES, RTMODT_E_CAPACITY, "the source holds up to %d boxes per frame (at most %d)", cap, HM_MAX_BOXES);
     RT_HIP(hipSetDevice(p->device));
-    if ((size_t)cap > p->gather_cap) {
-        RT_HIP(hipStreamSynchronize(q));
-        if (p->d_gather) { hipFree(p->d_gather); p->d_gather = nullptr; }
-        p->gather_cap = 0;
-        RT_HIP(hipMalloc((void **)&p->d_gather, (size_t)n * cap * sizeof(HmStamp)));
-        p->gather_cap = cap;
-    }
+    RT_TRY(dev_grow(&p->d_gather, &p->gather_bytes, (size_t)n * cap * sizeof(HmStamp)));
     HmGatherArgs g{};
     g.sc = hm_stamp_cfg(p->cfg, p->cfg.classes ? p->d_classes : nullptr);
     g.h = p->cfg.height; g.w = p->cfg.width; g.cap = cap; g.out = p->d_gather; g.n_out = p->d_gn;
@@ -475,9 +454,9 @@ void rtmodt_heatmap_destroy(rtmodt_heatmap *p) {
     if (!p) return;
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_grid); hipFree(p->d_maxpart); hipFree(p->d_part); hipFree(p->d_lut); hipFree(p->d_cmd); hipFree(p->d_stage);
+    hipFree(p->d_grid); hipFree(p->d_maxpart); hipFree(p->d_part); hipFree(p->d_lut); p->cmd.release(); p->stage.release();
     hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
-    hipHostFree(p->h_cmd); hipHostFree(p->h_part);
+    hipHostFree(p->h_part);
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
@@ -617,10 +596,10 @@ int rtmodt_heatmap_set_colormap(rtmodt_heatmap *p, const uint8_t *lut_bgr) {
 int rtmodt_heatmap_overlay(rtmodt_heatmap *p, uint8_t *const *frames, const int32_t *streams, int n, int h, int w, int stride_bytes, int mem_kind,
                            int alpha, int min_level, uint32_t scale_max) {
     RT_CHECK(p && n >= 0 && (n == 0 || frames), RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
+    RT_TRY(check_mem_kind(mem_kind));                      // (the geometry is the handle's: this entry point words its own refusals)
     RT_CHECK(h == p->cfg.height && w == p->cfg.width, RTMODT_E_INVALID, "frames of %dx%d, the heatmap was created for %dx%d", w, h, p->cfg.width,
              p->cfg.height);
-    RT_CHECK((long long)stride_bytes >= 3LL * w, RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
+    RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     RT_CHECK(alpha >= 0 && alpha <= 256, RTMODT_E_INVALID, "alpha %d outside 0..256", alpha);
     RT_CHECK(min_level >= 1 && min_level <= 255, RTMODT_E_INVALID, "min_level %d outside 1..255", min_level);
     RT_CHECK(n <= 65535, RTMODT_E_CAPACITY, "%d frames in one call (at most 65535)", n);
@@ -633,28 +612,17 @@ int rtmodt_heatmap_overlay(rtmodt_heatmap *p, uint8_t *const *frames, const int3
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
-    const bool host = mem_kind == RTMODT_MEM_HOST;
-    const size_t dpitch = align_up((size_t)3 * w, 16), fbytes = (size_t)h * dpitch;
-    if (host && (size_t)n * fbytes > p->stage_cap) {
-        RT_HIP(hipStreamSynchronize(q));
-        if (p->d_stage) { hipFree(p->d_stage); p->d_stage = nullptr; }
-        p->stage_cap = 0;
-        RT_HIP(hipMalloc((void **)&p->d_stage, (size_t)n * fbytes));
-        p->stage_cap = (size_t)n * fbytes;
-    }
-    RT_TRY(hm_cmd(p, q, (size_t)n * sizeof(HmOvFrame)));
-    HmOvFrame *F = (HmOvFrame *)p->h_cmd;
-    for (int i = 0; i < n; ++i)
-        F[i] = HmOvFrame{(uint64_t)(uintptr_t)(host ? p->d_stage + (size_t)i * fbytes : frames[i]), streams ? streams[i] : i, 0};
-    RT_HIP(hipMemcpyAsync(p->d_cmd, p->h_cmd, (size_t)n * sizeof(HmOvFrame), hipMemcpyHostToDevice, q));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(p->d_stage + (size_t)i * fbytes, dpitch, frames[i], stride_bytes, (size_t)3 * w, h, hipMemcpyHostToDevice, q));
+    RT_TRY(p->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_TIGHT16));
+    RT_TRY(p->cmd.reserve((size_t)n * sizeof(HmOvFrame)));
+    HmOvFrame *F = (HmOvFrame *)p->cmd.h;
+    for (int i = 0; i < n; ++i) F[i] = HmOvFrame{(uint64_t)(uintptr_t)p->stage.at(frames, i), streams ? streams[i] : i, 0};
+    RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, (size_t)n * sizeof(HmOvFrame), hipMemcpyHostToDevice, q));
+    RT_TRY(p->stage.copy_in(frames, q));
     HmOvArgs a{};
-    a.frames = (const HmOvFrame *)p->d_cmd; a.grid = p->d_grid; a.gstride = p->cells; a.gw = p->gw;
+    a.frames = (const HmOvFrame *)p->cmd.d; a.grid = p->d_grid; a.gstride = p->cells; a.gw = p->gw;
     a.cell_shift = p->cfg.cell == 1 ? 0 : p->cfg.cell == 2 ? 1 : p->cfg.cell == 4 ? 2 : p->cfg.cell == 8 ? 3 : 4;
     a.h = h; a.w = w; a.tiles_x = cdiv(w, HM_TW);
-    a.stride = host ? (long long)dpitch : (long long)stride_bytes;
+    a.stride = (long long)p->stage.pitch;
     a.alpha = alpha; a.min_level = min_level; a.scale_max = scale_max;
     a.maxpart = p->d_maxpart; a.lut = p->d_lut;
     const dim3 block(HM_THREADS);
@@ -663,9 +631,7 @@ int rtmodt_heatmap_overlay(rtmodt_heatmap *p, uint8_t *const *frames, const int3
     hipLaunchKernelGGL(heatmap_overlay, dim3((unsigned)(a.tiles_x * cdiv(h, HM_TH)), n), block, 0, q, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(p->ev1, q));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(frames[i], stride_bytes, p->d_stage + (size_t)i * fbytes, dpitch, (size_t)3 * w, h, hipMemcpyDeviceToHost, q));
+    RT_TRY(p->stage.copy_out(frames, q));
     RT_HIP(hipStreamSynchronize(q));
     p->timed = true;
     return RTMODT_OK;
@@ -675,36 +641,19 @@ int rtmodt_heatmap_zone_sums(rtmodt_heatmap *p, int stream, const int32_t *const
     RT_CHECK(p && n >= 0 && (n == 0 || (polygons_xy && n_points && sums)), RTMODT_E_INVALID, "bad argument");
     RT_TRY(hm_check_stream(p, stream));
     RT_CHECK(n <= HM_MAX_POLYS, RTMODT_E_CAPACITY, "%d polygons (at most %d)", n, HM_MAX_POLYS);
-    std::vector<int2> pts;
-    std::vector<int32_t> off(1, 0);
-    std::vector<int4> bbox;
-    for (int z = 0; z < n; ++z) {
-        const int np = n_points[z];
-        RT_CHECK(np >= 0 && (np == 0 || polygons_xy[z]), RTMODT_E_INVALID, "polygon %d: bad polygon", z);
-        RT_CHECK(pts.size() + np <= (size_t)HM_MAX_POINTS, RTMODT_E_CAPACITY, "%zu polygon points (at most %d)", pts.size() + np, HM_MAX_POINTS);
-        int4 b = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
-        for (int k = 0; k < np; ++k) {
-            const int x = polygons_xy[z][2 * k], y = polygons_xy[z][2 * k + 1];
-            pts.push_back(make_int2(x, y));
-            b.x = std::min(b.x, x); b.y = std::min(b.y, y); b.z = std::max(b.z, x); b.w = std::max(b.w, y);
-        }
-        off.push_back((int32_t)pts.size());
-        bbox.push_back(b);
-    }
+    PolyTable T;
+    RT_TRY(T.build(polygons_xy, n_points, n, HM_MAX_POINTS, "polygon"));
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
-    const size_t o_off = align_up(std::max<size_t>(pts.size(), 1) * sizeof(int2), 16), o_box = align_up(o_off + off.size() * 4, 16);
-    const size_t total = o_box + bbox.size() * sizeof(int4);
-    RT_TRY(hm_cmd(p, q, total));
-    if (!pts.empty()) memcpy(p->h_cmd, pts.data(), pts.size() * sizeof(int2));
-    memcpy(p->h_cmd + o_off, off.data(), off.size() * 4);
-    memcpy(p->h_cmd + o_box, bbox.data(), bbox.size() * sizeof(int4));
-    RT_HIP(hipMemcpyAsync(p->d_cmd, p->h_cmd, total, hipMemcpyHostToDevice, q));
+    const size_t total = T.layout();
+    RT_TRY(p->cmd.reserve(total));
+    T.write(p->cmd.h);
+    RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, total, hipMemcpyHostToDevice, q));
     HmZoneArgs a{};
     a.grid = p->d_grid + (long long)stream * p->cells;
     a.gw = p->gw; a.gh = p->gh; a.cell = p->cfg.cell; a.h = p->cfg.height; a.w = p->cfg.width;
-    a.pts = (const int2 *)p->d_cmd; a.off = (const int32_t *)(p->d_cmd + o_off); a.bbox = (const int4 *)(p->d_cmd + o_box);
+    T.view(p->cmd.d, &a);
     a.part = p->d_part;
     hipLaunchKernelGGL(heatmap_zone_sums, dim3(HM_PARTS, n), dim3(HM_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());

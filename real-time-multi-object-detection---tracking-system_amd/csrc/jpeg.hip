@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "common.h"
+#include "frame_stage.h"
 
 namespace rtmodt {
 
@@ -526,23 +527,10 @@ struct rtmodt_jpeg {
     uint32_t *d_ilen = nullptr, *d_ioff = nullptr, *d_sizes = nullptr, *d_fits = nullptr;
     uint64_t *d_ptrs = nullptr, *h_ptrs = nullptr;          // h_*: page-locked
     uint32_t *h_sizes = nullptr;
-    uint8_t *d_stage = nullptr, *d_out = nullptr;           // host frames staged on the device; the scans before they go to the host
-    size_t stage_cap = 0, out_cap = 0;
+    FrameStage stage;                                       // host frames staged on the device
+    uint8_t *d_out = nullptr;                               // the scans before they go to the host
+    size_t out_cap = 0;
 };
-
-namespace {
-
-int grow(rtmodt_jpeg *j, uint8_t *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return RTMODT_OK;
-    RT_HIP(hipStreamSynchronize(j->stream));
-    if (p) { hipFree(p); p = nullptr; }
-    cap = 0;
-    RT_HIP(hipMalloc((void **)&p, bytes));
-    cap = bytes;
-    return RTMODT_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -561,7 +549,7 @@ void rtmodt_jpeg_destroy(rtmodt_jpeg *j) {
     hipSetDevice(j->device);
     if (j->stream) hipStreamSynchronize(j->stream);
     hipFree(j->d_tab); hipFree(j->d_coef); hipFree(j->d_ilen); hipFree(j->d_ioff); hipFree(j->d_sizes); hipFree(j->d_fits);
-    hipFree(j->d_ptrs); hipFree(j->d_stage); hipFree(j->d_out);
+    hipFree(j->d_ptrs); j->stage.release(); hipFree(j->d_out);
     hipHostFree(j->h_ptrs); hipHostFree(j->h_sizes);
     if (j->ev0) hipEventDestroy(j->ev0);
     if (j->ev1) hipEventDestroy(j->ev1);
@@ -613,9 +601,7 @@ int rtmodt_jpeg_create(int device, const rtmodt_jpeg_cfg *cfg, rtmodt_jpeg **out
 int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind, uint8_t *out,
                              size_t slot_bytes, uint32_t *sizes) {
     RT_CHECK(j && n >= 0 && (n == 0 || (frames && out && sizes)), RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    RT_CHECK(h >= 1 && w >= 1 && (long long)stride_bytes >= 3LL * w, RTMODT_E_INVALID, "bad frame geometry %dx%d, stride %d", w, h, stride_bytes);
-    for (int i = 0; i < n; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
+    RT_TRY(check_frames(frames, n, h, w, stride_bytes, mem_kind, kJpegFrames));
     RT_CHECK(n <= j->max_batch && h <= j->max_h && w <= j->max_w, RTMODT_E_CAPACITY,
              "%d frames of %dx%d: the handle was made for %d frames of %dx%d", n, w, h, j->max_batch, j->max_w, j->max_h);
     j->timed = false;
@@ -628,20 +614,16 @@ int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n
     const size_t worst = (size_t)mcus_x * mcus_y * 6 * JP_BLOCK_BYTES + 2 * (size_t)mcus_y;
     const size_t cap = slot_bytes > hdr ? std::min(slot_bytes - hdr, worst) : 0;
     const size_t out_stride = align_up(std::max<size_t>(cap, 16), 16);
-    RT_TRY(grow(j, j->d_out, j->out_cap, (size_t)n * out_stride));
-    const bool host = mem_kind == RTMODT_MEM_HOST;
-    const size_t dpitch = align_up((size_t)3 * w, 16);
-    if (host) RT_TRY(grow(j, j->d_stage, j->stage_cap, (size_t)n * h * dpitch));
+    RT_TRY(dev_grow(&j->d_out, &j->out_cap, (size_t)n * out_stride));
+    RT_TRY(j->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_TIGHT16));
     RT_HIP(hipStreamSynchronize(j->stream));               // the pinned buffers may still feed the previous call's copies
-    for (int i = 0; i < n; ++i) j->h_ptrs[i] = (uint64_t)(uintptr_t)(host ? j->d_stage + (size_t)i * h * dpitch : frames[i]);
+    for (int i = 0; i < n; ++i) j->h_ptrs[i] = (uint64_t)(uintptr_t)j->stage.at(frames, i);
     RT_HIP(hipMemcpyAsync(j->d_ptrs, j->h_ptrs, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, j->stream));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(j->d_stage + (size_t)i * h * dpitch, dpitch, frames[i], stride_bytes, (size_t)3 * w, h, hipMemcpyHostToDevice, j->stream));
+    RT_TRY(j->stage.copy_in(frames, j->stream));
 
     DctArgs da{};
     da.frames = j->d_ptrs; da.tab = j->d_tab; da.coef = j->d_coef;
-    da.stride = host ? (long long)dpitch : (long long)stride_bytes;
+    da.stride = (long long)j->stage.pitch;
     da.coef_frame = (long long)mcus_x * mcus_y * 384;
     da.h = h; da.w = w; da.mcus_x = mcus_x; da.mcus_y = mcus_y;
     CodeArgs ca{};

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "common.h"
+#include "frame_stage.h"
 #include "jpeg_dec_core.h"
 
 namespace rtmodt {
@@ -297,23 +298,10 @@ struct rtmodt_jpegdec {
     uint8_t *h_bytes = nullptr, *d_bytes = nullptr;         // h_*: page-locked
     JdFrame *h_frames = nullptr, *d_frames = nullptr;
     int32_t *h_status = nullptr, *d_status = nullptr;
-    uint8_t *d_marks = nullptr, *d_coef = nullptr, *d_planes = nullptr, *d_stage = nullptr;      // grown on demand
-    size_t marks_cap = 0, coef_cap = 0, planes_cap = 0, stage_cap = 0;
+    uint8_t *d_marks = nullptr, *d_coef = nullptr, *d_planes = nullptr;      // grown on demand
+    size_t marks_cap = 0, coef_cap = 0, planes_cap = 0;
+    FrameStage stage;                                       // host frames are decoded here, rows of 3w bytes
 };
-
-namespace {
-
-int jd_grow(rtmodt_jpegdec *j, uint8_t *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return RTMODT_OK;
-    RT_HIP(hipStreamSynchronize(j->stream));
-    if (p) { hipFree(p); p = nullptr; }
-    cap = 0;
-    RT_HIP(hipMalloc((void **)&p, bytes));
-    cap = bytes;
-    return RTMODT_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -337,7 +325,7 @@ void rtmodt_jpegdec_destroy(rtmodt_jpegdec *j) {
     hipSetDevice(j->device);
     if (j->stream) hipStreamSynchronize(j->stream);
     hipFree(j->d_bytes); hipFree(j->d_frames); hipFree(j->d_status); hipFree(j->d_marks); hipFree(j->d_coef); hipFree(j->d_planes);
-    hipFree(j->d_stage);
+    j->stage.release();
     hipHostFree(j->h_bytes); hipHostFree(j->h_frames); hipHostFree(j->h_status);
     if (j->ev0) hipEventDestroy(j->ev0);
     if (j->ev1) hipEventDestroy(j->ev1);
@@ -385,8 +373,7 @@ int rtmodt_jpegdec_create(int device, const rtmodt_jpegdec_cfg *cfg, rtmodt_jpeg
 int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, const size_t *sizes, int n, uint8_t *const *frames, int h, int w,
                                 int stride_bytes, int mem_kind, int32_t *status) {
     RT_CHECK(j && n >= 0 && (n == 0 || (files && sizes && frames && status)), RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    RT_CHECK(h >= 1 && w >= 1 && (long long)stride_bytes >= 3LL * w, RTMODT_E_INVALID, "bad frame geometry %dx%d, stride %d", w, h, stride_bytes);
+    RT_TRY(check_frame_block(n, h, w, stride_bytes, mem_kind, kJpegFrames));
     for (int i = 0; i < n; ++i) RT_CHECK(files[i] && frames[i], RTMODT_E_INVALID, "file or frame %d is null", i);
     RT_CHECK(n <= j->max_batch && h <= j->max_h && w <= j->max_w, RTMODT_E_CAPACITY,
              "%d frames of %dx%d: the handle was made for %d frames of %dx%d", n, w, h, j->max_batch, j->max_w, j->max_h);
@@ -397,8 +384,7 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(j->device));
     RT_HIP(hipStreamSynchronize(j->stream));               // the pinned buffers may still feed the previous call's copies
-    const bool host = mem_kind == RTMODT_MEM_HOST;
-    const size_t dpitch = (size_t)3 * w;
+    RT_TRY(j->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_TIGHT));      // nothing is copied in: the decoder writes every pixel
     size_t total_bytes = 0, total_slots = 0, total_blocks = 0;
     int max_intervals = 0;
     uint32_t max_blocks = 0;
@@ -418,18 +404,14 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
             max_intervals = std::max(max_intervals, fr.hd.intervals);
             max_blocks = std::max(max_blocks, fr.blocks);
         }
-        fr.dst = (uint64_t)(uintptr_t)(host ? nullptr : frames[i]);
-        fr.dst_pitch = host ? (long long)dpitch : (long long)stride_bytes;
+        fr.dst = (uint64_t)(uintptr_t)j->stage.at(frames, i);
+        fr.dst_pitch = (long long)j->stage.pitch;
         total_bytes += align_up(sizes[i], 16);
     }
     RT_CHECK(total_slots < (1ull << 32), RTMODT_E_CAPACITY, "%zu restart intervals in one call", total_slots);
-    if (host) {
-        RT_TRY(jd_grow(j, j->d_stage, j->stage_cap, (size_t)n * h * dpitch));
-        for (int i = 0; i < n; ++i) j->h_frames[i].dst = (uint64_t)(uintptr_t)(j->d_stage + (size_t)i * h * dpitch);
-    }
-    RT_TRY(jd_grow(j, j->d_marks, j->marks_cap, std::max<size_t>(total_slots, 1) * sizeof(uint32_t)));
-    RT_TRY(jd_grow(j, j->d_coef, j->coef_cap, std::max<size_t>(total_blocks, 1) * 64 * sizeof(int16_t)));
-    RT_TRY(jd_grow(j, j->d_planes, j->planes_cap, std::max<size_t>(total_blocks, 1) * 64));
+    RT_TRY(dev_grow(&j->d_marks, &j->marks_cap, std::max<size_t>(total_slots, 1) * sizeof(uint32_t)));
+    RT_TRY(dev_grow(&j->d_coef, &j->coef_cap, std::max<size_t>(total_blocks, 1) * 64 * sizeof(int16_t)));
+    RT_TRY(dev_grow(&j->d_planes, &j->planes_cap, std::max<size_t>(total_blocks, 1) * 64));
     RT_HIP(hipMemcpyAsync(j->d_bytes, j->h_bytes, std::max<size_t>(total_bytes, 16), hipMemcpyHostToDevice, j->stream));
     RT_HIP(hipMemcpyAsync(j->d_frames, j->h_frames, (size_t)n * sizeof(JdFrame), hipMemcpyHostToDevice, j->stream));
     if (total_blocks) RT_HIP(hipMemsetAsync(j->d_coef, 0, total_blocks * 64 * sizeof(int16_t), j->stream));
@@ -456,10 +438,9 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
     j->last_n = n;
     for (int i = 0; i < n; ++i) {
         status[i] = j->h_status[i];
-        if (host && status[i] == JD_OK)
-            RT_HIP(hipMemcpy2DAsync(frames[i], stride_bytes, j->d_stage + (size_t)i * h * dpitch, dpitch, dpitch, h, hipMemcpyDeviceToHost, j->stream));
+        if (j->stage.host && status[i] == JD_OK) RT_TRY(j->stage.copy_out_one(frames[i], i, j->stream));      // a rejected file leaves its frame as it was
     }
-    if (host) RT_HIP(hipStreamSynchronize(j->stream));
+    if (j->stage.host) RT_HIP(hipStreamSynchronize(j->stream));
     return RTMODT_OK;
 }
 

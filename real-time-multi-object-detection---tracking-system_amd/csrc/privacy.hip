@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "frame_stage.h"
 #include "polygon.h"
 
 #define PV_HD __host__ __device__
@@ -404,13 +405,14 @@ struct rtmodt_privacy {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     char *ppool = nullptr;              // polygon table (device)
+    size_t ppool_cap = 0;
     PolyView pv{};
-    char *h_cmd = nullptr, *d_cmd = nullptr;
-    size_t cmd_cap = 0;
-    uint8_t *d_stage = nullptr, *d_scratch = nullptr, *d_mask = nullptr;
-    size_t stage_cap = 0, scratch_cap = 0, mask_cap = 0;
+    CmdBuf cmd;                         // (every call ends with a synchronize: the pinned half is idle when the next one writes it)
+    FrameStage stage;
+    uint8_t *d_scratch = nullptr, *d_mask = nullptr;
+    size_t scratch_cap = 0, mask_cap = 0;
     PvRect *d_gather = nullptr; int32_t *d_gn = nullptr;
-    size_t gather_frames = 0, gather_cap = 0;
+    size_t gather_bytes = 0, gn_bytes = 0;
 };
 
 namespace {
@@ -448,24 +450,9 @@ int pv_pack_boxes(const PvRegionCfg &rc, const float *xyxy, const int32_t *cls, 
     return RTMODT_OK;
 }
 
-template <typename T> int pv_grow(hipStream_t q, T **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return RTMODT_OK;
-    RT_HIP(hipStreamSynchronize(q));
-    if (*buf) { hipFree(*buf); *buf = nullptr; }
-    *cap = 0;
-    RT_HIP(hipMalloc((void **)buf, need));
-    *cap = need;
-    return RTMODT_OK;
-}
-
 int pv_check_frames(uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind) {
     RT_CHECK(n >= 0 && (n == 0 || frames), RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    RT_CHECK(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (long long)stride_bytes >= 3LL * w, RTMODT_E_INVALID,
-             "bad frame geometry %dx%d, stride %d", w, h, stride_bytes);
-    RT_CHECK(n <= 65535, RTMODT_E_CAPACITY, "%d frames in one call (at most 65535)", n);
-    for (int i = 0; i < n; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-    return RTMODT_OK;
+    return check_frames(frames, n, h, w, stride_bytes, mem_kind, kPaintFrames);
 }
 
 // Everything after the argument checks: stage host frames, send the command buffer, [gather], paint / blur, [commit], copy back.
@@ -476,15 +463,15 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     const rtmodt_privacy_cfg &c = p->cfg;
-    const bool host = mem_kind == RTMODT_MEM_HOST, blur = c.mode == RTMODT_PRIVACY_BLUR;
-    const size_t dpitch = align_up((size_t)3 * w, 16);
-    if (host) RT_TRY(pv_grow(q, &p->d_stage, &p->stage_cap, (size_t)n * h * dpitch));
+    const bool blur = c.mode == RTMODT_PRIVACY_BLUR;
+    RT_TRY(p->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_TIGHT16));
+    const bool host = p->stage.host;
     bool in_place = false;
     for (int i = 0; i < n; ++i) in_place |= host || !dst || dst[i] == src[i];
     const bool scratch = blur && in_place;
 
     PaintArgs a{};
-    a.h = h; a.w = w; a.stride = host ? (long long)dpitch : (long long)stride_bytes;
+    a.h = h; a.w = w; a.stride = (long long)p->stage.pitch;
     a.mode = c.mode; a.cell = c.cell; a.radius = c.radius; a.passes = c.passes;
     a.fill = c.fill_bgr[0] | (uint32_t)c.fill_bgr[1] << 8 | (uint32_t)c.fill_bgr[2] << 16;
     a.tw = PV_TW; a.th = PV_TH;
@@ -495,9 +482,9 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
     a.tiles = (int)tiles;
     a.pv = p->pv;
     if (scratch) {
-        a.spitch = (long long)dpitch; a.sframe = (long long)h * a.spitch;
-        RT_TRY(pv_grow(q, &p->d_scratch, &p->scratch_cap, (size_t)n * h * dpitch));
-        RT_TRY(pv_grow(q, &p->d_mask, &p->mask_cap, (size_t)n * tiles * PV_THREADS));
+        a.spitch = (long long)tight16_pitch(w); a.sframe = (long long)h * a.spitch;      // the blur's scratch copy has the staged layout
+        RT_TRY(dev_grow(&p->d_scratch, &p->scratch_cap, (size_t)n * a.sframe));
+        RT_TRY(dev_grow(&p->d_mask, &p->mask_cap, (size_t)n * tiles * PV_THREADS));
         a.scratch = p->d_scratch; a.maskbuf = p->d_mask;
     }
 
@@ -505,21 +492,12 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
     size_t n_rects = 0;
     if (host_rects) for (const auto &v : *host_rects) n_rects += v.size();
     const size_t off_rects = align_up((size_t)n * sizeof(PvFrame), 16), bytes = off_rects + std::max<size_t>(n_rects, 1) * sizeof(PvRect);
-    if (bytes > p->cmd_cap) {
-        const size_t cap = std::max(bytes, 2 * p->cmd_cap);
-        RT_HIP(hipStreamSynchronize(q));
-        if (p->h_cmd) { hipHostFree(p->h_cmd); p->h_cmd = nullptr; }
-        if (p->d_cmd) { hipFree(p->d_cmd); p->d_cmd = nullptr; }
-        p->cmd_cap = 0;
-        RT_HIP(hipHostMalloc((void **)&p->h_cmd, cap, hipHostMallocDefault));
-        RT_HIP(hipMalloc((void **)&p->d_cmd, cap));
-        p->cmd_cap = cap;
-    }
-    PvFrame *F = (PvFrame *)p->h_cmd;                     // (every call ends with a synchronize: the pinned buffer is idle)
-    PvRect *Rr = (PvRect *)(p->h_cmd + off_rects);
+    RT_TRY(p->cmd.reserve(bytes));
+    PvFrame *F = (PvFrame *)p->cmd.h;
+    PvRect *Rr = (PvRect *)(p->cmd.h + off_rects);
     size_t ro = 0;
     for (int i = 0; i < n; ++i) {
-        uint8_t *s = host ? p->d_stage + (size_t)i * h * dpitch : src[i];
+        uint8_t *s = p->stage.at(src, i);
         uint8_t *d = host ? s : (dst ? dst[i] : src[i]);
         F[i] = PvFrame{(uint64_t)(uintptr_t)s, (uint64_t)(uintptr_t)d, 0, 0, 0};
         if (host_rects) {
@@ -531,19 +509,16 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
             F[i].rect_off = (int64_t)i * g->cap;
         }
     }
-    RT_HIP(hipMemcpyAsync(p->d_cmd, p->h_cmd, bytes, hipMemcpyHostToDevice, q));
-    a.frames = (const PvFrame *)p->d_cmd;
+    RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, bytes, hipMemcpyHostToDevice, q));
+    a.frames = (const PvFrame *)p->cmd.d;
     if (host_rects) {
-        a.rects = (const PvRect *)(p->d_cmd + off_rects);
+        a.rects = (const PvRect *)(p->cmd.d + off_rects);
     } else {
         a.rects = g->out; a.n_dev = g->n_out; a.cap = g->cap;
     }
-    for (int i = 0; i < n; ++i) {
-        if (host)
-            RT_HIP(hipMemcpy2DAsync(p->d_stage + (size_t)i * h * dpitch, dpitch, src[i], stride_bytes, (size_t)3 * w, h, hipMemcpyHostToDevice, q));
-        else if (dst && dst[i] != src[i])
-            RT_HIP(hipMemcpy2DAsync(dst[i], stride_bytes, src[i], stride_bytes, (size_t)3 * w, h, hipMemcpyDeviceToDevice, q));
-    }
+    RT_TRY(p->stage.copy_in(src, q));
+    for (int i = 0; i < n; ++i)
+        if (!host && dst && dst[i] != src[i]) RT_TRY(copy_bgr_rows(dst[i], stride_bytes, src[i], stride_bytes, h, w, hipMemcpyDeviceToDevice, q));
     const dim3 grid((unsigned)tiles, n), block(PV_THREADS);
     RT_HIP(hipEventRecord(p->ev0, q));
     if (g) hipLaunchKernelGGL(privacy_gather, dim3(n), block, 0, q, *g);
@@ -552,10 +527,7 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
     if (scratch) hipLaunchKernelGGL(privacy_commit, grid, block, 0, q, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(p->ev1, q));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(dst ? dst[i] : src[i], stride_bytes, p->d_stage + (size_t)i * h * dpitch, dpitch, (size_t)3 * w, h,
-                                    hipMemcpyDeviceToHost, q));
+    RT_TRY(p->stage.copy_out(dst ? dst : src, q));
     RT_HIP(hipStreamSynchronize(q));
     p->timed = true;
     return RTMODT_OK;
@@ -571,16 +543,8 @@ template <typename F> int pv_apply_view(rtmodt_privacy *p, int src_device, int n
     p->timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
-    if ((size_t)n > p->gather_frames || (size_t)cap > p->gather_cap) {
-        const size_t nf = std::max<size_t>(n, p->gather_frames), nc = std::max<size_t>(cap, p->gather_cap);
-        RT_HIP(hipStreamSynchronize(q));
-        if (p->d_gather) { hipFree(p->d_gather); p->d_gather = nullptr; }
-        if (p->d_gn) { hipFree(p->d_gn); p->d_gn = nullptr; }
-        p->gather_frames = p->gather_cap = 0;
-        RT_HIP(hipMalloc((void **)&p->d_gather, nf * nc * sizeof(PvRect)));
-        RT_HIP(hipMalloc((void **)&p->d_gn, nf * sizeof(int32_t)));
-        p->gather_frames = nf; p->gather_cap = nc;
-    }
+    RT_TRY(dev_grow(&p->d_gather, &p->gather_bytes, (size_t)n * cap * sizeof(PvRect)));
+    RT_TRY(dev_grow(&p->d_gn, &p->gn_bytes, (size_t)n * sizeof(int32_t)));
     GatherArgs g{};
     g.rc = pv_region_cfg(p->cfg, p->cfg.classes ? p->d_classes : nullptr);
     g.h = h; g.w = w; g.cap = cap; g.out = p->d_gather; g.n_out = p->d_gn;
@@ -606,9 +570,8 @@ void rtmodt_privacy_destroy(rtmodt_privacy *p) {
     if (!p) return;
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->ppool); hipFree(p->d_cmd); hipFree(p->d_stage); hipFree(p->d_scratch); hipFree(p->d_mask);
+    hipFree(p->ppool); p->cmd.release(); p->stage.release(); hipFree(p->d_scratch); hipFree(p->d_mask);
     hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
-    hipHostFree(p->h_cmd);
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
@@ -655,41 +618,19 @@ int rtmodt_privacy_create(const rtmodt_privacy_cfg *cfg, rtmodt_privacy **out) {
 int rtmodt_privacy_set_polygons(rtmodt_privacy *p, const int32_t *const *polygons_xy, const int32_t *n_points, int n) {
     RT_CHECK(p && n >= 0 && (n == 0 || (polygons_xy && n_points)), RTMODT_E_INVALID, "bad argument");
     RT_CHECK(n <= PV_MAX_POLYS, RTMODT_E_CAPACITY, "%d privacy polygons (at most %d)", n, PV_MAX_POLYS);
-    std::vector<int2> pts;
-    std::vector<int32_t> off(1, 0);
-    std::vector<int4> bbox;
-    int4 stage = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
-    for (int z = 0; z < n; ++z) {
-        const int np = n_points[z];
-        RT_CHECK(np >= 0 && (np == 0 || polygons_xy[z]), RTMODT_E_INVALID, "polygon %d: bad polygon", z);
-        RT_CHECK(pts.size() + np <= (size_t)PV_MAX_POINTS, RTMODT_E_CAPACITY, "%zu polygon points (at most %d)", pts.size() + np, PV_MAX_POINTS);
-        int4 b = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
-        for (int k = 0; k < np; ++k) {
-            const int x = polygons_xy[z][2 * k], y = polygons_xy[z][2 * k + 1];
-            pts.push_back(make_int2(x, y));
-            b.x = std::min(b.x, x); b.y = std::min(b.y, y); b.z = std::max(b.z, x); b.w = std::max(b.w, y);
-        }
-        off.push_back((int32_t)pts.size());
-        bbox.push_back(b);
-        if (np > 0) {
-            stage.x = std::min(stage.x, b.x); stage.y = std::min(stage.y, b.y); stage.z = std::max(stage.z, b.z); stage.w = std::max(stage.w, b.w);
-        }
-    }
+    PolyTable T;
+    RT_TRY(T.build(polygons_xy, n_points, n, PV_MAX_POINTS, "polygon"));
     RT_HIP(hipSetDevice(p->device));
     RT_HIP(hipDeviceSynchronize());                        // a device form may have queued work that reads the table on another stream
-    if (p->ppool) { hipFree(p->ppool); p->ppool = nullptr; }
     p->pv = PolyView{};
-    if (n == 0 || pts.empty()) return RTMODT_OK;
-    const size_t o_pts = 0, o_off = align_up(pts.size() * sizeof(int2), 16), o_box = align_up(o_off + off.size() * 4, 16);
-    const size_t total = align_up(o_box + bbox.size() * sizeof(int4), 16);
+    if (n == 0 || T.pts.empty()) return RTMODT_OK;
+    const size_t total = T.layout();
     std::vector<char> hostbuf(total, 0);
-    memcpy(hostbuf.data() + o_pts, pts.data(), pts.size() * sizeof(int2));
-    memcpy(hostbuf.data() + o_off, off.data(), off.size() * 4);
-    memcpy(hostbuf.data() + o_box, bbox.data(), bbox.size() * sizeof(int4));
-    RT_HIP(hipMalloc((void **)&p->ppool, total));
+    T.write(hostbuf.data());
+    RT_TRY(dev_grow(&p->ppool, &p->ppool_cap, total));
     RT_HIP(hipMemcpy(p->ppool, hostbuf.data(), total, hipMemcpyHostToDevice));
-    p->pv.pts = (const int2 *)(p->ppool + o_pts); p->pv.off = (const int32_t *)(p->ppool + o_off); p->pv.bbox = (const int4 *)(p->ppool + o_box);
-    p->pv.Z = n; p->pv.n_pts = (int)pts.size(); p->pv.stage = stage;
+    T.view(p->ppool, &p->pv);
+    p->pv.Z = n; p->pv.n_pts = (int)T.pts.size(); p->pv.stage = T.stage;
     return RTMODT_OK;
 }
 

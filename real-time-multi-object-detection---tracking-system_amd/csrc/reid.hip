@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "frame_stage.h"
 
 namespace rtmodt {
 
@@ -517,7 +518,7 @@ struct rtmodt_reid {
     f16 *x1 = nullptr, *tmp[4] = {}, *lvl[4][4] = {}, *x2 = nullptr, *big[2] = {};       // scratch: lvl[level][stream]; big: downsample / pre-pool
     int8_t *desc = nullptr;                                 // standalone embed
     float4 *d_box = nullptr; int32_t *d_n = nullptr;
-    uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;
+    FrameStage stage;                        // host frames of rtmodt_reid_embed
     int last_count = 0, last_mb = 0;
 };
 
@@ -631,7 +632,7 @@ void reid_close(rtmodt_reid *e) {
     hipFree(e->t_trans[0]); hipFree(e->t_trans[1]); hipFree(e->t_conv5); hipFree(e->pooled); hipFree(e->feat); hipFree(e->x1); hipFree(e->x2);
     for (auto p : e->tmp) hipFree(p);
     for (auto &l : e->lvl) for (auto p : l) hipFree(p);
-    hipFree(e->big[0]); hipFree(e->big[1]); hipFree(e->desc); hipFree(e->d_box); hipFree(e->d_n); hipFree(e->d_frames);
+    hipFree(e->big[0]); hipFree(e->big[1]); hipFree(e->desc); hipFree(e->d_box); hipFree(e->d_n); e->stage.release();
     if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
     delete e;
 }
@@ -777,8 +778,7 @@ int rtmodt_reid_embed(rtmodt_reid *e, const uint8_t *const *frames, int n_frames
     RT_CHECK(n_frames >= 0 && n_frames <= e->max_frames, RTMODT_E_CAPACITY, "%d frames > max_frames %d", n_frames, e->max_frames);
     if (n_frames == 0) return RTMODT_OK;
     RT_CHECK(frames && xyxy && n_boxes && desc, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(h >= 1 && w >= 1 && h <= 16384 && w <= 16384 && stride_bytes >= 3 * w, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", w, h, stride_bytes);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
+    RT_TRY(check_frame_block(n_frames, h, w, stride_bytes, mem_kind, kAppFrames));
     RT_CHECK(max_boxes >= 1 && max_boxes <= e->max_boxes, RTMODT_E_CAPACITY, "max_boxes %d: 1..%d", max_boxes, e->max_boxes);
     for (int i = 0; i < n_frames; ++i) {
         RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
@@ -788,21 +788,8 @@ int rtmodt_reid_embed(rtmodt_reid *e, const uint8_t *const *frames, int n_frames
     RT_HIP(hipSetDevice(e->device));
     hipStream_t q = e->stream;
     AppFrames fp{};
-    const size_t fbytes = (size_t)h * stride_bytes;
-    if (mem_kind == RTMODT_MEM_HOST) {
-        if (e->d_frames_bytes < fbytes * n_frames) {
-            RT_HIP(hipStreamSynchronize(q));
-            hipFree(e->d_frames); e->d_frames = nullptr; e->d_frames_bytes = 0;
-            RT_HIP(hipMalloc((void **)&e->d_frames, fbytes * n_frames));
-            e->d_frames_bytes = fbytes * n_frames;
-        }
-        for (int i = 0; i < n_frames; ++i) {
-            RT_HIP(hipMemcpyAsync(e->d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice, q));
-            fp.p[i] = e->d_frames + fbytes * i;
-        }
-    } else {
-        for (int i = 0; i < n_frames; ++i) fp.p[i] = frames[i];
-    }
+    RT_TRY(e->stage.in(frames, n_frames, h, w, stride_bytes, mem_kind, q, FRAMES_AS_GIVEN));
+    for (int i = 0; i < n_frames; ++i) fp.p[i] = e->stage.at(frames, i);
     const size_t nb = (size_t)n_frames * max_boxes;
     RT_HIP(hipMemcpyAsync(e->d_box, xyxy, nb * 16, hipMemcpyHostToDevice, q));
     RT_HIP(hipMemcpyAsync(e->d_n, n_boxes, (size_t)n_frames * 4, hipMemcpyHostToDevice, q));

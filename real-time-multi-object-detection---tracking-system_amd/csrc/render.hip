@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "font_atlas.h"
+#include "frame_stage.h"
 #include "polygon.h"
 
 namespace rtmodt {
@@ -497,29 +498,11 @@ struct rtmodt_renderer {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     char *zpool = nullptr;              // zone table (device)
+    size_t zpool_cap = 0;
     ZoneView zv{};
-    char *h_cmd = nullptr, *d_cmd = nullptr;
-    size_t cmd_cap = 0;
-    uint8_t *d_stage = nullptr;         // host path: frames staged on the device
-    size_t stage_cap = 0;
+    CmdBuf cmd;
+    FrameStage stage;                   // host path: frames staged on the device
 };
-
-namespace {
-
-int grow_cmd(rtmodt_renderer *r, size_t bytes) {
-    if (bytes <= r->cmd_cap) return RTMODT_OK;
-    const size_t cap = std::max(bytes, 2 * r->cmd_cap);
-    RT_HIP(hipStreamSynchronize(r->stream));
-    if (r->h_cmd) { hipHostFree(r->h_cmd); r->h_cmd = nullptr; }
-    if (r->d_cmd) { hipFree(r->d_cmd); r->d_cmd = nullptr; }
-    r->cmd_cap = 0;
-    RT_HIP(hipHostMalloc((void **)&r->h_cmd, cap, hipHostMallocDefault));
-    RT_HIP(hipMalloc((void **)&r->d_cmd, cap));
-    r->cmd_cap = cap;
-    return RTMODT_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -528,9 +511,8 @@ void rtmodt_renderer_destroy(rtmodt_renderer *r) {
     hipSetDevice(r->device);
     if (r->stream) hipStreamSynchronize(r->stream);
     hipFree(r->zpool);
-    hipFree(r->d_cmd);
-    hipFree(r->d_stage);
-    hipHostFree(r->h_cmd);
+    r->cmd.release();
+    r->stage.release();
     if (r->ev0) hipEventDestroy(r->ev0);
     if (r->ev1) hipEventDestroy(r->ev1);
     if (r->stream) hipStreamDestroy(r->stream);
@@ -565,57 +547,36 @@ int rtmodt_renderer_create(int device, const rtmodt_render_cfg *cfg, rtmodt_rend
 int rtmodt_renderer_set_zones(rtmodt_renderer *r, const int32_t *const *polygons_xy, const int32_t *n_points, const char *const *names, int n_zones) {
     RT_CHECK(r && n_zones >= 0 && (n_zones == 0 || (polygons_xy && n_points)), RTMODT_E_INVALID, "bad argument");
     RT_CHECK(n_zones <= RD_MAX_ZONES, RTMODT_E_CAPACITY, "%d zones (at most %d)", n_zones, RD_MAX_ZONES);
-    std::vector<int2> pts;
-    std::vector<int32_t> off(1, 0);
-    std::vector<int4> bbox;
+    PolyTable T;
     std::vector<Prim> nm;
     std::vector<uint8_t> chars;
-    int4 stage = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
-    auto grow = [&](int4 b) {
-        if (b.x > b.z || b.y > b.w) return;
-        stage.x = std::min(stage.x, b.x); stage.y = std::min(stage.y, b.y); stage.z = std::max(stage.z, b.z); stage.w = std::max(stage.w, b.w);
-    };
     for (int z = 0; z < n_zones; ++z) {
         const int np = n_points[z];
-        RT_CHECK(np >= 0 && (np == 0 || polygons_xy[z]), RTMODT_E_INVALID, "zone %d: bad polygon", z);
-        RT_CHECK(pts.size() + np <= (size_t)RD_MAX_POINTS, RTMODT_E_CAPACITY, "%zu polygon points (at most %d)", pts.size() + np, RD_MAX_POINTS);
-        int4 b = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
-        for (int p = 0; p < np; ++p) {
-            const int x = polygons_xy[z][2 * p], y = polygons_xy[z][2 * p + 1];
-            pts.push_back(make_int2(x, y));
-            b.x = std::min(b.x, x); b.y = std::min(b.y, y); b.z = std::max(b.z, x); b.w = std::max(b.w, y);
-        }
-        off.push_back((int32_t)pts.size());
-        bbox.push_back(b);
-        grow(b);
+        RT_TRY(T.add(polygons_xy[z], np, z, RD_MAX_POINTS, "zone"));
         int ax, ay, co = 0, len = 0;
         if (np > 0 && name_anchor(polygons_xy[z], np, ax, ay)) {
             RT_TRY(put_text(names ? names[z] : nullptr, chars, co, len, "zone name"));
         }
         const Prim p = make_text(0, 0xffffffu, len ? ax - 30 : 0, len ? ay : 0, co, len);
         nm.push_back(p);
-        grow(prim_bbox(p));
+        T.enclose(prim_bbox(p));
     }
     RT_HIP(hipSetDevice(r->device));
     RT_HIP(hipStreamSynchronize(r->stream));
-    if (r->zpool) { hipFree(r->zpool); r->zpool = nullptr; }
     r->zv = ZoneView{};
     if (n_zones == 0) return RTMODT_OK;
-    size_t o_pts = 0, o_off = align_up(o_pts + std::max<size_t>(pts.size(), 1) * sizeof(int2), 16);
-    size_t o_box = align_up(o_off + off.size() * 4, 16), o_nm = align_up(o_box + bbox.size() * sizeof(int4), 16);
-    size_t o_ch = align_up(o_nm + nm.size() * sizeof(Prim), 16), total = align_up(o_ch + std::max<size_t>(chars.size(), 1), 16);
+    // the zone names go behind the polygon table: names | chars
+    const size_t o_nm = T.layout(), o_ch = align_up(o_nm + nm.size() * sizeof(Prim), 16), total = align_up(o_ch + std::max<size_t>(chars.size(), 1), 16);
     std::vector<char> host(total, 0);
-    if (!pts.empty()) memcpy(host.data() + o_pts, pts.data(), pts.size() * sizeof(int2));
-    memcpy(host.data() + o_off, off.data(), off.size() * 4);
-    memcpy(host.data() + o_box, bbox.data(), bbox.size() * sizeof(int4));
+    T.write(host.data());
     memcpy(host.data() + o_nm, nm.data(), nm.size() * sizeof(Prim));
     if (!chars.empty()) memcpy(host.data() + o_ch, chars.data(), chars.size());
-    RT_HIP(hipMalloc((void **)&r->zpool, total));
+    RT_TRY(dev_grow(&r->zpool, &r->zpool_cap, total));
     RT_HIP(hipMemcpy(r->zpool, host.data(), total, hipMemcpyHostToDevice));
     ZoneView &v = r->zv;
-    v.pts = (const int2 *)(r->zpool + o_pts); v.off = (const int32_t *)(r->zpool + o_off); v.bbox = (const int4 *)(r->zpool + o_box);
+    T.view(r->zpool, &v);
     v.names = (const Prim *)(r->zpool + o_nm); v.chars = (const uint8_t *)(r->zpool + o_ch);
-    v.Z = n_zones; v.n_pts = (int)pts.size(); v.stage = stage;
+    v.Z = n_zones; v.n_pts = (int)T.pts.size(); v.stage = T.stage;
     return RTMODT_OK;
 }
 
@@ -638,40 +599,26 @@ int rtmodt_render_pack(const rtmodt_render_cfg *cfg, const rtmodt_render_list *l
 int rtmodt_render_batch(rtmodt_renderer *r, uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind,
                         const rtmodt_render_list *lists, int draw_zones, double fps, double latency_ms) {
     RT_CHECK(r && n >= 0 && (n == 0 || frames), RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    RT_CHECK(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (long long)stride_bytes >= 3LL * w, RTMODT_E_INVALID,
-             "bad frame geometry %dx%d, stride %d", w, h, stride_bytes);
-    RT_CHECK(n <= 65535, RTMODT_E_CAPACITY, "%d frames in one call (at most 65535)", n);
-    for (int i = 0; i < n; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
+    RT_TRY(check_frames(frames, n, h, w, stride_bytes, mem_kind, kPaintFrames));
     Packed P;
     RT_TRY(pack_lists(r->cfg, lists, n, draw_zones, fps, latency_ms, P));
     r->timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(r->device));
     // host frames: staged tightly on the device (16-byte aligned rows), drawn there, copied back row by row
-    const size_t dpitch = align_up((size_t)3 * w, 16);
-    const bool host = mem_kind == RTMODT_MEM_HOST;
-    if (host && (size_t)n * h * dpitch > r->stage_cap) {
-        RT_HIP(hipStreamSynchronize(r->stream));
-        if (r->d_stage) { hipFree(r->d_stage); r->d_stage = nullptr; }
-        r->stage_cap = 0;
-        RT_HIP(hipMalloc((void **)&r->d_stage, (size_t)n * h * dpitch));
-        r->stage_cap = (size_t)n * h * dpitch;
-    }
-    for (int i = 0; i < n; ++i) P.frames[i].ptr = (uint64_t)(uintptr_t)(host ? r->d_stage + (size_t)i * h * dpitch : frames[i]);
+    RT_TRY(r->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_TIGHT16));
+    for (int i = 0; i < n; ++i) P.frames[i].ptr = (uint64_t)(uintptr_t)r->stage.at(frames, i);
     CmdHeader H;
     const size_t bytes = cmd_layout(P, H, h, w);
-    RT_TRY(grow_cmd(r, bytes));
+    RT_TRY(r->cmd.reserve(bytes));
     RT_HIP(hipStreamSynchronize(r->stream));               // the pinned buffer may still feed the previous copy
-    cmd_write(P, H, r->h_cmd);
-    RT_HIP(hipMemcpyAsync(r->d_cmd, r->h_cmd, bytes, hipMemcpyHostToDevice, r->stream));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(r->d_stage + (size_t)i * h * dpitch, dpitch, frames[i], stride_bytes, (size_t)3 * w, h, hipMemcpyHostToDevice, r->stream));
+    cmd_write(P, H, r->cmd.h);
+    RT_HIP(hipMemcpyAsync(r->cmd.d, r->cmd.h, bytes, hipMemcpyHostToDevice, r->stream));
+    RT_TRY(r->stage.copy_in(frames, r->stream));
     RenderArgs a{};
-    a.frames = (const FrameRec *)(r->d_cmd + H.off_frames); a.items = (const ItemRec *)(r->d_cmd + H.off_items);
-    a.prims = (const Prim *)(r->d_cmd + H.off_prims); a.chars = (const uint8_t *)(r->d_cmd + H.off_chars);
-    a.h = h; a.w = w; a.tiles_x = cdiv(w, RD_TW); a.stride = host ? (long long)dpitch : (long long)stride_bytes;
+    a.frames = (const FrameRec *)(r->cmd.d + H.off_frames); a.items = (const ItemRec *)(r->cmd.d + H.off_items);
+    a.prims = (const Prim *)(r->cmd.d + H.off_prims); a.chars = (const uint8_t *)(r->cmd.d + H.off_chars);
+    a.h = h; a.w = w; a.tiles_x = cdiv(w, RD_TW); a.stride = (long long)r->stage.pitch;
     a.zv = r->zv;
     const long long tiles = (long long)a.tiles_x * cdiv(h, RD_TH);
     RT_CHECK(tiles <= INT32_MAX, RTMODT_E_INVALID, "frame too large");
@@ -679,9 +626,7 @@ int rtmodt_render_batch(rtmodt_renderer *r, uint8_t *const *frames, int n, int h
     hipLaunchKernelGGL(render_tiles, dim3((unsigned)tiles, n), dim3(RD_THREADS), 0, r->stream, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(r->ev1, r->stream));
-    if (host)
-        for (int i = 0; i < n; ++i)
-            RT_HIP(hipMemcpy2DAsync(frames[i], stride_bytes, r->d_stage + (size_t)i * h * dpitch, dpitch, (size_t)3 * w, h, hipMemcpyDeviceToHost, r->stream));
+    RT_TRY(r->stage.copy_out(frames, r->stream));
     RT_HIP(hipStreamSynchronize(r->stream));
     r->timed = true;
     return RTMODT_OK;

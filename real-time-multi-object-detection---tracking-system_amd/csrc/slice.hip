@@ -26,6 +26,7 @@
 //   Capacities: 64 tiles per frame, I x max_det <= 8192 candidates per frame (the LDS sort), max_frames x I <= 64 (a detector batch).
 #include <vector>
 
+#include "frame_stage.h"
 #include "letterbox_dev.h"
 #include "slice_grid.h"
 
@@ -341,7 +342,7 @@ struct rtmodt_slicer {
     int max_det = 0;
     SlicePlan plan;
     hipStream_t stream = nullptr;            // staging copies + slice_gather; idle before the detector is handed the tile pointers
-    uint8_t *d_stage = nullptr;              // host frames, repacked to pitch 3 * frame_w: [max_frames][frame_h * 3 * frame_w]
+    FrameStage stage;                        // host frames, repacked to pitch 3 * frame_w; sized for max_frames at create
     uint8_t *d_tiles[2] = {nullptr, nullptr};   // the image batch of the two sliced batches that may be in flight
     int32_t *d_tab = nullptr; ResizeTables tabs{};
     float4 *d_sbox = nullptr; int32_t *d_scls = nullptr;      // merge scratch [max_frames][cap]
@@ -381,17 +382,9 @@ static int slicer_run_gather(rtmodt_slicer *s, const uint8_t *const *frames, int
     a.lb = s->plan.lb.g;
     a.t = s->tabs;
     a.out = s->d_tiles[buf];
-    if (mem_kind == RTMODT_MEM_HOST) {
-        const size_t row = (size_t)3 * c.frame_w, per = row * c.frame_h;
-        for (int i = 0; i < n; ++i) {
-            RT_HIP(hipMemcpy2DAsync(s->d_stage + per * i, row, frames[i], (size_t)pitch, row, (size_t)c.frame_h, hipMemcpyHostToDevice, s->stream));
-            a.frames.p[i] = s->d_stage + per * i;
-        }
-        a.pitch = (int)row;
-    } else {
-        for (int i = 0; i < n; ++i) a.frames.p[i] = frames[i];
-        a.pitch = pitch;
-    }
+    RT_TRY(s->stage.in(frames, n, c.frame_h, c.frame_w, pitch, mem_kind, s->stream, FRAMES_TIGHT));
+    for (int i = 0; i < n; ++i) a.frames.p[i] = s->stage.at(frames, i);
+    a.pitch = (int)s->stage.pitch;
     RT_HIP(hipEventRecord(s->g0, s->stream));
     RT_TRY(launch_slice_gather(a, n, s->stream));
     RT_HIP(hipEventRecord(s->g1, s->stream));
@@ -400,13 +393,12 @@ static int slicer_run_gather(rtmodt_slicer *s, const uint8_t *const *frames, int
     return RTMODT_OK;
 }
 
-static int check_frames(const rtmodt_slicer *s, const uint8_t *const *frames, int n, int pitch, int mem_kind) {
+static int slicer_check_frames(const rtmodt_slicer *s, const uint8_t *const *frames, int n, int pitch, int mem_kind) {
     RT_CHECK(s && frames, RTMODT_E_INVALID, "null argument");
     RT_CHECK(n >= 1 && n <= s->cfg.max_frames, RTMODT_E_INVALID, "n %d outside [1, max_frames %d]", n, s->cfg.max_frames);
-    RT_CHECK(pitch >= 3 * s->cfg.frame_w, RTMODT_E_INVALID, "pitch %d < 3 x frame_w %d", pitch, s->cfg.frame_w);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    for (int i = 0; i < n; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-    return RTMODT_OK;
+    RT_CHECK(pitch_holds(pitch, s->cfg.frame_w), RTMODT_E_INVALID, "pitch %d < 3 x frame_w %d", pitch, s->cfg.frame_w);      // (h and w are the handle's)
+    RT_TRY(check_mem_kind(mem_kind));
+    return check_frame_ptrs(frames, n);
 }
 
 extern "C" {
@@ -442,7 +434,7 @@ void rtmodt_slicer_destroy(rtmodt_slicer *s) {
     }
     if (s->g0) hipEventDestroy(s->g0);
     if (s->g1) hipEventDestroy(s->g1);
-    hipFree(s->d_stage); hipFree(s->d_tiles[0]); hipFree(s->d_tiles[1]); hipFree(s->d_tab); hipFree(s->d_sbox); hipFree(s->d_scls);
+    s->stage.release(); hipFree(s->d_tiles[0]); hipFree(s->d_tiles[1]); hipFree(s->d_tab); hipFree(s->d_sbox); hipFree(s->d_scls);
     if (s->stream) hipStreamDestroy(s->stream);
     delete s;
 }
@@ -453,7 +445,7 @@ static int slicer_create_impl(rtmodt_slicer *s) {
     RT_HIP(hipSetDevice(c.device));
     RT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     RT_HIP(hipEventCreate(&s->g0)); RT_HIP(hipEventCreate(&s->g1));
-    RT_HIP(hipMalloc((void **)&s->d_stage, (size_t)c.max_frames * c.frame_h * c.frame_w * 3));
+    RT_TRY(s->stage.reserve((size_t)c.max_frames * c.frame_h * c.frame_w * 3));      // max_frames in the FRAMES_TIGHT layout: every call fits
     const size_t batch_bytes = (size_t)c.max_frames * p.I * p.img_bytes;
     for (int b = 0; b < 2; ++b) RT_HIP(hipMalloc((void **)&s->d_tiles[b], batch_bytes + 256));      // (slack: a reader may take the last row in wide loads)
     if (c.overview && p.lb.g.resize) {
@@ -504,7 +496,7 @@ int rtmodt_slicer_info(rtmodt_slicer *s, int32_t *n_tiles, int32_t *images_per_f
 }
 
 int rtmodt_slicer_gather(rtmodt_slicer *s, const uint8_t *const *frames, int n, int pitch, int mem_kind, uint8_t *tiles_out_host) {
-    RT_TRY(check_frames(s, frames, n, pitch, mem_kind));
+    RT_TRY(slicer_check_frames(s, frames, n, pitch, mem_kind));
     RT_CHECK(tiles_out_host, RTMODT_E_INVALID, "null argument");
     RT_CHECK(s->pending == 0, RTMODT_E_INVALID, "gather with %d sliced batches in flight: fetch them first", s->pending);
     RT_HIP(hipSetDevice(s->cfg.device));
@@ -563,7 +555,7 @@ int rtmodt_slice_merge(int device, const rtmodt_slice_cfg *cfg, int max_det, int
 
 int rtmodt_slicer_enqueue(rtmodt_slicer *s, rtmodt_detector *det, const uint8_t *const *frames, int n, int pitch, int mem_kind) {
     RT_CHECK(det, RTMODT_E_INVALID, "null argument");
-    RT_TRY(check_frames(s, frames, n, pitch, mem_kind));
+    RT_TRY(slicer_check_frames(s, frames, n, pitch, mem_kind));
     RT_CHECK(s->pending < 2, RTMODT_E_INVALID, "two sliced batches already in flight: fetch before enqueueing more");
     const SlicePlan &p = s->plan;
     DetLimits lim;

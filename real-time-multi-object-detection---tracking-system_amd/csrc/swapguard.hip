@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "frame_stage.h"
 #include "lap.h"
 #include "track_layout.h"
 
@@ -389,7 +390,7 @@ struct rtmodt_swapguard {
     rtmodt_swap_event *ev = nullptr; int32_t *ev_n = nullptr;
     char *h_pin = nullptr;                // pinned mirror of the event block (records, counts per stream) + meta
     size_t ev_bytes = 0;
-    uint8_t *d_frames = nullptr; size_t d_frames_bytes = 0;      // host frames are staged here
+    FrameStage stage;                     // host frames are staged here
     std::vector<int32_t> iota;            // 0, 1, 2, ...: the host list is passed as it is
 };
 
@@ -433,25 +434,10 @@ SgArgs sg_args(rtmodt_swapguard *g, int64_t frame_id) {
 }
 
 // frames of a call -> device pointers (host frames are staged on stream q)
-int sg_frames(rtmodt_swapguard *g, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
-    RT_CHECK(fh >= 1 && fw >= 1 && fh <= 16384 && fw <= 16384 && pitch >= 3 * fw, RTMODT_E_INVALID, "bad frame geometry %dx%d, pitch %d", fw, fh, pitch);
-    RT_CHECK(mem_kind == RTMODT_MEM_HOST || mem_kind == RTMODT_MEM_DEVICE, RTMODT_E_INVALID, "mem_kind %d", mem_kind);
-    for (int i = 0; i < count; ++i) RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-    const size_t fbytes = (size_t)fh * pitch;
-    if (mem_kind == RTMODT_MEM_HOST) {
-        if (g->d_frames_bytes < fbytes * count) {
-            RT_HIP(hipStreamSynchronize(q));
-            hipFree(g->d_frames); g->d_frames = nullptr; g->d_frames_bytes = 0;
-            RT_HIP(hipMalloc((void **)&g->d_frames, fbytes * count));
-            g->d_frames_bytes = fbytes * count;
-        }
-        for (int i = 0; i < count; ++i) {
-            RT_HIP(hipMemcpyAsync(g->d_frames + fbytes * i, frames[i], fbytes, hipMemcpyHostToDevice, q));
-            out->p[i] = g->d_frames + fbytes * i;
-        }
-    } else {
-        for (int i = 0; i < count; ++i) out->p[i] = frames[i];
-    }
+int sg_stage(rtmodt_swapguard *g, const uint8_t *const *frames, int count, int fh, int fw, int pitch, int mem_kind, hipStream_t q, AppFrames *out) {
+    RT_TRY(check_frames(frames, count, fh, fw, pitch, mem_kind, kAppFrames));
+    RT_TRY(g->stage.in(frames, count, fh, fw, pitch, mem_kind, q, FRAMES_AS_GIVEN));
+    for (int i = 0; i < count; ++i) out->p[i] = g->stage.at(frames, i);
     return RTMODT_OK;
 }
 
@@ -530,7 +516,7 @@ void rtmodt_swapguard_destroy(rtmodt_swapguard *g) {
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
     for (auto &e : g->ev_t) if (e) hipEventDestroy(e);
-    hipFree(g->pool); hipFree(g->d_frames);
+    hipFree(g->pool); g->stage.release();
     hipHostFree(g->h_pin);
     if (g->stream) hipStreamDestroy(g->stream);
     delete g;
@@ -587,7 +573,7 @@ int rtmodt_swapguard_process(rtmodt_swapguard *g, int stream, const int64_t *tra
     RT_HIP(hipSetDevice(g->device));
     hipStream_t q = g->stream;
     AppFrames fp{};
-    RT_TRY(sg_frames(g, &frame, 1, h, w, stride_bytes, mem_kind, q, &fp));
+    RT_TRY(sg_stage(g, &frame, 1, h, w, stride_bytes, mem_kind, q, &fp));
     const size_t o = (size_t)stream * g->Mc;
     if (n) {
         RT_HIP(hipMemcpyAsync(g->s_ids + o, track_ids, (size_t)n * 8, hipMemcpyHostToDevice, q));
@@ -616,7 +602,7 @@ int rtmodt_swapguard_process_tracker(rtmodt_swapguard *g, rtmodt_tracker *trk, c
     RT_HIP(hipSetDevice(g->device));
     hipStream_t q = v.stream;                              // the stream the tracker's last update ran on: ordered after it
     AppFrames fp{};
-    RT_TRY(sg_frames(g, frames, v.n_streams, h, w, stride_bytes, mem_kind, q, &fp));
+    RT_TRY(sg_stage(g, frames, v.n_streams, h, w, stride_bytes, mem_kind, q, &fp));
     RT_HIP(hipEventRecord(g->ev_t[0], q));
     SgGatherArgs ga{v.states, v.meta, v.max_tracks, report_tsu, g->Mc, g->g_box, g->g_src, g->g_n, g->d_meta};
     hipLaunchKernelGGL(swapguard_gather, dim3(v.n_streams), dim3(SG_THREADS), 0, q, ga);

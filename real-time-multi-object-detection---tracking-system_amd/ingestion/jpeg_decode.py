@@ -70,15 +70,7 @@ class JpegDecoder:
         if isinstance(out, _ffi.DeviceBuffer):
             if mem_kind not in (None, _ffi.MEM_DEVICE):
                 raise ValueError("a DeviceBuffer is device memory")
-            if height is None or width is None:
-                raise ValueError("device frames need height and width")
-            h, w = int(height), int(width)
-            st = 3 * w if stride is None else int(stride)
-            if h < 1 or w < 1 or st < 3 * w:
-                raise ValueError(f"bad frame geometry {w}x{h}, stride {st}")
-            if offset < 0 or (n and offset + (n - 1) * h * st + (h - 1) * st + 3 * w > out.nbytes):
-                raise ValueError(f"{n} frames of {w}x{h} (stride {st}) from offset {offset} overrun the {out.nbytes}-byte buffer")
-            ptrs, mem = [out.ptr + offset + i * h * st for i in range(n)], _ffi.MEM_DEVICE
+            rows = out
         else:
             if mem_kind not in (None, _ffi.MEM_HOST):
                 raise ValueError("device frames are passed as a _ffi.DeviceBuffer")
@@ -90,12 +82,10 @@ class JpegDecoder:
                     raise JpegDecodeError(info.status, info.message.decode(errors="replace"))
                 out = np.zeros((n, info.h, info.w, 3), np.uint8)
             if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 4 or out.shape[0] < n or out.shape[3] != 3 \
-                    or out.strides[3] != 1 or out.strides[2] != 3 or out.strides[1] < 3 * out.shape[2] or not out.flags.writeable:
-                raise ValueError("out is a writable (n, h, w, 3) uint8 array with packed pixels and a row pitch >= 3w")
-            h, w, st = out.shape[1], out.shape[2], out.strides[1]
-            if h < 1 or w < 1:
-                raise ValueError(f"empty frames {out.shape}")
-            ptrs, mem = [out[i].ctypes.data for i in range(n)], _ffi.MEM_HOST
+                    or out.shape[1] < 1 or out.shape[2] < 1:
+                raise ValueError(f"out is a writable (n, h, w, 3) uint8 array of non-empty frames, got {getattr(out, 'shape', type(out))}")
+            rows = list(out[:n])                          # frame i as an (h, w, 3) view: the row pitch is out.strides[1]
+        ptrs, h, w, st, mem, _ = _ffi.batch_frames(rows, n, height=height, width=width, stride=stride, offset=offset, strict=True)
         if n == 0:
             return out, np.zeros(0, np.int32)
         biggest = max(len(f) for f in files)

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi
-from .privacy import PrivacyMask, boxes_of
+from .privacy import boxes_of
 
 FOOTPRINTS = {"box": 0, "disc": 1, "foot": 2}
 
@@ -140,7 +140,7 @@ class Heatmap:
         ``_ffi.DeviceBuffer`` holding the frames one after another from ``offset``, rows ``stride`` bytes apart.  Frame i shows
         the grid of ``streams[i]``; None: one frame per stream, in order."""
         n = self.n_streams if streams is None else len(streams)
-        ptrs, h, w, st, mem = PrivacyMask._frames(frames, n, self.height, self.width, stride, offset, writable=True)
+        ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=self.height, width=self.width, stride=stride, offset=offset)
         if n == 0:
             return frames
         fp = (C.c_void_p * n)(*ptrs)

@@ -58,28 +58,8 @@ class JpegEncoder:
         ``3 * width``; ``count`` defaults to the frames that fit behind ``offset``), read where they are.  ``slot_bytes``: the
         room per file in the first attempt (default: header + ``h * w * 3 / 2``); a file that needs more is encoded again with
         the size the library reported."""
-        if isinstance(frames, _ffi.DeviceBuffer):
-            if height is None or width is None:
-                raise ValueError("device frames need height and width")
-            h, w = int(height), int(width)
-            st = 3 * w if stride is None else int(stride)
-            if h < 1 or w < 1 or st < 3 * w:
-                raise ValueError(f"bad frame geometry {w}x{h}, stride {st}")
-            n = (frames.nbytes - offset + st - 3 * w) // (h * st) if count is None else int(count)
-            if offset < 0 or n < 0 or (n and offset + (n - 1) * h * st + (h - 1) * st + 3 * w > frames.nbytes):
-                raise ValueError(f"{n} frames of {w}x{h} (stride {st}) from offset {offset} overrun the {frames.nbytes}-byte buffer")
-            ptrs = [frames.ptr + offset + i * h * st for i in range(n)]
-            mem = _ffi.MEM_DEVICE
-        else:
-            n = len(frames)
-            if n == 0:
-                return []
-            h, w, st = self._host_geometry(frames[0])
-            for f in frames[1:]:
-                if self._host_geometry(f) != (h, w, st):
-                    raise ValueError("every frame of a batch must have one shape and row stride")
-            ptrs = [f.ctypes.data for f in frames]
-            mem = _ffi.MEM_HOST
+        ptrs, h, w, st, mem, n = _ffi.batch_frames(frames, count if isinstance(frames, _ffi.DeviceBuffer) else None, height=height, width=width,
+                                                   stride=stride, offset=offset, writable=False, strict=True)
         if n == 0:
             return []
         if h > self._max[0] or w > self._max[1] or n > self._max[2]:      # a larger frame or batch: a larger handle
@@ -128,16 +108,6 @@ class JpegEncoder:
         h = C.c_void_p()
         _ffi.check(_ffi.lib().rtmodt_jpeg_create(self._device, C.byref(cfg), C.byref(h)))
         self._h = h
-
-    @staticmethod
-    def _host_geometry(f: np.ndarray):
-        if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-            raise ValueError("a frame is an H x W x 3 uint8 array")
-        if f.shape[0] < 1 or f.shape[1] < 1:
-            raise ValueError(f"empty frame {f.shape}")
-        if f.strides[1] != 3 or f.strides[2] != 1 or (f.shape[0] > 1 and f.strides[0] < 3 * f.shape[1]):
-            raise ValueError(f"frame rows must be packed BGR pixels (strides {f.strides})")
-        return f.shape[0], f.shape[1], max(f.strides[0], 3 * f.shape[1])
 
 
 def multipart_chunk(jpeg_bytes: bytes, boundary: bytes = b"frame") -> bytes:

@@ -138,10 +138,10 @@ class PrivacyMask:
         (same kind, same geometry; a device buffer from ``out_offset``): receives the masked frames and ``frames`` stays
         clean; None: in place.  Returns ``out`` or ``frames``."""
         n = len(tracks_per_frame)
-        ptrs, h, w, st, mem = self._frames(frames, n, height, width, stride, offset, writable=out is None)
+        ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=height, width=width, stride=stride, offset=offset, writable=out is None)
         dp = None
         if out is not None:
-            optrs, oh, ow, ost, omem = self._frames(out, n, height, width, stride, out_offset, writable=True)
+            optrs, oh, ow, ost, omem, _ = _ffi.batch_frames(out, n, height=height, width=width, stride=stride, offset=out_offset)
             if n and (oh, ow, ost, omem) != (h, w, st, mem):
                 raise ValueError("out must have the frames' kind, shape and row stride")
             dp = (C.c_void_p * max(n, 1))(*optrs)
@@ -169,7 +169,7 @@ class PrivacyMask:
             raise TypeError(f"apply_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; "
                             f"hand the tracks of a {type(tracker).__name__} over as a list: apply(frame, tracks)")
         n = core.n_streams
-        ptrs, h, w, st, mem = self._frames(frames, n, height, width, stride, offset, writable=True)
+        ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=height, width=width, stride=stride, offset=offset)
         fp = (C.c_void_p * max(n, 1))(*ptrs)
         L = _ffi.lib()
         if isinstance(core, _ByteTrackCore):
@@ -189,7 +189,7 @@ class PrivacyMask:
         """Masks the first ``len(frames)`` (``count`` for a device buffer) frames of ``detector``'s newest batch in place with every
         detection of that batch, read from its device-resident outputs; returns ``frames``."""
         n = int(count) if count is not None else (1 if isinstance(frames, _ffi.DeviceBuffer) else len(frames))
-        ptrs, h, w, st, mem = self._frames(frames, n, height, width, stride, offset, writable=True)
+        ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=height, width=width, stride=stride, offset=offset)
         fp = (C.c_void_p * max(n, 1))(*ptrs)
         _ffi.check(_ffi.lib().rtmodt_privacy_apply_detector(self._h, detector.model.handle, fp, n, h, w, st, mem))
         return frames
@@ -210,33 +210,3 @@ class PrivacyMask:
             self.close()
         except Exception:
             pass
-
-    # ------------------------------------------------------------------ internals
-    @staticmethod
-    def _frames(frames, n, height, width, stride, offset, writable):
-        """-> (addresses, h, w, row stride, mem_kind) of ``n`` frames."""
-        if isinstance(frames, _ffi.DeviceBuffer):
-            if height is None or width is None:
-                raise ValueError("device frames need height and width")
-            h, w = int(height), int(width)
-            st = 3 * w if stride is None else int(stride)
-            if n and (offset < 0 or offset + (n - 1) * h * st + (h - 1) * st + 3 * w > frames.nbytes):
-                raise ValueError(f"{n} frames of {w}x{h} (stride {st}) from offset {offset} overrun the {frames.nbytes}-byte buffer")
-            return [frames.ptr + offset + i * h * st for i in range(n)], h, w, st, _ffi.MEM_DEVICE
-        if len(frames) != n:
-            raise ValueError(f"{len(frames)} frames, {n} expected")
-        if n == 0:
-            return [], 0, 0, 0, _ffi.MEM_HOST
-        geo = None
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError("a frame is an H x W x 3 uint8 array")
-            if f.strides[1] != 3 or f.strides[2] != 1 or f.strides[0] < 3 * f.shape[1]:
-                raise ValueError(f"frame rows must be packed BGR pixels (strides {f.strides})")
-            if writable and not f.flags.writeable:
-                raise ValueError("the frame is read-only; it is masked in place")
-            g = (f.shape[0], f.shape[1], f.strides[0])
-            if geo is not None and g != geo:
-                raise ValueError("every frame of a batch must have one shape and row stride")
-            geo = g
-        return [f.ctypes.data for f in frames], geo[0], geo[1], geo[2], _ffi.MEM_HOST

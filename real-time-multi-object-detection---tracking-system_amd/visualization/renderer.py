@@ -69,27 +69,9 @@ class FrameRenderer:
 
         ``frames``: a list of host arrays of one shape and row stride, or a ``_ffi.DeviceBuffer`` holding the frames one after
         another (frame i at ``offset + i * height * stride``; ``stride`` defaults to ``3 * width``), drawn where they are."""
-        n = len(tracks_per_frame)
-        if isinstance(frames, _ffi.DeviceBuffer):
-            if height is None or width is None:
-                raise ValueError("device frames need height and width")
-            h, w = int(height), int(width)
-            st = 3 * w if stride is None else int(stride)
-            if n and (offset < 0 or offset + (n - 1) * h * st + (h - 1) * st + 3 * w > frames.nbytes):
-                raise ValueError(f"{n} frames of {w}x{h} (stride {st}) from offset {offset} overrun the {frames.nbytes}-byte buffer")
-            ptrs = [frames.ptr + offset + i * h * st for i in range(n)]
-            mem = _ffi.MEM_DEVICE
-        else:
-            if len(frames) != n:
-                raise ValueError(f"{len(frames)} frames, {n} track lists")
-            if n == 0:
-                return frames
-            h, w, st = self._host_geometry(frames[0])
-            for f in frames[1:]:
-                if self._host_geometry(f) != (h, w, st):
-                    raise ValueError("every frame of a batch must have one shape and row stride")
-            ptrs = [f.ctypes.data for f in frames]
-            mem = _ffi.MEM_HOST
+        ptrs, h, w, st, mem, n = _ffi.batch_frames(frames, len(tracks_per_frame), height=height, width=width, stride=stride, offset=offset)
+        if n == 0 and mem == _ffi.MEM_HOST:
+            return frames
         if self._cfg_key() != self._key:                  # a show_* flag or trail_length changed since the handle was made
             self.close()
             self._open()
@@ -149,16 +131,6 @@ class FrameRenderer:
             cfg.palette_bgr = self._palette.ctypes.data_as(C.POINTER(C.c_uint8))
             cfg.n_palette = len(self._palette)
         return cfg
-
-    @staticmethod
-    def _host_geometry(f: np.ndarray):
-        if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-            raise ValueError("a frame is an H x W x 3 uint8 array")
-        if f.strides[1] != 3 or f.strides[2] != 1 or f.strides[0] < 3 * f.shape[1]:
-            raise ValueError(f"frame rows must be packed BGR pixels (strides {f.strides})")
-        if not f.flags.writeable:
-            raise ValueError("the frame is read-only; render draws in place")
-        return f.shape[0], f.shape[1], f.strides[0]
 
     def _marshal(self, tracks: Sequence, keep: list):
         return marshal_tracks(tracks, self.trail_length, keep)
