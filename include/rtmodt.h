@@ -1237,6 +1237,81 @@ int rtmodt_heatmap_reset(rtmodt_heatmap *h, int stream);
 /* Device time (ms, HIP events around the launches) of the last accumulate or overlay call that launched.  PARITY UNPINNED. */
 int rtmodt_heatmap_last_ms(rtmodt_heatmap *h, float *kernel_ms);
 
+/* ---- motion detection: a background model per stream tells still frames from moving ones ------------------------------------ */
+/* The reference drops frames blind to content (design document B.1) and offers a smaller model or input against a low frame rate
+ * (G.1 row 2, G.3); it has nothing that looks at the pixels.  PARITY UNPINNED throughout: no counterpart in the reference, no
+ * OpenCV BackgroundSubtractorMOG2 and no Frigate to compare with, no default validated on real footage.  PINNED, exactly, against
+ * tests/motion_ref.py: the model, the mask, every count, the regions and the status.  csrc/motion_model.h states the per-cell
+ * rules, csrc/motion.hip's header the mask and the regions; all of it is integer arithmetic.  A handle holds, per stream, bg and
+ * dev (unsigned 8.8 fixed point) for each cell of a ceil(height / scale) x ceil(width / scale) luma grid, frames_seen, the last
+ * mask and the last block grid. */
+#define RTMODT_MOTION_WARMUP 0          /* frames_seen < warmup at entry: the model learns, nothing is foreground                  */
+#define RTMODT_MOTION_STILL 1           /* no region                                                                               */
+#define RTMODT_MOTION_MOTION 2          /* at least one region                                                                     */
+#define RTMODT_MOTION_SCENE_CHANGE 3    /* 1000 * n_raw >= scene_pm * cells: covered, moved, lights switched; the model restarts   */
+typedef struct rtmodt_motion rtmodt_motion;
+typedef struct rtmodt_motion_cfg {
+    int32_t streams;            /* 1..1024                                                                                      */
+    int32_t height, width;      /* the frame size, 1..32768 each; the grid at most 2^24 cells, all streams 2^28                 */
+    int32_t scale;              /* 1, 2, 4 or 8 pixels per cell side                                                            */
+    int32_t learn_shift;        /* 1..8: bg += (Yc * 256 - bg) >> learn_shift for the cells that are not raw foreground         */
+    int32_t learn_shift_fg;     /* 0: raw foreground never updates the model; else learn_shift..12                              */
+    int32_t threshold;          /* 1..255 luma levels                                                                           */
+    int32_t dev_gain;           /* 0..8: raw = |d| > threshold * 256 + dev_gain * dev                                           */
+    int32_t min_neighbors;      /* 1..9 raw cells in the 3 x 3 neighbourhood (the cell included) for a raw cell to be kept      */
+    int32_t dilate;             /* 0..3 cells (Chebyshev)                                                                       */
+    int32_t warmup;             /* 1..255 frames                                                                                */
+    int32_t scene_pm;           /* 1..1000 per mille of the cells                                                               */
+    int32_t min_area;           /* >= 1 cells for a component to be a region                                                    */
+    int32_t max_regions;        /* 1..256 regions stored per frame                                                              */
+    int32_t block;              /* 4, 8, 16 or 32 cells per side of a block of the activity grid                                */
+    int32_t device;
+} rtmodt_motion_cfg;
+typedef struct rtmodt_motion_result {
+    int32_t status;             /* RTMODT_MOTION_*                                                                              */
+    int32_t stream;
+    int32_t frames_seen;        /* after the call: 0 after a SCENE_CHANGE                                                       */
+    uint32_t n_raw, n_fg;       /* raw foreground cells; mask cells                                                             */
+    int32_t n_regions;          /* stored: min(n_regions_total, max_regions)                                                    */
+    int32_t n_regions_total;
+    int32_t bbox[4];            /* of the mask, pixels x0, y0, x1, y1 (x1, y1 exclusive); all zero when the mask is empty       */
+    int32_t reserved;
+    uint64_t luma_sum;          /* the sum of the cells' luma                                                                   */
+} rtmodt_motion_result;
+/* Host only: 1 stream, height and width 0 (the caller sets them), scale 4, learn_shift 4, learn_shift_fg 8, threshold 12, dev_gain
+ * 2, min_neighbors 3, dilate 1, warmup 8, scene_pm 600, min_area 4, max_regions 32, block 16, device 0.  No default has been
+ * validated on real footage.  PARITY UNPINNED. */
+void rtmodt_motion_default_cfg(rtmodt_motion_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range is RTMODT_E_INVALID, a grid above 2^24 cells (or
+ * 2^28 over all streams) RTMODT_E_CAPACITY.  Every model starts with frames_seen 0.  PARITY UNPINNED. */
+int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_motion_destroy(rtmodt_motion *m);
+/* One frame for each of n distinct streams: frame i (BGR24, height x width as created, row pitch stride_bytes >= 3w, host or
+ * device memory by mem_kind, read only) updates the model of streams[i] (streams == NULL: stream i, and n must be the stream
+ * count).  results[i] and regions[i][max_regions][5] (x0, y0, x1, y1 in pixels, area in cells; the entries past n_regions are zero)
+ * describe it.  A frame size other than the handle's, a stream outside 0..streams - 1 or named twice, a null frame and n above the
+ * stream count are RTMODT_E_INVALID with nothing launched.  Seven launches, whatever the frames show; all results come back in one
+ * copy.  Streams the call does not name keep their state.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_motion_process(rtmodt_motion *m, const uint8_t *const *frames, const int32_t *streams, int n, int height, int width,
+                          int stride_bytes, int mem_kind, rtmodt_motion_result *results, int32_t *regions);
+/* The mask of the stream's last frame, uint8[gh][gw] of 0 / 1 (all zero before the first).  PARITY UNPINNED. */
+int rtmodt_motion_read_mask(rtmodt_motion *m, int stream, uint8_t *out);
+/* The mask cells per block x block group of cells, uint32[ceil(gh / block)][ceil(gw / block)].  PARITY UNPINNED. */
+int rtmodt_motion_read_blocks(rtmodt_motion *m, int stream, uint32_t *out);
+/* One stream's model to host memory: bg and dev as uint16[gh][gw] each, and frames_seen.  PARITY UNPINNED. */
+int rtmodt_motion_read_state(rtmodt_motion *m, int stream, uint16_t *bg, uint16_t *dev, int32_t *frames_seen);
+/* Replaces one stream's model (frames_seen 0..2^30), so that it survives a restart.  PARITY UNPINNED. */
+int rtmodt_motion_load_state(rtmodt_motion *m, int stream, const uint16_t *bg, const uint16_t *dev, int32_t frames_seen);
+/* Forgets one stream's model, mask and block grid (frames_seen 0), or every stream's with stream == -1.  PARITY UNPINNED. */
+int rtmodt_motion_reset(rtmodt_motion *m, int stream);
+/* Device time (ms, HIP events around the launches) of the last process call that launched.  PARITY UNPINNED. */
+int rtmodt_motion_last_ms(rtmodt_motion *m, float *kernel_ms);
+/* Host only, no device needed: csrc/motion_model.h's rule on one cell of luma yc (0..255) of a stream that has seen frames_seen
+ * frames: *bg and *dev are updated, *raw is 1 for raw foreground.  Only the five rule fields of cfg are read (learn_shift,
+ * learn_shift_fg, threshold, dev_gain, warmup).  The parity surface of csrc/motion_model.h.  PARITY UNPINNED. */
+int rtmodt_motion_cell(const rtmodt_motion_cfg *cfg, uint32_t yc, int32_t frames_seen, uint16_t *bg, uint16_t *dev, int32_t *raw);
+
 #ifdef __cplusplus
 }
 #endif

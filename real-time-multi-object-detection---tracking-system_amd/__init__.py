@@ -11,6 +11,8 @@ library being built):
 * ``detection.detector`` -- ``Detector`` / ``Detections``  (reference: src/detection/detector.py:29-135)
 * ``detection.sliced``   -- ``SlicedDetector``: overlapping tiles plus an overview per frame, cut and merged on the GPU (the SAHI
                             scheme; the cure for the design document's "Missed small objects", B.4)
+* ``detection.motion``   -- ``MotionDetector``: a background model per stream on the GPU tells still frames from moving ones, so that
+                            ``pipeline.run(motion=...)`` keeps the detector off still scenes (the reference drops frames blind to content)
 * ``tracking.tracker``   --``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
@@ -45,12 +47,14 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "SlicedDetector", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
+__all__ = ["Detector", "Detections", "SlicedDetector", "MotionDetector", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
     "Detections": ".detection.detector",
     "SlicedDetector": ".detection.sliced",
+    "MotionDetector": ".detection.motion",
+    "MotionResult": ".detection.motion",
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",

@@ -221,6 +221,17 @@ class HeatmapCfg(C.Structure):                      # struct rtmodt_heatmap_cfg
                 ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32), ("device", C.c_int32)]
 
 
+class MotionCfg(C.Structure):                       # struct rtmodt_motion_cfg
+    _fields_ = [(n, C.c_int32) for n in ("streams", "height", "width", "scale", "learn_shift", "learn_shift_fg", "threshold", "dev_gain",
+                                         "min_neighbors", "dilate", "warmup", "scene_pm", "min_area", "max_regions", "block", "device")]
+
+
+class MotionResult(C.Structure):                    # struct rtmodt_motion_result
+    _fields_ = [("status", C.c_int32), ("stream", C.c_int32), ("frames_seen", C.c_int32), ("n_raw", C.c_uint32), ("n_fg", C.c_uint32),
+                ("n_regions", C.c_int32), ("n_regions_total", C.c_int32), ("bbox", C.c_int32 * 4), ("reserved", C.c_int32),
+                ("luma_sum", C.c_uint64)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -399,6 +410,17 @@ def lib() -> C.CDLL:
         "rtmodt_heatmap_load": (C.c_int, [vp, C.c_int, vp]),
         "rtmodt_heatmap_reset": (C.c_int, [vp, C.c_int]),
         "rtmodt_heatmap_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_motion_default_cfg": (None, [C.POINTER(MotionCfg)]),
+        "rtmodt_motion_create": (C.c_int, [C.POINTER(MotionCfg), C.POINTER(vp)]),
+        "rtmodt_motion_destroy": (None, [vp]),
+        "rtmodt_motion_process": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "rtmodt_motion_read_mask": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_motion_read_blocks": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_motion_read_state": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(i32)]),
+        "rtmodt_motion_load_state": (C.c_int, [vp, C.c_int, vp, vp, i32]),
+        "rtmodt_motion_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_motion_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_motion_cell": (C.c_int, [C.POINTER(MotionCfg), C.c_uint32, i32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(i32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -1,4 +1,5 @@
 from .detector import Detections, Detector
+from .motion import MotionDetector, MotionResult
 from .sliced import SlicedDetector
 
-__all__ = ["Detector", "Detections", "SlicedDetector"]
+__all__ = ["Detector", "Detections", "SlicedDetector", "MotionDetector", "MotionResult"]

@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -99,7 +99,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``heatmap``: a one-stream ``visualization.Heatmap`` of the frames' size, called inside a ``heatmap`` stage after ``privacy`` and
     directly before ``visualization``, so that boxes and labels are drawn over the heat.  Every frame is accumulated -- the
     materialised track list when there is one, else the tracker's device-resident tracks -- and the heat is blended onto the frame
-    only if the object's ``overlay_enabled`` is set.  ``None``: the stage table and every output are unchanged."""
+    only if the object's ``overlay_enabled`` is set.  ``None``: the stage table and every output are unchanged.
+
+    ``motion``: a one-stream ``detection.MotionDetector`` of the frames' size, called inside a ``motion`` stage directly after
+    ``decode``.  On a frame it calls ``STILL`` the ``inference``, ``tracking`` and ``swap_guard`` stages are skipped -- unless
+    ``motion.max_still`` consecutive frames were already skipped (0: never forced), or the detector has not run yet -- and every
+    later stage runs on what the last detector frame left: the held detections, the held track list or the tracker's
+    device-resident state.  Dwell events keep counting on a person who stands still and the heatmap keeps heating under a parked
+    car.  The summary then carries ``motion_frames``, ``still_frames`` and ``scene_changes``, the frames of each status.  ``None``:
+    today's loop exactly."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -111,22 +119,37 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("visualization"), "heatmap")
         profiler.STAGE_ORDER = order
+    if motion is not None and "motion" not in profiler.STAGE_ORDER:            # likewise, directly after decode
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("decode") + 1, "motion")
+        profiler.STAGE_ORDER = order
+    n_status = [0, 0, 0, 0]                                                    # frames per motion status
+    still_run = 0                                                              # consecutive frames whose detector pass was skipped
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
         profiler.tock("decode")
         if not ok or frame is None:
             continue
-        profiler.tick("inference")
-        detections = detector.detect(frame)
-        total_inf = profiler.tock("inference")
-        if device_stages and hasattr(detector, "stage_times"):
-            pre, fwd, nms = detector.stage_times()
-            # split the wall-clock "inference" stage the way the reference's STAGE_ORDER intends:
-            # preprocess + inference (forward+decode, host overhead included) + nms == the bracketed time
-            profiler.record("preprocess", pre)
-            profiler.record("nms", nms)
-            profiler.record("inference", max(total_inf - pre - nms, 0.0))
+        skip = False
+        if motion is not None:
+            profiler.tick("motion")
+            status = motion.process([frame])[0].status
+            profiler.tock("motion")
+            n_status[status] += 1
+            skip = status == 1 and detections is not None and (motion.max_still == 0 or still_run < motion.max_still)      # 1: STILL
+            still_run = still_run + 1 if skip else 0
+        if not skip:
+            profiler.tick("inference")
+            detections = detector.detect(frame)
+            total_inf = profiler.tock("inference")
+            if device_stages and hasattr(detector, "stage_times"):
+                pre, fwd, nms = detector.stage_times()
+                # split the wall-clock "inference" stage the way the reference's STAGE_ORDER intends:
+                # preprocess + inference (forward+decode, host overhead included) + nms == the bracketed time
+                profiler.record("preprocess", pre)
+                profiler.record("nms", nms)
+                profiler.record("inference", max(total_inf - pre - nms, 0.0))
         handoff = device_handoff and hasattr(tracker, "update_from_detector") and hasattr(detector, "model")
         # the track list stays on the device only when the event stage can read it there; an engine with the reference's
         # host API alone (`process(tracks, fid)`) must be handed the materialised list, trails included
@@ -139,13 +162,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         crossings_on_device = events_on_device
         if crossing_counter is not None and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
-        profiler.tick("tracking")
-        if needs_frame:                                    # a tracker that describes its detections on the frame (DeepSortTracker) or estimates the camera motion from it (BotSortTracker(gmc=))
-            tracks = tracker.update_from_detector(detector, frame=frame, materialize=not events_on_device) if handoff else tracker.update(detections, frame=frame)
-        else:
-            tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
-        profiler.tock("tracking")
-        if swap_guard is not None:
+        if not skip:
+            profiler.tick("tracking")
+            if needs_frame:                                # a tracker that describes its detections on the frame (DeepSortTracker) or estimates the camera motion from it (BotSortTracker(gmc=))
+                tracks = tracker.update_from_detector(detector, frame=frame, materialize=not events_on_device) if handoff else tracker.update(detections, frame=frame)
+            else:
+                tracks = tracker.update_from_detector(detector, materialize=not events_on_device) if handoff else tracker.update(detections)
+            profiler.tock("tracking")
+        if swap_guard is not None and not skip:
             profiler.tick("swap_guard")
             reverted = swap_guard.process_tracker(tracker, [frame], fid)[0]
             if reverted and tracks:
@@ -204,4 +228,6 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["crossings"] = n_crossings
     if swap_guard is not None:
         out["id_swaps_reverted"] = n_reverted
+    if motion is not None:
+        out["motion_frames"], out["still_frames"], out["scene_changes"] = n_status[2], n_status[1], n_status[3]
     return out
