@@ -648,6 +648,139 @@ int rtmodt_crossing_reset_counts(rtmodt_crossing *c);
 int rtmodt_crossing_state(rtmodt_crossing *c, int stream, int64_t *ids, int64_t *last_frame, int32_t *prev_xy, uint32_t *side_pos,
                           uint32_t *side_neg, uint32_t *inside, int32_t *entry_xy, int64_t *entry_frame, int32_t *n);
 
+/* ---- speed estimator: track speed and proximity on a ground plane ---------------------------- */
+/* How fast tracked objects move in real units, and which two are closer than d metres: the speeding / stopped-vehicle / wrong-way
+ * alarms, the speed histogram (85th percentile) and the near-miss pairs that traffic and site-safety deployments ask for.  The
+ * reference has nothing of the kind (its Track carries no velocity).  csrc/speed.hip: one launch per call for the ledgers and alarms
+ * of all streams, one more for the pairs when proximity_mm > 0; csrc/ground_plane.h states the per-point rules (anchor, projection,
+ * integer distance and speed), the header of speed.hip the ledger rules; tests/speed_ref.py restates both and the kernels equal it
+ * exactly.  PARITY UNPINNED against Ultralytics' SpeedEstimator / DistanceCalculation.
+ * A FIXED camera and ONE ground plane per stream: no PTZ, no camera-motion compensation, no lens model.
+ * Every call carries a timestamp in microseconds per stream, strictly increasing per stream (else RTMODT_E_INVALID, nothing
+ * changes).  A box is SAMPLED when its class passes the filter, its coordinates are finite and its anchor projects onto the plane
+ * (ground_plane.h); only sampled tracks touch the ledger. */
+#define RTMODT_SPEED_FOOT 0     /* anchor ((x1 + x2) / 2, y2): the point on the ground (default) */
+#define RTMODT_SPEED_CENTRE 1   /* anchor ((x1 + x2) / 2, (y1 + y2) / 2) */
+#define RTMODT_SPEED_EV_SPEEDING 0
+#define RTMODT_SPEED_EV_STOPPED 1
+#define RTMODT_SPEED_EV_WRONG_WAY 2
+/* row flags: bits 0..2 = the alarm of that kind has fired and not re-armed; bit 3 = the stop timer runs; bit 4 = the row was
+ * created by this call */
+#define RTMODT_SPEED_F_TIMER 8
+#define RTMODT_SPEED_F_NEW 16
+typedef struct rtmodt_speed rtmodt_speed;
+typedef struct rtmodt_speed_cfg {
+    int32_t anchor;             /* RTMODT_SPEED_FOOT | RTMODT_SPEED_CENTRE */
+    int32_t window;             /* 2..32: ring of the last `window` samples (X, Y, t_us) per track */
+    int32_t min_samples;        /* 2..window: speed is -1 (unknown) with fewer samples in the ring */
+    int32_t hold;               /* >= 1: SPEEDING / WRONG_WAY need this many consecutive samples */
+    int64_t max_gap_us;         /* >= 0: a row not sampled for longer is dropped, the id starts fresh */
+    int64_t stop_us;            /* >= 0: STOPPED needs the speed below stop_mm_s for this long */
+    int32_t min_step_mm;        /* >= 0: the odometer gains a step only when it is at least this long (dead band against box jitter) */
+    int32_t limit_mm_s;         /* SPEEDING: speed > limit; 0 = off */
+    int32_t stop_mm_s;          /* STOPPED: 0 <= speed < stop_mm_s; 0 = off */
+    int32_t wrong_way_min_mm_s; /* WRONG_WAY needs at least this speed */
+    int32_t allowed_dir[2];     /* WRONG_WAY: world direction of travel, |.| <= 2^20; (0, 0) = off */
+    int32_t bins, bin_mm_s;     /* speed histogram: bins 0..256 (0 = none) of bin_mm_s >= 1 each, the last one open-ended */
+    int32_t proximity_mm;       /* 0..2^30: pairs closer than this are reported; 0 = off */
+    int32_t max_pairs;          /* >= 1 */
+    int32_t max_events;         /* >= 1 */
+    int32_t n_classes;          /* with `classes`: only these class ids are sampled (at most 256); classes == NULL: all */
+    const int32_t *classes;
+} rtmodt_speed_cfg;
+/* One sampled track of this call, in list order.  `track`: index into the caller's list, or into the tracker's list.  speed_mm_s:
+ * the chord from the oldest ring sample to the newest over their time difference, -1 while unknown; heading: that chord (dx, dy) in
+ * mm, (0, 0) while unknown; peak_mm_s: the largest speed of the row so far (-1: none). */
+typedef struct rtmodt_speed_row {
+    int64_t track_id;
+    int64_t odometer_mm;
+    int32_t track, cls;
+    int32_t world[2];
+    int32_t speed_mm_s, peak_mm_s;
+    int32_t heading[2];
+    int32_t flags, n_samples;
+} rtmodt_speed_row;
+/* One alarm.  `value`: the speed in mm/s at the moment it fired; `track` as in the row. */
+typedef struct rtmodt_speed_event {
+    int64_t track_id;
+    int64_t t_us;
+    float xyxy[4];
+    int32_t world[2];
+    int32_t kind, value, cls, track;
+} rtmodt_speed_event;
+/* Two sampled tracks closer than proximity_mm (compared on the squared integers); a < b index the rows of this call. */
+typedef struct rtmodt_speed_pair {
+    int64_t track_a, track_b;
+    int32_t a, b;
+    int32_t dist_mm;            /* isqrt of the squared distance */
+    int32_t reserved;
+} rtmodt_speed_pair;
+/* What one call hands back; the struct pointer and every member may be null.  With none given nothing crosses to the host and the
+ * call does not wait for the device; otherwise the streams' result blocks come back in one copy.  One-stream calls: rows
+ * [max_tracks], events [max_events], pairs [max_pairs], counts [1]; all-stream calls: [n_streams][...] and counts [n_streams].
+ * n_pairs is the number delivered (<= max_pairs), total_pairs the number that exist. */
+typedef struct rtmodt_speed_out {
+    rtmodt_speed_row *rows;
+    int32_t *n_rows;
+    rtmodt_speed_event *events;
+    int32_t *n_events;
+    rtmodt_speed_pair *pairs;
+    int32_t *n_pairs;
+    int32_t *total_pairs;
+} rtmodt_speed_out;
+/* n_streams independent ledgers, histograms and planes; max_tracks <= 4096.  A ledger holds 2 x max_tracks rows, sorted by track
+ * id, with the crossing counter's capacity behaviour: the call that needs more returns RTMODT_E_CAPACITY, the idle rows are dropped
+ * to make room and the stream stays in error for good (every later call that asks for output, and _state, returns
+ * RTMODT_E_CAPACITY).  More alarms than max_events or more pairs than max_pairs in one call: RTMODT_E_CAPACITY with the first ones
+ * delivered and the counts reported; the stream goes on working.  A call made without outputs cannot report either; a ledger it
+ * filled surfaces in the next call that asks for output.  The rules per sampled track, in this order:
+ *   ring    the sample (X, Y, t_us) enters the ring (the oldest leaves once `window` are held);
+ *   odo     the step from the odometer's anchor point (the first sample, then every sample that moved it) is isqrt of the squared
+ *           distance; if step >= min_step_mm the odometer gains it and the anchor moves here;
+ *   speed   as in rtmodt_speed_row; the histogram bin min(speed / bin_mm_s, bins - 1) gains one whenever the speed is known;
+ *   SPEEDING   speed > limit_mm_s on `hold` consecutive samples fires once; re-arms when speed <= limit_mm_s (or unknown);
+ *   STOPPED    0 <= speed < stop_mm_s starts a timer at this sample; fires once when t_us - start >= stop_us; anything else stops
+ *              the timer and re-arms;
+ *   WRONG_WAY  speed >= wrong_way_min_mm_s and heading . allowed_dir < 0 on `hold` consecutive samples fires once; re-arms when the
+ *              condition fails.
+ * Events leave in list order, kinds in the order above. */
+int rtmodt_speed_create(int device, const rtmodt_speed_cfg *cfg, int n_streams, int max_tracks, rtmodt_speed **out);
+/* Waits for the handle's queued work, frees everything; null is allowed. */
+void rtmodt_speed_destroy(rtmodt_speed *h);
+/* The image-pixel -> world-millimetre homography of one stream, row-major.  Non-finite entries or a singular matrix:
+ * RTMODT_E_INVALID.  A stream without a plane makes every _process* that touches it return RTMODT_E_INVALID. */
+int rtmodt_speed_set_plane(rtmodt_speed *h, int stream, const double H[9]);
+/* The Ultralytics-style shorthand: H = diag(s, s, 1), s = mm_per_pixel, finite and > 0. */
+int rtmodt_speed_set_scale(rtmodt_speed *h, int stream, double mm_per_pixel);
+/* Host only, no device needed: fits H to n >= 4 correspondences image (u, v) -> world (x, y) mm by a normalised DLT (float64,
+ * Gaussian elimination with partial pivoting).  *max_residual_mm (may be null) = the largest reprojection residual, so that a bad
+ * survey shows.  Degenerate input (n < 4, three of four points collinear, repeated points): RTMODT_E_INVALID. */
+int rtmodt_speed_fit_plane(const double *img_xy, const double *world_xy, int n, double H_out[9], double *max_residual_mm);
+/* One stream, a caller-supplied track list (any order, unique ids, at most max_tracks). */
+int rtmodt_speed_process(rtmodt_speed *h, int stream, const int64_t *track_ids, const float *xyxy, const int32_t *cls, int n,
+                         int64_t t_us, const rtmodt_speed_out *out);
+/* Every stream in one call: track_ids / cls [n_streams][stride], xyxy [n_streams][stride][4], n [n_streams], t_us [n_streams]. */
+int rtmodt_speed_process_batch(rtmodt_speed *h, const int64_t *track_ids, const float *xyxy, const int32_t *cls, const int32_t *n,
+                               int stride, const int64_t *t_us, const rtmodt_speed_out *out);
+/* Every stream of a ByteTrack handle, straight on its device-resident state and on the HIP stream its last update ran on: exactly
+ * the tracks and boxes rtmodt_crossing_process_tracker passes.  t_us [n_streams of the tracker]. */
+int rtmodt_speed_process_tracker(rtmodt_speed *h, rtmodt_tracker *trk, const int64_t *t_us, int report_tsu, const rtmodt_speed_out *out);
+/* The same on a DeepSORT handle: the tracks rtmodt_crossing_process_deepsort passes. */
+int rtmodt_speed_process_deepsort(rtmodt_speed *h, rtmodt_deepsort *ds, const int64_t *t_us, int report_tsu, const rtmodt_speed_out *out);
+/* The same on an OC-SORT handle: the tracks rtmodt_crossing_process_ocsort passes. */
+int rtmodt_speed_process_ocsort(rtmodt_speed *h, rtmodt_ocsort *oc, const int64_t *t_us, const rtmodt_speed_out *out);
+/* The same on a BoT-SORT handle: the tracks rtmodt_crossing_process_botsort passes. */
+int rtmodt_speed_process_botsort(rtmodt_speed *h, rtmodt_botsort *bot, const int64_t *t_us, const rtmodt_speed_out *out);
+/* One stream's speed histogram, hist [bins]; reset != 0 zeroes it after the read (hist may be null then). */
+int rtmodt_speed_histogram(rtmodt_speed *h, int stream, int64_t *hist, int reset);
+/* Ledger snapshot of one stream, rows in ascending track id (the parity surface of tests/speed_ref.py); any array may be null.
+ * ring_xy [rows][window][2] and ring_t [rows][window] are the ring's slots as stored: ints[row] = {n_samples, head (slot of the newest
+ * sample), speed, peak, cls, flags, speeding run, wrong-way run}; the samples are the slots head - n_samples + 1 .. head (mod
+ * window), other slots are unspecified.  odo_anchor_xy [rows][2], heading [rows][2], stop_since [rows] (valid while the timer
+ * runs).  Arrays sized 2 x max_tracks rows. */
+int rtmodt_speed_state(rtmodt_speed *h, int stream, int64_t *ids, int64_t *last_t_us, int64_t *odometer_mm, int64_t *stop_since,
+                       int32_t *ring_xy, int64_t *ring_t, int32_t *odo_anchor_xy, int32_t *heading, int32_t *ints, int32_t *n);
+
 /* ---- frame renderer: replaces FrameRenderer.render (src/visualization/renderer.py) ---------- */
 /* Annotates BGR24 frames in place, one launch per batch (csrc/render.hip, whose header comment states the paint rules; they
  * restate cv2's drawing calls -- PARITY UNPINNED: no OpenCV to run against).  Per frame, in this order: zone tint (the

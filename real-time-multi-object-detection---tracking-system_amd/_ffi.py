@@ -122,6 +122,33 @@ class CrossingEventRec(C.Structure):                 # struct rtmodt_crossing_ev
                 ("reserved", C.c_int32)]
 
 
+class SpeedCfg(C.Structure):                         # struct rtmodt_speed_cfg
+    _fields_ = [("anchor", C.c_int32), ("window", C.c_int32), ("min_samples", C.c_int32), ("hold", C.c_int32), ("max_gap_us", C.c_int64),
+                ("stop_us", C.c_int64), ("min_step_mm", C.c_int32), ("limit_mm_s", C.c_int32), ("stop_mm_s", C.c_int32),
+                ("wrong_way_min_mm_s", C.c_int32), ("allowed_dir", C.c_int32 * 2), ("bins", C.c_int32), ("bin_mm_s", C.c_int32),
+                ("proximity_mm", C.c_int32), ("max_pairs", C.c_int32), ("max_events", C.c_int32), ("n_classes", C.c_int32),
+                ("classes", C.POINTER(C.c_int32))]
+
+
+class SpeedRow(C.Structure):                         # struct rtmodt_speed_row
+    _fields_ = [("track_id", C.c_int64), ("odometer_mm", C.c_int64), ("track", C.c_int32), ("cls", C.c_int32), ("world", C.c_int32 * 2),
+                ("speed_mm_s", C.c_int32), ("peak_mm_s", C.c_int32), ("heading", C.c_int32 * 2), ("flags", C.c_int32), ("n_samples", C.c_int32)]
+
+
+class SpeedEventRec(C.Structure):                    # struct rtmodt_speed_event
+    _fields_ = [("track_id", C.c_int64), ("t_us", C.c_int64), ("xyxy", C.c_float * 4), ("world", C.c_int32 * 2), ("kind", C.c_int32),
+                ("value", C.c_int32), ("cls", C.c_int32), ("track", C.c_int32)]
+
+
+class SpeedPair(C.Structure):                        # struct rtmodt_speed_pair
+    _fields_ = [("track_a", C.c_int64), ("track_b", C.c_int64), ("a", C.c_int32), ("b", C.c_int32), ("dist_mm", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SpeedOut(C.Structure):                         # struct rtmodt_speed_out
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_void_p), ("events", C.c_void_p), ("n_events", C.c_void_p), ("pairs", C.c_void_p),
+                ("n_pairs", C.c_void_p), ("total_pairs", C.c_void_p)]
+
+
 class RenderCfg(C.Structure):                        # struct rtmodt_render_cfg
     _fields_ = [("show_boxes", C.c_int32), ("show_ids", C.c_int32), ("show_trails", C.c_int32), ("show_zones", C.c_int32),
                 ("show_fps", C.c_int32), ("trail_length", C.c_int32), ("palette_bgr", C.POINTER(C.c_uint8)), ("n_palette", C.c_int32)]
@@ -364,6 +391,19 @@ def lib() -> C.CDLL:
         "rtmodt_crossing_counts": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "rtmodt_crossing_reset_counts": (C.c_int, [vp]),
         "rtmodt_crossing_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_speed_create": (C.c_int, [C.c_int, C.POINTER(SpeedCfg), C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtmodt_speed_destroy": (None, [vp]),
+        "rtmodt_speed_set_plane": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_speed_set_scale": (C.c_int, [vp, C.c_int, C.c_double]),
+        "rtmodt_speed_fit_plane": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(C.c_double)]),
+        "rtmodt_speed_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, i64, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_process_batch": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_process_tracker": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_process_deepsort": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_process_ocsort": (C.c_int, [vp, vp, vp, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_process_botsort": (C.c_int, [vp, vp, vp, C.POINTER(SpeedOut)]),
+        "rtmodt_speed_histogram": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+        "rtmodt_speed_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
         "rtmodt_swapguard_create": (C.c_int, [C.POINTER(SwapGuardCfg), C.POINTER(vp)]),
         "rtmodt_swapguard_destroy": (None, [vp]),
         "rtmodt_swapguard_process": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp, vp, C.POINTER(i32)]),

@@ -1,4 +1,5 @@
 from .crossing import CrossingCounter, CrossingEvent
+from .speed import SpeedEstimator, SpeedEvent
 from .zone_engine import Zone, ZoneEvent, ZoneEventEngine
 
-__all__ = ["ZoneEventEngine", "ZoneEvent", "Zone", "CrossingCounter", "CrossingEvent"]
+__all__ = ["ZoneEventEngine", "ZoneEvent", "Zone", "CrossingCounter", "CrossingEvent", "SpeedEstimator", "SpeedEvent"]

@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -107,7 +107,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     later stage runs on what the last detector frame left: the held detections, the held track list or the tracker's
     device-resident state.  Dwell events keep counting on a person who stands still and the heatmap keeps heating under a parked
     car.  The summary then carries ``motion_frames``, ``still_frames`` and ``scene_changes``, the frames of each status.  ``None``:
-    today's loop exactly."""
+    today's loop exactly.
+
+    ``speed``: an ``events.SpeedEstimator`` (fixed camera, one ground plane), called inside a ``speed`` stage directly after
+    ``crossings`` -- so after the swap guard: its ledger follows the corrected ids -- with the timestamp
+    ``speed.frame_time_us(frame_id)``.  It reads the tracker's device-resident state when the crossings stage would, else the
+    materialised list, and runs on the held tracks of a motion-gated still frame (a parked car's STOPPED alarm still fires).  The
+    summary then carries ``speed_events``, the number of alarms of stream 0.  ``None``: the stage is absent."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -123,6 +129,11 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("decode") + 1, "motion")
         profiler.STAGE_ORDER = order
+    if speed is not None and "speed" not in profiler.STAGE_ORDER:              # likewise, directly after events (crossings has no row)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("events") + 1, "speed")
+        profiler.STAGE_ORDER = order
+    n_speed = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     for _ in range(max_frames):
@@ -160,7 +171,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
                             and hasattr(event_engine, "process_tracker"))
         # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
         crossings_on_device = events_on_device
-        if crossing_counter is not None and event_engine is None and renderer is None and handoff:
+        if (crossing_counter is not None or speed is not None) and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
         if not skip:
             profiler.tick("tracking")
@@ -191,6 +202,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_crossings += len(crossing_counter.process(tracks, fid))
             profiler.tock("crossings")
+        if speed is not None:
+            profiler.tick("speed")
+            if crossings_on_device:
+                n_speed += len(speed.process_tracker(tracker, speed.frame_time_us(fid), class_names=getattr(detector.model, "names", None))[0])
+            else:
+                n_speed += len(speed.process(tracks, speed.frame_time_us(fid)))
+            profiler.tock("speed")
         if privacy is not None:
             profiler.tick("privacy")
             if tracks is None or events_on_device:
@@ -226,6 +244,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     out["events"] = n_events
     if crossing_counter is not None:
         out["crossings"] = n_crossings
+    if speed is not None:
+        out["speed_events"] = n_speed
     if swap_guard is not None:
         out["id_swaps_reverted"] = n_reverted
     if motion is not None:
