@@ -655,7 +655,8 @@ int rtmodt_crossing_state(rtmodt_crossing *c, int stream, int64_t *ids, int64_t 
  * of all streams, one more for the pairs when proximity_mm > 0; csrc/ground_plane.h states the per-point rules (anchor, projection,
  * integer distance and speed), the header of speed.hip the ledger rules; tests/speed_ref.py restates both and the kernels equal it
  * exactly.  PARITY UNPINNED against Ultralytics' SpeedEstimator / DistanceCalculation.
- * A FIXED camera and ONE ground plane per stream: no PTZ, no camera-motion compensation, no lens model.
+ * A FIXED camera and ONE ground plane per stream: no PTZ, no camera-motion compensation, no lens model (rectify the frames first: the
+ * lens correction section at the end of this header).
  * Every call carries a timestamp in microseconds per stream, strictly increasing per stream (else RTMODT_E_INVALID, nothing
  * changes).  A box is SAMPLED when its class passes the filter, its coordinates are finite and its anchor projects onto the plane
  * (ground_plane.h); only sampled tracks touch the ledger. */
@@ -1444,6 +1445,77 @@ int rtmodt_motion_last_ms(rtmodt_motion *m, float *kernel_ms);
  * frames: *bg and *dev are updated, *raw is 1 for raw foreground.  Only the five rule fields of cfg are read (learn_shift,
  * learn_shift_fg, threshold, dev_gain, warmup).  The parity surface of csrc/motion_model.h.  PARITY UNPINNED. */
 int rtmodt_motion_cell(const rtmodt_motion_cfg *cfg, uint32_t yc, int32_t frames_seen, uint16_t *bg, uint16_t *dev, int32_t *raw);
+
+/* ---- lens correction: frames are undistorted once, directly after decode ------------------------------------------------------ */
+/* Every geometric module of this library (zones, crossings, privacy polygons, heatmap zone sums, the ground-plane speed estimator)
+ * assumes a pinhole picture; a short surveillance lens bows straight lines by tens of pixels.  This module produces the rectified
+ * picture those modules assume.  The reference has no counterpart: src/ingestion/rtsp_reader.py hands cap.read()'s frame straight
+ * to the detector and cv2.undistort appears nowhere in it.  csrc/lens_model.h states the rules (the map of OpenCV's pinhole +
+ * Brown-Conrady / rational model, 5 fractional bits, four integer-weighted taps, (sum + 512) >> 10); tests/lens_ref.py restates
+ * them and the table and every output byte equal it exactly.  PARITY UNPINNED against cv2.undistort /
+ * initUndistortRectifyMap / remap (cv2's table rounds differently and is not installed where this is tested) and on real footage.
+ * No fisheye model (its atan cannot be pinned across libm, NumPy and the device): such a lens enters through rtmodt_lens_set_map. */
+typedef struct rtmodt_lens rtmodt_lens;
+typedef struct rtmodt_lens_cfg {
+    int32_t device;
+    int32_t streams;            /* 1..1024 lenses                                                                               */
+    int32_t src_h, src_w;       /* the source frame size, 1..16384 each                                                         */
+    int32_t out_h, out_w;       /* the rectified frame size, 1..16384 each                                                      */
+    uint8_t border_bgr[3];      /* what a tap off the source, and a pixel OUTSIDE the map, reads                                 */
+    uint8_t reserved;
+} rtmodt_lens_cfg;
+typedef struct rtmodt_lens_params {
+    double fx, fy, cx, cy;      /* source intrinsics; integer pixel coordinates are pixel centres                               */
+    double k[8];                /* k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order); all zero: no distortion                            */
+    double nfx, nfy, ncx, ncy;  /* output intrinsics; nfx == 0: all four are copied from the source intrinsics                  */
+    double r2_limit;            /* 0: none; else an output pixel whose normalised r^2 exceeds it is OUTSIDE                     */
+} rtmodt_lens_params;
+/* Host only: device 0, 1 stream, every size 0 (the caller sets them), a black border.  No reference counterpart (rtsp_reader.py
+ * hands cap.read()'s frame straight to the detector).  PARITY UNPINNED. */
+void rtmodt_lens_default_cfg(rtmodt_lens_cfg *cfg);
+/* Allocates one table of 8 bytes per output pixel for each stream; no stream has a lens yet.  streams outside 1..1024 or a size
+ * outside 1..16384 is RTMODT_E_INVALID.  No reference counterpart (as above).  PARITY UNPINNED. */
+int rtmodt_lens_create(const rtmodt_lens_cfg *cfg, rtmodt_lens **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  No reference counterpart.  PARITY UNPINNED. */
+void rtmodt_lens_destroy(rtmodt_lens *l);
+/* Builds one stream's table on the host from the model (csrc/lens_model.h rules 1 and 2) and uploads it: once per lens, not per
+ * frame.  *n_outside (may be null) = the output pixels that are border, so that a caller can choose nfx (zoom) knowingly.  fx, fy,
+ * nfx or nfy not finite or not > 0 is RTMODT_E_INVALID and the stream keeps the lens it had.  No reference counterpart.  PARITY
+ * UNPINNED. */
+int rtmodt_lens_set_model(rtmodt_lens *l, int stream, const rtmodt_lens_params *params, int32_t *n_outside);
+/* The same from a caller's map: map_x, map_y float32[out_h][out_w], the source position of each output pixel, the form cv2.remap
+ * takes (rule 2 of csrc/lens_model.h; a NaN, an infinity or a position at or beyond +-2^20 is OUTSIDE).  The door for fisheye and
+ * any other lens.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_set_map(rtmodt_lens *l, int stream, const float *map_x, const float *map_y, int32_t *n_outside);
+/* One stream's table as the device holds it, in canonical form whatever the packing: qx, qy int32[out_h][out_w] (5 fractional
+ * bits; 0 where outside), outside uint8[out_h][out_w] of 0 / 1; any array may be null.  A stream without a lens is
+ * RTMODT_E_INVALID.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_read_map(rtmodt_lens *l, int stream, int32_t *qx, int32_t *qy, uint8_t *outside);
+/* Rectifies n frames in ONE launch: dst[i] (BGR24 out_h x out_w, row pitch dst_stride >= 3 out_w) is src[i] (BGR24 src_h x src_w,
+ * row pitch src_stride >= 3 src_w) seen through the lens of streams[i] (streams == NULL: stream i).  Source and destination memory
+ * kinds are independent (host -> device is the ingest path: upload and rectify).  Bytes beyond 3 out_w of a destination row are
+ * never written.  RTMODT_E_INVALID with nothing launched: a stream without a lens or outside 0..streams - 1, a pitch below 3 w, a
+ * null frame, a destination range that overlaps any source range of the call (a gather cannot work in place); more than 65535
+ * frames is RTMODT_E_CAPACITY.  The geometry is the handle's.  n == 0 is a no-op.  Synchronous.  No reference counterpart
+ * (rtsp_reader.py hands cap.read()'s frame straight to the detector).  PARITY UNPINNED. */
+int rtmodt_lens_process(rtmodt_lens *l, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride,
+                        int dst_mem_kind, const int32_t *streams, int n);
+/* Device time (ms, HIP events around the launch) of the last process call that launched.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_last_ms(rtmodt_lens *l, float *kernel_ms);
+/* Host only, float64, no device needed: n points xy[n][2] of the RECTIFIED picture -> the original picture (rule 4's closed form): a
+ * rectified box is drawn back on an original frame.  residual is not written (pass null).  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_distort_points(const rtmodt_lens_params *params, const double *xy, int n, double *out_xy, double *residual);
+/* Host only: n points of the ORIGINAL picture -> the rectified picture by 20 fixed iterations of OpenCV's fixed-point scheme; zones,
+ * tripwires, privacy polygons and the surveyed points of rtmodt_speed_fit_plane are carried over once.  residual[n] (may be null):
+ * |distort(undistort(p)) - p| (largest axis) in pixels, +infinity when not a number.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_undistort_points(const rtmodt_lens_params *params, const double *xy, int n, double *out_xy, double *residual);
+/* Host only: the canonical table of a model without a device (read_map's arrays, none may be null).  No reference counterpart.
+ * PARITY UNPINNED. */
+int rtmodt_lens_build_map(const rtmodt_lens_params *params, int src_h, int src_w, int out_h, int out_w, int32_t *qx, int32_t *qy,
+                          uint8_t *outside);
+/* Host only: the canonical table of a caller's map (set_map's rule) without a device.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_lens_quantise_map(const float *map_x, const float *map_y, int src_h, int src_w, int out_h, int out_w, int32_t *qx, int32_t *qy,
+                             uint8_t *outside);
 
 #ifdef __cplusplus
 }

@@ -259,6 +259,16 @@ class MotionResult(C.Structure):                    # struct rtmodt_motion_resul
                 ("luma_sum", C.c_uint64)]
 
 
+class LensCfg(C.Structure):                         # struct rtmodt_lens_cfg
+    _fields_ = [("device", C.c_int32), ("streams", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("border_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class LensParams(C.Structure):                      # struct rtmodt_lens_params
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 8), ("nfx", C.c_double),
+                ("nfy", C.c_double), ("ncx", C.c_double), ("ncy", C.c_double), ("r2_limit", C.c_double)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -461,6 +471,18 @@ def lib() -> C.CDLL:
         "rtmodt_motion_reset": (C.c_int, [vp, C.c_int]),
         "rtmodt_motion_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_motion_cell": (C.c_int, [C.POINTER(MotionCfg), C.c_uint32, i32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(i32)]),
+        "rtmodt_lens_default_cfg": (None, [C.POINTER(LensCfg)]),
+        "rtmodt_lens_create": (C.c_int, [C.POINTER(LensCfg), C.POINTER(vp)]),
+        "rtmodt_lens_destroy": (None, [vp]),
+        "rtmodt_lens_set_model": (C.c_int, [vp, C.c_int, C.POINTER(LensParams), C.POINTER(i32)]),
+        "rtmodt_lens_set_map": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(i32)]),
+        "rtmodt_lens_read_map": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "rtmodt_lens_process": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int]),
+        "rtmodt_lens_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_lens_distort_points": (C.c_int, [C.POINTER(LensParams), vp, C.c_int, vp, vp]),
+        "rtmodt_lens_undistort_points": (C.c_int, [C.POINTER(LensParams), vp, C.c_int, vp, vp]),
+        "rtmodt_lens_build_map": (C.c_int, [C.POINTER(LensParams), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "rtmodt_lens_quantise_map": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -6,7 +6,7 @@ alarms, the 85th-percentile speed of a lane, "two tracked objects closer than d 
 
 A **fixed camera** and **one ground plane per stream**: a homography ``H`` maps image pixels to world millimetres (``plane=``,
 fitted from a survey with ``fit_plane``), or a single scale (``mm_per_pixel=``, the Ultralytics shorthand ``H = diag(s, s, 1)``).
-There is no PTZ handling, no camera-motion compensation and no lens model.  A box is sampled at its *foot* ``((x1 + x2) / 2, y2)``
+There is no PTZ handling, no camera-motion compensation and no lens model (rectify the frames first: ``ingestion.LensCorrector``).  A box is sampled at its *foot* ``((x1 + x2) / 2, y2)``
 -- the point that stands on the ground -- or its centre, projected in float64 and rounded to integer millimetres; everything after
 that rounding is integer arithmetic (``csrc/ground_plane.h``).  The per-frame work -- ledger upkeep, ring, odometer, speed, alarms,
 histogram, pair search -- runs in ``csrc/speed.hip`` (two launches per call for all streams); there is no CPU implementation here.

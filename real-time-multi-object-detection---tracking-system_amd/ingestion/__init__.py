@@ -1,5 +1,6 @@
 from .reader import FrameReader, RTSPReader, RawVideoCapture, SyntheticCapture, register_backend  # noqa: F401
 from .jpeg_decode import JpegDecodeError, JpegDecoder  # noqa: F401
 from .mjpeg import MjpegCapture  # noqa: F401
+from .lens import LensCorrector, fisheye_map, monotonic_r2  # noqa: F401
 
 register_backend("mjpeg", MjpegCapture)          # FrameReader("x.avi", backend="mjpeg"): Motion-JPEG decoded on the GPU

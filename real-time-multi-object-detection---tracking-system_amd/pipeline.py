@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -113,7 +113,12 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``crossings`` -- so after the swap guard: its ledger follows the corrected ids -- with the timestamp
     ``speed.frame_time_us(frame_id)``.  It reads the tracker's device-resident state when the crossings stage would, else the
     materialised list, and runs on the held tracks of a motion-gated still frame (a parked car's STOPPED alarm still fires).  The
-    summary then carries ``speed_events``, the number of alarms of stream 0.  ``None``: the stage is absent."""
+    summary then carries ``speed_events``, the number of alarms of stream 0.  ``None``: the stage is absent.
+
+    ``lens``: a one-stream ``ingestion.LensCorrector`` for the frames' size with its lens set, called inside an ``undistort`` stage
+    directly after ``decode`` and before ``motion``: the frame is replaced by the rectified one for every later stage and for the
+    recorder, so zones, tripwires, privacy polygons and the ground plane are given in rectified coordinates
+    (``LensCorrector.undistort_points`` carries them over).  ``None``: the loop, the stage table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -133,6 +138,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("events") + 1, "speed")
         profiler.STAGE_ORDER = order
+    if lens is not None and "undistort" not in profiler.STAGE_ORDER:           # likewise, directly after decode (and so before motion)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("decode") + 1, "undistort")
+        profiler.STAGE_ORDER = order
     n_speed = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
@@ -142,6 +151,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         profiler.tock("decode")
         if not ok or frame is None:
             continue
+        if lens is not None:
+            profiler.tick("undistort")
+            frame = lens.process([frame])[0]
+            profiler.tock("undistort")
         skip = False
         if motion is not None:
             profiler.tick("motion")
