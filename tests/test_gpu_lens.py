@@ -1,8 +1,10 @@
 """GPU: the lens corrector (``csrc/lens.hip``) against ``tests/lens_ref.py``: the table the device holds after ``set_model`` and
 ``set_map`` and every output byte of ``process`` are equal to the restatement (``==`` on integers, nothing is tolerated); every
 memory kind, padded rows whose padding stays untouched, odd base addresses, a border colour; streams; every refusal; the hand-over
-of rectified device frames to the motion detector; the pipeline's ``undistort`` stage.  Shapes are small (the largest frame is
-131 x 77): partial tiles in both axes, rows that are no multiple of any vector width, outputs larger and smaller than the source.
+of rectified device frames to the motion detector; the pipeline's ``undistort`` stage.  Shapes here stay inside the kernel's first
+256-pixel tile column (the widest output is 131 pixels): partial tiles in both axes, rows that are no multiple of any vector width,
+outputs larger and smaller than the source.  ``tests/test_gpu_lens_tiles.py`` goes past one tile, one wave and to the largest extents
+with the cases of ``tests/lens_cases.py``, and compares the kernel with a float64 reference that is independent of the restatement.
 Content is random bytes, the worst case for a wrong weight or tap.  PARITY UNPINNED: cv2.undistort / remap are not compared."""
 import ctypes as C
 import os
@@ -11,34 +13,11 @@ import numpy as np
 import pytest
 
 import lens_ref as R
+from lens_cases import BORDER, image, padded, random_frames, rectify
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0xA5
-BORDER = (17, 200, 93)
 CASES = [((23, 37), (19, 41)), ((77, 131), (48, 64)), ((1, 1), (1, 1))]      # (src, out) as (h, w): 37 x 23 -> 41 x 19, 131 x 77 -> 64 x 48, 1 x 1
-
-
-def random_frames(n, size, seed):
-    return list(np.random.default_rng(seed).integers(0, 256, (n,) + tuple(size) + (3,), np.uint8))
-
-
-def padded(frame, pitch, lead=0):
-    """A host frame with rows ``pitch`` bytes apart ``lead`` bytes into its buffer, everything else SENT -> (buffer, view)."""
-    h, w, _ = frame.shape
-    buf = np.full(lead + h * pitch, SENT, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[lead:], (h, w, 3), (pitch, 3, 1))
-    view[...] = frame
-    return buf, view
-
-
-def image(frames, pitch, offset):
-    """The bytes of a device buffer that holds ``frames`` one after another from ``offset``, rows ``pitch`` apart, SENT elsewhere."""
-    h, w, _ = frames[0].shape
-    buf = np.full(offset + len(frames) * h * pitch + 8, SENT, np.uint8)
-    for i, f in enumerate(frames):
-        np.lib.stride_tricks.as_strided(buf[offset + i * h * pitch:], (h, w, 3), (pitch, 3, 1))[...] = f
-    return buf
 
 
 def lenses_for(src, out):
@@ -47,33 +26,6 @@ def lenses_for(src, out):
 
 def set_lens(lc, stream, lens):
     return lc.set_model(stream, lens.K, lens.k, lens.new_K, lens.r2_limit)
-
-
-def rectify(lc, pkg, frames, streams, out_size, *, src_kind, dst_kind, spitch, dpitch, offset=0):
-    """One process call in the given memory kinds and pitches -> the output frames; asserts that no byte outside them changed."""
-    F = pkg._ffi
-    n, (sh, sw), (oh, ow) = len(frames), frames[0].shape[:2], out_size
-    if src_kind == "host":
-        src, kw = [padded(f, spitch, i)[1] for i, f in enumerate(frames)], {}
-    else:
-        src = F.DeviceBuffer(offset + n * sh * spitch + 8)
-        src.upload(image(frames, spitch, offset))
-        kw = dict(stride=spitch, offset=offset)
-    blank = [np.full((oh, ow, 3), SENT, np.uint8)] * n
-    if dst_kind == "host":
-        bufs = [padded(b, dpitch, 3 + i) for i, b in enumerate(blank)]
-        got = lc.process(src, streams, [v for _, v in bufs], **kw)
-        for i, (buf, view) in enumerate(bufs):
-            want = padded(view, dpitch, 3 + i)[0]
-            assert np.array_equal(buf, want), f"frame {i}: a byte outside the pixels changed"
-        return [np.array(g) for g in got]
-    dst = F.DeviceBuffer(offset + n * oh * dpitch + 8)
-    dst.upload(image(blank, dpitch, offset))
-    assert lc.process(src, streams, dst, out_stride=dpitch, out_offset=offset, **kw) is dst
-    raw = dst.download()
-    got = [np.array(np.lib.stride_tricks.as_strided(raw[offset + i * oh * dpitch:], (oh, ow, 3), (dpitch, 3, 1))) for i in range(n)]
-    assert np.array_equal(raw, image(got, dpitch, offset)), "a byte outside the pixels changed"
-    return got
 
 
 # ---------------------------------------------------------------------------------------------------------------- table and bytes

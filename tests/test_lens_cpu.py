@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lens_cases as LC  # noqa: E402
 import lens_ref as R  # noqa: E402
 from test_lap_cpu import CSRC, ROOT, host_compilers  # noqa: E402
 
@@ -173,7 +174,24 @@ def header_cases():
     line, w = sample_case()
     lines.append(line)
     want.append(w)
+    for c in LC.CASES:                                                                          # past one tile, and the largest extents
+        (sh, sw), (oh, ow) = c.src, c.out
+        if c.lens is not None:
+            lines.append(f"m {sh} {sw} {oh} {ow} {lens_bits(c.lens)}")
+        else:
+            lines.append(f"c {sh} {sw} {oh} {ow} " + " ".join(f"{b32(x)} {b32(y)}" for x, y in zip(c.map[0].ravel(), c.map[1].ravel())))
+        want.append(table_line(LC.table(c.name)))
     return lines, want
+
+
+def header_subset(lines, want, sanitize):
+    """The sanitised program gets every case but max_height (16384 rows of 3 pixels add nothing a sanitizer can see that max_width's 3
+    rows of 16384 do not); the plain one gets all."""
+    if not sanitize:
+        return lines, want
+    skip = len(lines) - len(LC.CASES) + [c.name for c in LC.CASES].index("max_height")
+    assert lines[skip].startswith("m 16384 3 16384 3 ")
+    return lines[:skip] + lines[skip + 1:], want[:skip] + want[skip + 1:]
 
 
 def nan_insensitive(line):
@@ -188,7 +206,7 @@ def nan_insensitive(line):
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitized"])
 def test_lens_model_header_equals_restatement(tmp_path, header_cases, sanitize):
-    lines, want = header_cases
+    lines, want = header_subset(*header_cases, sanitize)
     exe = build(tmp_path, sanitize)
     out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
