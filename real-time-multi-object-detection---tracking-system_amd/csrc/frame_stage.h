@@ -86,7 +86,7 @@ inline int check_frames(const uint8_t *const *frames, int n, int h, int w, int s
 // ---------------------------------------------------------------------------------------------------------------- staging
 // Where host frames stand on the device.  Device frames are never staged: the kernels get the caller's pointers and pitch.
 enum FrameLayout {
-    FRAMES_AS_GIVEN,     // rows at the caller's pitch, one copy of h * pitch bytes per frame (the read-only descriptor modules)
+    FRAMES_AS_GIVEN,     // rows at the caller's pitch, one copy of (h - 1) * pitch + 3w bytes per frame into a slot of h * pitch (the read-only descriptor modules)
     FRAMES_TIGHT16,      // rows of align_up(3w, 16) bytes, copied row by row (the in-place modules; jpeg)
     FRAMES_TIGHT         // rows of 3w bytes (jpeg_dec, slice)
 };
@@ -125,7 +125,8 @@ struct FrameStage {
     int copy_in(const uint8_t *const *frames, hipStream_t q) {
         if (!host) return RTMODT_OK;
         for (int i = 0; i < n; ++i) {
-            if (layout == FRAMES_AS_GIVEN) RT_HIP(hipMemcpyAsync(d + (size_t)i * fbytes, frames[i], fbytes, hipMemcpyHostToDevice, q));
+            // a frame owns (h - 1) pitch + 3w bytes: a crop that touches its parent's last byte has nothing behind its last row
+            if (layout == FRAMES_AS_GIVEN) RT_HIP(hipMemcpyAsync(d + (size_t)i * fbytes, frames[i], fbytes - pitch + (size_t)3 * w, hipMemcpyHostToDevice, q));
             else RT_TRY(copy_bgr_rows(d + (size_t)i * fbytes, pitch, frames[i], src_pitch, h, w, hipMemcpyHostToDevice, q));
         }
         return RTMODT_OK;
