@@ -1517,6 +1517,154 @@ int rtmodt_lens_build_map(const rtmodt_lens_params *params, int src_h, int src_w
 int rtmodt_lens_quantise_map(const float *map_x, const float *map_y, int src_h, int src_w, int out_h, int out_w, int32_t *qx, int32_t *qy,
                              uint8_t *outside);
 
+/* ---- snapshot gallery: the best-shot thumbnail of every track, kept on the device ----------------------------------------------- */
+/* What the object LOOKED like, for the alert record and the review queue: the reference's alert carries bbox_xyxy and a frame_id and
+ * no picture.  Per track the gallery decides on the device whether this frame's view is better than the one kept and, if so,
+ * resamples the crop into a fixed-size BGR24 thumbnail slot in device memory; it reports which thumbnails changed and which tracks
+ * ended.  csrc/snapshot_rule.h states the per-box rules (crop rectangle, fit, exact area average, score, replacement), the header
+ * of csrc/snapshot.hip the ledger rules; tests/snapshot_ref.py restates both and the kernels equal it exactly (DESIGN.md section
+ * 32).  No reference counterpart.  PARITY UNPINNED against cv2.resize INTER_AREA, Ultralytics' ObjectCropper and Frigate's
+ * snapshot choice; every default is unvalidated on real footage; sharpness is no term of the score.
+ * Two launches per call whatever the tracks do: the decision (selection, score, occlusion pairs, ledger merge, slot assignment, a
+ * device-side work list) and the resampler, which walks the work list and costs nothing for a track whose thumbnail is kept.
+ * Every call carries a frame_id per stream, strictly increasing per stream (else RTMODT_E_INVALID, nothing changes).  Frames are
+ * BGR24, h x w at a row pitch of stride_bytes >= 3 w, in host or device memory, and are only read.  A box is SAMPLED when its class
+ * passes the filter, its coordinates are finite and its clipped crop has at least min_side pixels on both sides; only sampled
+ * tracks touch the ledger. */
+#define RTMODT_SNAPSHOT_F_NEW 1        /* the row was created by this call (it always takes its shot) */
+#define RTMODT_SNAPSHOT_F_REWRITTEN 2  /* the row's thumbnail was replaced by this call */
+#define RTMODT_SNAPSHOT_F_CUT 4        /* the kept shot's box reaches the frame border */
+#define RTMODT_SNAPSHOT_F_OCCLUDED 8   /* the kept shot overlapped another sampled box of its list */
+typedef struct rtmodt_snapshot rtmodt_snapshot;
+typedef struct rtmodt_snapshot_cfg {
+    int32_t thumb_h, thumb_w;   /* 8..512 each: the slot */
+    int32_t margin_pm;          /* 0..1000: the box grows by this many thousandths of its own width / height on each side */
+    int32_t min_side;           /* >= 1: a clipped crop narrower or lower than this is not sampled */
+    int32_t area_cap;           /* 1..2^28: the area term of the score saturates here */
+    int32_t occl_iou_pm;        /* 0..1000: another sampled box with IoU above this many thousandths halves the score; 0 = off */
+    int32_t min_gain_pm;        /* 0..10000: a new shot must beat the kept one by more than this many thousandths */
+    int32_t retire_after;       /* >= 0: a row whose track was last sampled more than this many frame ids ago is retired */
+    uint8_t pad_bgr[4];         /* the slot around the image (3 used) */
+    int32_t max_updated;        /* >= 1: entries of `updated` per stream and call */
+    int32_t max_retired;        /* >= 1: entries of `retired` per stream and call */
+    int32_t device;
+    int32_t n_classes;          /* with `classes`: only these class ids are sampled (at most 256); classes == NULL: all */
+    const int32_t *classes;
+} rtmodt_snapshot_cfg;
+/* One thumbnail this call wrote, in list order.  `track`: index into the caller's list, or into the tracker's list. */
+typedef struct rtmodt_snapshot_update {
+    int64_t track_id;
+    int64_t score;
+    int32_t slot, flags, track, reserved;
+} rtmodt_snapshot_update;
+/* One row this call retired, in ascending track id: the best shot's frame id, box, confidence and class. */
+typedef struct rtmodt_snapshot_retired {
+    int64_t track_id;
+    int64_t best_frame, first_seen, last_seen;
+    float xyxy[4];
+    float conf;
+    int32_t slot, cls, n_rewrites;
+} rtmodt_snapshot_retired;
+/* What one call hands back; the struct pointer and every member may be null.  With none given nothing crosses to the host and the
+ * call does not wait for the device; otherwise the streams' result blocks come back in one copy.  One-stream calls: updated
+ * [max_updated], retired [max_retired], counts [1]; all-stream calls: [n_streams][...] and counts [n_streams].  n_updated /
+ * n_retired are the numbers delivered; n_rewritten counts the thumbnails of EXISTING rows this call replaced (new rows excluded). */
+typedef struct rtmodt_snapshot_out {
+    rtmodt_snapshot_update *updated;
+    int32_t *n_updated;
+    rtmodt_snapshot_retired *retired;
+    int32_t *n_retired;
+    int32_t *n_rewritten;
+} rtmodt_snapshot_out;
+/* The plan of one box (the parity surface of csrc/snapshot_rule.h): rectangles are inclusive x0, y0, x1, y1. */
+typedef struct rtmodt_snapshot_plan_out {
+    int32_t sampled;            /* 0: the box is skipped, nothing else is written */
+    int32_t raw[4];             /* truncated corners, neither grown nor clipped */
+    int32_t box[4];             /* raw clipped to the frame (x1 < x0 or y1 < y0: empty) */
+    int32_t crop[4];            /* grown by the margin and clipped: the pixels that are read */
+    int32_t sw, sh;             /* the crop's size */
+    int32_t dw, dh, ox, oy;     /* size and place of the image in the slot */
+    int32_t cut, area;          /* the raw rectangle reaches the frame border; min(area of box, area_cap) */
+} rtmodt_snapshot_plan_out;
+/* thumb 96 x 96, margin 100, min_side 8, area_cap 2^16, occl_iou_pm 300, min_gain_pm 100, retire_after 30, pad 114 114 114 (the
+ * letterbox's grey), max_updated / max_retired 1024, device 0, every class. */
+void rtmodt_snapshot_default_cfg(rtmodt_snapshot_cfg *cfg);
+/* n_streams independent ledgers and thumbnail atlases; max_tracks <= 4096.  A ledger holds 2 x max_tracks rows sorted by track id,
+ * and a stream's atlas one BGR24 slot of thumb_h x thumb_w per row at a row pitch of align_up(3 thumb_w, 16).  The rules, per call
+ * and stream, in this order:
+ *   retire   a row with frame_id - last_seen > retire_after leaves the ledger and is reported in `retired` (a track of the same id
+ *            sampled in this call starts a new row).  Its slot is free from the NEXT call on that stream: until then the
+ *            thumbnail stays intact, which is the host's window to read or encode it;
+ *   score    every sampled box gets its score (snapshot_rule.h);
+ *   keep     a sampled track with a row: last_seen = frame_id; its thumbnail is rewritten iff score * 1000 > best_score * (1000 +
+ *            min_gain_pm), and then best_score / best_frame / box / conf / cls / flags follow and n_rewrites gains one;
+ *   birth    a sampled track without a row takes its shot at once; the new rows of a call take the slots that were free when the
+ *            call began, in ascending slot index, in list order.
+ * Capacity, as the crossing counter's: the call that needs more than 2 x max_tracks rows, or more free slots than there are,
+ * returns RTMODT_E_CAPACITY, the idle rows are dropped (their slots, and those of the rows retired by that call, are reused at once)
+ * and the stream stays in error for good (every later call that asks for output, and _state, returns RTMODT_E_CAPACITY) until
+ * rtmodt_snapshot_reset.  More updated or retired entries than the maxima: RTMODT_E_CAPACITY with the first ones delivered and the
+ * counts reported; every thumbnail is written all the same and the stream goes on working.  A call made without outputs cannot
+ * report either.  The error message names the atlas bytes when the allocation fails. */
+int rtmodt_snapshot_create(const rtmodt_snapshot_cfg *cfg, int n_streams, int max_tracks, rtmodt_snapshot **out);
+/* Waits for the handle's queued work, frees everything; null is allowed. */
+void rtmodt_snapshot_destroy(rtmodt_snapshot *h);
+/* One stream, a caller-supplied track list (any order, unique ids, at most max_tracks) and its frame.  conf may be null: every
+ * entry then scores as confidence 1. */
+int rtmodt_snapshot_process(rtmodt_snapshot *h, int stream, const int64_t *track_ids, const float *xyxy, const float *conf,
+                            const int32_t *cls, int n, const uint8_t *frame, int fh, int fw, int stride_bytes, int mem_kind,
+                            int64_t frame_id, const rtmodt_snapshot_out *out);
+/* Every stream in one call: track_ids / conf / cls [n_streams][stride], xyxy [n_streams][stride][4], n [n_streams], frames
+ * [n_streams] of one geometry, frame_id [n_streams]. */
+int rtmodt_snapshot_process_batch(rtmodt_snapshot *h, const int64_t *track_ids, const float *xyxy, const float *conf, const int32_t *cls,
+                                  const int32_t *n, int stride, const uint8_t *const *frames, int fh, int fw, int stride_bytes,
+                                  int mem_kind, const int64_t *frame_id, const rtmodt_snapshot_out *out);
+/* Every stream of a ByteTrack handle, straight on its device-resident state (box, conf, cls) and on the HIP stream its last update
+ * ran on: exactly the tracks rtmodt_crossing_process_tracker passes.  frames / frame_id [n_streams of the tracker]. */
+int rtmodt_snapshot_process_tracker(rtmodt_snapshot *h, rtmodt_tracker *trk, const uint8_t *const *frames, int fh, int fw,
+                                    int stride_bytes, int mem_kind, const int64_t *frame_id, int report_tsu, const rtmodt_snapshot_out *out);
+/* The same on a DeepSORT handle: the tracks rtmodt_crossing_process_deepsort passes. */
+int rtmodt_snapshot_process_deepsort(rtmodt_snapshot *h, rtmodt_deepsort *ds, const uint8_t *const *frames, int fh, int fw,
+                                     int stride_bytes, int mem_kind, const int64_t *frame_id, int report_tsu, const rtmodt_snapshot_out *out);
+/* The same on an OC-SORT handle: the tracks rtmodt_crossing_process_ocsort passes. */
+int rtmodt_snapshot_process_ocsort(rtmodt_snapshot *h, rtmodt_ocsort *oc, const uint8_t *const *frames, int fh, int fw, int stride_bytes,
+                                   int mem_kind, const int64_t *frame_id, const rtmodt_snapshot_out *out);
+/* The same on a BoT-SORT handle: the tracks rtmodt_crossing_process_botsort passes. */
+int rtmodt_snapshot_process_botsort(rtmodt_snapshot *h, rtmodt_botsort *bot, const uint8_t *const *frames, int fh, int fw, int stride_bytes,
+                                    int mem_kind, const int64_t *frame_id, const rtmodt_snapshot_out *out);
+/* The device address of one stream's atlas: slot s begins at dev_ptr + s * slot_bytes, rows `pitch` bytes apart, so that the JPEG
+ * encoder takes slots where they lie (frame pointers dev_ptr + slot * slot_bytes, h = thumb_h, w = thumb_w, stride = pitch,
+ * RTMODT_MEM_DEVICE).  Waits for the handle's queued work. */
+int rtmodt_snapshot_atlas(rtmodt_snapshot *h, int stream, void **dev_ptr, size_t *slot_bytes, int32_t *pitch);
+/* n thumbnails of one stream to the host, tight thumb_h * thumb_w * 3 bytes each, in the order of slots[n]. */
+int rtmodt_snapshot_read(rtmodt_snapshot *h, int stream, const int32_t *slots, int n, uint8_t *out);
+/* Ledger snapshot of one stream, rows in ascending track id (the parity surface of tests/snapshot_ref.py); any array may be null.
+ * ints[row] = {slot, cls, n_rewrites, flags}; xyxy / conf / cls are the best shot's; bitmap [(2 max_tracks + 31) / 32] words, bit
+ * s set while slot s belongs to a row.  Arrays sized 2 x max_tracks rows.  A stream in error fills them all the same (the rows of
+ * the overflowing call and of the calls since) and returns RTMODT_E_CAPACITY. */
+int rtmodt_snapshot_state(rtmodt_snapshot *h, int stream, int64_t *ids, int64_t *best_score, int64_t *best_frame, int64_t *first_seen,
+                          int64_t *last_seen, float *xyxy, float *conf, int32_t *ints, uint32_t *bitmap, int32_t *n);
+/* Empties one stream's ledger and bitmap, forgets its last frame_id and its error; the atlas bytes stay as they are. */
+int rtmodt_snapshot_reset(rtmodt_snapshot *h, int stream);
+/* Host only, no device needed: the crop rectangle, the fit and the placement of one box xyxy[4] of any class in an h x w frame. */
+int rtmodt_snapshot_plan(const rtmodt_snapshot_cfg *cfg, const float *xyxy, int h, int w, rtmodt_snapshot_plan_out *out);
+/* Stateless, the same resampler without a ledger: box i, xyxy[i] of frames[frame_idx[i]], becomes thumbnail i of `out`, tight
+ * thumb_h * thumb_w * 3 bytes each, in host or device memory (out_mem_kind).  sampled[i] (may be null) = 1 when the box was
+ * sampled; the thumbnail of a box that is not is left untouched.  The class filter does not apply.  Synchronous. */
+int rtmodt_snapshot_crop(rtmodt_snapshot *h, const uint8_t *const *frames, int n_frames, int fh, int fw, int stride_bytes, int mem_kind,
+                         const float *xyxy, const int32_t *frame_idx, int n_boxes, uint8_t *out, int out_mem_kind, int32_t *sampled);
+/* The review queue (low-confidence detections for a human to label), stateless: the detections of the detector's newest batch with
+ * conf_lo <= confidence < conf_hi, read from its device-resident outputs behind the NMS on its post-processing stream -- no box
+ * crosses to the host.  Per frame the first max_out of them (1..max_det) in slot order: thumbnail [frame][k] of `out` ([n][max_out],
+ * tight thumb_h * thumb_w * 3 bytes each, host or device memory), index [n][max_out] = the detection's slot (-1 past the frame's
+ * count), counts [n], sampled [n][max_out] (may be null) = 1 when the box was sampled; other thumbnails are left untouched.
+ * frames [n <= the batch's frames]: the frames the batch was detected on.  The class filter does not apply.  Synchronous. */
+int rtmodt_snapshot_crop_detector(rtmodt_snapshot *h, rtmodt_detector *det, const uint8_t *const *frames, int n, int fh, int fw,
+                                  int stride_bytes, int mem_kind, float conf_lo, float conf_hi, int max_out, uint8_t *out,
+                                  int out_mem_kind, int32_t *index, int32_t *counts, int32_t *sampled);
+/* Device time (ms, HIP events around the two launches) of the last _process*, _crop or _crop_detector call. */
+int rtmodt_snapshot_last_ms(rtmodt_snapshot *h, float *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,31 @@ class SpeedOut(C.Structure):                         # struct rtmodt_speed_out
                 ("n_pairs", C.c_void_p), ("total_pairs", C.c_void_p)]
 
 
+class SnapshotCfg(C.Structure):                      # struct rtmodt_snapshot_cfg
+    _fields_ = [("thumb_h", C.c_int32), ("thumb_w", C.c_int32), ("margin_pm", C.c_int32), ("min_side", C.c_int32), ("area_cap", C.c_int32),
+                ("occl_iou_pm", C.c_int32), ("min_gain_pm", C.c_int32), ("retire_after", C.c_int32), ("pad_bgr", C.c_uint8 * 4),
+                ("max_updated", C.c_int32), ("max_retired", C.c_int32), ("device", C.c_int32), ("n_classes", C.c_int32),
+                ("classes", C.POINTER(C.c_int32))]
+
+
+class SnapshotUpdate(C.Structure):                   # struct rtmodt_snapshot_update
+    _fields_ = [("track_id", C.c_int64), ("score", C.c_int64), ("slot", C.c_int32), ("flags", C.c_int32), ("track", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SnapshotRetired(C.Structure):                  # struct rtmodt_snapshot_retired
+    _fields_ = [("track_id", C.c_int64), ("best_frame", C.c_int64), ("first_seen", C.c_int64), ("last_seen", C.c_int64), ("xyxy", C.c_float * 4),
+                ("conf", C.c_float), ("slot", C.c_int32), ("cls", C.c_int32), ("n_rewrites", C.c_int32)]
+
+
+class SnapshotOut(C.Structure):                      # struct rtmodt_snapshot_out
+    _fields_ = [("updated", C.c_void_p), ("n_updated", C.c_void_p), ("retired", C.c_void_p), ("n_retired", C.c_void_p), ("n_rewritten", C.c_void_p)]
+
+
+class SnapshotPlan(C.Structure):                     # struct rtmodt_snapshot_plan_out
+    _fields_ = [("sampled", C.c_int32), ("raw", C.c_int32 * 4), ("box", C.c_int32 * 4), ("crop", C.c_int32 * 4), ("sw", C.c_int32), ("sh", C.c_int32),
+                ("dw", C.c_int32), ("dh", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("cut", C.c_int32), ("area", C.c_int32)]
+
+
 class RenderCfg(C.Structure):                        # struct rtmodt_render_cfg
     _fields_ = [("show_boxes", C.c_int32), ("show_ids", C.c_int32), ("show_trails", C.c_int32), ("show_zones", C.c_int32),
                 ("show_fps", C.c_int32), ("trail_length", C.c_int32), ("palette_bgr", C.POINTER(C.c_uint8)), ("n_palette", C.c_int32)]
@@ -483,6 +508,23 @@ def lib() -> C.CDLL:
         "rtmodt_lens_undistort_points": (C.c_int, [C.POINTER(LensParams), vp, C.c_int, vp, vp]),
         "rtmodt_lens_build_map": (C.c_int, [C.POINTER(LensParams), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "rtmodt_lens_quantise_map": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "rtmodt_snapshot_default_cfg": (None, [C.POINTER(SnapshotCfg)]),
+        "rtmodt_snapshot_create": (C.c_int, [C.POINTER(SnapshotCfg), C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtmodt_snapshot_destroy": (None, [vp]),
+        "rtmodt_snapshot_process": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_process_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_process_tracker": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_process_deepsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_process_ocsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_process_botsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SnapshotOut)]),
+        "rtmodt_snapshot_atlas": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(i32)]),
+        "rtmodt_snapshot_read": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
+        "rtmodt_snapshot_state": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]),
+        "rtmodt_snapshot_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_snapshot_plan": (C.c_int, [C.POINTER(SnapshotCfg), vp, C.c_int, C.c_int, C.POINTER(SnapshotPlan)]),
+        "rtmodt_snapshot_crop": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
+        "rtmodt_snapshot_crop_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp]),
+        "rtmodt_snapshot_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -56,6 +56,7 @@ static const FrameLimits kAppFrames = {16384, 0, false, "pitch"};        // the 
 static const FrameLimits kPaintFrames = {32768, 65535, true, "stride"};  // render, privacy
 static const FrameLimits kJpegFrames = {0, 0, true, "stride"};           // jpeg, jpeg_dec: the handle's max_h / max_w / max_batch bound them
 static const FrameLimits kGmcFrames = {0, 0, false, "pitch"};            // gmc: GMC_MAX_W x GMC_MAX_H and its streams, checked by the estimator itself
+static const FrameLimits kSnapFrames = {16384, 0, false, "pitch"};       // snapshot: read-only, one frame per stream of the handle (or of the crop call)
 static const FrameLimits kLensFrames = {16384, 65535, true, "pitch"};    // lens: sources and destinations alike (n becomes gridDim.y)
 
 inline int check_mem_kind(int mem_kind) {

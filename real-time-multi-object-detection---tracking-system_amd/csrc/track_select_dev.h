@@ -10,6 +10,7 @@
 
 struct TrackSel {
     const int64_t *ids = nullptr; const float4 *box = nullptr; const int32_t *cls = nullptr;
+    const float *conf = nullptr;                                           // null: a host list without confidences (snapshot.hip reads it)
     const int32_t *tsu = nullptr, *flag = nullptr, *streak = nullptr;      // null: the field does not take part
     int n = 0, want_tsu = 0, min_hits = 0;
     bool early = false;                                                    // OC-SORT: the first min_hits frames return every matched track
@@ -23,26 +24,26 @@ __device__ __forceinline__ TrackSel select_list(const int64_t *ids, const float4
 __device__ __forceinline__ TrackSel select_bytetrack(const TrackerState *st, const int64_t *tm, int report_tsu) {
     const int c = (int)tm[0] & 1;
     TrackSel s;
-    s.ids = st->ids[c]; s.box = st->box[c]; s.cls = st->cls[c]; s.tsu = st->tsu[c]; s.n = (int)tm[1]; s.want_tsu = report_tsu;
+    s.ids = st->ids[c]; s.box = st->box[c]; s.cls = st->cls[c]; s.conf = st->conf[c]; s.tsu = st->tsu[c]; s.n = (int)tm[1]; s.want_tsu = report_tsu;
     return s;
 }
 __device__ __forceinline__ TrackSel select_deepsort(const DsState *st, const int64_t *tm, int report_tsu) {
     const int c = (int)tm[0] & 1;
     TrackSel s;
-    s.ids = st->ids[c]; s.box = st->dbox[c]; s.cls = st->cls[c]; s.tsu = st->tsu[c]; s.flag = st->flag[c]; s.n = (int)tm[1]; s.want_tsu = report_tsu;
+    s.ids = st->ids[c]; s.box = st->dbox[c]; s.cls = st->cls[c]; s.conf = st->conf[c]; s.tsu = st->tsu[c]; s.flag = st->flag[c]; s.n = (int)tm[1]; s.want_tsu = report_tsu;
     return s;
 }
 __device__ __forceinline__ TrackSel select_ocsort(const OcState *st, const int64_t *tm, int min_hits) {
     const int c = (int)tm[0] & 1;
     TrackSel s;
-    s.ids = st->ids[c]; s.box = st->obox[c]; s.cls = st->cls[c]; s.tsu = st->tsu[c]; s.streak = st->streak[c]; s.n = (int)tm[1];
+    s.ids = st->ids[c]; s.box = st->obox[c]; s.cls = st->cls[c]; s.conf = st->conf[c]; s.tsu = st->tsu[c]; s.streak = st->streak[c]; s.n = (int)tm[1];
     s.min_hits = min_hits; s.early = tm[5] <= (int64_t)min_hits;
     return s;
 }
 __device__ __forceinline__ TrackSel select_botsort(const BotState *st, const int64_t *tm) {
     const int c = (int)tm[0] & 1;
     TrackSel s;
-    s.ids = st->ids[c]; s.box = st->dbox[c]; s.cls = st->cls[c]; s.tsu = st->tsu[c]; s.flag = st->flag[c]; s.n = (int)tm[1];
+    s.ids = st->ids[c]; s.box = st->dbox[c]; s.cls = st->cls[c]; s.conf = st->conf[c]; s.tsu = st->tsu[c]; s.flag = st->flag[c]; s.n = (int)tm[1];
     return s;
 }
 // is entry i of the list selected?  (a host list selects every entry)

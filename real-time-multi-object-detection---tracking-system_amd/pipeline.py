@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -118,7 +118,16 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``lens``: a one-stream ``ingestion.LensCorrector`` for the frames' size with its lens set, called inside an ``undistort`` stage
     directly after ``decode`` and before ``motion``: the frame is replaced by the rectified one for every later stage and for the
     recorder, so zones, tripwires, privacy polygons and the ground plane are given in rectified coordinates
-    (``LensCorrector.undistort_points`` carries them over).  ``None``: the loop, the stage table and the summary are unchanged."""
+    (``LensCorrector.undistort_points`` carries them over).  ``None``: the loop, the stage table and the summary are unchanged.
+
+    ``snapshots``: a ``visualization.SnapshotGallery``, called inside a ``snapshots`` stage directly BEFORE ``privacy``: the gallery reads
+    the clean pixels, so its thumbnails are not redacted -- a deployment that wants redacted thumbnails leaves this argument out and
+    calls the gallery itself after ``privacy``.  Like ``speed`` it reads the tracker's device-resident state when the crossings stage
+    would, else the materialised list, and it runs on the held tracks of a motion-gated still frame.  For the device-resident form
+    the gallery must be made with at least the tracker's ``max_tracks`` (2048 for a default ``MultiObjectTracker``; the gallery's own
+    default is 256): ``process_tracker`` raises ``ValueError`` otherwise.  The summary then carries
+    ``snapshots_rewritten`` (thumbnails of existing tracks that a better shot replaced) and ``snapshots_retired`` for stream 0.
+    ``None``: the loop, the stage table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -142,7 +151,11 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("decode") + 1, "undistort")
         profiler.STAGE_ORDER = order
-    n_speed = 0
+    if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
+        profiler.STAGE_ORDER = order
+    n_speed = n_snap_rewritten = n_snap_retired = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     for _ in range(max_frames):
@@ -184,7 +197,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
                             and hasattr(event_engine, "process_tracker"))
         # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
         crossings_on_device = events_on_device
-        if (crossing_counter is not None or speed is not None) and event_engine is None and renderer is None and handoff:
+        if (crossing_counter is not None or speed is not None or snapshots is not None) and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
         if not skip:
             profiler.tick("tracking")
@@ -222,6 +235,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_speed += len(speed.process(tracks, speed.frame_time_us(fid)))
             profiler.tock("speed")
+        if snapshots is not None:
+            profiler.tick("snapshots")
+            if crossings_on_device:
+                _, gone = snapshots.process_tracker(tracker, [frame], fid)
+            else:
+                _, gone = snapshots.process(tracks or [], frame, fid)
+            n_snap_rewritten += snapshots.n_rewritten
+            n_snap_retired += len(gone)
+            profiler.tock("snapshots")
         if privacy is not None:
             profiler.tick("privacy")
             if tracks is None or events_on_device:
@@ -259,6 +281,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["crossings"] = n_crossings
     if speed is not None:
         out["speed_events"] = n_speed
+    if snapshots is not None:
+        out["snapshots_rewritten"], out["snapshots_retired"] = n_snap_rewritten, n_snap_retired
     if swap_guard is not None:
         out["id_swaps_reverted"] = n_reverted
     if motion is not None:
