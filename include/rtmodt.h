@@ -1665,6 +1665,114 @@ int rtmodt_snapshot_crop_detector(rtmodt_snapshot *h, rtmodt_detector *det, cons
 /* Device time (ms, HIP events around the two launches) of the last _process*, _crop or _crop_detector call. */
 int rtmodt_snapshot_last_ms(rtmodt_snapshot *h, float *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Cross-camera linker (csrc/crosscam.hip; the per-pair rules in csrc/crosscam_rule.h): the tracks of n_streams cameras are linked
+ * to site-wide identities.  The reference has no counterpart (its Track has no global id, its tracker sees one source).  PARITY
+ * UNPINNED: no published multi-camera tracker is installed where this runs; every default is validated on no real footage.
+ *
+ * An ENTRY is (local track id, class, int8 row of dim values).  An IDENTITY holds gid (from 1, never reused), class, the smoothed
+ * feature s16 / s8, first_seen and last_seen[n_streams] (the call of the last sighting per stream, 0 never); the table is in gid
+ * order.  Per stream a ledger binds local ids to gids.  The call counter c is 1 in the first call.  Per call, in order:
+ *   1. retire   an identity with c - max(last_seen) > max_age leaves with its bindings and is reported; a binding not sighted for
+ *               more than bind_age calls is dropped;
+ *   2. bound    an entry whose local id is in its stream's ledger is BOUND (its identity is live in the stream); any other entry
+ *               with a non-zero row is a query, numbered in (stream, entry) order; those past max_queries are DEFERRED; a zero
+ *               row is NO_DESCRIPTOR;
+ *   3. sim      dot = <q, s8> (int32), sim = dot <= 0 ? 0 : min(1000, 1000 dot / max(1, isqrt(|q|^2 |s8|^2))), all exact;
+ *   4. match    per stream the exact maximum of sum(sim - min_sim_milli + 1) over the admissible pairs, one-to-one: sim >=
+ *               min_sim_milli, equal classes (match_class), the identity not live in the stream, and some stream f with
+ *               last_seen[f] > 0 and tmin[f][s] <= c - last_seen[f] <= tmax[f][s] on start-of-call values.  A matched query is
+ *               LINKED, an older binding of that identity in the stream is removed.  Past the solver's contested limits (256
+ *               rows / 256 columns / 2048 pairs) the stream's queries are UNBOUND this call and the stream's sticky error is 2;
+ *   5. births   serially in query order over the rest: JOINED to an identity born earlier in this call by another stream (sim
+ *               against its birth feature >= min_sim_milli, equal classes, not live in the stream, tmin[f][s] == 0 <= tmax[f][s]
+ *               for a stream f it is live in; best sim, then lowest gid), else BORN, else TABLE_FULL;
+ *   6. feature  BoT-SORT's integer EMA once per sighting with a non-zero row, in ascending stream order; last_seen[s] = c.
+ * sim of an entry: LINKED against the identity's s8, JOINED against the birth feature, else 0.  An event per LINKED / JOINED
+ * entry, in (stream, entry) order; from_stream = the stream of the greatest start-of-call last_seen (lowest on a tie; JOINED:
+ * the founder's stream, gap 0). */
+typedef struct rtmodt_crosscam rtmodt_crosscam;
+#define RTMODT_CROSSCAM_NONE 0
+#define RTMODT_CROSSCAM_BOUND 1
+#define RTMODT_CROSSCAM_LINKED 2
+#define RTMODT_CROSSCAM_JOINED 3
+#define RTMODT_CROSSCAM_BORN 4
+#define RTMODT_CROSSCAM_NO_DESCRIPTOR 5
+#define RTMODT_CROSSCAM_DEFERRED 6
+#define RTMODT_CROSSCAM_TABLE_FULL 7
+#define RTMODT_CROSSCAM_UNBOUND 8
+typedef struct rtmodt_crosscam_cfg {
+    int32_t device;
+    int32_t n_streams;       /* 1..64                                                                          */
+    int32_t dim;             /* 64..512 in multiples of 64                                                     */
+    int32_t max_tracks;      /* entries per stream per call, 1..256                                            */
+    int32_t max_identities;  /* 1..4096                                                                        */
+    int32_t max_queries;     /* per call over all streams, 1..1024 (with max_identities: the int32 product buffer
+                              * max_queries x (max_identities + max_queries), 21 MB at the caps; design limits)  */
+    int32_t min_sim_milli;   /* 1..1000                                                                        */
+    int32_t max_age;         /* calls                                                                          */
+    int32_t bind_age;        /* calls; 0 = max_age                                                             */
+    int32_t match_class;
+} rtmodt_crosscam_cfg;
+typedef struct rtmodt_crosscam_event {
+    int64_t gid, local_id;
+    int32_t stream, from_stream, gap, sim;
+} rtmodt_crosscam_event;
+typedef struct rtmodt_crosscam_retired {
+    int64_t gid, first_seen, last_seen;
+    uint64_t stream_mask;    /* bit s: the identity was sighted in stream s                                    */
+} rtmodt_crosscam_retired;
+/* Any pointer may be null; with all null nothing is copied back.  gid / status / sim [n_streams][max_tracks]; events
+ * [n_streams * max_tracks]; retired [max_identities]; counters[8] = {call, identities, next gid, queries, deferred, table-full,
+ * events, retired}. */
+typedef struct rtmodt_crosscam_out {
+    int64_t *gid;
+    int32_t *status, *sim;
+    rtmodt_crosscam_event *events;
+    int32_t *n_events;
+    rtmodt_crosscam_retired *retired;
+    int32_t *n_retired;
+    int64_t *counters;
+} rtmodt_crosscam_out;
+void rtmodt_crosscam_default_cfg(rtmodt_crosscam_cfg *cfg);
+/* A parameter outside its range is RTMODT_E_INVALID with nothing allocated.  The transit table starts at (0, max_age) everywhere. */
+int rtmodt_crosscam_create(const rtmodt_crosscam_cfg *cfg, rtmodt_crosscam **out);
+/* Waits for the handle's queued work, frees everything; null is allowed. */
+void rtmodt_crosscam_destroy(rtmodt_crosscam *h);
+/* The camera topology, one ordered pair of streams: min_calls = 0 for overlapping views, > 0 for disjoint ones, max_calls <
+ * min_calls for "cannot get there". */
+int rtmodt_crosscam_set_transit(rtmodt_crosscam *h, int src, int dst, int min_calls, int max_calls);
+/* One call on host lists: track_ids / cls [n_streams][stride], rows [n_streams][stride][dim], n [n_streams].  A local id twice
+ * in one stream's list, or more than max_tracks entries, is RTMODT_E_INVALID with nothing launched.  Float embeddings pass through
+ * rtmodt_appearance_quantize first.  One memset and nine launches, whatever the tracks do; the outputs in one copy. */
+int rtmodt_crosscam_process(rtmodt_crosscam *h, const int64_t *track_ids, const int32_t *cls, const int8_t *rows, const int32_t *n,
+                            int stride, const rtmodt_crosscam_out *out);
+/* One call on a BoT-SORT handle's device-resident state, queued on the HIP stream its last update ran on: the tracks
+ * rtmodt_crossing_process_botsort passes, each with its smoothed int8 feature.  A handle of another dim, stream count or device,
+ * one without appearance, or one with more tracks than max_tracks is RTMODT_E_INVALID with nothing launched. */
+int rtmodt_crosscam_process_botsort(rtmodt_crosscam *h, rtmodt_botsort *bot, const rtmodt_crosscam_out *out);
+/* The same on a DeepSORT handle: confirmed tracks matched this frame, each with the newest row of its gallery ring. */
+int rtmodt_crosscam_process_deepsort(rtmodt_crosscam *h, rtmodt_deepsort *ds, const rtmodt_crosscam_out *out);
+/* The whole state (the parity surface of tests/crosscam_ref.py, and what a restart carries over); any array but header may be
+ * null.  header[3] = {calls so far, next gid, identities n}; gid / cls / first_seen [n], last_seen [n][n_streams], s16 / s8
+ * [n][dim] (arrays sized for max_identities); n_bind [n_streams]; bind_lid / bind_gid / bind_last [n_streams][max_identities], a
+ * stream's bindings in ascending local id.  Waits for the handle's queued work. */
+int rtmodt_crosscam_state(rtmodt_crosscam *h, int64_t *header, int64_t *gid, int32_t *cls, int64_t *first_seen, int64_t *last_seen,
+                          int16_t *s16, int8_t *s8, int32_t *n_bind, int64_t *bind_lid, int64_t *bind_gid, int64_t *bind_last);
+/* Replaces the state by one rtmodt_crosscam_state gave (same n_streams, dim and max_identities); the sticky errors are cleared.
+ * Unordered gids or local ids, a binding to no identity, or counts past the handle are RTMODT_E_INVALID and change nothing. */
+int rtmodt_crosscam_load(rtmodt_crosscam *h, const int64_t *header, const int64_t *gid, const int32_t *cls, const int64_t *first_seen,
+                         const int64_t *last_seen, const int16_t *s16, const int8_t *s8, const int32_t *n_bind, const int64_t *bind_lid,
+                         const int64_t *bind_gid, const int64_t *bind_last);
+/* The sticky error per stream (0 none, 2 the matching was too dense), and its reset. */
+int rtmodt_crosscam_errors(rtmodt_crosscam *h, int32_t *err);
+int rtmodt_crosscam_clear_errors(rtmodt_crosscam *h);
+/* Device time (ms, HIP events around the launches) of the last _process* call. */
+int rtmodt_crosscam_last_ms(rtmodt_crosscam *h, float *kernel_ms);
+/* The GEMM alone, stateless: dots [nq][nt] = q (nq x dim, int8) times t (nt x dim, int8) transposed, exact in int32, and sim
+ * [nq][nt] by rule 3; either output may be null.  nq <= 1024, nt <= 4096.  Synchronous. */
+int rtmodt_crosscam_similarity(int device, const int8_t *q, int nq, const int8_t *t, int nt, int dim, int32_t *dots, int32_t *sim);
+
 #ifdef __cplusplus
 }
 #endif

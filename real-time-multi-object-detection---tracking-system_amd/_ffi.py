@@ -299,6 +299,24 @@ class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
                 ("sims", C.c_int32 * 4)]
 
 
+class CrossCamCfg(C.Structure):                      # struct rtmodt_crosscam_cfg
+    _fields_ = [(k, C.c_int32) for k in ("device", "n_streams", "dim", "max_tracks", "max_identities", "max_queries", "min_sim_milli", "max_age",
+                                         "bind_age", "match_class")]
+
+
+class CrossCamEventRec(C.Structure):                 # struct rtmodt_crosscam_event
+    _fields_ = [("gid", C.c_int64), ("local_id", C.c_int64), ("stream", C.c_int32), ("from_stream", C.c_int32), ("gap", C.c_int32), ("sim", C.c_int32)]
+
+
+class CrossCamRetiredRec(C.Structure):               # struct rtmodt_crosscam_retired
+    _fields_ = [("gid", C.c_int64), ("first_seen", C.c_int64), ("last_seen", C.c_int64), ("stream_mask", C.c_uint64)]
+
+
+class CrossCamOut(C.Structure):                      # struct rtmodt_crosscam_out
+    _fields_ = [("gid", C.c_void_p), ("status", C.c_void_p), ("sim", C.c_void_p), ("events", C.c_void_p), ("n_events", C.POINTER(C.c_int32)),
+                ("retired", C.c_void_p), ("n_retired", C.POINTER(C.c_int32)), ("counters", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -525,6 +543,19 @@ def lib() -> C.CDLL:
         "rtmodt_snapshot_crop": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
         "rtmodt_snapshot_crop_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp]),
         "rtmodt_snapshot_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_crosscam_default_cfg": (None, [C.POINTER(CrossCamCfg)]),
+        "rtmodt_crosscam_create": (C.c_int, [C.POINTER(CrossCamCfg), C.POINTER(vp)]),
+        "rtmodt_crosscam_destroy": (None, [vp]),
+        "rtmodt_crosscam_set_transit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_crosscam_process": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.POINTER(CrossCamOut)]),
+        "rtmodt_crosscam_process_botsort": (C.c_int, [vp, vp, C.POINTER(CrossCamOut)]),
+        "rtmodt_crosscam_process_deepsort": (C.c_int, [vp, vp, C.POINTER(CrossCamOut)]),
+        "rtmodt_crosscam_state": (C.c_int, [vp] * 12),
+        "rtmodt_crosscam_load": (C.c_int, [vp] * 12),
+        "rtmodt_crosscam_errors": (C.c_int, [vp, vp]),
+        "rtmodt_crosscam_clear_errors": (C.c_int, [vp]),
+        "rtmodt_crosscam_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_crosscam_similarity": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

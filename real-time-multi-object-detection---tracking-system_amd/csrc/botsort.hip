@@ -494,6 +494,11 @@ int botsort_device_view(rtmodt_botsort *t, BotDeviceView *out) {
     out->states = t->d_states;
     return track_view(t, out);
 }
+int botsort_feature_view(rtmodt_botsort *t, const int8_t **feat8, int *dim) {
+    RT_CHECK(t && feat8 && dim, RTMODT_E_INVALID, "null argument");
+    *feat8 = t->d_feat8; *dim = t->dim;
+    return RTMODT_OK;
+}
 }  // namespace rtmodt
 
 static int bot_create_impl(rtmodt_botsort *t) {

@@ -284,6 +284,11 @@ int deepsort_device_view(rtmodt_deepsort *t, DsDeviceView *out) {
     out->states = t->d_states;
     return track_view(t, out);
 }
+int deepsort_gallery_view(rtmodt_deepsort *t, const int8_t **gallery, int *dim, int *budget) {
+    RT_CHECK(t && gallery && dim && budget, RTMODT_E_INVALID, "null argument");
+    *gallery = t->gallery; *dim = t->dim; *budget = t->budget;
+    return RTMODT_OK;
+}
 }  // namespace rtmodt
 
 static int ds_create_impl(rtmodt_deepsort *t) {

@@ -316,6 +316,8 @@ int tracker_device_view_mut(rtmodt_tracker *trk, TrackerDeviceViewMut *out);
 // the same of the DeepSORT tracker (deepsort.hip), consumed by the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, ...}
 struct DsDeviceView : TrackViewBase { const DsState *states; };
 int deepsort_device_view(rtmodt_deepsort *ds, DsDeviceView *out);
+// the gallery beside it, read-only, for the cross-camera linker (crosscam.hip): [stream][slot][budget][dim] int8
+int deepsort_gallery_view(rtmodt_deepsort *ds, const int8_t **gallery, int *dim, int *budget);
 
 // OC-SORT (ocsort.hip): one stream's state; device pointers; double-buffered like DsState
 constexpr int OC_MAX_TRACKS = 256, OC_MAX_DETS = 1024, OC_MAX_STREAMS = 64, OC_RING = 8;      // OC_RING = the largest delta_t (a power of two)
@@ -341,6 +343,9 @@ struct BotState {
 // its view for the crossing counter (crossing.hip); meta[n_streams][8] = {cur, n_tracks, err, n_returned, next_id, frame_count, ...}
 struct BotDeviceView : TrackViewBase { const BotState *states; };
 int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
+// the smoothed int8 features beside it, read-only, for the cross-camera linker (crosscam.hip): [stream][2][max_tracks][dim], the
+// rows of buffer meta[0] & 1 current; null and dim 0 for a motion-only handle
+int botsort_feature_view(rtmodt_botsort *bot, const int8_t **feat8, int *dim);
 
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };

@@ -1,4 +1,5 @@
 from .botsort import BotSortTracker
+from .crosscam import CrossCameraLinker, HandoffEvent
 from .deepsort import DeepSortTracker
 from .gmc import CameraMotionEstimator
 from .ocsort import OcSortTracker
@@ -6,4 +7,4 @@ from .reid import ReidEmbedder
 from .swapguard import IdSwapGuard, SwapEvent
 from .tracker import MultiObjectTracker, Track
 
-__all__ = ["BotSortTracker", "CameraMotionEstimator", "DeepSortTracker", "IdSwapGuard", "MultiObjectTracker", "OcSortTracker", "ReidEmbedder", "SwapEvent", "Track"]
+__all__ = ["BotSortTracker", "CameraMotionEstimator", "CrossCameraLinker", "DeepSortTracker", "HandoffEvent", "IdSwapGuard", "MultiObjectTracker", "OcSortTracker", "ReidEmbedder", "SwapEvent", "Track"]
