@@ -1773,6 +1773,88 @@ int rtmodt_crosscam_last_ms(rtmodt_crosscam *h, float *kernel_ms);
  * [nq][nt] by rule 3; either output may be null.  nq <= 1024, nt <= 4096.  Synchronous. */
 int rtmodt_crosscam_similarity(int device, const int8_t *q, int nq, const int8_t *t, int nt, int dim, int32_t *dots, int32_t *sim);
 
+/* ---- compositor: video-wall mosaics, sub-streams and zoom insets, BGR24 or 4:2:0 out ---- */
+/* A static LAYOUT (sources, outputs, cells) is set once and kept on the device; one RUN per frame set reads the sources where they
+ * lie and writes every output in ONE launch.  csrc/compose_rule.h states every rule (crop, fit, the three kinds of axis, the
+ * one-rounding pixel, painting order, the forward BT.601 conversion), tests/compose_ref.py restates them and every output byte
+ * equals that restatement.  No reference counterpart (its web page shows one image and tools/run_pipeline.py writes the full frame);
+ * PARITY UNPINNED against cv2.resize (INTER_AREA / INTER_LINEAR), cv2.cvtColor(COLOR_BGR2YUV_I420) and any encoder's reading of
+ * the NV12.  Not here: text and borders (the renderer draws on an output), alpha blending, other filters, BT.709 / full range. */
+typedef struct rtmodt_compose rtmodt_compose;
+#define RTMODT_COMPOSE_STRETCH 0   /* the crop is mapped onto the whole rectangle                                              */
+#define RTMODT_COMPOSE_FIT 1       /* aspect kept, picture centred, the bars take the cell's pad colour                         */
+#define RTMODT_COMPOSE_FILL 2      /* aspect kept, the crop is cut centrally until it covers the rectangle: no bars             */
+#define RTMODT_COMPOSE_SHRINK 0    /* kinds of axis in rtmodt_compose_plan_out: exact area average                              */
+#define RTMODT_COMPOSE_COPY 1      /* one tap                                                                                   */
+#define RTMODT_COMPOSE_ENLARGE 2   /* two taps with 11-bit weights (cv::resize INTER_LINEAR tables)                             */
+typedef struct rtmodt_compose_cfg {
+    int32_t device;
+    int32_t max_sources;   /* 64: 1..64                                                                                      */
+    int32_t max_outputs;   /* 16: 1..16                                                                                      */
+    int32_t max_cells;     /* 64: cells per output, 1..64                                                                    */
+    int32_t max_dim;       /* 16384: largest height / width of a source or an output, 1..16384                               */
+} rtmodt_compose_cfg;
+typedef struct rtmodt_compose_src_desc { int32_t h, w; } rtmodt_compose_src_desc;          /* BGR24 */
+typedef struct rtmodt_compose_out_desc {
+    int32_t h, w;
+    int32_t pixel_format;        /* RTMODT_PIX_BGR24 / _NV12 / _I420 (4:2:0: h and w even)                                    */
+    uint8_t background_bgr[3];   /* every pixel no cell covers                                                               */
+    uint8_t reserved;
+} rtmodt_compose_out_desc;
+typedef struct rtmodt_compose_cell {
+    int32_t output, source;
+    int32_t x, y, w, h;                          /* the rectangle inside the output, NOT clipped (4:2:0 outputs: all four even)   */
+    int32_t crop_x, crop_y, crop_w, crop_h;      /* the part of the source shown, inside the source; 0, 0, 0, 0 = all of it       */
+    int32_t fit;                                 /* RTMODT_COMPOSE_STRETCH / _FIT / _FILL                                         */
+    uint8_t pad_bgr[3];                          /* FIT's bars                                                                    */
+    uint8_t reserved0;
+    uint8_t offline_bgr[3];                      /* the whole rectangle in a run whose source pointer is null (camera down)       */
+    uint8_t reserved1;
+} rtmodt_compose_cell;
+typedef struct rtmodt_compose_plan_out {
+    int32_t crop[4];             /* x, y, w, h of the effective crop inside the source (FILL cuts it)                          */
+    int32_t inner[4];            /* x, y, w, h of the picture inside the OUTPUT (FIT shrinks it; 4:2:0: even)                   */
+    int32_t kind_x, kind_y;      /* RTMODT_COMPOSE_SHRINK / _COPY / _ENLARGE                                                   */
+} rtmodt_compose_plan_out;
+/* Host only: the limits above, device 0.  No reference counterpart, PARITY UNPINNED. */
+void rtmodt_compose_default_cfg(rtmodt_compose_cfg *cfg);
+/* Host only (the device is first touched by set_layout): a limit outside its range is RTMODT_E_INVALID.  No reference
+ * counterpart, PARITY UNPINNED. */
+int rtmodt_compose_create(const rtmodt_compose_cfg *cfg, rtmodt_compose **out);
+void rtmodt_compose_destroy(rtmodt_compose *h);
+/* Replaces the layout.  cells[] is the painting order: a later cell lies on top.  EVERYTHING is checked before anything is allocated
+ * or touched: counts past the handle's limits are RTMODT_E_CAPACITY; a size outside 1..max_dim, an odd 4:2:0 size or rectangle, an
+ * unknown format or fit, an index outside its list, a rectangle that leaves its output or a crop that leaves its source are
+ * RTMODT_E_INVALID.  A rejected layout leaves the previous one in force.  The tile work list and the enlarging axes' tables are
+ * built here and kept on the device.  No reference counterpart, PARITY UNPINNED. */
+int rtmodt_compose_set_layout(rtmodt_compose *h, const rtmodt_compose_src_desc *sources, int n_sources, const rtmodt_compose_out_desc *outputs,
+                              int n_outputs, const rtmodt_compose_cell *cells, int n_cells);
+/* Re-plans ONE cell (follow-zoom): its crop becomes x, y, w, h (0, 0, 0, 0: the whole source); the rest of the layout, the tile
+ * work list included, is left alone.  A crop that leaves the source is RTMODT_E_INVALID and changes nothing.  No reference
+ * counterpart, PARITY UNPINNED. */
+int rtmodt_compose_set_crop(rtmodt_compose *h, int cell, int x, int y, int w, int hgt);
+/* One run, one launch.  src[n_sources]: BGR24 frames, src_pitch[i] bytes per row (src_pitch null: 3w), host or device per
+ * src_mem_kind; a null src[i] is a camera that is down: its cells show their offline colour.  dst[n_outputs] with dst_fmt[i]
+ * placing output i's planes as rtmodt_detector_enqueue_batch_fmt reads them (same zero defaults, same checks; dst_fmt null: all
+ * defaults; the pixel format must be the layout's).  Device destinations are written in place; a host destination is composed in
+ * the handle's own buffer of that output and its rows are copied back; a null dst[i] (or dst null) leaves output i in the handle's
+ * own buffer (rtmodt_compose_output).  Only a row's 3w bytes (w per plane row) are ever written.  Refused with RTMODT_E_INVALID
+ * before anything is launched or written: no layout, a bad mem_kind, pitch or format, a destination that overlaps a source or
+ * another destination.  No reference counterpart, PARITY UNPINNED. */
+int rtmodt_compose_run(rtmodt_compose *h, const uint8_t *const *src, const int32_t *src_pitch, int src_mem_kind, uint8_t *const *dst,
+                       const rtmodt_frame_format *dst_fmt, int dst_mem_kind);
+/* The handle's own device buffer of output i, as rtmodt_snapshot_atlas hands out the atlas: rtmodt_render_batch and
+ * rtmodt_jpeg_encode_batch take a BGR24 output where it lies.  pitch: bytes per row (BGR24) or per Y row; a 4:2:0 output's chroma
+ * follows with rtmodt_frame_format's defaults for that pitch.  Valid until the next set_layout.  No reference counterpart, PARITY
+ * UNPINNED. */
+int rtmodt_compose_output(rtmodt_compose *h, int i, uint8_t **dev_ptr, size_t *pitch);
+/* Device time (ms, HIP events around the launch) of the last run.  No reference counterpart. */
+int rtmodt_compose_last_ms(rtmodt_compose *h, float *kernel_ms);
+/* Host only: set_layout's checks (against the largest limits) and, per cell, what it would plan: plans[n_cells].  Python's point
+ * mapping and the tests read it.  No reference counterpart, PARITY UNPINNED. */
+int rtmodt_compose_plan(const rtmodt_compose_src_desc *sources, int n_sources, const rtmodt_compose_out_desc *outputs, int n_outputs,
+                        const rtmodt_compose_cell *cells, int n_cells, rtmodt_compose_plan_out *plans);
+
 #ifdef __cplusplus
 }
 #endif

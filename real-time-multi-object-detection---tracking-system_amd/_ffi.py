@@ -317,6 +317,28 @@ class CrossCamOut(C.Structure):                      # struct rtmodt_crosscam_ou
                 ("retired", C.c_void_p), ("n_retired", C.POINTER(C.c_int32)), ("counters", C.c_void_p)]
 
 
+class ComposeCfg(C.Structure):                      # struct rtmodt_compose_cfg
+    _fields_ = [(k, C.c_int32) for k in ("device", "max_sources", "max_outputs", "max_cells", "max_dim")]
+
+
+class ComposeSource(C.Structure):                   # struct rtmodt_compose_src_desc
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32)]
+
+
+class ComposeOutput(C.Structure):                   # struct rtmodt_compose_out_desc
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("pixel_format", C.c_int32), ("background_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class ComposeCell(C.Structure):                     # struct rtmodt_compose_cell
+    _fields_ = [("output", C.c_int32), ("source", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("fit", C.c_int32),
+                ("pad_bgr", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("offline_bgr", C.c_uint8 * 3), ("reserved1", C.c_uint8)]
+
+
+class ComposePlan(C.Structure):                     # struct rtmodt_compose_plan_out
+    _fields_ = [("crop", C.c_int32 * 4), ("inner", C.c_int32 * 4), ("kind_x", C.c_int32), ("kind_y", C.c_int32)]
+
+
 _lib = None
 
 
@@ -556,6 +578,15 @@ def lib() -> C.CDLL:
         "rtmodt_crosscam_clear_errors": (C.c_int, [vp]),
         "rtmodt_crosscam_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_crosscam_similarity": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+        "rtmodt_compose_default_cfg": (None, [C.POINTER(ComposeCfg)]),
+        "rtmodt_compose_create": (C.c_int, [C.POINTER(ComposeCfg), C.POINTER(vp)]),
+        "rtmodt_compose_destroy": (None, [vp]),
+        "rtmodt_compose_set_layout": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int]),
+        "rtmodt_compose_set_crop": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rtmodt_compose_run": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int]),
+        "rtmodt_compose_output": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]),
+        "rtmodt_compose_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_compose_plan": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp]),
         "rtmodt_renderer_create": (C.c_int, [C.c_int, C.POINTER(RenderCfg), C.POINTER(vp)]),
         "rtmodt_renderer_destroy": (None, [vp]),
         "rtmodt_renderer_set_zones": (C.c_int, [vp, vp, vp, vp, C.c_int]),

@@ -65,7 +65,7 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -127,7 +127,12 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     the gallery must be made with at least the tracker's ``max_tracks`` (2048 for a default ``MultiObjectTracker``; the gallery's own
     default is 256): ``process_tracker`` raises ``ValueError`` otherwise.  The summary then carries
     ``snapshots_rewritten`` (thumbnails of existing tracks that a better shot replaced) and ``snapshots_retired`` for stream 0.
-    ``None``: the loop, the stage table and the summary are unchanged."""
+    ``None``: the loop, the stage table and the summary are unchanged.
+
+    ``compose``: a one-source ``visualization.Compositor`` for the frames' size (``Compositor.substream(...)``, or any layout of one
+    source whose output 0 is BGR24), called inside a ``compose`` stage directly after ``visualization``: the annotated frame is
+    scaled on the GPU and the recorder receives output 0 -- the sub-stream -- instead of the full frame.  ``None``: the loop, the
+    stage table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -154,6 +159,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
+        profiler.STAGE_ORDER = order
+    if compose is not None and "compose" not in profiler.STAGE_ORDER:          # likewise, directly after visualization
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("visualization") + 1, "compose")
         profiler.STAGE_ORDER = order
     n_speed = n_snap_rewritten = n_snap_retired = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
@@ -266,9 +275,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             renderer.render(frame, tracks, zones=zones, fps=profiler.current_fps,
                             latency_ms=sum(profiler._frame_ms.values()) if profiler._frame_ms else 0)
             profiler.tock("visualization")
+        shown = frame
+        if compose is not None:
+            profiler.tick("compose")
+            shown = compose.run([frame])[0]
+            profiler.tock("compose")
         profiler.end_frame()
         if recorder is not None:                           # tools/run_pipeline.py:160-161
-            recorder.write(frame)
+            recorder.write(shown)
     out = profiler.summary(p50=True)
     out["frames"] = max_frames
     out["last_detections"] = 0 if detections is None else len(detections)

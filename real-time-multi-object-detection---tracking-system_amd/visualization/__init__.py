@@ -1,3 +1,4 @@
+from .compose import Cell, Compositor, Output
 from .heatmap import Heatmap
 from .jpeg import JpegEncoder, MjpegRecorder, MjpegWriter, multipart_chunk
 from .privacy import PrivacyMask
@@ -5,4 +6,4 @@ from .renderer import FrameRenderer
 from .snapshots import SnapshotGallery, SnapshotRetired, SnapshotUpdate
 
 __all__ = ["FrameRenderer", "JpegEncoder", "MjpegWriter", "MjpegRecorder", "multipart_chunk", "PrivacyMask", "Heatmap", "SnapshotGallery",
-           "SnapshotUpdate", "SnapshotRetired"]
+           "SnapshotUpdate", "SnapshotRetired", "Compositor", "Cell", "Output"]
