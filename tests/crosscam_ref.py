@@ -275,6 +275,19 @@ class CrossCamRef:
         return dict(gid=gid, status=status, sim=sim, events=ev, retired=retired)
 
     # ---- the state as rtmodt_crosscam_state hands it out ----
+    def load(self, snap):
+        """The counterpart of rtmodt_crosscam_load: the call counter, next gid, table and ledgers of a snapshot; err is cleared."""
+        S, D = self.S, self.D
+        n = len(snap["gid"])
+        assert n <= self.I and len(snap["ledgers"]) == S
+        last = np.asarray(snap["last_seen"], np.int64).reshape(n, S)
+        s16, s8 = np.asarray(snap["s16"], np.int64).reshape(n, D), np.asarray(snap["s8"], np.int64).reshape(n, D)
+        self.c, self.next_gid = int(snap["call"]), int(snap["next_gid"])
+        self.table = [Identity(int(snap["gid"][i]), int(snap["cls"][i]), s16[i].tolist(), s8[i].tolist(), int(snap["first_seen"][i]), last[i].tolist())
+                      for i in range(n)]
+        self.ledgers = [{int(l): [int(g), int(t)] for l, g, t in np.asarray(led, np.int64).reshape(-1, 3)} for led in snap["ledgers"]]
+        self.err = [0] * S
+
     def snapshot(self):
         n = len(self.table)
         t = dict(call=self.c, next_gid=self.next_gid,
