@@ -1446,6 +1446,160 @@ int rtmodt_motion_last_ms(rtmodt_motion *m, float *kernel_ms);
  * learn_shift_fg, threshold, dev_gain, warmup).  The parity surface of csrc/motion_model.h.  PARITY UNPINNED. */
 int rtmodt_motion_cell(const rtmodt_motion_cfg *cfg, uint32_t yc, int32_t frames_seen, uint16_t *bg, uint16_t *dev, int32_t *raw);
 
+/* ---- left / removed objects: static foreground the detector has no class for ------------------------------------------------- */
+/* A bag left on a platform, a car in a no-parking bay, an exhibit taken away: things that stop moving (the motion detector folds
+ * them into its background) and that the 80 classes do not name.  The reference fires on tracked objects only (zone_engine.py) and
+ * has no counterpart: PARITY UNPINNED throughout, no default validated on real footage.  PINNED, exactly, against
+ * tests/leftobj_ref.py: the cell state, the mask, the regions, the ledger, the events and every count.  csrc/leftobj_rule.h states
+ * the rules, csrc/leftobj.hip's header the mask, the regions and the launches; all of it is integer arithmetic.  DELIBERATE LIMITS:
+ * a fixed camera (no camera-motion compensation), one luma channel, each handle reads its frames itself (no pixel pass shared with
+ * the motion detector).  A handle holds, per stream, the 8-byte cell state of a ceil(height / scale) x ceil(width / scale) grid
+ * (bg | cand << 16, unsigned 8.8 fixed point; age << 32; miss << 48; flags << 56, bit 0 = ignore), frames_seen, the last luma grid,
+ * the last mask and the object ledger. */
+#define RTMODT_LEFTOBJ_WARMUP 0         /* frames_seen < warmup at entry                                                            */
+#define RTMODT_LEFTOBJ_CLEAR 1          /* no region                                                                                */
+#define RTMODT_LEFTOBJ_STATIC 2         /* at least one region of static foreground                                                 */
+#define RTMODT_LEFTOBJ_SCENE_CHANGE 3   /* 1000 * n_fg >= scene_pm * cells: the model restarts, every ledger entry retires RESET    */
+#define RTMODT_LEFTOBJ_UNKNOWN 0        /* kinds                                                                                    */
+#define RTMODT_LEFTOBJ_ABANDONED 1      /* the region's edge is in the picture                                                      */
+#define RTMODT_LEFTOBJ_REMOVED 2        /* the region's edge is in the background model                                             */
+#define RTMODT_LEFTOBJ_TRACKED_STATIC 3 /* covered by a track of a report class                                                     */
+#define RTMODT_LEFTOBJ_CLEARED 1        /* retirement reasons: unmatched for more than miss_frames calls                            */
+#define RTMODT_LEFTOBJ_ABSORBED 2       /* older than absorb_frames: folded into the background                                     */
+#define RTMODT_LEFTOBJ_RESET 3          /* a scene change                                                                           */
+#define RTMODT_LEFTOBJ_TRACKS_NONE 0    /* track sources                                                                            */
+#define RTMODT_LEFTOBJ_TRACKS_LIST 1    /* host lists, one per frame of the call                                                    */
+#define RTMODT_LEFTOBJ_TRACKS_BYTETRACK 2
+#define RTMODT_LEFTOBJ_TRACKS_DEEPSORT 3
+#define RTMODT_LEFTOBJ_TRACKS_OCSORT 4
+#define RTMODT_LEFTOBJ_TRACKS_BOTSORT 5
+typedef struct rtmodt_leftobj rtmodt_leftobj;
+typedef struct rtmodt_leftobj_cfg {
+    int32_t streams;            /* 1..1024                                                                                      */
+    int32_t height, width;      /* the frame size, 1..32768 each; the grid at most 2^24 cells, all streams 2^28                 */
+    int32_t scale;              /* 1, 2, 4 or 8 pixels per cell side                                                            */
+    int32_t warmup;             /* 1..255 frames that only learn                                                                */
+    int32_t warm_shift;         /* 1..8: bg += (t - bg) >> warm_shift during the warm-up                                        */
+    int32_t learn_shift;        /* 1..12: the same for background cells afterwards                                              */
+    int32_t threshold;          /* 1..255 luma levels: fg = |t - bg| > threshold << 8                                           */
+    int32_t stable;             /* 1..255 luma levels: a foreground cell is stable while |t - cand| <= stable << 8              */
+    int32_t cand_shift;         /* 1..8: cand += (t - cand) >> cand_shift on a stable cell                                      */
+    int32_t occlusion;          /* 0..254 frames a candidate survives something else in front of it                             */
+    int32_t static_frames;      /* 1..65535: static = age >= static_frames                                                      */
+    int32_t min_neighbors;      /* 1..9 static cells in the 3 x 3 neighbourhood (the cell included) for a mask cell             */
+    int32_t min_area, max_area; /* 1 <= min_area <= max_area cells for a component to be a region                               */
+    int32_t max_regions;        /* 1..256 regions stored per frame                                                              */
+    int32_t scene_pm;           /* 1..1000 per mille of foreground cells                                                        */
+    int32_t max_objects;        /* 1..256 ledger entries per stream                                                             */
+    int32_t miss_frames;        /* 0..65535 unmatched calls an entry survives                                                   */
+    int32_t alarm_frames;       /* 1..2^30 idle calls until the event                                                           */
+    int32_t absorb_frames;      /* 0: never; else 1..2^30 frames after first_frame                                              */
+    int32_t covered_pm;         /* 1..1000 per mille of the region's pixel box                                                  */
+    int32_t attend_margin;      /* 0..32768 pixels                                                                              */
+    int32_t max_tracks;         /* 1..4096 tracks per list                                                                      */
+    int32_t n_owner_classes;    /* 0..8                                                                                         */
+    int32_t owner_classes[8];
+    int32_t n_report_classes;   /* 0..8                                                                                         */
+    int32_t report_classes[8];
+    int32_t device;
+} rtmodt_leftobj_cfg;
+typedef struct rtmodt_leftobj_result {
+    int32_t status;             /* RTMODT_LEFTOBJ_WARMUP .. SCENE_CHANGE                                                        */
+    int32_t stream;
+    int32_t frames_seen;        /* after the call: 0 after a SCENE_CHANGE                                                       */
+    uint32_t n_fg, n_static;    /* foreground cells; mask cells                                                                 */
+    int32_t n_regions;          /* stored: min(n_regions_total, max_regions)                                                    */
+    int32_t n_regions_total;
+    int32_t n_objects;          /* ledger entries after the call                                                                */
+    int32_t n_events, n_retired;
+    int32_t dropped;            /* births of this call that found the ledger full                                               */
+    int32_t next_oid;           /* the oid the next birth takes                                                                 */
+} rtmodt_leftobj_result;
+typedef struct rtmodt_leftobj_region {
+    int32_t box[4];             /* pixels x0, y0, x1, y1 (x1, y1 exclusive)                                                     */
+    int32_t cells[4];           /* cx0, cy0, cx1, cy1 (inclusive)                                                               */
+    int32_t area;               /* cells                                                                                        */
+    int32_t kind;               /* UNKNOWN, ABANDONED or REMOVED by the edge test                                               */
+    int32_t age_min, age_max;
+    int32_t covered;            /* bit 0: by a selected track; bit 1: by one of a report class                                  */
+    int32_t attended;
+    int32_t oid;                /* the ledger entry it matched or bore; 0: none (dropped, or a scene change)                    */
+    int32_t root;               /* the region's first cell in raster order                                                      */
+} rtmodt_leftobj_region;
+typedef struct rtmodt_leftobj_object {
+    int64_t first_frame;
+    int64_t owner;              /* the last attending track id, -1: none yet                                                    */
+    int32_t oid, kind, area, idle, unmatched, alarmed;
+    int32_t cells[4];
+    int32_t box[4];
+} rtmodt_leftobj_object;
+typedef struct rtmodt_leftobj_event {
+    int64_t first_frame, frame_id, owner;
+    int32_t oid, kind, area, reserved;
+    int32_t box[4];
+} rtmodt_leftobj_event;
+typedef struct rtmodt_leftobj_retired { int32_t oid, reason, alarmed, reserved; } rtmodt_leftobj_retired;
+typedef struct rtmodt_leftobj_tracks {
+    int32_t source;             /* RTMODT_LEFTOBJ_TRACKS_*                                                                      */
+    int32_t stride;             /* LIST: entries per row of the arrays below                                                    */
+    const int64_t *ids;         /* LIST: [n][stride]                                                                            */
+    const float *xyxy;          /*       [n][stride][4]                                                                         */
+    const int32_t *cls;         /*       [n][stride]                                                                            */
+    const int32_t *n;           /*       [n] entries used, each 0..min(stride, max_tracks)                                      */
+    void *tracker;              /* BYTETRACK .. BOTSORT: the handle; its stream s is this handle's stream s                     */
+    int32_t report_tsu;         /* BYTETRACK, DEEPSORT: the time_since_update that selects a track (csrc/track_select_dev.h)    */
+    int32_t reserved;
+} rtmodt_leftobj_tracks;
+typedef struct rtmodt_leftobj_out {          /* any pointer may be NULL; all NULL (or out == NULL): nothing is copied back      */
+    rtmodt_leftobj_result *results;          /* [n]                                                                             */
+    rtmodt_leftobj_region *regions;          /* [n][max_regions]                                                                */
+    rtmodt_leftobj_event *events;            /* [n][2 * max_objects]: old rows that alarm, then births that alarm               */
+    rtmodt_leftobj_retired *retired;         /* [n][max_objects]                                                                */
+    rtmodt_leftobj_object *objects;          /* [n][max_objects]: the ledger after the call                                     */
+} rtmodt_leftobj_out;
+/* Host only: 1 stream, no frame size, scale 4, warmup 8, warm_shift 2, learn_shift 6, threshold 16, stable 10, cand_shift 3,
+ * occlusion 50, static_frames 100, min_neighbors 4, min_area 4, max_area 2^24, max_regions 32, scene_pm 600, max_objects 64,
+ * miss_frames 50, alarm_frames 250, absorb_frames 0, covered_pm 500, attend_margin 32, max_tracks 256, owner class 0, no report
+ * class.  No default has been validated on real footage.  PARITY UNPINNED. */
+void rtmodt_leftobj_default_cfg(rtmodt_leftobj_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range is RTMODT_E_INVALID, a grid above 2^24 cells (or
+ * 2^28 over all streams) RTMODT_E_CAPACITY.  PARITY UNPINNED. */
+int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_leftobj_destroy(rtmodt_leftobj *p);
+/* One frame for each of n distinct streams, as rtmodt_motion_process takes them; frame_ids[i] is the frame's number (first_frame
+ * and the absorb timer count in it).  tracks == NULL: no tracks.  A frame size other than the handle's, a null frame, a stream out
+ * of range or named twice, n above the stream count, a list longer than max_tracks and a tracker whose stream count differs from
+ * the handle's are RTMODT_E_INVALID with nothing launched.  Nine launches and one memset, whatever the frames show; everything out
+ * asks for comes back in one copy.  Streams the call does not name keep their state.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, const int32_t *streams, const int64_t *frame_ids, int n, int height,
+                           int width, int stride_bytes, int mem_kind, const rtmodt_leftobj_tracks *tracks, const rtmodt_leftobj_out *out);
+/* One stream's model: the cells as uint64[gh][gw] (layout above), the last luma grid uint8[gh][gw], frames_seen.  cells or luma
+ * may be NULL.  PARITY UNPINNED. */
+int rtmodt_leftobj_read_state(rtmodt_leftobj *p, int stream, uint64_t *cells, uint8_t *luma, int32_t *frames_seen);
+/* Replaces one stream's model (frames_seen 0..2^30), the ignore bits included, so that it survives a restart.  PARITY UNPINNED. */
+int rtmodt_leftobj_load_state(rtmodt_leftobj *p, int stream, const uint64_t *cells, const uint8_t *luma, int32_t frames_seen);
+/* The mask of the stream's last frame, uint8[gh][gw] of 0 / 1.  PARITY UNPINNED. */
+int rtmodt_leftobj_read_mask(rtmodt_leftobj *p, int stream, uint8_t *out);
+/* Replaces it (entries 0 / 1), so that a restarted handle answers as the one it was saved from.  PARITY UNPINNED. */
+int rtmodt_leftobj_load_mask(rtmodt_leftobj *p, int stream, const uint8_t *mask);
+/* The ledger: *n entries in oid order (objects holds max_objects), and the oid the next birth takes.  PARITY UNPINNED. */
+int rtmodt_leftobj_read_ledger(rtmodt_leftobj *p, int stream, rtmodt_leftobj_object *objects, int32_t *n, int32_t *next_oid);
+/* Replaces the ledger: n <= max_objects entries with oids ascending, each below next_oid, next_oid >= 1.  PARITY UNPINNED. */
+int rtmodt_leftobj_load_ledger(rtmodt_leftobj *p, int stream, const rtmodt_leftobj_object *objects, int n, int32_t next_oid);
+/* The ignore grid, uint8[gh][gw]: a cell whose entry is not 0 is never static.  The rest of the cell state stays.  PARITY UNPINNED. */
+int rtmodt_leftobj_set_ignore(rtmodt_leftobj *p, int stream, const uint8_t *grid);
+int rtmodt_leftobj_read_ignore(rtmodt_leftobj *p, int stream, uint8_t *grid);
+/* Forgets one stream's model, mask and ledger (frames_seen 0, next oid 1; the ignore grid stays), or every stream's with
+ * stream == -1.  PARITY UNPINNED. */
+int rtmodt_leftobj_reset(rtmodt_leftobj *p, int stream);
+/* Device time (ms, HIP events around the launches) of the last process call that launched.  PARITY UNPINNED. */
+int rtmodt_leftobj_last_ms(rtmodt_leftobj *p, float *kernel_ms);
+/* Host only, no device needed: csrc/leftobj_rule.h's rule on one cell of luma yc (0..255) of a stream that has seen frames_seen
+ * frames: *state (the 8-byte cell) is updated, *fg is 1 for foreground, *is_static 1 for a static cell.  Only the eight rule fields
+ * of cfg are read (warmup .. static_frames).  The parity surface of csrc/leftobj_rule.h.  PARITY UNPINNED. */
+int rtmodt_leftobj_cell(const rtmodt_leftobj_cfg *cfg, uint32_t yc, int32_t frames_seen, uint64_t *state, int32_t *fg, int32_t *is_static);
+
 /* ---- lens correction: frames are undistorted once, directly after decode ------------------------------------------------------ */
 /* Every geometric module of this library (zones, crossings, privacy polygons, heatmap zone sums, the ground-plane speed estimator)
  * assumes a pinhole picture; a short surveillance lens bows straight lines by tens of pixels.  This module produces the rectified

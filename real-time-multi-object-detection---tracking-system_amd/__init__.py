@@ -13,6 +13,8 @@ library being built):
                             scheme; the cure for the design document's "Missed small objects", B.4)
 * ``detection.motion``   -- ``MotionDetector``: a background model per stream on the GPU tells still frames from moving ones, so that
                             ``pipeline.run(motion=...)`` keeps the detector off still scenes (the reference drops frames blind to content)
+* ``detection.left_objects`` -- ``LeftObjectDetector``: static foreground the detector has no class for (a bag left behind, an exhibit
+                            taken away) found, followed in a device-resident ledger and told from standing people by the tracks
 * ``tracking.tracker``   --``MultiObjectTracker`` / ``Track`` (reference: src/tracking/tracker.py:27-259)
 * ``tracking.deepsort``  -- ``DeepSortTracker``: DeepSORT with appearance matching on the GPU (reference: config/default.yaml:53-60)
 * ``tracking.ocsort``    -- ``OcSortTracker``: OC-SORT, the motion-only tracker of the design document's H.2 comparison, on the GPU
@@ -48,7 +50,7 @@ library being built):
 """
 import importlib as _importlib
 
-__all__ = ["Detector", "Detections", "SlicedDetector", "MotionDetector", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
+__all__ = ["Detector", "Detections", "SlicedDetector", "MotionDetector", "LeftObjectDetector", "MultiObjectTracker", "Track", "DeepSortTracker", "OcSortTracker", "BotSortTracker"]
 
 _LAZY = {
     "Detector": ".detection.detector",
@@ -56,6 +58,9 @@ _LAZY = {
     "SlicedDetector": ".detection.sliced",
     "MotionDetector": ".detection.motion",
     "MotionResult": ".detection.motion",
+    "LeftObjectDetector": ".detection.left_objects",
+    "LeftObjectEvent": ".detection.left_objects",
+    "LeftObjectResult": ".detection.left_objects",
     "MultiObjectTracker": ".tracking.tracker",
     "Track": ".tracking.tracker",
     "DeepSortTracker": ".tracking.deepsort",

@@ -284,6 +284,49 @@ class MotionResult(C.Structure):                    # struct rtmodt_motion_resul
                 ("luma_sum", C.c_uint64)]
 
 
+class LeftObjCfg(C.Structure):                      # struct rtmodt_leftobj_cfg
+    _fields_ = ([(n, C.c_int32) for n in ("streams", "height", "width", "scale", "warmup", "warm_shift", "learn_shift", "threshold", "stable",
+                                          "cand_shift", "occlusion", "static_frames", "min_neighbors", "min_area", "max_area", "max_regions",
+                                          "scene_pm", "max_objects", "miss_frames", "alarm_frames", "absorb_frames", "covered_pm", "attend_margin",
+                                          "max_tracks")] +
+                [("n_owner_classes", C.c_int32), ("owner_classes", C.c_int32 * 8), ("n_report_classes", C.c_int32), ("report_classes", C.c_int32 * 8),
+                 ("device", C.c_int32)])
+
+
+class LeftObjResult(C.Structure):                   # struct rtmodt_leftobj_result
+    _fields_ = [("status", C.c_int32), ("stream", C.c_int32), ("frames_seen", C.c_int32), ("n_fg", C.c_uint32), ("n_static", C.c_uint32),
+                ("n_regions", C.c_int32), ("n_regions_total", C.c_int32), ("n_objects", C.c_int32), ("n_events", C.c_int32),
+                ("n_retired", C.c_int32), ("dropped", C.c_int32), ("next_oid", C.c_int32)]
+
+
+class LeftObjRegion(C.Structure):                   # struct rtmodt_leftobj_region
+    _fields_ = [("box", C.c_int32 * 4), ("cells", C.c_int32 * 4), ("area", C.c_int32), ("kind", C.c_int32), ("age_min", C.c_int32),
+                ("age_max", C.c_int32), ("covered", C.c_int32), ("attended", C.c_int32), ("oid", C.c_int32), ("root", C.c_int32)]
+
+
+class LeftObjObject(C.Structure):                   # struct rtmodt_leftobj_object
+    _fields_ = [("first_frame", C.c_int64), ("owner", C.c_int64), ("oid", C.c_int32), ("kind", C.c_int32), ("area", C.c_int32), ("idle", C.c_int32),
+                ("unmatched", C.c_int32), ("alarmed", C.c_int32), ("cells", C.c_int32 * 4), ("box", C.c_int32 * 4)]
+
+
+class LeftObjEvent(C.Structure):                    # struct rtmodt_leftobj_event
+    _fields_ = [("first_frame", C.c_int64), ("frame_id", C.c_int64), ("owner", C.c_int64), ("oid", C.c_int32), ("kind", C.c_int32),
+                ("area", C.c_int32), ("reserved", C.c_int32), ("box", C.c_int32 * 4)]
+
+
+class LeftObjRetired(C.Structure):                  # struct rtmodt_leftobj_retired
+    _fields_ = [("oid", C.c_int32), ("reason", C.c_int32), ("alarmed", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LeftObjTracks(C.Structure):                   # struct rtmodt_leftobj_tracks
+    _fields_ = [("source", C.c_int32), ("stride", C.c_int32), ("ids", C.c_void_p), ("xyxy", C.c_void_p), ("cls", C.c_void_p), ("n", C.c_void_p),
+                ("tracker", C.c_void_p), ("report_tsu", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LeftObjOut(C.Structure):                      # struct rtmodt_leftobj_out
+    _fields_ = [("results", C.c_void_p), ("regions", C.c_void_p), ("events", C.c_void_p), ("retired", C.c_void_p), ("objects", C.c_void_p)]
+
+
 class LensCfg(C.Structure):                         # struct rtmodt_lens_cfg
     _fields_ = [("device", C.c_int32), ("streams", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("out_h", C.c_int32),
                 ("out_w", C.c_int32), ("border_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
@@ -536,6 +579,21 @@ def lib() -> C.CDLL:
         "rtmodt_motion_reset": (C.c_int, [vp, C.c_int]),
         "rtmodt_motion_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_motion_cell": (C.c_int, [C.POINTER(MotionCfg), C.c_uint32, i32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(i32)]),
+        "rtmodt_leftobj_default_cfg": (None, [C.POINTER(LeftObjCfg)]),
+        "rtmodt_leftobj_create": (C.c_int, [C.POINTER(LeftObjCfg), C.POINTER(vp)]),
+        "rtmodt_leftobj_destroy": (None, [vp]),
+        "rtmodt_leftobj_process": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LeftObjTracks), C.POINTER(LeftObjOut)]),
+        "rtmodt_leftobj_read_state": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(i32)]),
+        "rtmodt_leftobj_load_state": (C.c_int, [vp, C.c_int, vp, vp, i32]),
+        "rtmodt_leftobj_read_mask": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_leftobj_load_mask": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_leftobj_read_ledger": (C.c_int, [vp, C.c_int, vp, C.POINTER(i32), C.POINTER(i32)]),
+        "rtmodt_leftobj_load_ledger": (C.c_int, [vp, C.c_int, vp, C.c_int, i32]),
+        "rtmodt_leftobj_set_ignore": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_leftobj_read_ignore": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_leftobj_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_leftobj_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_leftobj_cell": (C.c_int, [C.POINTER(LeftObjCfg), C.c_uint32, i32, C.POINTER(C.c_uint64), C.POINTER(i32), C.POINTER(i32)]),
         "rtmodt_lens_default_cfg": (None, [C.POINTER(LensCfg)]),
         "rtmodt_lens_create": (C.c_int, [C.POINTER(LensCfg), C.POINTER(vp)]),
         "rtmodt_lens_destroy": (None, [vp]),

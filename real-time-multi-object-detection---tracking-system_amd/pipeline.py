@@ -65,7 +65,8 @@ class PinnedFrameRing:
 
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
-        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None) -> dict:
+        crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
+        left_objects=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -129,6 +130,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``snapshots_rewritten`` (thumbnails of existing tracks that a better shot replaced) and ``snapshots_retired`` for stream 0.
     ``None``: the loop, the stage table and the summary are unchanged.
 
+    ``left_objects``: a one-stream ``detection.LeftObjectDetector`` of the frames' size, called inside a ``left_objects`` stage directly
+    before ``snapshots`` (else before ``privacy``, else before ``visualization``): after the swap guard, on clean pixels.  It runs on
+    every frame, motion-gated still frames included (a left bag IS a still scene), on the held tracks; like ``speed`` it reads the
+    tracker's device-resident state when the crossings stage would, else the materialised list.  The summary then carries
+    ``left_object_alarms`` and ``left_objects_retired`` for stream 0.  ``None``: the loop, the stage table and the summary are
+    unchanged.
+
     ``compose``: a one-source ``visualization.Compositor`` for the frames' size (``Compositor.substream(...)``, or any layout of one
     source whose output 0 is BGR24), called inside a ``compose`` stage directly after ``visualization``: the annotated frame is
     scaled on the GPU and the recorder receives output 0 -- the sub-stream -- instead of the full frame.  ``None``: the loop, the
@@ -160,11 +168,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
         profiler.STAGE_ORDER = order
+    if left_objects is not None and "left_objects" not in profiler.STAGE_ORDER:    # likewise, directly before snapshots (else: privacy, visualization)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index(next(k for k in ("snapshots", "privacy", "visualization") if k in order)), "left_objects")
+        profiler.STAGE_ORDER = order
     if compose is not None and "compose" not in profiler.STAGE_ORDER:          # likewise, directly after visualization
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("visualization") + 1, "compose")
         profiler.STAGE_ORDER = order
-    n_speed = n_snap_rewritten = n_snap_retired = 0
+    n_speed = n_snap_rewritten = n_snap_retired = n_left_alarms = n_left_retired = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     for _ in range(max_frames):
@@ -206,7 +218,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
                             and hasattr(event_engine, "process_tracker"))
         # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
         crossings_on_device = events_on_device
-        if (crossing_counter is not None or speed is not None or snapshots is not None) and event_engine is None and renderer is None and handoff:
+        if (crossing_counter is not None or speed is not None or snapshots is not None or left_objects is not None) and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
         if not skip:
             profiler.tick("tracking")
@@ -244,6 +256,16 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_speed += len(speed.process(tracks, speed.frame_time_us(fid)))
             profiler.tock("speed")
+        if left_objects is not None:
+            profiler.tick("left_objects")
+            if crossings_on_device:
+                left = left_objects.process([frame], tracker=tracker, frame_id=fid)[0]
+            else:
+                held = tracks or []
+                left = left_objects.process([frame], frame_id=fid, tracks=[([t.track_id for t in held], [t.xyxy for t in held], [t.class_id for t in held])])[0]
+            n_left_alarms += len(left.events)
+            n_left_retired += len(left.retired)
+            profiler.tock("left_objects")
         if snapshots is not None:
             profiler.tick("snapshots")
             if crossings_on_device:
@@ -297,6 +319,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["speed_events"] = n_speed
     if snapshots is not None:
         out["snapshots_rewritten"], out["snapshots_retired"] = n_snap_rewritten, n_snap_retired
+    if left_objects is not None:
+        out["left_object_alarms"], out["left_objects_retired"] = n_left_alarms, n_left_retired
     if swap_guard is not None:
         out["id_swaps_reverted"] = n_reverted
     if motion is not None:
