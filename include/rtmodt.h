@@ -2009,6 +2009,92 @@ int rtmodt_compose_last_ms(rtmodt_compose *h, float *kernel_ms);
 int rtmodt_compose_plan(const rtmodt_compose_src_desc *sources, int n_sources, const rtmodt_compose_out_desc *outputs, int n_outputs,
                         const rtmodt_compose_cell *cells, int n_cells, rtmodt_compose_plan_out *plans);
 
+/* ---- stabiliser: frames of a shaking camera are steadied once, ahead of every fixed-camera stage ------------------------------- */
+/* The motion detector, the left-object detector, the speed estimator, the heatmap, zones, tripwires and privacy polygons assume a
+ * FIXED camera; one on a pole or a gantry shakes by several pixels.  Per stream this module keeps a camera path on the device,
+ * moves it by one similarity per call (supplied, or estimated by an rtmodt_gmc from the same frames with nothing crossing the
+ * host between the estimate and the pixels) and resamples the frame into the stabilised picture.  The reference has no
+ * counterpart: src/ingestion/rtsp_reader.py hands cap.read()'s frame to the detector, and cv2.estimateAffinePartial2D /
+ * warpAffine appear nowhere in it.  csrc/stab_rule.h states the rules (leaky path, per-component limits, four Q16 coefficients,
+ * 5 fractional bits, lens_model.h's four integer taps); tests/stab_ref.py restates them and every path (as bit patterns), status,
+ * coefficient and output byte equals it exactly.  PARITY UNPINNED against vidstab, OpenCV's videostab and
+ * warpAffine (installed nowhere this runs) and on real footage.  One similarity per frame: no rolling-shutter or perspective
+ * model; causal, no look-ahead. */
+#define RTMODT_STAB_OK 0       /* the path followed a valid input                                                             */
+#define RTMODT_STAB_HOLD 1     /* the input was invalid and counted as the identity                                           */
+#define RTMODT_STAB_CLAMPED 2  /* a valid input moved a component of the path onto its limit                                  */
+#define RTMODT_STAB_RESET 3    /* reset_after consecutive HOLD calls: the path is the identity again                          */
+typedef struct rtmodt_stab rtmodt_stab;
+typedef struct rtmodt_stab_cfg {
+    int32_t device;
+    int32_t streams;            /* 1..1024 camera paths                                                                        */
+    int32_t h, w;               /* the frame size (source and stabilised picture alike), 1..16384 each                         */
+    int32_t leak_shift;         /* 0: no decay (an anchor on the first frame); 1..16: the path decays by k = 1 - 2^-leak_shift  */
+    int32_t max_shift_px;       /* |tx|, |ty| <= this, 0..16384                                                                */
+    int32_t max_rot_milli;      /* |zb| <= this / 1000, 0..500                                                                 */
+    int32_t max_zoom_milli;     /* |za - 1| <= this / 1000, 0..500                                                             */
+    int32_t crop_zoom_milli;    /* a fixed enlargement about the centre, 1000..8000 (1000: none), hides the correction band    */
+    int32_t reset_after;        /* consecutive HOLD calls after which the path is the identity again; 0: never                 */
+    uint8_t border_bgr[3];      /* what a tap off the source reads                                                             */
+    uint8_t reserved;
+} rtmodt_stab_cfg;
+typedef struct rtmodt_stab_stream_result {
+    int32_t status;             /* RTMODT_STAB_* of the stream's last call (OK before the first)                               */
+    int32_t hold;               /* the run of HOLD calls so far                                                                */
+    double j[4];                /* za, zb, tx, ty                                                                              */
+    int64_t coef[4];            /* A, B, U, V in Q16: what the last frame was sampled with                                     */
+} rtmodt_stab_stream_result;
+/* Host only: device 0, 1 stream, size 0 (the caller sets it), leak_shift 6, max_shift_px 32, max_rot_milli 35, max_zoom_milli 50,
+ * crop_zoom_milli 1000, reset_after 30, a black border; no default is validated on real footage.  No reference counterpart
+ * (rtsp_reader.py hands cap.read()'s frame to the detector).  PARITY UNPINNED. */
+void rtmodt_stab_default_cfg(rtmodt_stab_cfg *cfg);
+/* Allocates 80 bytes of state per stream, every path the identity.  streams outside 1..1024, a size outside 1..16384 or a
+ * parameter outside the range above is RTMODT_E_INVALID.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_create(const rtmodt_stab_cfg *cfg, rtmodt_stab **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  No reference counterpart.  PARITY UNPINNED. */
+void rtmodt_stab_destroy(rtmodt_stab *s);
+/* One stream's path, status and HOLD run back to the fresh state, or every stream's with stream < 0.  No reference counterpart.
+ * PARITY UNPINNED. */
+int rtmodt_stab_reset(rtmodt_stab *s, int stream);
+/* Two launches for all n frames: dst[i] (BGR24 h x w, row pitch dst_stride >= 3 w) is src[i] (same size, row pitch src_stride)
+ * stabilised on the path of streams[i] (streams == NULL: stream i; a stream may occur once in a call) after that path took
+ * warps[i] = float32 [a, -b, tx; b, a, ty], previous frame -> this frame in full-resolution pixels, with valid[i] != 0 (valid ==
+ * NULL: all valid; warps == NULL: the identity for all).  Source and destination memory kinds are independent; bytes beyond 3 w
+ * of a destination row are never written.  RTMODT_E_INVALID with nothing launched and every path as it was: a stream outside the
+ * handle or named twice, a pitch below 3 w, a null frame, a destination range that overlaps a source range of the call, a valid
+ * warp that is not finite or has |det| < 1e-6; more frames than streams is RTMODT_E_CAPACITY.  n == 0 is a no-op.  Synchronous.
+ * No reference counterpart (cv2.warpAffine appears nowhere in it).  PARITY UNPINNED. */
+int rtmodt_stab_process(rtmodt_stab *s, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride,
+                        int dst_mem_kind, const int32_t *streams, int n, const float *warps, const uint8_t *valid);
+/* The same with the warps estimated by gmc from src (frame i is the estimator's stream i; valid = its status 0): the estimate is
+ * queued on the estimator's stream, the step waits for it by an event, and neither warp nor status crosses the host.  mask_xyxy,
+ * mask_conf, mask_n: optional host mask boxes as rtmodt_gmc_estimate_batch takes them, rows of the estimator's max_boxes, n rows.
+ * Refused as above, and with RTMODT_E_INVALID / RTMODT_E_CAPACITY by the estimator's own checks: an estimator on another device,
+ * one that has seen another frame size, fewer estimator streams than frames, a frame beyond its limits.  rtmodt_gmc_result
+ * returns what the step consumed.  No reference counterpart (cv2.estimateAffinePartial2D appears nowhere in it).  PARITY
+ * UNPINNED. */
+int rtmodt_stab_process_gmc(rtmodt_stab *s, rtmodt_gmc *gmc, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst,
+                            int dst_stride, int dst_mem_kind, const int32_t *streams, int n, const float *mask_xyxy, const float *mask_conf,
+                            const int32_t *mask_n);
+/* Every stream's status, HOLD run, path and coefficients: out[streams].  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_result(rtmodt_stab *s, rtmodt_stab_stream_result *out);
+/* One stream's path j[4] and HOLD run to host memory.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_state(rtmodt_stab *s, int stream, double *j, int32_t *hold);
+/* Replaces them, so that a path survives a restart; a path outside the handle's limits or a run outside 0..2^30 is
+ * RTMODT_E_INVALID.  The stream's status becomes OK.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_load_state(rtmodt_stab *s, int stream, const double *j, int32_t hold);
+/* Device time (ms, HIP events around the two launches) of the last process call that launched; the estimator's part of
+ * rtmodt_stab_process_gmc is rtmodt_gmc_last_ms.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_last_ms(rtmodt_stab *s, float *kernel_ms);
+/* Host only, float64, no device: n points xy[n][2] through the path j[4] under cfg (h, w and crop_zoom_milli are read).
+ * to_source != 0: stabilised picture -> raw frame (a stabilised box drawn back on the raw frame, gmc mask boxes in raw
+ * coordinates); else raw frame -> stabilised picture, the closed-form inverse.  No reference counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_points(const rtmodt_stab_cfg *cfg, const double *j, int to_source, const double *xy, int n, double *out_xy);
+/* Host only: csrc/stab_rule.h on one stream's state without a device: j[4] and *hold are moved by warp[6] (NULL: the identity)
+ * with `valid`; *status and coef[4] (each may be null) are the call's.  The parity surface of csrc/stab_rule.h.  No reference
+ * counterpart.  PARITY UNPINNED. */
+int rtmodt_stab_step(const rtmodt_stab_cfg *cfg, double *j, int32_t *hold, const float *warp, int valid, int32_t *status, int64_t *coef);
+
 #ifdef __cplusplus
 }
 #endif

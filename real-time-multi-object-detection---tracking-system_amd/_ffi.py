@@ -337,6 +337,15 @@ class LensParams(C.Structure):                      # struct rtmodt_lens_params
                 ("nfy", C.c_double), ("ncx", C.c_double), ("ncy", C.c_double), ("r2_limit", C.c_double)]
 
 
+class StabCfg(C.Structure):                         # struct rtmodt_stab_cfg
+    _fields_ = [(k, C.c_int32) for k in ("device", "streams", "h", "w", "leak_shift", "max_shift_px", "max_rot_milli", "max_zoom_milli",
+                                         "crop_zoom_milli", "reset_after")] + [("border_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class StabStreamResult(C.Structure):                # struct rtmodt_stab_stream_result
+    _fields_ = [("status", C.c_int32), ("hold", C.c_int32), ("j", C.c_double * 4), ("coef", C.c_int64 * 4)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -606,6 +615,18 @@ def lib() -> C.CDLL:
         "rtmodt_lens_undistort_points": (C.c_int, [C.POINTER(LensParams), vp, C.c_int, vp, vp]),
         "rtmodt_lens_build_map": (C.c_int, [C.POINTER(LensParams), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "rtmodt_lens_quantise_map": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "rtmodt_stab_default_cfg": (None, [C.POINTER(StabCfg)]),
+        "rtmodt_stab_create": (C.c_int, [C.POINTER(StabCfg), C.POINTER(vp)]),
+        "rtmodt_stab_destroy": (None, [vp]),
+        "rtmodt_stab_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_stab_process": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+        "rtmodt_stab_process_gmc": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+        "rtmodt_stab_result": (C.c_int, [vp, C.POINTER(StabStreamResult)]),
+        "rtmodt_stab_state": (C.c_int, [vp, C.c_int, vp, C.POINTER(i32)]),
+        "rtmodt_stab_load_state": (C.c_int, [vp, C.c_int, vp, i32]),
+        "rtmodt_stab_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_stab_points": (C.c_int, [C.POINTER(StabCfg), vp, C.c_int, vp, C.c_int, vp]),
+        "rtmodt_stab_step": (C.c_int, [C.POINTER(StabCfg), vp, C.POINTER(i32), vp, C.c_int, C.POINTER(i32), vp]),
         "rtmodt_snapshot_default_cfg": (None, [C.POINTER(SnapshotCfg)]),
         "rtmodt_snapshot_create": (C.c_int, [C.POINTER(SnapshotCfg), C.c_int, C.c_int, C.POINTER(vp)]),
         "rtmodt_snapshot_destroy": (None, [vp]),

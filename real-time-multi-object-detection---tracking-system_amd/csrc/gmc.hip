@@ -444,7 +444,7 @@ struct rtmodt_gmc {
     int device = 0, S = 1;
     rtmodt_gmc_cfg cfg = {};
     hipStream_t stream = nullptr;
-    hipEvent_t foreign_done = nullptr, ev[2] = {};
+    hipEvent_t foreign_done = nullptr, own_done = nullptr, ev[2] = {};
     bool foreign_pending = false, timed = false;
     int gh = 0, gw = 0;                                      // the geometry the buffers are carved for (0: none yet)
     int W0 = 0, H0 = 0, W1 = 0, H1 = 0, BX = 0, BY = 0, nb = 0;
@@ -566,6 +566,46 @@ int gmc_enqueue_detector(rtmodt_gmc *g, const DetOutputs &o, const uint8_t *cons
     if (warp_dev) *warp_dev = g->d_warp;
     return RTMODT_OK;
 }
+
+// stab.hip: the estimate of caller frames queued on the estimator's own stream, as rtmodt_gmc_estimate_batch queues it, for streams
+// [0, n_frames); nothing is fetched and the host does not wait: *done is recorded behind the estimate
+int gmc_enqueue_frames(rtmodt_gmc *g, int device, const uint8_t *const *frames, int n_frames, int h, int w, int pitch, int mem_kind, const float *mask_xyxy,
+                       const float *mask_conf, const int32_t *mask_n, bool check_only, const float **warp_dev, const int32_t **status_dev,
+                       hipEvent_t *done) {
+    RT_CHECK(g && frames, RTMODT_E_INVALID, "null argument");
+    RT_CHECK(device == g->device, RTMODT_E_INVALID, "estimator on device %d, caller on device %d", g->device, device);
+    RT_CHECK(n_frames >= 1 && n_frames <= g->S, RTMODT_E_INVALID, "%d frames > estimator streams %d", n_frames, g->S);
+    RT_TRY(check_frame_ptrs(frames, n_frames));
+    RT_TRY(gmc_check_geometry(g, h, w, pitch, mem_kind));
+    bool any = false;
+    if (mask_n)
+        for (int s = 0; s < n_frames; ++s) {
+            RT_CHECK(mask_n[s] >= 0, RTMODT_E_INVALID, "stream %d: %d mask boxes", s, mask_n[s]);
+            RT_CHECK(mask_n[s] <= g->cfg.max_boxes, RTMODT_E_CAPACITY, "stream %d: %d mask boxes > max_boxes %d", s, mask_n[s], g->cfg.max_boxes);
+            any |= mask_n[s] > 0;
+        }
+    RT_CHECK(!any || (mask_xyxy && mask_conf), RTMODT_E_INVALID, "null mask boxes");
+    if (check_only) return RTMODT_OK;
+    RT_HIP(hipSetDevice(g->device));
+    RT_TRY(gmc_join(g));
+    RT_TRY(gmc_set_geometry(g, h, w));
+    hipStream_t q = g->stream;
+    AppFrames fp{};
+    RT_TRY(gmc_stage(g, frames, n_frames, h, w, pitch, mem_kind, q, &fp));
+    const size_t SM = (size_t)n_frames * g->cfg.max_boxes;
+    for (int s = 0; s < g->S; ++s) g->h_mn[s] = mask_n && s < n_frames ? mask_n[s] : 0;
+    if (any) {
+        RT_HIP(hipMemcpyAsync(g->d_mbox, mask_xyxy, SM * 16, hipMemcpyHostToDevice, q));
+        RT_HIP(hipMemcpyAsync(g->d_mconf, mask_conf, SM * 4, hipMemcpyHostToDevice, q));
+    }
+    RT_HIP(hipMemcpyAsync(g->d_mn, g->h_mn, (size_t)g->S * 4, hipMemcpyHostToDevice, q));
+    RT_TRY(gmc_run(g, fp, n_frames, h, w, pitch, g->d_mbox, g->d_mconf, g->d_mn, g->cfg.max_boxes, q));
+    RT_HIP(hipEventRecord(g->own_done, q));
+    if (warp_dev) *warp_dev = g->d_warp;
+    if (status_dev) *status_dev = g->d_status;
+    if (done) *done = g->own_done;
+    return RTMODT_OK;
+}
 }  // namespace rtmodt
 
 extern "C" {
@@ -584,6 +624,7 @@ void rtmodt_gmc_destroy(rtmodt_gmc *g) {
     if (g->foreign_done) hipEventSynchronize(g->foreign_done);
     if (g->stream) hipStreamSynchronize(g->stream);
     if (g->foreign_done) hipEventDestroy(g->foreign_done);
+    if (g->own_done) hipEventDestroy(g->own_done);
     for (auto &e : g->ev) if (e) hipEventDestroy(e);
     gmc_free_geometry(g);
     hipFree(g->d_table); hipFree(g->d_coarse); hipFree(g->d_nvalid); hipFree(g->d_scores); hipFree(g->d_bestk); hipFree(g->d_sums); hipFree(g->d_model);
@@ -597,6 +638,7 @@ static int gmc_create_impl(rtmodt_gmc *g) {
     RT_HIP(hipSetDevice(g->device));
     RT_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     RT_HIP(hipEventCreateWithFlags(&g->foreign_done, hipEventDisableTiming));
+    RT_HIP(hipEventCreateWithFlags(&g->own_done, hipEventDisableTiming));
     for (auto &e : g->ev) RT_HIP(hipEventCreate(&e));
     const size_t S = (size_t)g->S, MB = (size_t)std::max(g->cfg.max_boxes, 1);
     RT_HIP(hipMalloc((void **)&g->d_table, S * GMC_TABLE * 4)); RT_HIP(hipMemset(g->d_table, 0, S * GMC_TABLE * 4));

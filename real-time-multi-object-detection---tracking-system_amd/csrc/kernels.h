@@ -359,5 +359,13 @@ int slicer_outputs(rtmodt_slicer *s, DetOutputs *out);
 // gmc.hip: the camera-motion estimate of the detector's batch, queued on its stream; *warp_dev = the estimator's [stream][6] device buffer
 int gmc_enqueue_detector(rtmodt_gmc *g, const DetOutputs &o, const uint8_t *const *frames, int n_frames, int h, int w, int pitch, int mem_kind,
                          const float **warp_dev);
+// gmc.hip, for the stabiliser (stab.hip): the estimate of n_frames caller frames (streams 0..n_frames - 1) queued on the estimator's own
+// stream, host mask boxes optional as rtmodt_gmc_estimate_batch takes them (rows of the estimator's max_boxes).  *warp_dev / *status_dev
+// = the [stream][6] / [stream] device buffers gmc_fit writes; *done = an event recorded behind the estimate, for another stream to wait
+// on (no host wait).  `device`: the caller's; another one is refused.  Everything is checked before anything is queued; check_only: the
+// checks alone, so that a caller with checks of its own can make all of them before the estimator's state moves
+int gmc_enqueue_frames(rtmodt_gmc *g, int device, const uint8_t *const *frames, int n_frames, int h, int w, int pitch, int mem_kind, const float *mask_xyxy,
+                       const float *mask_conf, const int32_t *mask_n, bool check_only, const float **warp_dev, const int32_t **status_dev,
+                       hipEvent_t *done);
 
 }  // namespace rtmodt

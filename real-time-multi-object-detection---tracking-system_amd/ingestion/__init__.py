@@ -2,5 +2,6 @@ from .reader import FrameReader, RTSPReader, RawVideoCapture, SyntheticCapture, 
 from .jpeg_decode import JpegDecodeError, JpegDecoder  # noqa: F401
 from .mjpeg import MjpegCapture  # noqa: F401
 from .lens import LensCorrector, fisheye_map, monotonic_r2  # noqa: F401
+from .stabilizer import Stabilizer  # noqa: F401
 
 register_backend("mjpeg", MjpegCapture)          # FrameReader("x.avi", backend="mjpeg"): Motion-JPEG decoded on the GPU

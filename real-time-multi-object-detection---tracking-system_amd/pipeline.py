@@ -66,7 +66,7 @@ class PinnedFrameRing:
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
         crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
-        left_objects=None) -> dict:
+        left_objects=None, stabilize=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -140,7 +140,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``compose``: a one-source ``visualization.Compositor`` for the frames' size (``Compositor.substream(...)``, or any layout of one
     source whose output 0 is BGR24), called inside a ``compose`` stage directly after ``visualization``: the annotated frame is
     scaled on the GPU and the recorder receives output 0 -- the sub-stream -- instead of the full frame.  ``None``: the loop, the
-    stage table and the summary are unchanged."""
+    stage table and the summary are unchanged.
+
+    ``stabilize``: a one-stream ``ingestion.Stabilizer`` of the frames' size (with ``gmc=`` it estimates the camera motion from the
+    frames themselves; without, the path stays the identity), called inside a ``stabilize`` stage directly after ``undistort`` (else
+    directly after ``decode``) and before ``motion``: the frame is replaced by the stabilised one for every later stage and for the
+    recorder, so the fixed-camera stages work on a camera that is mounted firmly but not rigidly.  The summary then carries
+    ``stabilize_holds``, ``stabilize_clamped`` and ``stabilize_resets``, the frames of each status.  ``None``: the loop, the stage
+    table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -164,6 +171,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("decode") + 1, "undistort")
         profiler.STAGE_ORDER = order
+    if stabilize is not None and "stabilize" not in profiler.STAGE_ORDER:      # likewise, directly after undistort (else: decode), before motion
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("undistort" if "undistort" in order else "decode") + 1, "stabilize")
+        profiler.STAGE_ORDER = order
     if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
@@ -178,6 +189,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         profiler.STAGE_ORDER = order
     n_speed = n_snap_rewritten = n_snap_retired = n_left_alarms = n_left_retired = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
+    n_stab = [0, 0, 0, 0]                                                      # frames per stabiliser status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     for _ in range(max_frames):
         profiler.tick("decode")
@@ -189,6 +201,11 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             profiler.tick("undistort")
             frame = lens.process([frame])[0]
             profiler.tock("undistort")
+        if stabilize is not None:
+            profiler.tick("stabilize")
+            frame = stabilize.process([frame])[0]
+            n_stab[stabilize.result()[0].status] += 1
+            profiler.tock("stabilize")
         skip = False
         if motion is not None:
             profiler.tick("motion")
@@ -323,6 +340,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["left_object_alarms"], out["left_objects_retired"] = n_left_alarms, n_left_retired
     if swap_guard is not None:
         out["id_swaps_reverted"] = n_reverted
+    if stabilize is not None:
+        out["stabilize_holds"], out["stabilize_clamped"], out["stabilize_resets"] = n_stab[1], n_stab[2], n_stab[3]
     if motion is not None:
         out["motion_frames"], out["still_frames"], out["scene_changes"] = n_status[2], n_status[1], n_status[3]
     return out
