@@ -2095,6 +2095,113 @@ int rtmodt_stab_points(const rtmodt_stab_cfg *cfg, const double *j, int to_sourc
  * counterpart.  PARITY UNPINNED. */
 int rtmodt_stab_step(const rtmodt_stab_cfg *cfg, double *j, int32_t *hold, const float *warp, int valid, int32_t *status, int64_t *coef);
 
+/* ---- camera health: is the picture still a valid picture of the scene the camera was aimed at? ------------------------------- */
+/* A lens that is covered, a camera turned away, a lens out of focus, a stream that repeats its last frame, night without IR and a
+ * torch into the lens: every other stage takes such a picture for the scene, and the motion detector answers one SCENE_CHANGE and
+ * then learns it as background.  Per stream this module keeps a reference of the scene's coarse structure (R, unsigned 8.8 per cell
+ * of the motion detector's luma grid) and of its fine detail (ref_sharp), compares every frame with it and debounces six conditions
+ * into latched RAISED / CLEARED events; it gates nothing.  The reference has no counterpart (src/ingestion/rtsp_reader.py hands
+ * cap.read()'s frame on; its events come from tracks only): PARITY UNPINNED throughout, against any camera's or NVR's tamper
+ * detection too, and no default is validated on real footage.  PINNED, exactly, against tests/health_ref.py: every count, mask,
+ * event and the whole state.  csrc/health_rule.h states the rules, csrc/health.hip's header the launches; all of it is integer
+ * arithmetic.  DELIBERATE LIMITS: its own pixel pass (not shared with motion / leftobj), no colour-cast or IR-cut detection, no
+ * per-region tamper map, one reference per stream (rebase on a PTZ preset change), no gating of other stages. */
+#define RTMODT_HEALTH_DARK 0            /* 1000 n_dark >= dark_pm cells                                                          */
+#define RTMODT_HEALTH_BRIGHT 1          /* 1000 n_bright >= bright_pm cells                                                      */
+#define RTMODT_HEALTH_COVERED 2         /* the reference's structure is gone and the picture has none of its own                 */
+#define RTMODT_HEALTH_MOVED 3           /* the reference's structure is gone and the picture has structure elsewhere             */
+#define RTMODT_HEALTH_DEFOCUSED 4       /* the structure is in place and the fine detail is gone                                 */
+#define RTMODT_HEALTH_FROZEN 5          /* at most freeze_cells cells differ from the frame before                               */
+#define RTMODT_HEALTH_CONDITIONS 6      /* masks hold bit 1 << condition                                                         */
+#define RTMODT_HEALTH_NO_STRUCTURE 64   /* a bit of `raw` only: fewer than min_ref_edges reference edges, the structure tests rest */
+#define RTMODT_HEALTH_RAISED 1
+#define RTMODT_HEALTH_CLEARED 2
+#define RTMODT_HEALTH_REBASED 3         /* condition -1: the stream starts a new reference                                       */
+#define RTMODT_HEALTH_MAX_EVENTS 8      /* per stream and call; csrc/health_rule.h states why the rule cannot exceed it          */
+typedef struct rtmodt_health rtmodt_health;
+typedef struct rtmodt_health_cfg {
+    int32_t streams;            /* 1..1024                                                                                      */
+    int32_t height, width;      /* the frame size, 1..32768 each; the grid at most 2^24 cells, all streams 2^28                 */
+    int32_t scale;              /* 1, 2, 4 or 8 pixels per cell side                                                            */
+    int32_t edge_threshold;     /* 1..255: a cell is an edge with G >= this, a weak edge with 2 G >= this                       */
+    int32_t ref_shift;          /* 1..12: R += ((G << 8) - R) >> ref_shift, and the same for ref_sharp                          */
+    int32_t warmup;             /* 1..255 frames that only learn                                                                */
+    int32_t dark_level, dark_pm;        /* 0..255; 0..1000 per mille of the cells (0: off)                                      */
+    int32_t bright_level, bright_pm;    /* likewise                                                                             */
+    int32_t retain_pm;          /* 0..1000: lost = 1000 n_kept < retain_pm n_ref_edge (0: COVERED and MOVED off)                */
+    int32_t cover_pm;           /* 0..1000: COVERED = lost and 1000 n_edge < cover_pm n_ref_edge (0: off, a loss is MOVED)      */
+    int32_t defocus_pm;         /* 0..1000: DEFOCUSED = not lost and 1000 sharp < defocus_pm (ref_sharp >> 8) (0: off)          */
+    int32_t min_ref_edges;      /* 0..2^24 reference edges the structure tests need                                             */
+    int32_t hold_frames;        /* 1..65535 consecutive raw frames raise a condition                                            */
+    int32_t clear_frames;       /* 1..65535 consecutive frames without it clear it                                              */
+    int32_t freeze_frames;      /* 0..65535: FROZEN's hold_frames (it clears on the first changed frame); 0: off                */
+    int32_t freeze_cells;       /* 0..2^24: a frame with at most this many changed cells is a repeated frame                    */
+    int32_t relearn_frames;     /* 0..2^30: a structure condition active this long rebases the stream; 0: never                 */
+    int32_t device;
+} rtmodt_health_cfg;
+typedef struct rtmodt_health_result {
+    int32_t stream;
+    int32_t frames_seen;        /* after the call: 0 after a relearn                                                            */
+    uint32_t raw, active;       /* masks of 1 << RTMODT_HEALTH_*: this frame's raw conditions (and NO_STRUCTURE); the latched ones */
+    uint32_t n_dark, n_bright, n_changed, n_edge, n_ref_edge, n_kept;
+    int32_t n_events;           /* events[0 .. n_events - 1] of the stream's row are set, the rest are zero                      */
+    int32_t learned;            /* 0: the reference stood still; 1: it took an averaging step; 2: it was set from this frame     */
+    uint64_t luma_sum;          /* the sum of the cells' luma                                                                   */
+    uint64_t sharp;             /* the sum of |y(x + 1) - y(x)| over the frame's pixels                                         */
+    uint64_t ref_sharp;         /* after the call, 8 fractional bits                                                            */
+} rtmodt_health_result;
+typedef struct rtmodt_health_event {
+    int64_t frame_id;
+    int32_t condition;          /* RTMODT_HEALTH_DARK .. FROZEN; -1 for REBASED                                                 */
+    int32_t kind;               /* RTMODT_HEALTH_RAISED / CLEARED / REBASED                                                     */
+} rtmodt_health_event;
+typedef struct rtmodt_health_state {
+    uint64_t ref_sharp;
+    int32_t frames_seen;        /* 0..2^30                                                                                      */
+    uint32_t active;            /* mask of the latched conditions                                                               */
+    uint32_t pending;           /* events an rtmodt_health_rebase owes the next call: CLEARED bits | 256 (REBASED)              */
+    int32_t reserved;
+    int32_t run[6], off[6];     /* per condition: raw run (inactive) or age (active); frames without the raw condition          */
+} rtmodt_health_state;
+/* Host only: 1 stream, height and width 0 (the caller sets them), scale 4, edge_threshold 24, ref_shift 6, warmup 25, dark 16 / 950,
+ * bright 240 / 950, retain_pm 500, cover_pm 300, defocus_pm 500, min_ref_edges 16, hold_frames 25, clear_frames 25, freeze_frames
+ * 50, freeze_cells 0, relearn_frames 0, device 0.  No default has been validated on real footage.  PARITY UNPINNED. */
+void rtmodt_health_default_cfg(rtmodt_health_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range is RTMODT_E_INVALID, a grid above 2^24 cells (or
+ * 2^28 over all streams) RTMODT_E_CAPACITY.  Every stream starts with frames_seen 0 and nothing active.  PARITY UNPINNED. */
+int rtmodt_health_create(const rtmodt_health_cfg *cfg, rtmodt_health **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_health_destroy(rtmodt_health *m);
+/* One frame for each of n distinct streams: frame i (BGR24, height x width as created, row pitch stride_bytes >= 3w, host or
+ * device memory by mem_kind, read only) is judged against the reference of streams[i] (streams == NULL: stream i, and n must be
+ * the stream count); frame_ids[i] is the number its events carry (NULL: 0).  results[i] and events[i][RTMODT_HEALTH_MAX_EVENTS]
+ * describe it.  A frame size other than the handle's, a stream outside 0..streams - 1 or named twice, a null frame and n above the
+ * stream count are RTMODT_E_INVALID with nothing launched.  Four launches, whatever the frames show; all results come back in one
+ * copy.  Streams the call does not name keep their state.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_health_process(rtmodt_health *m, const uint8_t *const *frames, const int32_t *streams, const int64_t *frame_ids, int n, int height,
+                          int width, int stride_bytes, int mem_kind, rtmodt_health_result *results, rtmodt_health_event *events);
+/* One stream's state to host memory: R as uint16[gh][gw], the previous luma grid as uint8[gh][gw], and the rest.  PARITY UNPINNED. */
+int rtmodt_health_read_state(rtmodt_health *m, int stream, uint16_t *r, uint8_t *prev_y, rtmodt_health_state *state);
+/* Replaces one stream's state, so that a monitor survives a restart; a field outside its range (R above 255 << 8, frames_seen
+ * outside 0..2^30, an unknown mask bit, a counter outside 0..2^30) is RTMODT_E_INVALID and nothing is replaced.  PARITY UNPINNED. */
+int rtmodt_health_load_state(rtmodt_health *m, int stream, const uint16_t *r, const uint8_t *prev_y, const rtmodt_health_state *state);
+/* The operator's word that the camera now shows what it should: the stream's active structure conditions are cleared, frames_seen
+ * becomes 0 (the next frame starts a new reference), and the CLEARED and REBASED events are reported by the stream's next process
+ * call, ahead of that frame's own.  PARITY UNPINNED. */
+int rtmodt_health_rebase(rtmodt_health *m, int stream);
+/* Forgets one stream's reference, previous grid, counters and active conditions (no event), or every stream's with stream == -1.
+ * PARITY UNPINNED. */
+int rtmodt_health_reset(rtmodt_health *m, int stream);
+/* Device time (ms, HIP events around the memset and the four launches) of the last process call that launched.  PARITY UNPINNED. */
+int rtmodt_health_last_ms(rtmodt_health *m, float *kernel_ms);
+/* Host only, no device needed: csrc/health_rule.h's decision, debounce and relearn on one row of counts (row's n_*, luma_sum and
+ * sharp are read; frames_seen, raw, active, n_events, learned and ref_sharp are written) and one state of a stream with `cells`
+ * cells; events[RTMODT_HEALTH_MAX_EVENTS] carry frame_id.  Only the rule fields of cfg are read (edge_threshold .. relearn_frames).
+ * A count above cells or a state outside its ranges is RTMODT_E_INVALID.  The parity surface of csrc/health_rule.h.  PARITY
+ * UNPINNED. */
+int rtmodt_health_decide(const rtmodt_health_cfg *cfg, int64_t cells, int64_t frame_id, rtmodt_health_result *row, rtmodt_health_state *state,
+                         rtmodt_health_event *events);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,7 +43,8 @@ library being built):
 * ``ingestion``          -- ``FrameReader`` / ``RTSPReader``: latest-frame reader thread with pluggable capture back-ends,
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158); ``JpegDecoder`` /
                             ``MjpegCapture``: JPEG / Motion-JPEG files, AVI and multipart streams decoded on the GPU; ``Stabilizer``:
-                            frames of a shaking camera steadied on the GPU ahead of every fixed-camera stage
+                            frames of a shaking camera steadied on the GPU ahead of every fixed-camera stage; ``CameraHealth``:
+                            covered, re-aimed, defocused, dark, dazzled and frozen cameras told from healthy ones on the GPU
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
                             in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py); ``stitch_tracks`` /
                             ``correct_id_switches``: fragmented tracks merged and their gaps filled on the GPU (the design

@@ -346,6 +346,27 @@ class StabStreamResult(C.Structure):                # struct rtmodt_stab_stream_
     _fields_ = [("status", C.c_int32), ("hold", C.c_int32), ("j", C.c_double * 4), ("coef", C.c_int64 * 4)]
 
 
+class HealthCfg(C.Structure):                       # struct rtmodt_health_cfg
+    _fields_ = [(k, C.c_int32) for k in ("streams", "height", "width", "scale", "edge_threshold", "ref_shift", "warmup", "dark_level", "dark_pm",
+                                         "bright_level", "bright_pm", "retain_pm", "cover_pm", "defocus_pm", "min_ref_edges", "hold_frames",
+                                         "clear_frames", "freeze_frames", "freeze_cells", "relearn_frames", "device")]
+
+
+class HealthResult(C.Structure):                    # struct rtmodt_health_result
+    _fields_ = [("stream", C.c_int32), ("frames_seen", C.c_int32), ("raw", C.c_uint32), ("active", C.c_uint32), ("n_dark", C.c_uint32),
+                ("n_bright", C.c_uint32), ("n_changed", C.c_uint32), ("n_edge", C.c_uint32), ("n_ref_edge", C.c_uint32), ("n_kept", C.c_uint32),
+                ("n_events", C.c_int32), ("learned", C.c_int32), ("luma_sum", C.c_uint64), ("sharp", C.c_uint64), ("ref_sharp", C.c_uint64)]
+
+
+class HealthEvent(C.Structure):                     # struct rtmodt_health_event
+    _fields_ = [("frame_id", C.c_int64), ("condition", C.c_int32), ("kind", C.c_int32)]
+
+
+class HealthState(C.Structure):                     # struct rtmodt_health_state
+    _fields_ = [("ref_sharp", C.c_uint64), ("frames_seen", C.c_int32), ("active", C.c_uint32), ("pending", C.c_uint32), ("reserved", C.c_int32),
+                ("run", C.c_int32 * 6), ("off", C.c_int32 * 6)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -627,6 +648,16 @@ def lib() -> C.CDLL:
         "rtmodt_stab_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_stab_points": (C.c_int, [C.POINTER(StabCfg), vp, C.c_int, vp, C.c_int, vp]),
         "rtmodt_stab_step": (C.c_int, [C.POINTER(StabCfg), vp, C.POINTER(i32), vp, C.c_int, C.POINTER(i32), vp]),
+        "rtmodt_health_default_cfg": (None, [C.POINTER(HealthCfg)]),
+        "rtmodt_health_create": (C.c_int, [C.POINTER(HealthCfg), C.POINTER(vp)]),
+        "rtmodt_health_destroy": (None, [vp]),
+        "rtmodt_health_process": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "rtmodt_health_read_state": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(HealthState)]),
+        "rtmodt_health_load_state": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(HealthState)]),
+        "rtmodt_health_rebase": (C.c_int, [vp, C.c_int]),
+        "rtmodt_health_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_health_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_health_decide": (C.c_int, [C.POINTER(HealthCfg), i64, i64, C.POINTER(HealthResult), C.POINTER(HealthState), vp]),
         "rtmodt_snapshot_default_cfg": (None, [C.POINTER(SnapshotCfg)]),
         "rtmodt_snapshot_create": (C.c_int, [C.POINTER(SnapshotCfg), C.c_int, C.c_int, C.POINTER(vp)]),
         "rtmodt_snapshot_destroy": (None, [vp]),

@@ -66,7 +66,7 @@ class PinnedFrameRing:
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
         crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
-        left_objects=None, stabilize=None) -> dict:
+        left_objects=None, stabilize=None, health=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -147,6 +147,12 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     directly after ``decode``) and before ``motion``: the frame is replaced by the stabilised one for every later stage and for the
     recorder, so the fixed-camera stages work on a camera that is mounted firmly but not rigidly.  The summary then carries
     ``stabilize_holds``, ``stabilize_clamped`` and ``stabilize_resets``, the frames of each status.  ``None``: the loop, the stage
+    table and the summary are unchanged.
+
+    ``health``: a one-stream ``ingestion.CameraHealth`` of the frames' size, called inside a ``health`` stage directly after ``decode``
+    and before ``undistort``: it judges the picture the camera delivered -- covered, re-aimed, defocused, dark, dazzled, frozen -- and
+    its events carry the source's frame ids.  It gates nothing: what to do with an alarm is the caller's decision.  The summary then
+    carries ``health_alarms``, the RAISED events, and ``health_flags``, the OR of the active masks.  ``None``: the loop, the stage
     table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
@@ -175,6 +181,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("undistort" if "undistort" in order else "decode") + 1, "stabilize")
         profiler.STAGE_ORDER = order
+    if health is not None and "health" not in profiler.STAGE_ORDER:            # likewise, directly after decode, after the three above: before undistort
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("decode") + 1, "health")
+        profiler.STAGE_ORDER = order
     if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
@@ -191,12 +201,19 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     n_stab = [0, 0, 0, 0]                                                      # frames per stabiliser status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
+    n_health_alarms = health_flags = 0
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
         profiler.tock("decode")
         if not ok or frame is None:
             continue
+        if health is not None:
+            profiler.tick("health")
+            verdict = health.process([frame], frame_ids=[int(fid)])[0]
+            profiler.tock("health")
+            n_health_alarms += sum(1 for e in verdict.events if e.kind == 1)   # 1: RAISED
+            health_flags |= verdict.active
         if lens is not None:
             profiler.tick("undistort")
             frame = lens.process([frame])[0]
@@ -342,6 +359,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["id_swaps_reverted"] = n_reverted
     if stabilize is not None:
         out["stabilize_holds"], out["stabilize_clamped"], out["stabilize_resets"] = n_stab[1], n_stab[2], n_stab[3]
+    if health is not None:
+        out["health_alarms"], out["health_flags"] = n_health_alarms, health_flags
     if motion is not None:
         out["motion_frames"], out["still_frames"], out["scene_changes"] = n_status[2], n_status[1], n_status[3]
     return out
