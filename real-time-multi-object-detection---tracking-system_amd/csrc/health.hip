@@ -10,10 +10,9 @@
 //
 // Kernels (256 threads; FOUR launches and one memset per call for all its streams, whatever the frames show; no grid-wide barrier,
 // no spin on another workgroup; every sum is an integer sum, so its order cannot change a result):
-//   health_pixels  the hot path: every pixel is read once, motion.hip's way.  A thread owns a run of 4 / scale cells (at least one)
-//                  of one cell row, 12 bytes of each pixel row (24 at scale 8); lanes are adjacent runs.  WIDE (every frame base and
-//                  the pitch a multiple of 4): the full runs of full cell rows are read as dwords, all of them issued before the
-//                  first is used; else byte by byte.  The fine-detail term of a run's last pixel needs the first luma of the run to
+//   health_pixels  the hot path: every pixel is read once, by cell_grid.h's reader (a thread owns a run of 4 / scale cells of one
+//                  cell row; dwords where every frame base and the pitch are multiples of 4) with a visitor that sees each pixel's
+//                  luma.  The fine-detail term of a run's last pixel needs the first luma of the run to
 //                  its right: it comes from the next lane by a wave shuffle, and from memory (three bytes a row) only for lane 63,
 //                  whose neighbour belongs to another wave or tile.  A cell's Y replaces the previous grid's in place (one lane
 //                  reads and writes a cell), which gives n_changed.  luma_sum, sharp, n_dark, n_bright and n_changed are summed per
@@ -27,14 +26,15 @@
 #include <cstring>
 #include <vector>
 
-#include "frame_stage.h"
-
 #define MO_HD __host__ __device__
+#include "grid_host.h"
 #include "health_rule.h"
 
 namespace rtmodt {
 
-constexpr int HL_THREADS = 256, HL_WAVES = HL_THREADS / 64, HL_TW = 64, HL_TH = 16, HL_ROWS = 4;
+#include "wg_dev.h"
+
+constexpr int HL_THREADS = CG_THREADS, HL_WAVES = HL_THREADS / 64, HL_TW = GRID_TW, HL_TH = GRID_TH;
 constexpr int HL_MAX_STREAMS = 1024;
 constexpr long long HL_MAX_TOTAL_CELLS = 1LL << 28;
 static_assert(sizeof(rtmodt_health_result) == 72 && sizeof(rtmodt_health_event) == 16, "layout");
@@ -57,83 +57,31 @@ struct HlArgs {
     rtmodt_health_result *res; rtmodt_health_event *events;     // [n], [n][HL_MAX_EVENTS]
 };
 
-__device__ __forceinline__ uint32_t hl_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-
-// ---- pixels: cell luma, fine detail, the exposure counts, n_changed ------------------------------------------------------------
+// ---- pixels: cell luma (cell_grid.h), fine detail, the exposure counts, n_changed ---------------------------------------------
 template <int SCALE, bool WIDE> __global__ __launch_bounds__(HL_THREADS) void health_pixels(HlArgs a) {
-    constexpr int CPT = SCALE >= 4 ? 1 : 4 / SCALE, PX = SCALE * CPT, RUN = 3 * PX;     // cells, pixels and bytes of a thread's run
+    constexpr int CPT = CgRun<SCALE>::CPT, PX = CgRun<SCALE>::PX, RUN = CgRun<SCALE>::RUN;
     __shared__ uint32_t s_part[HL_WAVES][5];
     const int tid = threadIdx.x, lane = tid & 63;
     const HlSlot sl = a.slots[blockIdx.y];
     const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
     const int seen = a.state[sl.stream].frames_seen;
-    const int cy = (int)(blockIdx.x / a.tiles_x) * HL_ROWS + (tid >> 6);
-    const int cxb = ((int)(blockIdx.x % a.tiles_x) * 64 + lane) * CPT;
-    const bool live = cy < a.gh && cxb < a.gw;
-    const int px0 = cxb * SCALE, y0 = cy * SCALE;
-    const int npx = live ? min(PX, a.w - px0) : 0, nrows = live ? min(SCALE, a.h - y0) : 0;
-    const uint8_t *p = (const uint8_t *)sl.frame + (long long)y0 * a.pitch + 3LL * px0;     // (only dereferenced by live lanes)
+    const CgLane l = cg_lane<SCALE>(blockIdx.x, a.tiles_x, tid, (const uint8_t *)sl.frame, a.pitch, a.h, a.w, a.gw, a.gh);
     uint32_t luma = 0, n_dark = 0, n_bright = 0, n_changed = 0, fine = 0;
     uint32_t first[SCALE], last[SCALE];                         // the luma of the run's first and last pixel, per pixel row
 #pragma unroll
     for (int r = 0; r < SCALE; ++r) first[r] = last[r] = 0;
-    if (live) {
+    if (l.live) {
         uint32_t sum[CPT];
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) sum[j] = 0;
-        if (WIDE && npx == PX && nrows == SCALE) {
-            uint32_t v[SCALE][RUN / 4];                             // every load of the run is issued before the first is used
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r) {
-                const uint32_t *q = (const uint32_t *)(p + r * a.pitch);    // base, pitch and 3 * px0 (a multiple of 12) are multiples of 4
-#pragma unroll
-                for (int k = 0; k < RUN / 4; ++k) v[r][k] = q[k];
-            }
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r) {
-                uint32_t prev = 0;
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    uint32_t c[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c[k] = (v[r][(3 * i + k) >> 2] >> (8 * ((3 * i + k) & 3))) & 255u;
-                    const uint32_t yv = mo_luma(c[0], c[1], c[2]);
-                    sum[i / SCALE] += yv;
-                    if (i) fine += hl_absdiff(yv, prev);
-                    else first[r] = yv;
-                    prev = yv;
-                }
-                last[r] = prev;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r) {
-                if (r >= nrows) continue;
-                const uint8_t *q = p + r * a.pitch;
-                uint32_t prev = 0;
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    if (i >= npx) continue;
-                    const uint32_t yv = mo_luma(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
-                    sum[i / SCALE] += yv;
-                    if (i) fine += hl_absdiff(yv, prev);
-                    else first[r] = yv;
-                    prev = yv;
-                }
-                last[r] = prev;
-            }
-        }
-        uint8_t *yg = a.y + s_off + (size_t)cy * a.gw + cxb;
+        cg_read_run<SCALE, WIDE>(l.p, a.pitch, l.npx, l.nrows, sum, [&](int r, int i, uint32_t yv) {
+            if (i) fine += hl_absdiff(yv, last[r]);                 // (last[r] is the pixel to the left until the row ends)
+            else first[r] = yv;
+            last[r] = yv;
+        });
+        uint8_t *yg = a.y + s_off + (size_t)l.cy * a.gw + l.cxb;
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
-            const int cols = mo_cell_span(cxb + j, SCALE, a.w);
-            if (cols == 0) continue;
-            const uint32_t cnt = (uint32_t)(cols * nrows);
-            const uint32_t yc = cnt == SCALE * SCALE ? (sum[j] + SCALE * SCALE / 2) / (SCALE * SCALE) : mo_cell_mean(sum[j], cnt);
+            uint32_t yc;
+            if (!cg_cell_luma<SCALE>(sum[j], l.cxb + j, l.nrows, a.w, yc)) continue;
             const uint32_t old = yg[j];
             yg[j] = (uint8_t)yc;
             luma += yc;
@@ -144,19 +92,19 @@ template <int SCALE, bool WIDE> __global__ __launch_bounds__(HL_THREADS) void he
     }
     // the pixel right of the run: a full run that does not end the row has the next lane's first pixel (same cell row, so the same
     // rows), lane 63 reads it from memory
-    const bool need = live && npx == PX && px0 + PX < a.w;
+    const bool need = l.live && l.npx == PX && l.px0 + PX < a.w;
 #pragma unroll
     for (int r = 0; r < SCALE; ++r) {
         uint32_t nb = (uint32_t)__shfl_down((int)first[r], 1);      // (every lane of the wave takes part)
-        if (need && r < nrows) {
+        if (need && r < l.nrows) {
             if (lane == 63) {
-                const uint8_t *q = p + r * a.pitch + RUN;
+                const uint8_t *q = l.p + r * a.pitch + RUN;
                 nb = mo_luma(q[0], q[1], q[2]);
             }
             fine += hl_absdiff(nb, last[r]);
         }
     }
-    luma = hl_wave_sum(luma); n_dark = hl_wave_sum(n_dark); n_bright = hl_wave_sum(n_bright); n_changed = hl_wave_sum(n_changed); fine = hl_wave_sum(fine);
+    luma = wave_sum_u32(luma); n_dark = wave_sum_u32(n_dark); n_bright = wave_sum_u32(n_bright); n_changed = wave_sum_u32(n_changed); fine = wave_sum_u32(fine);
     if (lane == 0) {
         uint32_t *d = s_part[tid >> 6];
         d[0] = luma; d[1] = fine; d[2] = n_dark; d[3] = n_bright; d[4] = n_changed;
@@ -201,7 +149,7 @@ __global__ __launch_bounds__(HL_THREADS) void health_edges(HlArgs a) {
         n_ref += ref ? 1u : 0u;
         n_kept += ref && hl_weak_edge(g, t) ? 1u : 0u;
     }
-    n_edge = hl_wave_sum(n_edge); n_ref = hl_wave_sum(n_ref); n_kept = hl_wave_sum(n_kept);
+    n_edge = wave_sum_u32(n_edge); n_ref = wave_sum_u32(n_ref); n_kept = wave_sum_u32(n_kept);
     if ((tid & 63) == 0) {
         uint32_t *d = s_part[tid >> 6];
         d[0] = n_edge; d[1] = n_ref; d[2] = n_kept;
@@ -258,8 +206,7 @@ using namespace rtmodt;
 struct rtmodt_health {
     int device = 0;
     rtmodt_health_cfg cfg{};
-    int gw = 0, gh = 0;
-    long long cells = 0;                // per stream
+    GridGeom g;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -300,19 +247,8 @@ int hl_check_rule(const rtmodt_health_cfg *c) {
 
 int hl_check_cfg(const rtmodt_health_cfg *c) {
     RT_TRY(hl_check_rule(c));
-    RT_CHECK(c->streams >= 1 && c->streams <= HL_MAX_STREAMS, RTMODT_E_INVALID, "streams %d outside 1..%d", c->streams, HL_MAX_STREAMS);
-    RT_CHECK(c->height >= 1 && c->width >= 1 && c->height <= MO_MAX_DIM && c->width <= MO_MAX_DIM, RTMODT_E_INVALID, "bad frame geometry %dx%d",
-             c->width, c->height);
-    RT_CHECK(mo_scale_ok(c->scale), RTMODT_E_INVALID, "scale %d: one of 1, 2, 4, 8", c->scale);
-    const long long cells = (long long)mo_grid(c->height, c->scale) * mo_grid(c->width, c->scale);
-    RT_CHECK(cells <= MO_MAX_CELLS, RTMODT_E_CAPACITY, "a grid of %lld cells (at most %lld)", cells, MO_MAX_CELLS);
-    RT_CHECK(cells * c->streams <= HL_MAX_TOTAL_CELLS, RTMODT_E_CAPACITY, "%lld cells in all (at most %lld)", cells * c->streams, HL_MAX_TOTAL_CELLS);
-    return RTMODT_OK;
-}
-
-int hl_check_stream(const rtmodt_health *p, int stream) {
-    RT_CHECK(stream >= 0 && stream < p->cfg.streams, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, p->cfg.streams - 1);
-    return RTMODT_OK;
+    RT_TRY(check_grid_cfg(c->streams, c->height, c->width, c->scale, HL_MAX_STREAMS));
+    return check_grid_cells(c->streams, c->height, c->width, c->scale, HL_MAX_TOTAL_CELLS);
 }
 
 HlState hl_state_in(const rtmodt_health_state &s) {
@@ -322,15 +258,7 @@ HlState hl_state_in(const rtmodt_health_state &s) {
 }
 void hl_state_out(const HlState &s, rtmodt_health_state *o) { memcpy(o, &s, sizeof(s)); }
 
-template <bool WIDE> void hl_launch_pixels(int scale, dim3 grid, hipStream_t q, const HlArgs &a) {
-    const dim3 block(HL_THREADS);
-    switch (scale) {
-    case 1: hipLaunchKernelGGL((health_pixels<1, WIDE>), grid, block, 0, q, a); break;
-    case 2: hipLaunchKernelGGL((health_pixels<2, WIDE>), grid, block, 0, q, a); break;
-    case 4: hipLaunchKernelGGL((health_pixels<4, WIDE>), grid, block, 0, q, a); break;
-    default: hipLaunchKernelGGL((health_pixels<8, WIDE>), grid, block, 0, q, a); break;
-    }
-}
+void (*const hl_pixel_kernels[2][4])(HlArgs) = RTMODT_SCALE_KERNELS(health_pixels);
 
 }  // namespace
 
@@ -366,10 +294,9 @@ int rtmodt_health_create(const rtmodt_health_cfg *cfg, rtmodt_health **out) {
     rtmodt_health *p = new rtmodt_health();
     p->device = cfg->device;
     p->cfg = *cfg;
-    p->gw = mo_grid(cfg->width, cfg->scale); p->gh = mo_grid(cfg->height, cfg->scale);
-    p->cells = (long long)p->gw * p->gh;
+    p->g.set(cfg->height, cfg->width, cfg->scale);
     auto body = [&]() -> int {
-        const size_t S = (size_t)cfg->streams, all = S * (size_t)p->cells;
+        const size_t S = (size_t)cfg->streams, all = S * (size_t)p->g.cells;
         RT_HIP(hipSetDevice(p->device));
         RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         RT_HIP(hipEventCreate(&p->ev0));
@@ -427,16 +354,7 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
              p->cfg.height);
     RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     const int S = p->cfg.streams;
-    RT_CHECK(n <= S, RTMODT_E_INVALID, "%d frames in one call for %d streams", n, S);
-    RT_CHECK(streams || n == S || n == 0, RTMODT_E_INVALID, "%d frames for %d streams and no stream list", n, S);
-    std::vector<char> named(S, 0);
-    for (int i = 0; i < n; ++i) {
-        RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-        const int s = streams ? streams[i] : i;
-        RT_TRY(hl_check_stream(p, s));
-        RT_CHECK(!named[s], RTMODT_E_INVALID, "stream %d is named twice in one call", s);
-        named[s] = 1;
-    }
+    RT_TRY(check_stream_list(frames, streams, n, S));
     p->timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
@@ -444,11 +362,7 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
     RT_TRY(p->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_AS_GIVEN));
     RT_TRY(p->cmd.reserve((size_t)n * sizeof(HlSlot)));
     HlSlot *sl = (HlSlot *)p->cmd.h;
-    bool wide = p->stage.pitch % 4 == 0;
-    for (int i = 0; i < n; ++i) {
-        sl[i] = HlSlot{(uint64_t)(uintptr_t)p->stage.at(frames, i), frame_ids ? frame_ids[i] : 0, streams ? streams[i] : i, 0};
-        wide = wide && sl[i].frame % 4 == 0;
-    }
+    for (int i = 0; i < n; ++i) sl[i] = HlSlot{(uint64_t)(uintptr_t)p->stage.at(frames, i), frame_ids ? frame_ids[i] : 0, streams ? streams[i] : i, 0};
     RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, (size_t)n * sizeof(HlSlot), hipMemcpyHostToDevice, q));
     RT_TRY(p->stage.copy_in(frames, q));
 
@@ -457,27 +371,25 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
     const size_t ev_bytes = (size_t)n * HL_MAX_EVENTS * sizeof(rtmodt_health_event);
     HlArgs a{};
     a.slots = (const HlSlot *)p->cmd.d;
-    a.pitch = (long long)p->stage.pitch; a.cells = p->cells;
-    a.n = n; a.h = h; a.w = w; a.gw = p->gw; a.gh = p->gh;
+    a.pitch = (long long)p->stage.pitch; a.cells = p->g.cells;
+    a.n = n; a.h = h; a.w = w; a.gw = p->g.gw; a.gh = p->g.gh;
     a.rule = hl_rule(c);
     a.r = p->d_r; a.y = p->d_y; a.g = p->d_g; a.state = p->d_state;
     a.work = (HlWork *)p->d_out;
     a.res = (rtmodt_health_result *)(p->d_out + off_res); a.events = (rtmodt_health_event *)(p->d_out + off_res + res_bytes);
 
     const dim3 block(HL_THREADS);
-    const int cpt = c.scale >= 4 ? 1 : 4 / c.scale;
+    const GridGeom &g = p->g;
     RT_HIP(hipEventRecord(p->ev0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, off_res + res_bytes + ev_bytes, q));
     HlArgs m = a;
-    m.tiles_x = cdiv(p->gw, 64 * cpt);
-    const dim3 mgrid((unsigned)(m.tiles_x * cdiv(p->gh, HL_ROWS)), n);
-    if (wide) hl_launch_pixels<true>(c.scale, mgrid, q, m);
-    else hl_launch_pixels<false>(c.scale, mgrid, q, m);
+    m.tiles_x = g.model_tiles_x();
+    launch_by_scale(hl_pixel_kernels, c.scale, frames_wide(p->stage, sl, n), g.model_grid(n), q, m);
     HlArgs e = a;
-    e.tiles_x = cdiv(p->gw, HL_TW);
-    hipLaunchKernelGGL(health_edges, dim3((unsigned)(e.tiles_x * cdiv(p->gh, HL_TH)), n), block, 0, q, e);
+    e.tiles_x = g.filter_tiles_x();
+    hipLaunchKernelGGL(health_edges, g.filter_grid(n), block, 0, q, e);
     hipLaunchKernelGGL(health_decide, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, q, a);
-    hipLaunchKernelGGL(health_learn, dim3((unsigned)((p->cells + HL_THREADS - 1) / HL_THREADS), n), block, 0, q, a);
+    hipLaunchKernelGGL(health_learn, g.per_cell(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(p->ev1, q));
     RT_HIP(hipMemcpyAsync(p->h_out, p->d_out + off_res, res_bytes + ev_bytes, hipMemcpyDeviceToHost, q));       // every result in one copy
@@ -490,10 +402,10 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
 
 int rtmodt_health_read_state(rtmodt_health *p, int stream, uint16_t *r, uint8_t *prev_y, rtmodt_health_state *state) {
     RT_CHECK(p && r && prev_y && state, RTMODT_E_INVALID, "null argument");
-    RT_TRY(hl_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(r, p->d_r + (size_t)stream * p->cells, (size_t)p->cells * sizeof(uint16_t), hipMemcpyDeviceToHost, p->stream));
-    RT_HIP(hipMemcpyAsync(prev_y, p->d_y + (size_t)stream * p->cells, (size_t)p->cells, hipMemcpyDeviceToHost, p->stream));
+    RT_HIP(hipMemcpyAsync(r, p->d_r + (size_t)stream * p->g.cells, (size_t)p->g.cells * sizeof(uint16_t), hipMemcpyDeviceToHost, p->stream));
+    RT_HIP(hipMemcpyAsync(prev_y, p->d_y + (size_t)stream * p->g.cells, (size_t)p->g.cells, hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipMemcpyAsync(state, p->d_state + stream, sizeof(HlState), hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
@@ -501,13 +413,13 @@ int rtmodt_health_read_state(rtmodt_health *p, int stream, uint16_t *r, uint8_t 
 
 int rtmodt_health_load_state(rtmodt_health *p, int stream, const uint16_t *r, const uint8_t *prev_y, const rtmodt_health_state *state) {
     RT_CHECK(p && r && prev_y && state, RTMODT_E_INVALID, "null argument");
-    RT_TRY(hl_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     const HlState st = hl_state_in(*state);
     RT_CHECK(hl_state_ok(st), RTMODT_E_INVALID, "a health state outside its ranges or with owed events behind no rebase (frames_seen %d, active %u, pending %u)", st.frames_seen, st.active, st.pending);
-    for (long long i = 0; i < p->cells; ++i) RT_CHECK(r[i] <= 255u << 8, RTMODT_E_INVALID, "cell %lld: a reference of %u above 255 << 8", i, (unsigned)r[i]);
+    for (long long i = 0; i < p->g.cells; ++i) RT_CHECK(r[i] <= 255u << 8, RTMODT_E_INVALID, "cell %lld: a reference of %u above 255 << 8", i, (unsigned)r[i]);
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(p->d_r + (size_t)stream * p->cells, r, (size_t)p->cells * sizeof(uint16_t), hipMemcpyHostToDevice, p->stream));
-    RT_HIP(hipMemcpyAsync(p->d_y + (size_t)stream * p->cells, prev_y, (size_t)p->cells, hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_r + (size_t)stream * p->g.cells, r, (size_t)p->g.cells * sizeof(uint16_t), hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_y + (size_t)stream * p->g.cells, prev_y, (size_t)p->g.cells, hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipMemcpyAsync(p->d_state + stream, &st, sizeof(HlState), hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
@@ -515,7 +427,7 @@ int rtmodt_health_load_state(rtmodt_health *p, int stream, const uint16_t *r, co
 
 int rtmodt_health_rebase(rtmodt_health *p, int stream) {
     RT_CHECK(p, RTMODT_E_INVALID, "null argument");
-    RT_TRY(hl_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     HlState st;
     RT_HIP(hipSetDevice(p->device));
     RT_HIP(hipMemcpyAsync(&st, p->d_state + stream, sizeof(HlState), hipMemcpyDeviceToHost, p->stream));
@@ -528,11 +440,11 @@ int rtmodt_health_rebase(rtmodt_health *p, int stream) {
 
 int rtmodt_health_reset(rtmodt_health *p, int stream) {
     RT_CHECK(p, RTMODT_E_INVALID, "null argument");
-    if (stream != -1) RT_TRY(hl_check_stream(p, stream));
+    if (stream != -1) RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
     const size_t first = stream < 0 ? 0 : (size_t)stream, count = stream < 0 ? (size_t)p->cfg.streams : 1;
-    RT_HIP(hipMemsetAsync(p->d_r + first * p->cells, 0, count * p->cells * sizeof(uint16_t), p->stream));
-    RT_HIP(hipMemsetAsync(p->d_y + first * p->cells, 0, count * p->cells, p->stream));
+    RT_HIP(hipMemsetAsync(p->d_r + first * p->g.cells, 0, count * p->g.cells * sizeof(uint16_t), p->stream));
+    RT_HIP(hipMemsetAsync(p->d_y + first * p->g.cells, 0, count * p->g.cells, p->stream));
     RT_HIP(hipMemsetAsync(p->d_state + first, 0, count * sizeof(HlState), p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;

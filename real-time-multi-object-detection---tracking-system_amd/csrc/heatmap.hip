@@ -86,12 +86,6 @@ struct HmZoneArgs {
     unsigned long long *part;                   // [Z][HM_PARTS]
 };
 
-__device__ __forceinline__ uint32_t hm_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-
 // ---- device forms: tracks / detections -> stamps (the selection of privacy_gather) ------------------------------------
 __global__ __launch_bounds__(HM_THREADS) void heatmap_gather(HmGatherArgs a) {
     __shared__ int s_wcnt[HM_WAVES];
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(HM_THREADS) void heatmap_max(const uint32_t *grid, 
     const uint32_t *g = grid + (long long)s * gstride;
     uint32_t v = 0;
     for (long long i = (long long)blockIdx.x * HM_THREADS + tid; i < gstride; i += (long long)HM_PARTS * HM_THREADS) v = max(v, g[i]);
-    v = hm_wave_max(v);
+    v = wave_max_u32(v);
     if ((tid & 63) == 0) s_w[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) maxpart[(size_t)s * HM_PARTS + blockIdx.x] = max(max(s_w[0], s_w[1]), max(s_w[2], s_w[3]));
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(HM_THREADS) void heatmap_overlay(HmOvArgs a) {
     uint32_t m = a.scale_max;
     if (!m) {                                               // (uniform: a launch argument)
         if (tid < 64) {
-            const uint32_t v = hm_wave_max(a.maxpart[(size_t)fr.stream * HM_PARTS + tid]);
+            const uint32_t v = wave_max_u32(a.maxpart[(size_t)fr.stream * HM_PARTS + tid]);
             if (tid == 0) s_m = v;
         }
         __syncthreads();

@@ -19,8 +19,8 @@
 //
 // Kernels (256 threads; nine launches and one memset per call for all its streams, whatever the frames show; no grid-wide
 // barrier, no spin on another workgroup, no floats but the one rounding of a track box):
-//   leftobj_model   the hot path: every pixel is read once, with motion_model's thread-to-run mapping and its dword path (every
-//                   frame base and the pitch a multiple of 4).  A cell is read and written by one lane with one 8-byte access; the
+//   leftobj_model   the hot path: every pixel is read once, by cell_grid.h's reader (its thread-to-run mapping and its dword path:
+//                   every frame base and the pitch a multiple of 4).  A cell is read and written by one lane with one 8-byte access; the
 //                   luma grid is written; the foreground cells are summed per wave and added with one atomic.
 //   leftobj_filter  one workgroup per tile of 64 x 16 cells: static through LDS with a halo of 1, the 3 x 3 count; writes the mask,
 //                   makes every mask cell its own union-find root with empty accumulators, adds n_static.
@@ -41,11 +41,10 @@
 #include <cstring>
 #include <vector>
 
-#include "frame_stage.h"
+#define MO_HD __host__ __device__
+#include "grid_host.h"
 #include "kernels.h"
 #include "track_layout.h"
-
-#define MO_HD __host__ __device__
 #include "leftobj_rule.h"
 
 namespace rtmodt {
@@ -54,7 +53,7 @@ namespace rtmodt {
 #include "ccl_dev.h"
 #include "track_select_dev.h"
 
-constexpr int LO_THREADS = 256, LO_WAVES = LO_THREADS / 64, LO_TW = 64, LO_TH = 16, LO_ROWS = 4, LO_CHUNK = 4096;
+constexpr int LO_THREADS = CG_THREADS, LO_WAVES = LO_THREADS / 64, LO_TW = GRID_TW, LO_TH = GRID_TH;
 constexpr int LO_MAX_STREAMS = 1024;
 constexpr long long LO_MAX_TOTAL_CELLS = 1LL << 28;
 static_assert(sizeof(rtmodt_leftobj_result) == 48 && sizeof(rtmodt_leftobj_region) == 64 && sizeof(rtmodt_leftobj_object) == 72 &&
@@ -88,72 +87,31 @@ struct LoArgs {
     const int64_t *t_meta; int report_tsu, o_min_hits;
 };
 
-__device__ __forceinline__ uint32_t lo_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-__device__ __forceinline__ uint32_t lo_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-
-// ---- model: pixels -> cell luma -> the 8-byte cell ---------------------------------------------------------------------------
+// ---- model: pixels -> cell luma (cell_grid.h) -> the 8-byte cell ---------------------------------------------------------------
 template <int SCALE, bool WIDE> __global__ __launch_bounds__(LO_THREADS) void leftobj_model(LoArgs a) {
-    constexpr int CPT = SCALE >= 4 ? 1 : 4 / SCALE, PX = SCALE * CPT, RUN = 3 * PX;     // cells, pixels and bytes of a thread's run
+    constexpr int CPT = CgRun<SCALE>::CPT;
     const int tid = threadIdx.x;
     const LoSlot sl = a.slots[blockIdx.y];
     const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
     const int seen = a.seen[sl.stream];
-    const int cy = (int)(blockIdx.x / a.tiles_x) * LO_ROWS + (tid >> 6);
-    const int cxb = ((int)(blockIdx.x % a.tiles_x) * 64 + (tid & 63)) * CPT;
+    const CgLane l = cg_lane<SCALE>(blockIdx.x, a.tiles_x, tid, (const uint8_t *)sl.frame, a.pitch, a.h, a.w, a.gw, a.gh);
     uint32_t n_fg = 0;
-    if (cy < a.gh && cxb < a.gw) {
-        const int px0 = cxb * SCALE, npx = min(PX, a.w - px0);
-        const int y0 = cy * SCALE, nrows = min(SCALE, a.h - y0);
-        const uint8_t *p = (const uint8_t *)sl.frame + (long long)y0 * a.pitch + 3LL * px0;
+    if (l.live) {
         uint32_t sum[CPT];
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) sum[j] = 0;
-        if (WIDE && npx == PX && nrows == SCALE) {
-            uint32_t v[SCALE][RUN / 4];                             // every load of the run is issued before the first is used
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r) {
-                const uint32_t *q = (const uint32_t *)(p + r * a.pitch);    // base, pitch and 3 * px0 (a multiple of 12) are multiples of 4
-#pragma unroll
-                for (int k = 0; k < RUN / 4; ++k) v[r][k] = q[k];
-            }
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r)
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    uint32_t c[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c[k] = (v[r][(3 * i + k) >> 2] >> (8 * ((3 * i + k) & 3))) & 255u;
-                    sum[i / SCALE] += mo_luma(c[0], c[1], c[2]);
-                }
-        } else {
-            for (int r = 0; r < nrows; ++r, p += a.pitch)
-#pragma unroll
-                for (int i = 0; i < PX; ++i)
-                    if (i < npx) sum[i / SCALE] += mo_luma(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-        }
-        uint64_t *m = a.state + s_off + (size_t)cy * a.gw + cxb;
-        uint8_t *lu = a.luma + s_off + (size_t)cy * a.gw + cxb;
+        cg_read_run<SCALE, WIDE>(l.p, a.pitch, l.npx, l.nrows, sum);
+        uint64_t *m = a.state + s_off + (size_t)l.cy * a.gw + l.cxb;
+        uint8_t *lu = a.luma + s_off + (size_t)l.cy * a.gw + l.cxb;
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
-            const int cols = mo_cell_span(cxb + j, SCALE, a.w);
-            if (cols == 0) continue;
-            const uint32_t cnt = (uint32_t)(cols * nrows);
-            const uint32_t yc = cnt == SCALE * SCALE ? (sum[j] + SCALE * SCALE / 2) / (SCALE * SCALE) : mo_cell_mean(sum[j], cnt);
+            uint32_t yc;
+            if (!cg_cell_luma<SCALE>(sum[j], l.cxb + j, l.nrows, a.w, yc)) continue;
             LoCell c = lo_unpack(m[j]);
             n_fg += lo_cell(a.rule, yc, seen, c) ? 1u : 0u;
             m[j] = lo_pack(c);
             lu[j] = (uint8_t)yc;
         }
     }
-    n_fg = lo_wave_sum(n_fg);
+    n_fg = wave_sum_u32(n_fg);
     if ((tid & 63) == 0 && n_fg) atomicAdd(&a.work[blockIdx.y].n_fg, n_fg);
 }
 
@@ -190,7 +148,7 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_filter(LoArgs a) {
         a.acc[s_off + idx] = LoAcc{};
         ++n_static;
     }
-    n_static = lo_wave_sum(n_static);
+    n_static = wave_sum_u32(n_static);
     if ((tid & 63) == 0 && n_static) atomicAdd(&a.work[blockIdx.y].n_static, n_static);
 }
 
@@ -199,21 +157,7 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_link(LoArgs a) {
     const LoSlot sl = a.slots[blockIdx.y];
     const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
     const long long idx = (long long)blockIdx.x * LO_THREADS + threadIdx.x;
-    if (idx >= a.cells) return;
-    const uint8_t *mk = a.mask + s_off;
-    if (!mk[idx]) return;
-    const int cx = (int)(idx % a.gw), cy = (int)(idx / a.gw);
-    int32_t *par = a.parent + s_off;
-    const bool up = cy > 0;
-    const bool W = cx > 0 && mk[idx - 1];
-    const bool N = up && mk[idx - a.gw];
-    const bool NW = up && cx > 0 && mk[idx - a.gw - 1];
-    const bool NE = up && cx + 1 < a.gw && mk[idx - a.gw + 1];
-    // N joins W, NW and NE already (N's own W link, NE's W link, W's link upwards); without N, W joins NW
-    if (N) { ccl_unite(par, (int)idx, (int)(idx - a.gw)); return; }
-    if (W) ccl_unite(par, (int)idx, (int)idx - 1);
-    else if (NW) ccl_unite(par, (int)idx, (int)(idx - a.gw - 1));
-    if (NE) ccl_unite(par, (int)idx, (int)(idx - a.gw + 1));
+    if (idx < a.cells) ccl_link_cell(a.mask + s_off, a.parent + s_off, a.gw, idx);
 }
 
 __global__ __launch_bounds__(LO_THREADS) void leftobj_roots(LoArgs a) {
@@ -241,17 +185,14 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_roots(LoArgs a) {
             bgc += (uint32_t)lo_absdiff(bg, (int)(lo_unpack(a.state[ni]).bg >> 8));
         }
     }
-    const unsigned long long act = __ballot(m);
-    if (!act) return;                                       // (wave-uniform)
-    const int lead = __ffsll((long long)act) - 1;
-    const int root0 = __shfl(root, lead);
-    const bool same = __ballot(m && root != root0) == 0;
-    const uint32_t wx0 = lo_wave_max(bx0), wy0 = lo_wave_max(by0), wx1 = lo_wave_max(bx1), wy1 = lo_wave_max(by1);
-    const uint32_t wmin = lo_wave_max(amin), wmax = lo_wave_max(amax), wcur = lo_wave_sum(cur), wbgc = lo_wave_sum(bgc);
+    CclWave wv;
+    if (!ccl_wave_roots(m, root, wv)) return;
+    const uint32_t wx0 = wave_max_u32(bx0), wy0 = wave_max_u32(by0), wx1 = wave_max_u32(bx1), wy1 = wave_max_u32(by1);
+    const uint32_t wmin = wave_max_u32(amin), wmax = wave_max_u32(amax), wcur = wave_sum_u32(cur), wbgc = wave_sum_u32(bgc);
     uint32_t n = 1;
-    if (same) {                                             // one add per wave
-        if ((int)(threadIdx.x & 63) != lead) return;
-        n = (uint32_t)__popcll(act); bx0 = wx0; by0 = wy0; bx1 = wx1; by1 = wy1; amin = wmin; amax = wmax; cur = wcur; bgc = wbgc;
+    if (wv.same) {                                          // one add per wave
+        if ((int)(threadIdx.x & 63) != wv.lead) return;
+        n = wv.n; bx0 = wx0; by0 = wy0; bx1 = wx1; by1 = wy1; amin = wmin; amax = wmax; cur = wcur; bgc = wbgc;
     } else if (!m) {
         return;
     }
@@ -271,31 +212,15 @@ __device__ __forceinline__ bool lo_is_region(const LoArgs &a, size_t s_off, long
 
 __global__ __launch_bounds__(LO_THREADS) void leftobj_count(LoArgs a) {
     __shared__ int s_wcnt[LO_WAVES];
-    const LoSlot sl = a.slots[blockIdx.y];
-    const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
-    const long long base = (long long)blockIdx.x * LO_CHUNK;
-    int mine = 0;
-    for (int r = 0; r < LO_CHUNK / LO_THREADS; ++r) mine += lo_is_region(a, s_off, base + r * LO_THREADS + threadIdx.x) ? 1 : 0;
-    int total;
-    block_scan_count<LO_WAVES>(mine, s_wcnt, total);
-    if (threadIdx.x == 0) a.chunk[(size_t)blockIdx.y * (a.n_chunks + 1) + blockIdx.x] = (uint32_t)total;
+    const size_t s_off = (size_t)a.slots[blockIdx.y].stream * (size_t)a.cells;
+    ccl_count_chunk<LO_WAVES>(a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1), s_wcnt, [&](long long idx) { return lo_is_region(a, s_off, idx); });
 }
 
 __global__ __launch_bounds__(LO_THREADS) void leftobj_finish(LoArgs a) {
     __shared__ int s_wcnt[LO_WAVES];
-    const int tid = threadIdx.x, slot = blockIdx.x;
-    uint32_t *ch = a.chunk + (size_t)slot * (a.n_chunks + 1);
-    uint32_t run = 0;
-    for (int b = 0; b < a.n_chunks; b += LO_THREADS) {
-        const int i = b + tid;
-        const int v = i < a.n_chunks ? (int)ch[i] : 0;
-        int tot;
-        const int pos = block_scan_count<LO_WAVES>(v, s_wcnt, tot);
-        if (i < a.n_chunks) ch[i] = run + (uint32_t)pos;
-        run += (uint32_t)tot;
-    }
-    if (tid != 0) return;
-    ch[a.n_chunks] = run;
+    const int slot = blockIdx.x;
+    const uint32_t run = ccl_scan_chunks<LO_WAVES>(a.chunk + (size_t)slot * (a.n_chunks + 1), a.n_chunks, s_wcnt);
+    if (threadIdx.x != 0) return;
     const LoSlot sl = a.slots[slot];
     const LoWork wk = a.work[slot];
     const int seen = a.seen[sl.stream];
@@ -312,20 +237,11 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_finish(LoArgs a) {
 
 __global__ __launch_bounds__(LO_THREADS) void leftobj_emit(LoArgs a) {
     __shared__ int s_wcnt[LO_WAVES];
-    const uint32_t *ch = a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1);
-    const uint32_t first = ch[blockIdx.x], n_here = ch[blockIdx.x + 1] - first;
-    if (n_here == 0 || first >= (uint32_t)a.max_regions) return;       // (uniform)
-    const LoSlot sl = a.slots[blockIdx.y];
-    const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
-    const long long base = (long long)blockIdx.x * LO_CHUNK;
+    const size_t s_off = (size_t)a.slots[blockIdx.y].stream * (size_t)a.cells;
     rtmodt_leftobj_region *regs = (rtmodt_leftobj_region *)(a.blocks + (size_t)blockIdx.y * a.block_stride + a.off_regions);
-    uint32_t run = first;
-    for (int r = 0; r < LO_CHUNK / LO_THREADS; ++r) {
-        const long long idx = base + r * LO_THREADS + threadIdx.x;
-        const bool f = lo_is_region(a, s_off, idx);
-        int tot;
-        const uint32_t pos = run + (uint32_t)block_scan_count<LO_WAVES>(f ? 1 : 0, s_wcnt, tot);
-        if (f && pos < (uint32_t)a.max_regions) {
+    ccl_emit_chunk<LO_WAVES>(
+        a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1), a.max_regions, s_wcnt, [&](long long idx) { return lo_is_region(a, s_off, idx); },
+        [&](long long idx, uint32_t pos) {
             const LoAcc c = a.acc[s_off + idx];
             rtmodt_leftobj_region g{};
             g.cells[0] = a.gw - (int)c.bx0; g.cells[1] = a.gh - (int)c.by0; g.cells[2] = (int)c.bx1 - 1; g.cells[3] = (int)c.by1 - 1;
@@ -335,9 +251,7 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_emit(LoArgs a) {
             g.age_min = 65535 - (int32_t)c.amin; g.age_max = (int32_t)c.amax;
             g.root = (int32_t)idx;
             regs[pos] = g;
-        }
-        run += (uint32_t)tot;
-    }
+        });
 }
 
 // ---- the ledger ----------------------------------------------------------------------------------------------------------------
@@ -551,8 +465,7 @@ using namespace rtmodt;
 struct rtmodt_leftobj {
     int device = 0;
     rtmodt_leftobj_cfg cfg{};
-    int gw = 0, gh = 0, n_chunks = 0;
-    long long cells = 0;                // per stream
+    GridGeom g;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -590,10 +503,7 @@ int lo_check_rule(const rtmodt_leftobj_cfg *c) {
 
 int lo_check_cfg(const rtmodt_leftobj_cfg *c) {
     RT_TRY(lo_check_rule(c));
-    RT_CHECK(c->streams >= 1 && c->streams <= LO_MAX_STREAMS, RTMODT_E_INVALID, "streams %d outside 1..%d", c->streams, LO_MAX_STREAMS);
-    RT_CHECK(c->height >= 1 && c->width >= 1 && c->height <= MO_MAX_DIM && c->width <= MO_MAX_DIM, RTMODT_E_INVALID, "bad frame geometry %dx%d",
-             c->width, c->height);
-    RT_CHECK(mo_scale_ok(c->scale), RTMODT_E_INVALID, "scale %d: one of 1, 2, 4, 8", c->scale);
+    RT_TRY(check_grid_cfg(c->streams, c->height, c->width, c->scale, LO_MAX_STREAMS));
     RT_CHECK(c->min_neighbors >= 1 && c->min_neighbors <= 9, RTMODT_E_INVALID, "min_neighbors %d outside 1..9", c->min_neighbors);
     RT_CHECK(c->min_area >= 1 && c->max_area >= c->min_area, RTMODT_E_INVALID, "min_area %d / max_area %d: 1 <= min_area <= max_area", c->min_area,
              c->max_area);
@@ -608,26 +518,10 @@ int lo_check_cfg(const rtmodt_leftobj_cfg *c) {
     RT_CHECK(c->max_tracks >= 1 && c->max_tracks <= LO_MAX_TRACKS, RTMODT_E_INVALID, "max_tracks %d outside 1..%d", c->max_tracks, LO_MAX_TRACKS);
     RT_CHECK(c->n_owner_classes >= 0 && c->n_owner_classes <= LO_MAX_CLASSES && c->n_report_classes >= 0 && c->n_report_classes <= LO_MAX_CLASSES,
              RTMODT_E_INVALID, "n_owner_classes %d / n_report_classes %d outside 0..%d", c->n_owner_classes, c->n_report_classes, LO_MAX_CLASSES);
-    const long long cells = (long long)mo_grid(c->height, c->scale) * mo_grid(c->width, c->scale);
-    RT_CHECK(cells <= MO_MAX_CELLS, RTMODT_E_CAPACITY, "a grid of %lld cells (at most %lld)", cells, MO_MAX_CELLS);
-    RT_CHECK(cells * c->streams <= LO_MAX_TOTAL_CELLS, RTMODT_E_CAPACITY, "%lld cells in all (at most %lld)", cells * c->streams, LO_MAX_TOTAL_CELLS);
-    return RTMODT_OK;
+    return check_grid_cells(c->streams, c->height, c->width, c->scale, LO_MAX_TOTAL_CELLS);
 }
 
-int lo_check_stream(const rtmodt_leftobj *p, int stream) {
-    RT_CHECK(stream >= 0 && stream < p->cfg.streams, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, p->cfg.streams - 1);
-    return RTMODT_OK;
-}
-
-template <bool WIDE> void lo_launch_model(int scale, dim3 grid, hipStream_t q, const LoArgs &a) {
-    const dim3 block(LO_THREADS);
-    switch (scale) {
-    case 1: hipLaunchKernelGGL((leftobj_model<1, WIDE>), grid, block, 0, q, a); break;
-    case 2: hipLaunchKernelGGL((leftobj_model<2, WIDE>), grid, block, 0, q, a); break;
-    case 4: hipLaunchKernelGGL((leftobj_model<4, WIDE>), grid, block, 0, q, a); break;
-    default: hipLaunchKernelGGL((leftobj_model<8, WIDE>), grid, block, 0, q, a); break;
-    }
-}
+void (*const lo_model_kernels[2][4])(LoArgs) = RTMODT_SCALE_KERNELS(leftobj_model);
 
 int lo_sync(rtmodt_leftobj *p) {
     RT_HIP(hipSetDevice(p->device));
@@ -676,9 +570,7 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
     rtmodt_leftobj *p = new rtmodt_leftobj();
     p->device = cfg->device;
     p->cfg = *cfg;
-    p->gw = mo_grid(cfg->width, cfg->scale); p->gh = mo_grid(cfg->height, cfg->scale);
-    p->cells = (long long)p->gw * p->gh;
-    p->n_chunks = (int)((p->cells + LO_CHUNK - 1) / LO_CHUNK);
+    p->g.set(cfg->height, cfg->width, cfg->scale);
     const size_t S = (size_t)cfg->streams, MO = (size_t)cfg->max_objects;
     p->off_abs = align_up(S * sizeof(LoWork), 16);
     p->off_blocks = align_up(p->off_abs + S * (1 + MO) * sizeof(int32_t), 16);
@@ -689,7 +581,7 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
     p->block_stride = align_up(p->off_objects + MO * sizeof(rtmodt_leftobj_object), 16);
     p->out_bytes = p->off_blocks + S * p->block_stride;
     auto body = [&]() -> int {
-        const size_t all = S * (size_t)p->cells;
+        const size_t all = S * (size_t)p->g.cells;
         RT_HIP(hipSetDevice(p->device));
         RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         RT_HIP(hipEventCreate(&p->ev0));
@@ -699,7 +591,7 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
         RT_HIP(hipMalloc((void **)&p->d_mask, all));
         RT_HIP(hipMalloc((void **)&p->d_parent, all * sizeof(int32_t)));
         RT_HIP(hipMalloc((void **)&p->d_acc, all * sizeof(LoAcc)));
-        RT_HIP(hipMalloc((void **)&p->d_chunk, S * (size_t)(p->n_chunks + 1) * sizeof(uint32_t)));
+        RT_HIP(hipMalloc((void **)&p->d_chunk, S * (size_t)(p->g.n_chunks + 1) * sizeof(uint32_t)));
         RT_HIP(hipMalloc((void **)&p->d_seen, S * sizeof(int32_t)));
         RT_HIP(hipMalloc((void **)&p->d_meta, S * 4 * sizeof(int32_t)));
         RT_HIP(hipMalloc((void **)&p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object)));
@@ -745,16 +637,7 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     const rtmodt_leftobj_cfg &c = p->cfg;
     const int S = c.streams, Mc = c.max_tracks;
-    RT_CHECK(n <= S, RTMODT_E_INVALID, "%d frames in one call for %d streams", n, S);
-    RT_CHECK(streams || n == S || n == 0, RTMODT_E_INVALID, "%d frames for %d streams and no stream list", n, S);
-    std::vector<char> named(S, 0);
-    for (int i = 0; i < n; ++i) {
-        RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-        const int s = streams ? streams[i] : i;
-        RT_TRY(lo_check_stream(p, s));
-        RT_CHECK(!named[s], RTMODT_E_INVALID, "stream %d is named twice in one call", s);
-        named[s] = 1;
-    }
+    RT_TRY(check_stream_list(frames, streams, n, S));
     const int source = tracks ? tracks->source : RTMODT_LEFTOBJ_TRACKS_NONE;
     RT_CHECK(source >= RTMODT_LEFTOBJ_TRACKS_NONE && source <= RTMODT_LEFTOBJ_TRACKS_BOTSORT, RTMODT_E_INVALID, "track source %d", source);
     LoArgs a{};
@@ -806,10 +689,8 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     RT_TRY(p->cmd.reserve(cmd_bytes));
     memset(p->cmd.h, 0, cmd_bytes);
     LoSlot *sl = (LoSlot *)p->cmd.h;
-    bool wide = p->stage.pitch % 4 == 0;
     for (int i = 0; i < n; ++i) {
         sl[i] = LoSlot{(uint64_t)(uintptr_t)p->stage.at(frames, i), frame_ids[i], streams ? streams[i] : i, 0};
-        wide = wide && sl[i].frame % 4 == 0;
         if (!list) continue;
         const int m = tracks->n[i];
         ((int32_t *)(p->cmd.h + o_n))[i] = m;
@@ -822,11 +703,11 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     RT_TRY(p->stage.copy_in(frames, q));
 
     a.slots = (const LoSlot *)p->cmd.d;
-    a.pitch = (long long)p->stage.pitch; a.cells = p->cells;
-    a.h = h; a.w = w; a.scale = c.scale; a.gw = p->gw; a.gh = p->gh;
+    a.pitch = (long long)p->stage.pitch; a.cells = p->g.cells;
+    a.h = h; a.w = w; a.scale = c.scale; a.gw = p->g.gw; a.gh = p->g.gh;
     a.rule = lo_rule(c);
     a.min_neighbors = c.min_neighbors; a.scene_pm = c.scene_pm; a.min_area = c.min_area; a.max_area = c.max_area; a.max_regions = c.max_regions;
-    a.n_chunks = p->n_chunks;
+    a.n_chunks = p->g.n_chunks;
     a.max_objects = c.max_objects; a.miss_frames = c.miss_frames; a.alarm_frames = c.alarm_frames; a.absorb_frames = c.absorb_frames;
     a.covered_pm = c.covered_pm; a.attend_margin = c.attend_margin;
     a.n_owner = c.n_owner_classes; a.n_report = c.n_report_classes;
@@ -843,26 +724,23 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     }
 
     const dim3 block(LO_THREADS);
-    const int cpt = c.scale >= 4 ? 1 : 4 / c.scale;
-    const unsigned per_cell = (unsigned)((p->cells + LO_THREADS - 1) / LO_THREADS);
+    const GridGeom &g = p->g;
     const size_t blocks_bytes = (size_t)n * p->block_stride;
     RT_HIP(hipEventRecord(p->ev0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, p->off_blocks + blocks_bytes, q));
     LoArgs m = a;
-    m.tiles_x = cdiv(p->gw, 64 * cpt);
-    const dim3 mgrid((unsigned)(m.tiles_x * cdiv(p->gh, LO_ROWS)), n);
-    if (wide) lo_launch_model<true>(c.scale, mgrid, q, m);
-    else lo_launch_model<false>(c.scale, mgrid, q, m);
+    m.tiles_x = g.model_tiles_x();
+    launch_by_scale(lo_model_kernels, c.scale, frames_wide(p->stage, sl, n), g.model_grid(n), q, m);
     LoArgs f = a;
-    f.tiles_x = cdiv(p->gw, LO_TW);
-    hipLaunchKernelGGL(leftobj_filter, dim3((unsigned)(f.tiles_x * cdiv(p->gh, LO_TH)), n), block, 0, q, f);
-    hipLaunchKernelGGL(leftobj_link, dim3(per_cell, n), block, 0, q, a);
-    hipLaunchKernelGGL(leftobj_roots, dim3(per_cell, n), block, 0, q, a);
-    hipLaunchKernelGGL(leftobj_count, dim3((unsigned)p->n_chunks, n), block, 0, q, a);
+    f.tiles_x = g.filter_tiles_x();
+    hipLaunchKernelGGL(leftobj_filter, g.filter_grid(n), block, 0, q, f);
+    hipLaunchKernelGGL(leftobj_link, g.per_cell(n), block, 0, q, a);
+    hipLaunchKernelGGL(leftobj_roots, g.per_cell(n), block, 0, q, a);
+    hipLaunchKernelGGL(leftobj_count, g.per_chunk(n), block, 0, q, a);
     hipLaunchKernelGGL(leftobj_finish, dim3(n), block, 0, q, a);
-    hipLaunchKernelGGL(leftobj_emit, dim3((unsigned)p->n_chunks, n), block, 0, q, a);
+    hipLaunchKernelGGL(leftobj_emit, g.per_chunk(n), block, 0, q, a);
     hipLaunchKernelGGL(leftobj_step, dim3(n), block, 0, q, a);
-    hipLaunchKernelGGL(leftobj_absorb, dim3(per_cell, n), block, 0, q, a);
+    hipLaunchKernelGGL(leftobj_absorb, g.per_cell(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(p->ev1, q));
     const bool any = out && (out->results || out->regions || out->events || out->retired || out->objects);
@@ -885,10 +763,10 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
 
 int rtmodt_leftobj_read_state(rtmodt_leftobj *p, int stream, uint64_t *cells, uint8_t *luma, int32_t *frames_seen) {
     RT_CHECK(p && frames_seen, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
-    if (cells) RT_HIP(hipMemcpyAsync(cells, p->d_state + (size_t)stream * p->cells, (size_t)p->cells * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
-    if (luma) RT_HIP(hipMemcpyAsync(luma, p->d_luma + (size_t)stream * p->cells, (size_t)p->cells, hipMemcpyDeviceToHost, p->stream));
+    if (cells) RT_HIP(hipMemcpyAsync(cells, p->d_state + (size_t)stream * p->g.cells, (size_t)p->g.cells * sizeof(uint64_t), hipMemcpyDeviceToHost, p->stream));
+    if (luma) RT_HIP(hipMemcpyAsync(luma, p->d_luma + (size_t)stream * p->g.cells, (size_t)p->g.cells, hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipMemcpyAsync(frames_seen, p->d_seen + stream, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
@@ -896,11 +774,11 @@ int rtmodt_leftobj_read_state(rtmodt_leftobj *p, int stream, uint64_t *cells, ui
 
 int rtmodt_leftobj_load_state(rtmodt_leftobj *p, int stream, const uint64_t *cells, const uint8_t *luma, int32_t frames_seen) {
     RT_CHECK(p && cells && luma, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_CHECK(frames_seen >= 0 && frames_seen <= MO_MAX_SEEN, RTMODT_E_INVALID, "frames_seen %d outside 0..%d", frames_seen, MO_MAX_SEEN);
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(p->d_state + (size_t)stream * p->cells, cells, (size_t)p->cells * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
-    RT_HIP(hipMemcpyAsync(p->d_luma + (size_t)stream * p->cells, luma, (size_t)p->cells, hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_state + (size_t)stream * p->g.cells, cells, (size_t)p->g.cells * sizeof(uint64_t), hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_luma + (size_t)stream * p->g.cells, luma, (size_t)p->g.cells, hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipMemcpyAsync(p->d_seen + stream, &frames_seen, sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
@@ -908,26 +786,26 @@ int rtmodt_leftobj_load_state(rtmodt_leftobj *p, int stream, const uint64_t *cel
 
 int rtmodt_leftobj_read_mask(rtmodt_leftobj *p, int stream, uint8_t *out) {
     RT_CHECK(p && out, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(out, p->d_mask + (size_t)stream * p->cells, (size_t)p->cells, hipMemcpyDeviceToHost, p->stream));
+    RT_HIP(hipMemcpyAsync(out, p->d_mask + (size_t)stream * p->g.cells, (size_t)p->g.cells, hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
 }
 
 int rtmodt_leftobj_load_mask(rtmodt_leftobj *p, int stream, const uint8_t *mask) {
     RT_CHECK(p && mask, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
-    for (long long i = 0; i < p->cells; ++i) RT_CHECK(mask[i] <= 1, RTMODT_E_INVALID, "mask cell %lld is %d (0 or 1)", i, (int)mask[i]);
+    RT_TRY(check_stream(stream, p->cfg.streams));
+    for (long long i = 0; i < p->g.cells; ++i) RT_CHECK(mask[i] <= 1, RTMODT_E_INVALID, "mask cell %lld is %d (0 or 1)", i, (int)mask[i]);
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(p->d_mask + (size_t)stream * p->cells, mask, (size_t)p->cells, hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_mask + (size_t)stream * p->g.cells, mask, (size_t)p->g.cells, hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
 }
 
 int rtmodt_leftobj_read_ledger(rtmodt_leftobj *p, int stream, rtmodt_leftobj_object *objects, int32_t *n, int32_t *next_oid) {
     RT_CHECK(p && n && next_oid, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_TRY(lo_sync(p));
     int32_t m[4];
     RT_HIP(hipMemcpy(m, p->d_meta + 4 * stream, sizeof(m), hipMemcpyDeviceToHost));
@@ -941,7 +819,7 @@ int rtmodt_leftobj_read_ledger(rtmodt_leftobj *p, int stream, rtmodt_leftobj_obj
 
 int rtmodt_leftobj_load_ledger(rtmodt_leftobj *p, int stream, const rtmodt_leftobj_object *objects, int n, int32_t next_oid) {
     RT_CHECK(p && (objects || n == 0), RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_CHECK(n >= 0 && n <= p->cfg.max_objects && next_oid >= 1, RTMODT_E_INVALID, "%d rows (0..%d), next oid %d (>= 1)", n, p->cfg.max_objects, next_oid);
     for (int i = 0; i < n; ++i)
         RT_CHECK(objects[i].oid >= 1 && objects[i].oid < next_oid && (i == 0 || objects[i].oid > objects[i - 1].oid), RTMODT_E_INVALID,
@@ -955,36 +833,36 @@ int rtmodt_leftobj_load_ledger(rtmodt_leftobj *p, int stream, const rtmodt_lefto
 
 int rtmodt_leftobj_set_ignore(rtmodt_leftobj *p, int stream, const uint8_t *grid) {
     RT_CHECK(p && grid, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_TRY(lo_sync(p));
-    p->h_cells.resize((size_t)p->cells);
-    uint64_t *d = p->d_state + (size_t)stream * p->cells;
-    RT_HIP(hipMemcpy(p->h_cells.data(), d, (size_t)p->cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (long long i = 0; i < p->cells; ++i) p->h_cells[i] = (p->h_cells[i] & ~(1ull << 56)) | (grid[i] ? 1ull << 56 : 0);
-    RT_HIP(hipMemcpy(d, p->h_cells.data(), (size_t)p->cells * sizeof(uint64_t), hipMemcpyHostToDevice));
+    p->h_cells.resize((size_t)p->g.cells);
+    uint64_t *d = p->d_state + (size_t)stream * p->g.cells;
+    RT_HIP(hipMemcpy(p->h_cells.data(), d, (size_t)p->g.cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < p->g.cells; ++i) p->h_cells[i] = (p->h_cells[i] & ~(1ull << 56)) | (grid[i] ? 1ull << 56 : 0);
+    RT_HIP(hipMemcpy(d, p->h_cells.data(), (size_t)p->g.cells * sizeof(uint64_t), hipMemcpyHostToDevice));
     return RTMODT_OK;
 }
 
 int rtmodt_leftobj_read_ignore(rtmodt_leftobj *p, int stream, uint8_t *grid) {
     RT_CHECK(p && grid, RTMODT_E_INVALID, "null argument");
-    RT_TRY(lo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_TRY(lo_sync(p));
-    p->h_cells.resize((size_t)p->cells);
-    RT_HIP(hipMemcpy(p->h_cells.data(), p->d_state + (size_t)stream * p->cells, (size_t)p->cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (long long i = 0; i < p->cells; ++i) grid[i] = (uint8_t)(p->h_cells[i] >> 56 & 1);
+    p->h_cells.resize((size_t)p->g.cells);
+    RT_HIP(hipMemcpy(p->h_cells.data(), p->d_state + (size_t)stream * p->g.cells, (size_t)p->g.cells * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (long long i = 0; i < p->g.cells; ++i) grid[i] = (uint8_t)(p->h_cells[i] >> 56 & 1);
     return RTMODT_OK;
 }
 
 int rtmodt_leftobj_reset(rtmodt_leftobj *p, int stream) {
     RT_CHECK(p, RTMODT_E_INVALID, "null argument");
-    if (stream != -1) RT_TRY(lo_check_stream(p, stream));
+    if (stream != -1) RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
     const size_t first = stream < 0 ? 0 : (size_t)stream, count = stream < 0 ? (size_t)p->cfg.streams : 1;
-    const long long nc = (long long)count * p->cells;
-    hipLaunchKernelGGL(leftobj_clear, dim3((unsigned)((nc + LO_THREADS - 1) / LO_THREADS)), dim3(LO_THREADS), 0, p->stream, p->d_state + first * p->cells, nc);
+    const long long nc = (long long)count * p->g.cells;
+    hipLaunchKernelGGL(leftobj_clear, dim3((unsigned)((nc + LO_THREADS - 1) / LO_THREADS)), dim3(LO_THREADS), 0, p->stream, p->d_state + first * p->g.cells, nc);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemsetAsync(p->d_luma + first * p->cells, 0, count * p->cells, p->stream));
-    RT_HIP(hipMemsetAsync(p->d_mask + first * p->cells, 0, count * p->cells, p->stream));
+    RT_HIP(hipMemsetAsync(p->d_luma + first * p->g.cells, 0, count * p->g.cells, p->stream));
+    RT_HIP(hipMemsetAsync(p->d_mask + first * p->g.cells, 0, count * p->g.cells, p->stream));
     RT_HIP(hipMemsetAsync(p->d_seen + first, 0, count * sizeof(int32_t), p->stream));
     RT_HIP(hipMemsetAsync(p->d_meta + first * 4, 0, count * 4 * sizeof(int32_t), p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));

@@ -14,17 +14,15 @@
 //
 // Kernels (256 threads; seven launches and one memset per call for all its streams, whatever the frames show; no grid-wide
 // barrier, no spin on another workgroup):
-//   motion_model   the hot path: every pixel is read once.  A thread owns a run of 4 / scale cells (at least one) of one cell row,
-//                  12 bytes of each pixel row (24 at scale 8); lanes are adjacent runs, so a wave reads 768 contiguous bytes per
-//                  pixel row.  WIDE (every frame base and the pitch a multiple of 4): the full runs of full cell rows are read as
-//                  dwords, all of them issued before the first is used; else byte by byte.  No atomics and no floats on the model:
-//                  a cell is read and written by one lane.  n_raw and luma_sum are summed per wave and added with one integer
+//   motion_model   the hot path: every pixel is read once, by cell_grid.h's reader (a thread owns a run of 4 / scale cells of one
+//                  cell row; dwords where every frame base and the pitch are multiples of 4).  No atomics and no floats on the
+//                  model: a cell is read and written by one lane.  n_raw and luma_sum are summed per wave and added with one integer
 //                  atomic each.  The kernel also zeroes the stream's block grid.
 //   motion_filter  one workgroup per tile of 64 x 16 cells: raw through LDS with a halo of 1 + dilate, the 3 x 3 count, the
 //                  dilation; writes the mask, makes every mask cell its own union-find root, adds n_fg, the box and (through LDS)
 //                  the block grid.
-//   motion_link    union-find over the mask (stitch.hip's: compare-and-swap hooks the larger root under the smaller, path halving);
-//                  a cell looks at W, NW, N, NE and skips the links its neighbours make.
+//   motion_link    union-find over the mask (ccl_dev.h: compare-and-swap hooks the larger root under the smaller, path halving); a
+//                  cell looks at W, NW, N, NE and skips the links its neighbours make.
 //   motion_roots   every mask cell adds its area and box at its root; a wave whose mask cells share one root adds once.
 //   motion_count   qualifying roots (parent == self, area >= min_area) per chunk of 4096 cells.  A root is the smallest index of
 //                  its component, that is its first cell in raster order.
@@ -35,16 +33,15 @@
 #include <cstring>
 #include <vector>
 
-#include "frame_stage.h"
-
 #define MO_HD __host__ __device__
-#include "motion_model.h"
+#include "grid_host.h"
 
 namespace rtmodt {
 
 #include "wg_dev.h"
+#include "ccl_dev.h"
 
-constexpr int MO_THREADS = 256, MO_WAVES = MO_THREADS / 64, MO_TW = 64, MO_TH = 16, MO_ROWS = 4, MO_CHUNK = 4096, MO_MAX_HALO = 4;
+constexpr int MO_THREADS = CG_THREADS, MO_WAVES = MO_THREADS / 64, MO_TW = GRID_TW, MO_TH = GRID_TH, MO_MAX_HALO = 4;
 constexpr int MO_MAX_STREAMS = 1024;
 constexpr long long MO_MAX_TOTAL_CELLS = 1LL << 28;
 static_assert(sizeof(rtmodt_motion_result) == 56, "layout");
@@ -68,20 +65,9 @@ struct MoArgs {
     rtmodt_motion_result *res; int32_t *regions;
 };
 
-__device__ __forceinline__ uint32_t mo_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-__device__ __forceinline__ uint32_t mo_wave_max(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
-
-// ---- model: pixels -> cell luma -> bg / dev / raw ------------------------------------------------------------------------
+// ---- model: pixels -> cell luma (cell_grid.h) -> bg / dev / raw ----------------------------------------------------------
 template <int SCALE, bool WIDE> __global__ __launch_bounds__(MO_THREADS) void motion_model(MoArgs a) {
-    constexpr int CPT = SCALE >= 4 ? 1 : 4 / SCALE, PX = SCALE * CPT, RUN = 3 * PX;     // cells, pixels and bytes of a thread's run
+    constexpr int CPT = CgRun<SCALE>::CPT;
     const int tid = threadIdx.x;
     const MoSlot sl = a.slots[blockIdx.y];
     const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
@@ -89,47 +75,17 @@ template <int SCALE, bool WIDE> __global__ __launch_bounds__(MO_THREADS) void mo
     for (int i = blockIdx.x * MO_THREADS + tid; i < n_blocks; i += gridDim.x * MO_THREADS) a.blocks[(size_t)sl.stream * n_blocks + i] = 0;
 
     const int seen = a.seen[sl.stream];
-    const int cy = (int)(blockIdx.x / a.tiles_x) * MO_ROWS + (tid >> 6);
-    const int cxb = ((int)(blockIdx.x % a.tiles_x) * 64 + (tid & 63)) * CPT;
+    const CgLane l = cg_lane<SCALE>(blockIdx.x, a.tiles_x, tid, (const uint8_t *)sl.frame, a.pitch, a.h, a.w, a.gw, a.gh);
     uint32_t luma = 0, n_raw = 0;
-    if (cy < a.gh && cxb < a.gw) {
-        const int px0 = cxb * SCALE, npx = min(PX, a.w - px0);
-        const int y0 = cy * SCALE, nrows = min(SCALE, a.h - y0);
-        const uint8_t *p = (const uint8_t *)sl.frame + (long long)y0 * a.pitch + 3LL * px0;
+    if (l.live) {
         uint32_t sum[CPT];
-#pragma unroll
-        for (int j = 0; j < CPT; ++j) sum[j] = 0;
-        if (WIDE && npx == PX && nrows == SCALE) {
-            uint32_t v[SCALE][RUN / 4];                             // every load of the run is issued before the first is used
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r) {
-                const uint32_t *q = (const uint32_t *)(p + r * a.pitch);    // base, pitch and 3 * px0 (a multiple of 12) are multiples of 4
-#pragma unroll
-                for (int k = 0; k < RUN / 4; ++k) v[r][k] = q[k];
-            }
-#pragma unroll
-            for (int r = 0; r < SCALE; ++r)
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    uint32_t c[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c[k] = (v[r][(3 * i + k) >> 2] >> (8 * ((3 * i + k) & 3))) & 255u;
-                    sum[i / SCALE] += mo_luma(c[0], c[1], c[2]);
-                }
-        } else {
-            for (int r = 0; r < nrows; ++r, p += a.pitch)
-#pragma unroll
-                for (int i = 0; i < PX; ++i)
-                    if (i < npx) sum[i / SCALE] += mo_luma(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-        }
-        uint32_t *m = a.model + s_off + (size_t)cy * a.gw + cxb;
-        uint8_t *rw = a.raw + s_off + (size_t)cy * a.gw + cxb;
+        cg_read_run<SCALE, WIDE>(l.p, a.pitch, l.npx, l.nrows, sum);
+        uint32_t *m = a.model + s_off + (size_t)l.cy * a.gw + l.cxb;
+        uint8_t *rw = a.raw + s_off + (size_t)l.cy * a.gw + l.cxb;
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
-            const int cols = mo_cell_span(cxb + j, SCALE, a.w);
-            if (cols == 0) continue;
-            const uint32_t cnt = (uint32_t)(cols * nrows);
-            const uint32_t yc = cnt == SCALE * SCALE ? (sum[j] + SCALE * SCALE / 2) / (SCALE * SCALE) : mo_cell_mean(sum[j], cnt);
+            uint32_t yc;
+            if (!cg_cell_luma<SCALE>(sum[j], l.cxb + j, l.nrows, a.w, yc)) continue;
             const uint32_t packed = m[j];
             uint32_t bg = packed & 0xffffu, dev = packed >> 16;
             const bool raw = mo_cell(a.rule, yc, seen, bg, dev);
@@ -139,8 +95,8 @@ template <int SCALE, bool WIDE> __global__ __launch_bounds__(MO_THREADS) void mo
             n_raw += raw ? 1u : 0u;
         }
     }
-    luma = mo_wave_sum(luma);
-    n_raw = mo_wave_sum(n_raw);
+    luma = wave_sum_u32(luma);
+    n_raw = wave_sum_u32(n_raw);
     if ((tid & 63) == 0) {
         MoWork *wk = a.work + blockIdx.y;
         if (luma) atomicAdd(&wk->luma, (unsigned long long)luma);
@@ -198,8 +154,8 @@ __global__ __launch_bounds__(MO_THREADS) void motion_filter(MoArgs a) {
         bx1 = max(bx1, (uint32_t)(cx + 1)); by1 = max(by1, (uint32_t)(cy + 1));
         atomicAdd(&s_blk[(ly >> bshift) * bpr + (lx >> bshift)], 1u);
     }
-    n_fg = mo_wave_sum(n_fg);
-    bx0 = mo_wave_max(bx0); by0 = mo_wave_max(by0); bx1 = mo_wave_max(bx1); by1 = mo_wave_max(by1);
+    n_fg = wave_sum_u32(n_fg);
+    bx0 = wave_max_u32(bx0); by0 = wave_max_u32(by0); bx1 = wave_max_u32(bx1); by1 = wave_max_u32(by1);
     if ((tid & 63) == 0 && n_fg) {
         MoWork *wk = a.work + blockIdx.y;
         atomicAdd(&wk->n_fg, n_fg);
@@ -212,50 +168,12 @@ __global__ __launch_bounds__(MO_THREADS) void motion_filter(MoArgs a) {
     }
 }
 
-// ---- labelling: union-find, the larger root under the smaller ---------------------------------------------------------------
-__device__ __forceinline__ int mo_ld(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void mo_st(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ int mo_find(int32_t *p, int x) {
-    int c = mo_ld(&p[x]);
-    while (c != x) {                                        // parents only ever point at smaller cells: no cycle
-        const int g = mo_ld(&p[c]);
-        if (g == c) return c;
-        mo_st(&p[x], g);                                    // path halving: any ancestor is a valid parent
-        x = c;
-        c = g;
-    }
-    return x;
-}
-__device__ void mo_unite(int32_t *p, int x, int y) {
-    while (true) {
-        x = mo_find(p, x);
-        y = mo_find(p, y);
-        if (x == y) return;
-        if (x < y) { const int t = x; x = y; y = t; }
-        if (atomicCAS(&p[x], x, y) == x) return;
-    }
-}
-
+// ---- labelling (ccl_dev.h) ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MO_THREADS) void motion_link(MoArgs a) {
     const MoSlot sl = a.slots[blockIdx.y];
     const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
     const long long idx = (long long)blockIdx.x * MO_THREADS + threadIdx.x;
-    if (idx >= a.cells) return;
-    const uint8_t *mk = a.mask + s_off;
-    if (!mk[idx]) return;
-    const int cx = (int)(idx % a.gw), cy = (int)(idx / a.gw);
-    int32_t *par = a.parent + s_off;
-    const bool up = cy > 0;
-    const bool W = cx > 0 && mk[idx - 1];
-    const bool N = up && mk[idx - a.gw];
-    const bool NW = up && cx > 0 && mk[idx - a.gw - 1];
-    const bool NE = up && cx + 1 < a.gw && mk[idx - a.gw + 1];
-    // N joins W, NW and NE already (N's own W link, NE's W link, W's link upwards); without N, W joins NW
-    if (N) { mo_unite(par, (int)idx, (int)(idx - a.gw)); return; }
-    if (W) mo_unite(par, (int)idx, (int)idx - 1);
-    else if (NW) mo_unite(par, (int)idx, (int)(idx - a.gw - 1));
-    if (NE) mo_unite(par, (int)idx, (int)(idx - a.gw + 1));
+    if (idx < a.cells) ccl_link_cell(a.mask + s_off, a.parent + s_off, a.gw, idx);
 }
 
 __global__ __launch_bounds__(MO_THREADS) void motion_roots(MoArgs a) {
@@ -267,19 +185,16 @@ __global__ __launch_bounds__(MO_THREADS) void motion_roots(MoArgs a) {
     uint32_t bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;
     if (m) {
         const int cx = (int)(idx % a.gw), cy = (int)(idx / a.gw);
-        root = mo_find(a.parent + s_off, (int)idx);
+        root = ccl_find(a.parent + s_off, (int)idx);
         bx0 = (uint32_t)(a.gw - cx); by0 = (uint32_t)(a.gh - cy); bx1 = (uint32_t)(cx + 1); by1 = (uint32_t)(cy + 1);
     }
-    const unsigned long long act = __ballot(m);
-    if (!act) return;                                       // (wave-uniform)
-    const int lead = __ffsll((long long)act) - 1;
-    const int root0 = __shfl(root, lead);
-    const bool same = __ballot(m && root != root0) == 0;
-    const uint32_t wx0 = mo_wave_max(bx0), wy0 = mo_wave_max(by0), wx1 = mo_wave_max(bx1), wy1 = mo_wave_max(by1);
+    CclWave wv;
+    if (!ccl_wave_roots(m, root, wv)) return;
+    const uint32_t wx0 = wave_max_u32(bx0), wy0 = wave_max_u32(by0), wx1 = wave_max_u32(bx1), wy1 = wave_max_u32(by1);
     uint32_t n = 1;
-    if (same) {                                             // one add per wave
-        if ((int)(threadIdx.x & 63) != lead) return;
-        n = (uint32_t)__popcll(act); bx0 = wx0; by0 = wy0; bx1 = wx1; by1 = wy1;
+    if (wv.same) {                                          // one add per wave
+        if ((int)(threadIdx.x & 63) != wv.lead) return;
+        n = wv.n; bx0 = wx0; by0 = wy0; bx1 = wx1; by1 = wy1;
     } else if (!m) {
         return;
     }
@@ -288,37 +203,22 @@ __global__ __launch_bounds__(MO_THREADS) void motion_roots(MoArgs a) {
     atomicMax(b, bx0); atomicMax(b + 1, by0); atomicMax(b + 2, bx1); atomicMax(b + 3, by1);
 }
 
+// a qualifying root of stream offset s_off: the smallest index of its component, that is its first cell in raster order
 __device__ __forceinline__ bool mo_is_region(const MoArgs &a, size_t s_off, long long idx) {
     return idx < a.cells && a.mask[s_off + idx] && a.parent[s_off + idx] == (int32_t)idx && a.area[s_off + idx] >= (uint32_t)a.min_area;
 }
 
 __global__ __launch_bounds__(MO_THREADS) void motion_count(MoArgs a) {
     __shared__ int s_wcnt[MO_WAVES];
-    const MoSlot sl = a.slots[blockIdx.y];
-    const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
-    const long long base = (long long)blockIdx.x * MO_CHUNK;
-    int mine = 0;
-    for (int r = 0; r < MO_CHUNK / MO_THREADS; ++r) mine += mo_is_region(a, s_off, base + r * MO_THREADS + threadIdx.x) ? 1 : 0;
-    int total;
-    block_scan_count<MO_WAVES>(mine, s_wcnt, total);
-    if (threadIdx.x == 0) a.chunk[(size_t)blockIdx.y * (a.n_chunks + 1) + blockIdx.x] = (uint32_t)total;
+    const size_t s_off = (size_t)a.slots[blockIdx.y].stream * (size_t)a.cells;
+    ccl_count_chunk<MO_WAVES>(a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1), s_wcnt, [&](long long idx) { return mo_is_region(a, s_off, idx); });
 }
 
 __global__ __launch_bounds__(MO_THREADS) void motion_finish(MoArgs a) {
     __shared__ int s_wcnt[MO_WAVES];
-    const int tid = threadIdx.x, slot = blockIdx.x;
-    uint32_t *ch = a.chunk + (size_t)slot * (a.n_chunks + 1);
-    uint32_t run = 0;
-    for (int b = 0; b < a.n_chunks; b += MO_THREADS) {
-        const int i = b + tid;
-        const int v = i < a.n_chunks ? (int)ch[i] : 0;
-        int tot;
-        const int pos = block_scan_count<MO_WAVES>(v, s_wcnt, tot);
-        if (i < a.n_chunks) ch[i] = run + (uint32_t)pos;
-        run += (uint32_t)tot;
-    }
-    if (tid != 0) return;
-    ch[a.n_chunks] = run;
+    const int slot = blockIdx.x;
+    const uint32_t run = ccl_scan_chunks<MO_WAVES>(a.chunk + (size_t)slot * (a.n_chunks + 1), a.n_chunks, s_wcnt);
+    if (threadIdx.x != 0) return;
     const MoSlot sl = a.slots[slot];
     const MoWork wk = a.work[slot];
     const int seen = a.seen[sl.stream];
@@ -337,26 +237,15 @@ __global__ __launch_bounds__(MO_THREADS) void motion_finish(MoArgs a) {
 
 __global__ __launch_bounds__(MO_THREADS) void motion_emit(MoArgs a) {
     __shared__ int s_wcnt[MO_WAVES];
-    const uint32_t *ch = a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1);
-    const uint32_t first = ch[blockIdx.x], n_here = ch[blockIdx.x + 1] - first;
-    if (n_here == 0 || first >= (uint32_t)a.max_regions) return;       // (uniform)
-    const MoSlot sl = a.slots[blockIdx.y];
-    const size_t s_off = (size_t)sl.stream * (size_t)a.cells;
-    const long long base = (long long)blockIdx.x * MO_CHUNK;
-    uint32_t run = first;
-    for (int r = 0; r < MO_CHUNK / MO_THREADS; ++r) {
-        const long long idx = base + r * MO_THREADS + threadIdx.x;
-        const bool f = mo_is_region(a, s_off, idx);
-        int tot;
-        const uint32_t pos = run + (uint32_t)block_scan_count<MO_WAVES>(f ? 1 : 0, s_wcnt, tot);
-        if (f && pos < (uint32_t)a.max_regions) {
+    const size_t s_off = (size_t)a.slots[blockIdx.y].stream * (size_t)a.cells;
+    ccl_emit_chunk<MO_WAVES>(
+        a.chunk + (size_t)blockIdx.y * (a.n_chunks + 1), a.max_regions, s_wcnt, [&](long long idx) { return mo_is_region(a, s_off, idx); },
+        [&](long long idx, uint32_t pos) {
             const uint4 b = a.box[s_off + idx];
             int32_t *out = a.regions + ((size_t)blockIdx.y * a.max_regions + pos) * 5;
             mo_px_box(a.gw - (int)b.x, a.gh - (int)b.y, (int)b.z - 1, (int)b.w - 1, a.scale, a.w, a.h, out);
             out[4] = (int32_t)a.area[s_off + idx];
-        }
-        run += (uint32_t)tot;
-    }
+        });
 }
 
 }  // namespace rtmodt
@@ -369,8 +258,8 @@ using namespace rtmodt;
 struct rtmodt_motion {
     int device = 0;
     rtmodt_motion_cfg cfg{};
-    int gw = 0, gh = 0, bgw = 0, bgh = 0, n_chunks = 0;
-    long long cells = 0;                // per stream
+    GridGeom g;
+    int bgw = 0, bgh = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -402,36 +291,17 @@ int mo_check_rule(const rtmodt_motion_cfg *c) {
 
 int mo_check_cfg(const rtmodt_motion_cfg *c) {
     RT_TRY(mo_check_rule(c));
-    RT_CHECK(c->streams >= 1 && c->streams <= MO_MAX_STREAMS, RTMODT_E_INVALID, "streams %d outside 1..%d", c->streams, MO_MAX_STREAMS);
-    RT_CHECK(c->height >= 1 && c->width >= 1 && c->height <= MO_MAX_DIM && c->width <= MO_MAX_DIM, RTMODT_E_INVALID, "bad frame geometry %dx%d",
-             c->width, c->height);
-    RT_CHECK(mo_scale_ok(c->scale), RTMODT_E_INVALID, "scale %d: one of 1, 2, 4, 8", c->scale);
+    RT_TRY(check_grid_cfg(c->streams, c->height, c->width, c->scale, MO_MAX_STREAMS));
     RT_CHECK(c->min_neighbors >= 1 && c->min_neighbors <= 9, RTMODT_E_INVALID, "min_neighbors %d outside 1..9", c->min_neighbors);
     RT_CHECK(c->dilate >= 0 && c->dilate <= 3, RTMODT_E_INVALID, "dilate %d outside 0..3", c->dilate);
     RT_CHECK(c->scene_pm >= 1 && c->scene_pm <= 1000, RTMODT_E_INVALID, "scene_pm %d outside 1..1000", c->scene_pm);
     RT_CHECK(c->min_area >= 1, RTMODT_E_INVALID, "min_area %d below 1", c->min_area);
     RT_CHECK(c->max_regions >= 1 && c->max_regions <= MO_MAX_REGIONS, RTMODT_E_INVALID, "max_regions %d outside 1..%d", c->max_regions, MO_MAX_REGIONS);
     RT_CHECK(mo_block_ok(c->block), RTMODT_E_INVALID, "block %d: one of 4, 8, 16, 32", c->block);
-    const long long cells = (long long)mo_grid(c->height, c->scale) * mo_grid(c->width, c->scale);
-    RT_CHECK(cells <= MO_MAX_CELLS, RTMODT_E_CAPACITY, "a grid of %lld cells (at most %lld)", cells, MO_MAX_CELLS);
-    RT_CHECK(cells * c->streams <= MO_MAX_TOTAL_CELLS, RTMODT_E_CAPACITY, "%lld cells in all (at most %lld)", cells * c->streams, MO_MAX_TOTAL_CELLS);
-    return RTMODT_OK;
+    return check_grid_cells(c->streams, c->height, c->width, c->scale, MO_MAX_TOTAL_CELLS);
 }
 
-int mo_check_stream(const rtmodt_motion *p, int stream) {
-    RT_CHECK(stream >= 0 && stream < p->cfg.streams, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, p->cfg.streams - 1);
-    return RTMODT_OK;
-}
-
-template <bool WIDE> void mo_launch_model(int scale, dim3 grid, hipStream_t q, const MoArgs &a) {
-    const dim3 block(MO_THREADS);
-    switch (scale) {
-    case 1: hipLaunchKernelGGL((motion_model<1, WIDE>), grid, block, 0, q, a); break;
-    case 2: hipLaunchKernelGGL((motion_model<2, WIDE>), grid, block, 0, q, a); break;
-    case 4: hipLaunchKernelGGL((motion_model<4, WIDE>), grid, block, 0, q, a); break;
-    default: hipLaunchKernelGGL((motion_model<8, WIDE>), grid, block, 0, q, a); break;
-    }
-}
+void (*const mo_model_kernels[2][4])(MoArgs) = RTMODT_SCALE_KERNELS(motion_model);
 
 }  // namespace
 
@@ -466,12 +336,10 @@ int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out) {
     rtmodt_motion *p = new rtmodt_motion();
     p->device = cfg->device;
     p->cfg = *cfg;
-    p->gw = mo_grid(cfg->width, cfg->scale); p->gh = mo_grid(cfg->height, cfg->scale);
-    p->bgw = cdiv(p->gw, cfg->block); p->bgh = cdiv(p->gh, cfg->block);
-    p->cells = (long long)p->gw * p->gh;
-    p->n_chunks = (int)((p->cells + MO_CHUNK - 1) / MO_CHUNK);
+    p->g.set(cfg->height, cfg->width, cfg->scale);
+    p->bgw = cdiv(p->g.gw, cfg->block); p->bgh = cdiv(p->g.gh, cfg->block);
     auto body = [&]() -> int {
-        const size_t S = (size_t)cfg->streams, all = S * (size_t)p->cells, nb = S * (size_t)p->bgw * p->bgh;
+        const size_t S = (size_t)cfg->streams, all = S * (size_t)p->g.cells, nb = S * (size_t)p->bgw * p->bgh;
         RT_HIP(hipSetDevice(p->device));
         RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         RT_HIP(hipEventCreate(&p->ev0));
@@ -483,7 +351,7 @@ int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out) {
         RT_HIP(hipMalloc((void **)&p->d_area, all * sizeof(uint32_t)));
         RT_HIP(hipMalloc((void **)&p->d_box, all * sizeof(uint4)));
         RT_HIP(hipMalloc((void **)&p->d_blocks, nb * sizeof(uint32_t)));
-        RT_HIP(hipMalloc((void **)&p->d_chunk, S * (size_t)(p->n_chunks + 1) * sizeof(uint32_t)));
+        RT_HIP(hipMalloc((void **)&p->d_chunk, S * (size_t)(p->g.n_chunks + 1) * sizeof(uint32_t)));
         RT_HIP(hipMalloc((void **)&p->d_seen, S * sizeof(int32_t)));
         p->out_bytes = S * (sizeof(MoWork) + sizeof(rtmodt_motion_result) + (size_t)cfg->max_regions * 5 * sizeof(int32_t));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
@@ -523,16 +391,7 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
              p->cfg.width, p->cfg.height);
     RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     const int S = p->cfg.streams;
-    RT_CHECK(n <= S, RTMODT_E_INVALID, "%d frames in one call for %d streams", n, S);
-    RT_CHECK(streams || n == S || n == 0, RTMODT_E_INVALID, "%d frames for %d streams and no stream list", n, S);
-    std::vector<char> named(S, 0);
-    for (int i = 0; i < n; ++i) {
-        RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
-        const int s = streams ? streams[i] : i;
-        RT_TRY(mo_check_stream(p, s));
-        RT_CHECK(!named[s], RTMODT_E_INVALID, "stream %d is named twice in one call", s);
-        named[s] = 1;
-    }
+    RT_TRY(check_stream_list(frames, streams, n, S));
     p->timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
@@ -540,11 +399,7 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
     RT_TRY(p->stage.place(n, h, w, stride_bytes, mem_kind, FRAMES_AS_GIVEN));
     RT_TRY(p->cmd.reserve((size_t)n * sizeof(MoSlot)));
     MoSlot *sl = (MoSlot *)p->cmd.h;
-    bool wide = p->stage.pitch % 4 == 0;
-    for (int i = 0; i < n; ++i) {
-        sl[i] = MoSlot{(uint64_t)(uintptr_t)p->stage.at(frames, i), streams ? streams[i] : i, 0};
-        wide = wide && sl[i].frame % 4 == 0;
-    }
+    for (int i = 0; i < n; ++i) sl[i] = MoSlot{(uint64_t)(uintptr_t)p->stage.at(frames, i), streams ? streams[i] : i, 0};
     RT_HIP(hipMemcpyAsync(p->cmd.d, p->cmd.h, (size_t)n * sizeof(MoSlot), hipMemcpyHostToDevice, q));
     RT_TRY(p->stage.copy_in(frames, q));
 
@@ -553,33 +408,30 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
     const size_t reg_bytes = (size_t)n * c.max_regions * 5 * sizeof(int32_t);
     MoArgs a{};
     a.slots = (const MoSlot *)p->cmd.d;
-    a.pitch = (long long)p->stage.pitch; a.cells = p->cells;
-    a.h = h; a.w = w; a.scale = c.scale; a.gw = p->gw; a.gh = p->gh;
+    a.pitch = (long long)p->stage.pitch; a.cells = p->g.cells;
+    a.h = h; a.w = w; a.scale = c.scale; a.gw = p->g.gw; a.gh = p->g.gh;
     a.rule = mo_rule(c);
     a.min_neighbors = c.min_neighbors; a.dilate = c.dilate; a.scene_pm = c.scene_pm; a.min_area = c.min_area; a.max_regions = c.max_regions;
-    a.block = c.block; a.bgw = p->bgw; a.bgh = p->bgh; a.n_chunks = p->n_chunks;
+    a.block = c.block; a.bgw = p->bgw; a.bgh = p->bgh; a.n_chunks = p->g.n_chunks;
     a.model = p->d_model; a.seen = p->d_seen; a.raw = p->d_raw; a.mask = p->d_mask; a.parent = p->d_parent; a.area = p->d_area; a.box = p->d_box;
     a.blocks = p->d_blocks; a.work = (MoWork *)p->d_out; a.chunk = p->d_chunk;
     a.res = (rtmodt_motion_result *)(p->d_out + off_res); a.regions = (int32_t *)(p->d_out + off_res + res_bytes);
 
     const dim3 block(MO_THREADS);
-    const int cpt = c.scale >= 4 ? 1 : 4 / c.scale;
-    const unsigned per_cell = (unsigned)((p->cells + MO_THREADS - 1) / MO_THREADS);
+    const GridGeom &g = p->g;
     RT_HIP(hipEventRecord(p->ev0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, off_res + res_bytes + reg_bytes, q));
     MoArgs m = a;
-    m.tiles_x = cdiv(p->gw, 64 * cpt);
-    const dim3 mgrid((unsigned)(m.tiles_x * cdiv(p->gh, MO_ROWS)), n);
-    if (wide) mo_launch_model<true>(c.scale, mgrid, q, m);
-    else mo_launch_model<false>(c.scale, mgrid, q, m);
+    m.tiles_x = g.model_tiles_x();
+    launch_by_scale(mo_model_kernels, c.scale, frames_wide(p->stage, sl, n), g.model_grid(n), q, m);
     MoArgs f = a;
-    f.tiles_x = cdiv(p->gw, MO_TW);
-    hipLaunchKernelGGL(motion_filter, dim3((unsigned)(f.tiles_x * cdiv(p->gh, MO_TH)), n), block, 0, q, f);
-    hipLaunchKernelGGL(motion_link, dim3(per_cell, n), block, 0, q, a);
-    hipLaunchKernelGGL(motion_roots, dim3(per_cell, n), block, 0, q, a);
-    hipLaunchKernelGGL(motion_count, dim3((unsigned)p->n_chunks, n), block, 0, q, a);
+    f.tiles_x = g.filter_tiles_x();
+    hipLaunchKernelGGL(motion_filter, g.filter_grid(n), block, 0, q, f);
+    hipLaunchKernelGGL(motion_link, g.per_cell(n), block, 0, q, a);
+    hipLaunchKernelGGL(motion_roots, g.per_cell(n), block, 0, q, a);
+    hipLaunchKernelGGL(motion_count, g.per_chunk(n), block, 0, q, a);
     hipLaunchKernelGGL(motion_finish, dim3(n), block, 0, q, a);
-    hipLaunchKernelGGL(motion_emit, dim3((unsigned)p->n_chunks, n), block, 0, q, a);
+    hipLaunchKernelGGL(motion_emit, g.per_chunk(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(p->ev1, q));
     RT_HIP(hipMemcpyAsync(p->h_out, p->d_out + off_res, res_bytes + reg_bytes, hipMemcpyDeviceToHost, q));      // every result in one copy
@@ -592,16 +444,16 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
 
 int rtmodt_motion_read_mask(rtmodt_motion *p, int stream, uint8_t *out) {
     RT_CHECK(p && out, RTMODT_E_INVALID, "null argument");
-    RT_TRY(mo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(out, p->d_mask + (size_t)stream * p->cells, (size_t)p->cells, hipMemcpyDeviceToHost, p->stream));
+    RT_HIP(hipMemcpyAsync(out, p->d_mask + (size_t)stream * p->g.cells, (size_t)p->g.cells, hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
 }
 
 int rtmodt_motion_read_blocks(rtmodt_motion *p, int stream, uint32_t *out) {
     RT_CHECK(p && out, RTMODT_E_INVALID, "null argument");
-    RT_TRY(mo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     const size_t nb = (size_t)p->bgw * p->bgh;
     RT_HIP(hipSetDevice(p->device));
     RT_HIP(hipMemcpyAsync(out, p->d_blocks + (size_t)stream * nb, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
@@ -611,13 +463,13 @@ int rtmodt_motion_read_blocks(rtmodt_motion *p, int stream, uint32_t *out) {
 
 int rtmodt_motion_read_state(rtmodt_motion *p, int stream, uint16_t *bg, uint16_t *dev, int32_t *frames_seen) {
     RT_CHECK(p && bg && dev && frames_seen, RTMODT_E_INVALID, "null argument");
-    RT_TRY(mo_check_stream(p, stream));
-    p->h_model.resize((size_t)p->cells);
+    RT_TRY(check_stream(stream, p->cfg.streams));
+    p->h_model.resize((size_t)p->g.cells);
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(p->h_model.data(), p->d_model + (size_t)stream * p->cells, (size_t)p->cells * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+    RT_HIP(hipMemcpyAsync(p->h_model.data(), p->d_model + (size_t)stream * p->g.cells, (size_t)p->g.cells * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipMemcpyAsync(frames_seen, p->d_seen + stream, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
-    for (long long i = 0; i < p->cells; ++i) {
+    for (long long i = 0; i < p->g.cells; ++i) {
         bg[i] = (uint16_t)(p->h_model[i] & 0xffffu);
         dev[i] = (uint16_t)(p->h_model[i] >> 16);
     }
@@ -626,12 +478,12 @@ int rtmodt_motion_read_state(rtmodt_motion *p, int stream, uint16_t *bg, uint16_
 
 int rtmodt_motion_load_state(rtmodt_motion *p, int stream, const uint16_t *bg, const uint16_t *dev, int32_t frames_seen) {
     RT_CHECK(p && bg && dev, RTMODT_E_INVALID, "null argument");
-    RT_TRY(mo_check_stream(p, stream));
+    RT_TRY(check_stream(stream, p->cfg.streams));
     RT_CHECK(frames_seen >= 0 && frames_seen <= MO_MAX_SEEN, RTMODT_E_INVALID, "frames_seen %d outside 0..%d", frames_seen, MO_MAX_SEEN);
-    p->h_model.resize((size_t)p->cells);
-    for (long long i = 0; i < p->cells; ++i) p->h_model[i] = (uint32_t)bg[i] | (uint32_t)dev[i] << 16;
+    p->h_model.resize((size_t)p->g.cells);
+    for (long long i = 0; i < p->g.cells; ++i) p->h_model[i] = (uint32_t)bg[i] | (uint32_t)dev[i] << 16;
     RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipMemcpyAsync(p->d_model + (size_t)stream * p->cells, p->h_model.data(), (size_t)p->cells * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    RT_HIP(hipMemcpyAsync(p->d_model + (size_t)stream * p->g.cells, p->h_model.data(), (size_t)p->g.cells * sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipMemcpyAsync(p->d_seen + stream, &frames_seen, sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));
     return RTMODT_OK;
@@ -639,11 +491,11 @@ int rtmodt_motion_load_state(rtmodt_motion *p, int stream, const uint16_t *bg, c
 
 int rtmodt_motion_reset(rtmodt_motion *p, int stream) {
     RT_CHECK(p, RTMODT_E_INVALID, "null argument");
-    if (stream != -1) RT_TRY(mo_check_stream(p, stream));
+    if (stream != -1) RT_TRY(check_stream(stream, p->cfg.streams));
     RT_HIP(hipSetDevice(p->device));
     const size_t first = stream < 0 ? 0 : (size_t)stream, count = stream < 0 ? (size_t)p->cfg.streams : 1, nb = (size_t)p->bgw * p->bgh;
-    RT_HIP(hipMemsetAsync(p->d_model + first * p->cells, 0, count * p->cells * sizeof(uint32_t), p->stream));
-    RT_HIP(hipMemsetAsync(p->d_mask + first * p->cells, 0, count * p->cells, p->stream));
+    RT_HIP(hipMemsetAsync(p->d_model + first * p->g.cells, 0, count * p->g.cells * sizeof(uint32_t), p->stream));
+    RT_HIP(hipMemsetAsync(p->d_mask + first * p->g.cells, 0, count * p->g.cells, p->stream));
     RT_HIP(hipMemsetAsync(p->d_blocks + first * nb, 0, count * nb * sizeof(uint32_t), p->stream));
     RT_HIP(hipMemsetAsync(p->d_seen + first, 0, count * sizeof(int32_t), p->stream));
     RT_HIP(hipStreamSynchronize(p->stream));

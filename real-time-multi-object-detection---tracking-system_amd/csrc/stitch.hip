@@ -33,7 +33,7 @@
 //   stitch_links<true>   the same decisions again, written into A's CSR slice in (start frame, tracklet) order; column
 //                        degrees by integer atomics
 //   stitch_isolate       the degree rule: an isolated pair is linked at once; a contested row joins its columns in a
-//                        lock-free union-find forest (the larger root is hooked under the smaller: the label of a component
+//                        lock-free union-find forest (ccl_dev.h; the larger root goes under the smaller: the label of a component
 //                        is its smallest row, whatever the arrival order)
 //   stitch_label         key (label << 32 | row) per contested row, all ones otherwise; rocPRIM radix_sort_keys puts every
 //                        component's rows side by side in ascending row order -- a deterministic problem for the solver
@@ -56,6 +56,9 @@
 #include <vector>
 
 namespace rtmodt {
+
+#include "wg_dev.h"
+#include "ccl_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -95,9 +98,6 @@ struct StitchArgs {
     int64_t *fill_frame;
     double *fill_box;
 };
-
-__device__ __forceinline__ int ld_relaxed(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_relaxed(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(ST_THREADS) void stitch_summary(StitchArgs a) {
     const int t = blockIdx.x * ST_THREADS + threadIdx.x;
@@ -171,27 +171,6 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_links(StitchArgs a) {
     if (!WRITE) a.link_n[t] = cnt;
 }
 
-__device__ int uf_find(int32_t *p, int x) {
-    int c = ld_relaxed(&p[x]);
-    while (c != x) {                                       // parents only ever point at smaller nodes: no cycle
-        const int g = ld_relaxed(&p[c]);
-        if (g == c) return c;
-        st_relaxed(&p[x], g);                              // path halving: any ancestor is a valid parent
-        x = c;
-        c = g;
-    }
-    return x;
-}
-__device__ void uf_unite(int32_t *p, int x, int y) {
-    while (true) {
-        x = uf_find(p, x);
-        y = uf_find(p, y);
-        if (x == y) return;
-        if (x < y) { const int t = x; x = y; y = t; }      // the larger root goes under the smaller
-        if (atomicCAS(&p[x], x, y) == x) return;
-    }
-}
-
 __global__ __launch_bounds__(ST_THREADS) void stitch_isolate(StitchArgs a) {
     const int t = blockIdx.x * ST_THREADS + threadIdx.x;
     if (t >= a.n_trk) return;
@@ -204,7 +183,7 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_isolate(StitchArgs a) {
             a.succ_d2[t] = a.link_d2[l0];
             a.anc[b] = t;
         } else {
-            for (int64_t e = l0; e < l1; ++e) uf_unite(a.parent, t, a.n_trk + a.link_col[e]);
+            for (int64_t e = l0; e < l1; ++e) ccl_unite(a.parent, t, a.n_trk + a.link_col[e]);
             key = 0;                                       // contested: stitch_label writes the key
         }
     }
@@ -214,7 +193,7 @@ __global__ __launch_bounds__(ST_THREADS) void stitch_isolate(StitchArgs a) {
 __global__ __launch_bounds__(ST_THREADS) void stitch_label(StitchArgs a) {
     const int t = blockIdx.x * ST_THREADS + threadIdx.x;
     if (t >= a.n_trk) return;
-    if (a.key[t] != ST_NO_KEY) a.key[t] = ((unsigned long long)uf_find(a.parent, t) << 32) | (unsigned)t;
+    if (a.key[t] != ST_NO_KEY) a.key[t] = ((unsigned long long)ccl_find(a.parent, t) << 32) | (unsigned)t;
 }
 
 // one wave per sorted position; the wave at the head of a component solves it (one lane, as mot_accumulate's contested rest)
@@ -276,11 +255,11 @@ __global__ __launch_bounds__(64) void stitch_assign(StitchArgs a) {
 __global__ __launch_bounds__(ST_THREADS) void stitch_roots(StitchArgs a) {
     const int t = blockIdx.x * ST_THREADS + threadIdx.x;
     if (t >= a.n_trk) return;
-    int x = ld_relaxed(&a.anc[t]);
+    int x = ccl_ld(&a.anc[t]);
     while (true) {                                         // anc[] always holds an ancestor: jumps of other threads only help
-        const int g = ld_relaxed(&a.anc[x]);
+        const int g = ccl_ld(&a.anc[x]);
         if (g == x) break;
-        st_relaxed(&a.anc[t], g);
+        ccl_st(&a.anc[t], g);
         x = g;
     }
     a.root[t] = x;

@@ -1,5 +1,6 @@
-// wg_dev.h -- small device helpers shared by the trackers and the ledger kernels (zones.hip, crossing.hip, swapguard.hip,
-// ocsort.hip).  Include inside namespace rtmodt.
+// wg_dev.h -- small device helpers of a wave or a workgroup, shared by zones.hip, crossing.hip, swapguard.hip, ocsort.hip, gmc.hip,
+// crosscam.hip, speed.hip, snapshot.hip, privacy.hip, heatmap.hip, motion.hip, leftobj.hip, health.hip and ccl_dev.h.  Include inside
+// namespace rtmodt.
 #pragma once
 
 // neither infinite nor NaN, read off the bits
@@ -12,6 +13,18 @@ __device__ __forceinline__ int lower_bound_i64(const int64_t *a, int n, int64_t 
         if (a[mid] < x) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+
+// sum and maximum of a uint32 over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
+    return v;
 }
 
 // exclusive prefix of a per-thread count over a workgroup of WAVES waves (thread order); returns the position, writes the total.

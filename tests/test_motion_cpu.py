@@ -2,7 +2,8 @@
 are pinned to) against hand-worked literal cases and against its own loop forms and flood fill; the per-cell rule of
 ``csrc/motion_model.h`` against the restatement, through the host-only entry point ``rtmodt_motion_cell`` and through
 ``tests/native/motion_model_check.cpp``, a stand-alone program built plain and with the address / undefined-behaviour sanitizers
-(nothing is loaded into Python under a sanitizer).  PARITY UNPINNED: OpenCV's MOG2 and Frigate are installed nowhere this runs."""
+(nothing is loaded into Python under a sanitizer); the same program walks ``csrc/cell_grid.h``, the one reader of frame memory, over
+frames that end where their buffer ends.  PARITY UNPINNED: OpenCV's MOG2 and Frigate are installed nowhere this runs."""
 import functools
 import os
 import subprocess
@@ -251,13 +252,34 @@ def build(tmp_path, sanitize):
     raise AssertionError("no host compiler built motion_model_check" + (" with the sanitizers" if sanitize else "") + ":\n" + "\n".join(errors))
 
 
+def lcg_bytes(n, seed):
+    x = int(seed)
+    out = np.empty(n, np.uint8)
+    for i in range(n):
+        x = (x * 1664525 + 1013904223) & 0xffffffff
+        out[i] = x >> 24
+    return out
+
+
 def lcg_frame(h, w, seed):
-    x = np.uint64(seed)
-    out = np.empty(h * w * 3, np.uint8)
-    for i in range(out.size):
-        x = (x * np.uint64(1664525) + np.uint64(1013904223)) & np.uint64(0xffffffff)
-        out[i] = int(x) >> 24
-    return out.reshape(h, w, 3)
+    return lcg_bytes(h * w * 3, seed).reshape(h, w, 3)
+
+
+def reader_cases():
+    """(scale, h, w, pitch, base_offset, wide, seed): the smallest shapes that reach every branch of cell_grid.h's reader.  With PX the
+    pixels of a thread's run (4, at scale 8: 8), w = PX - 1 is one partial run, 2 PX two full runs, 2 PX + 1 two full runs and a run of
+    one pixel; h = scale is full cell rows only, scale + 1 adds a cell row one pixel high.  A pitch of 3w puts the frame's last byte
+    at the buffer's last byte.  The dword path is taken only as the host takes it: an aligned pitch and base."""
+    out = []
+    for scale in (1, 2, 4, 8):
+        px = 8 if scale == 8 else 4
+        for w in (px - 1, 2 * px, 2 * px + 1):
+            for h in (scale, scale + 1):
+                aligned = (3 * w + 3) // 4 * 4
+                for pitch in dict.fromkeys((3 * w, 3 * w + 1, aligned)):
+                    out += [(scale, h, w, pitch, base, 0) for base in (0, 1)]
+                out += [(scale, h, w, aligned, base, 1) for base in (0, 4)]
+    return [c + (100 + i,) for i, c in enumerate(out)]
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitized"])
@@ -271,6 +293,12 @@ def test_motion_model_header_equals_restatement(tmp_path, sanitize):
         lines.append(f"f {scale} {h} {w} {seed}")
         yc = MR.cell_luma(lcg_frame(h, w, seed), scale)
         want.append(" ".join(str(v) for v in [yc.shape[1], yc.shape[0]] + yc.ravel().tolist()))
+    for scale, h, w, pitch, base, wide, seed in reader_cases():
+        lines.append(f"r {scale} {h} {w} {pitch} {base} {wide} {seed}")
+        buf = lcg_bytes(base + (h - 1) * pitch + 3 * w, seed)
+        fr = np.stack([buf[base + y * pitch:base + y * pitch + 3 * w] for y in range(h)]).reshape(h, w, 3)
+        yc = MR.cell_luma(fr, scale)
+        want.append(" ".join(str(v) for v in [yc.shape[1], yc.shape[0]] + yc.ravel().tolist()))
     for box in ((0, 0, 0, 0, 4, 35, 22), (1, 2, 8, 5, 4, 35, 22), (3, 1, 7, 2, 8, 64, 24), (0, 0, 69, 36, 1, 70, 37), (2, 2, 2, 2, 2, 5, 5)):
         lines.append("b " + " ".join(str(v) for v in box))
         want.append(" ".join(str(v) for v in MR.px_box(*box[:5], box[6], box[5])))
@@ -280,7 +308,8 @@ def test_motion_model_header_equals_restatement(tmp_path, sanitize):
         lines.append(f"s {seen} {warm} {n_raw} {pm} {cells} {total}")
         st = MR.status_of(seen, n_raw, cells, total, MR.config(warmup=warm, scene_pm=pm))
         want.append(f"{st} {MR.next_seen(seen, st)}")
-    extra = ["c 0 8 12 2 8 10 1 0 0", "c 4 3 12 2 8 10 1 0 0", "c 4 8 12 2 8 256 1 0 0", "c 4 8 12 2 8 10 1 65536 0", "f 3 5 5 1", "b 0 0 1 1 5 10 10"]
+    extra = ["c 0 8 12 2 8 10 1 0 0", "c 4 3 12 2 8 10 1 0 0", "c 4 8 12 2 8 256 1 0 0", "c 4 8 12 2 8 10 1 65536 0", "f 3 5 5 1", "b 0 0 1 1 5 10 10",
+             "r 3 5 5 15 0 0 1", "r 4 5 5 14 0 0 1", "r 4 5 5 18 0 1 1", "r 4 5 5 16 1 1 1"]
     out = subprocess.run([exe], input="\n".join(lines + extra) + "\n", capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     got = out.stdout.splitlines()
