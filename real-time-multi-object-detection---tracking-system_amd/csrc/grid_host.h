@@ -44,6 +44,11 @@ inline int check_grid_cells(int streams, int height, int width, int scale, long 
     return RTMODT_OK;
 }
 
+// Zeroes a buffer of a new handle on the handle's own stream q; create synchronizes q once after the last of them.  hipMemset would
+// return before the device has written, on the null stream, which does not order a hipStreamNonBlocking stream: a load_state (a
+// copy on q) directly after create could then be zeroed again behind its back.
+inline hipError_t grid_zero(void *d, size_t bytes, hipStream_t q) { return hipMemsetAsync(d, 0, bytes, q); }
+
 inline int check_stream(int stream, int S) {
     RT_CHECK(stream >= 0 && stream < S, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, S - 1);
     return RTMODT_OK;

@@ -308,10 +308,11 @@ int rtmodt_health_create(const rtmodt_health_cfg *cfg, rtmodt_health **out) {
         p->out_bytes = S * (sizeof(HlWork) + sizeof(rtmodt_health_result) + HL_MAX_EVENTS * sizeof(rtmodt_health_event));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, p->out_bytes, hipHostMallocDefault));
-        RT_HIP(hipMemset(p->d_r, 0, all * sizeof(uint16_t)));
-        RT_HIP(hipMemset(p->d_y, 0, all));
-        RT_HIP(hipMemset(p->d_g, 0, all));
-        RT_HIP(hipMemset(p->d_state, 0, S * sizeof(HlState)));
+        RT_HIP(grid_zero(p->d_r, all * sizeof(uint16_t), p->stream));
+        RT_HIP(grid_zero(p->d_y, all, p->stream));
+        RT_HIP(grid_zero(p->d_g, all, p->stream));
+        RT_HIP(grid_zero(p->d_state, S * sizeof(HlState), p->stream));
+        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
         return RTMODT_OK;
     };
     const int rc = body();

@@ -597,12 +597,13 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
         RT_HIP(hipMalloc((void **)&p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object)));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, S * p->block_stride, hipHostMallocDefault));
-        RT_HIP(hipMemset(p->d_state, 0, all * sizeof(uint64_t)));
-        RT_HIP(hipMemset(p->d_luma, 0, all));
-        RT_HIP(hipMemset(p->d_mask, 0, all));
-        RT_HIP(hipMemset(p->d_seen, 0, S * sizeof(int32_t)));
-        RT_HIP(hipMemset(p->d_meta, 0, S * 4 * sizeof(int32_t)));
-        RT_HIP(hipMemset(p->d_ledger, 0, S * 2 * MO * sizeof(rtmodt_leftobj_object)));
+        RT_HIP(grid_zero(p->d_state, all * sizeof(uint64_t), p->stream));
+        RT_HIP(grid_zero(p->d_luma, all, p->stream));
+        RT_HIP(grid_zero(p->d_mask, all, p->stream));
+        RT_HIP(grid_zero(p->d_seen, S * sizeof(int32_t), p->stream));
+        RT_HIP(grid_zero(p->d_meta, S * 4 * sizeof(int32_t), p->stream));
+        RT_HIP(grid_zero(p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object), p->stream));
+        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
         return RTMODT_OK;
     };
     const int rc = body();

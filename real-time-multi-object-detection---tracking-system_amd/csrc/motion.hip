@@ -356,10 +356,11 @@ int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out) {
         p->out_bytes = S * (sizeof(MoWork) + sizeof(rtmodt_motion_result) + (size_t)cfg->max_regions * 5 * sizeof(int32_t));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, p->out_bytes, hipHostMallocDefault));
-        RT_HIP(hipMemset(p->d_model, 0, all * sizeof(uint32_t)));
-        RT_HIP(hipMemset(p->d_mask, 0, all));
-        RT_HIP(hipMemset(p->d_blocks, 0, nb * sizeof(uint32_t)));
-        RT_HIP(hipMemset(p->d_seen, 0, S * sizeof(int32_t)));
+        RT_HIP(grid_zero(p->d_model, all * sizeof(uint32_t), p->stream));
+        RT_HIP(grid_zero(p->d_mask, all, p->stream));
+        RT_HIP(grid_zero(p->d_blocks, nb * sizeof(uint32_t), p->stream));
+        RT_HIP(grid_zero(p->d_seen, S * sizeof(int32_t), p->stream));
+        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
         return RTMODT_OK;
     };
     const int rc = body();
