@@ -66,7 +66,7 @@ struct CcArgs {
     int32_t *sight;                             // [I][S]: entry + 1 of the new row's sighting in the stream, 0 none
     int64_t *o_counters, *o_gid; int32_t *o_status, *o_sim, *o_nev; rtmodt_crosscam_event *o_ev; rtmodt_crosscam_retired *o_ret;
     // a device source (cc_stage): the tracker's state, its meta rows, its int8 rows
-    const BotState *b_states; const DsState *d_states; const int64_t *t_meta; const int8_t *t_rows; int t_mc, t_budget;
+    TrackSrc trk; const int8_t *t_rows; int t_mc, t_budget;
 };
 
 __device__ __forceinline__ long long wave_sum_ll(long long v) {
@@ -79,9 +79,8 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
 __global__ __launch_bounds__(CC_THREADS) void cc_stage(CcArgs a) {
     __shared__ int wsum[CC_WAVES];
     const int s = blockIdx.x, tid = threadIdx.x, D = a.D;
-    const int64_t *tm = a.t_meta + (size_t)s * 8;
-    const int cur = (int)tm[0] & 1;
-    const TrackSel src = a.b_states ? select_botsort(a.b_states + s, tm) : select_deepsort(a.d_states + s, tm, 0);
+    const int cur = (int)a.trk.meta[(size_t)s * 8] & 1;
+    const TrackSel src = select_tracks(a.trk, s);
     const int n = src.n < 0 ? 0 : (src.n > a.t_mc ? a.t_mc : src.n);
     int cnt = 0;
     for (int base = 0; base < n; base += CC_THREADS) {
@@ -93,9 +92,9 @@ __global__ __launch_bounds__(CC_THREADS) void cc_stage(CcArgs a) {
             const size_t o = (size_t)s * a.Mc + pos;
             a.e_id[o] = src.ids[i]; a.e_cls[o] = src.cls[i];
             const int8_t *row = nullptr;
-            if (a.b_states) row = a.t_rows + (((size_t)s * 2 + cur) * a.t_mc + i) * D;
+            if (a.trk.botsort) row = a.t_rows + (((size_t)s * 2 + cur) * a.t_mc + i) * D;
             else {
-                const DsState &st = a.d_states[s];
+                const DsState &st = a.trk.deepsort[s];
                 const int slot = st.slot[cur][i], gc = st.gcount[cur][i];
                 if (gc > 0 && slot >= 0 && slot < a.t_mc) row = a.t_rows + (((size_t)s * a.t_mc + slot) * a.t_budget + (gc - 1) % a.t_budget) * D;
             }
@@ -792,14 +791,15 @@ int rtmodt_crosscam_process(rtmodt_crosscam *z, const int64_t *track_ids, const 
     RT_HIP(hipMemcpyAsync(a.e_row, rw.data(), rw.size(), hipMemcpyHostToDevice, z->stream));
     RT_HIP(hipMemcpyAsync(a.e_n, n, (size_t)S * 4, hipMemcpyHostToDevice, z->stream));
     RT_HIP(hipStreamSynchronize(z->stream));               // the vectors above are pageable and about to go away
-    a.b_states = nullptr; a.d_states = nullptr;
+    a.trk = TrackSrc{};
     return cc_run(z, z->stream, false, out);
 }
 
 int rtmodt_crosscam_process_botsort(rtmodt_crosscam *z, rtmodt_botsort *bot, const rtmodt_crosscam_out *out) {
     RT_CHECK(z && bot, RTMODT_E_INVALID, "bad argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
+    TrackSrc src;
+    TrackViewBase v;
+    RT_TRY(track_src(bot, 0, &src, &v));
     const int8_t *rows = nullptr; int dim = 0;
     RT_TRY(botsort_feature_view(bot, &rows, &dim));
     RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crosscam on device %d, tracker on device %d", z->device, v.device);
@@ -808,14 +808,15 @@ int rtmodt_crosscam_process_botsort(rtmodt_crosscam *z, rtmodt_botsort *bot, con
     RT_CHECK(v.max_tracks <= z->cfg.max_tracks, RTMODT_E_INVALID, "tracker max_tracks %d > crosscam max_tracks %d", v.max_tracks, z->cfg.max_tracks);
     RT_HIP(hipSetDevice(z->device));
     CcArgs &a = z->a;
-    a.b_states = v.states; a.d_states = nullptr; a.t_meta = v.meta; a.t_rows = rows; a.t_mc = v.max_tracks; a.t_budget = 1;
+    a.trk = src; a.t_rows = rows; a.t_mc = v.max_tracks; a.t_budget = 1;
     return cc_run(z, v.stream, true, out);                 // the stream the tracker's last update ran on: ordered after it
 }
 
 int rtmodt_crosscam_process_deepsort(rtmodt_crosscam *z, rtmodt_deepsort *ds, const rtmodt_crosscam_out *out) {
     RT_CHECK(z && ds, RTMODT_E_INVALID, "bad argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
+    TrackSrc src;
+    TrackViewBase v;
+    RT_TRY(track_src(ds, 0, &src, &v));
     const int8_t *rows = nullptr; int dim = 0, budget = 0;
     RT_TRY(deepsort_gallery_view(ds, &rows, &dim, &budget));
     RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crosscam on device %d, tracker on device %d", z->device, v.device);
@@ -824,7 +825,7 @@ int rtmodt_crosscam_process_deepsort(rtmodt_crosscam *z, rtmodt_deepsort *ds, co
     RT_CHECK(v.max_tracks <= z->cfg.max_tracks, RTMODT_E_INVALID, "tracker max_tracks %d > crosscam max_tracks %d", v.max_tracks, z->cfg.max_tracks);
     RT_HIP(hipSetDevice(z->device));
     CcArgs &a = z->a;
-    a.b_states = nullptr; a.d_states = v.states; a.t_meta = v.meta; a.t_rows = rows; a.t_mc = v.max_tracks; a.t_budget = budget;
+    a.trk = src; a.t_rows = rows; a.t_mc = v.max_tracks; a.t_budget = budget;
     return cc_run(z, v.stream, true, out);
 }
 

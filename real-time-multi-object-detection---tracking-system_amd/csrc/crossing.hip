@@ -1,7 +1,7 @@
 // crossing.hip -- directional line (tripwire) and gate crossing counts on the GPU: the meaning the reference's config gives a
 // `trigger: "crossing"` zone with a `direction` (config/default.yaml:73-77) and its engine never implements (zone_engine.py:150
 // parses the direction and nothing reads it).  ONE launch per frame, one 256-thread workgroup per video stream, run on a track
-// list the host hands over or straight on the device-resident state of the ByteTrack, the DeepSORT or the OC-SORT tracker.
+// list the host hands over or straight on the device-resident state of one of the four trackers (track_select_dev.h).
 //
 // tests/crossing_ref.py states the rules ("Crossing counter"); the kernel equals it exactly.  Everything after the
 // centroid is integer arithmetic: coordinates are held to +-2^20, so every cross product is below 2^43.
@@ -14,7 +14,8 @@
 //   2. the (track, item) pairs are spread over the lanes: P = the item count rounded up to a power of two lanes per track, one
 //      lane per line or gate; the pair's new bits travel to the row through a wave ballot (no atomics, no LDS), its count through
 //      an integer atomic add (any order gives the same sums);
-//   3. the new ledger = passed rows + retained idle rows, merged by rank (prefix sums + binary searches, no sort);
+//   3. the new ledger = passed rows + retained idle rows, merged by rank (prefix sums + binary searches, no sort): the steps of
+//      track_ledger_dev.h, which zones.hip, speed.hip and snapshot.hip run too;
 //   4. events leave in (list order, lines in order, gates in order) through a workgroup prefix sum.
 #include <algorithm>
 #include <cstring>
@@ -24,9 +25,14 @@
 #include "polygon.h"
 #include "track_layout.h"
 
+#define TL_HD __host__ __device__
+#include "track_ledger_host.h"
+
 namespace rtmodt {
 
 #include "wg_dev.h"
+#include "track_select_dev.h"
+#include "track_ledger_dev.h"
 
 constexpr int CR_THREADS = 256, CR_WAVES = CR_THREADS / 64;
 constexpr int CR_MAX_LINES = 32, CR_MAX_GATES = 32, CR_MAX_POINTS = 2048, CR_MAX_CLASSES = 256;
@@ -53,12 +59,8 @@ struct CrossArgs {
     int64_t max_gap, frame_id;
     // source A: a staged list [n_streams][cap], sorted by id; order = the caller's index of a sorted entry, inv = its inverse
     const int64_t *s_ids; const float4 *s_box; const int32_t *s_cls; const int32_t *s_order, *s_inv; const int32_t *s_n; int s_stride;
-    // source B / C: the ByteTrack / DeepSORT tracker's device state; passed tracks are those with tsu == report_tsu (C: and flag == 2)
-    const TrackerState *t_states; const DsState *d_states; const int64_t *t_meta; int report_tsu;
-    // source D: the OC-SORT tracker's device state; passed = returned: tsu == 0 and (hit_streak >= o_min_hits or frame_count <= o_min_hits)
-    const OcState *o_states; int o_min_hits;
-    // source E: the BoT-SORT tracker's device state; passed = returned (flag == 2) and matched this frame (tsu == 0)
-    const BotState *b_states;
+    // sources B..E: a tracker's device state (track_select_dev.h)
+    TrackSrc trk;
     // per-stream scratch [n_streams][cap]
     int32_t *p_idx, *oldpos; uint64_t *evmask;
     // events [n_streams][max_events]; ev_n = the number that fired (may exceed max_events)
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     int64_t *old_id = (int64_t *)smem;                    // [cap]
     int4 *line = (int4 *)(old_id + cap);                  // [CR_MAX_LINES]
     int2 *pts = (int2 *)(line + CR_MAX_LINES);            // [max(n_pts, 1)]
-    int *ret_pre = (int *)(pts + (a.tb.n_pts > 0 ? a.tb.n_pts : 1));     // [cap + 1] retained flags, then their exclusive prefix
+    int *ret_pre = (int *)(pts + (a.tb.n_pts > 0 ? a.tb.n_pts : 1));     // [cap + 1] retained flags, then their rank encoding (track_ledger.h)
     int *ppre = ret_pre + cap + 1;                        // [cap + 1] exclusive prefix of the list's passed flags
     int *idir = ppre + cap + 1;                           // [CR_MAX_LINES + CR_MAX_GATES]
     int *goff = idir + CR_MAX_LINES + CR_MAX_GATES;       // [CR_MAX_GATES + 1]
@@ -108,9 +110,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     __shared__ int s_err;
 
     int64_t *meta = a.meta + (size_t)sidx * 4;
-    const int cur = (int)meta[0] & 1, nxt = cur ^ 1;
-    int n_old = (int)meta[1];
-    n_old = n_old < 0 ? 0 : (n_old > cap ? cap : n_old);
+    const int cur = tl_meta_cur(meta), nxt = cur ^ 1, n_old = tl_meta_rows(meta, cap);
     const CrossLedger *Lp = a.ledgers + sidx;                 // (indexed where it lies: a local copy indexed by `cur` would live in scratch)
     const int64_t *o_id = Lp->id[cur], *o_last = Lp->last[cur], *o_entryf = Lp->entryf[cur];
     const int2 *o_prev = Lp->prev[cur], *o_entry = Lp->entry[cur];
@@ -119,109 +119,36 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     int2 *n_prev = Lp->prev[nxt], *n_entry = Lp->entry[nxt];
     uint32_t *n_pos = Lp->pos[nxt], *n_neg = Lp->neg[nxt], *n_in = Lp->in[nxt];
 
-    // ---- this frame's list (ids ascending in all three sources) ----
-    const int64_t *ids; const float4 *box; const int32_t *cls;
-    const int32_t *tsu = nullptr, *flag = nullptr, *streak = nullptr, *order = nullptr, *inv = nullptr;
-    bool early = false;                                    // OC-SORT: the first min_hits frames return every matched track
-    int n;
+    // ---- this frame's list ----
+    TrackSel src;
+    const int32_t *order = nullptr, *inv = nullptr;
     if (a.s_ids) {
         const size_t o = (size_t)sidx * a.s_stride;
-        ids = a.s_ids + o; box = a.s_box + o; cls = a.s_cls + o; order = a.s_order + o; inv = a.s_inv + o; n = a.s_n[sidx];
-    } else if (a.t_states) {
-        const TrackerState *st = a.t_states + sidx;
-        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
-        const int tc = (int)tm[0] & 1;
-        ids = st->ids[tc]; box = st->box[tc]; cls = st->cls[tc]; tsu = st->tsu[tc];
-        n = (int)tm[1];
-    } else if (a.o_states) {
-        const OcState *st = a.o_states + sidx;
-        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
-        const int tc = (int)tm[0] & 1;
-        ids = st->ids[tc]; box = st->obox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; streak = st->streak[tc];
-        early = tm[5] <= (int64_t)a.o_min_hits;
-        n = (int)tm[1];
-    } else if (a.b_states) {
-        const BotState *st = a.b_states + sidx;
-        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
-        const int tc = (int)tm[0] & 1;
-        ids = st->ids[tc]; box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-        n = (int)tm[1];
-    } else {
-        const DsState *st = a.d_states + sidx;
-        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
-        const int tc = (int)tm[0] & 1;
-        ids = st->ids[tc]; box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-        n = (int)tm[1];
-    }
-    n = n < 0 ? 0 : (n > cap ? cap : n);                   // host sizes cap >= the source's max_tracks
+        src = select_list(a.s_ids + o, a.s_box + o, a.s_cls + o, a.s_n[sidx]);
+        order = a.s_order + o; inv = a.s_inv + o;
+    } else src = select_tracks(a.trk, sidx);
+    const int n = src.n < 0 ? 0 : (src.n > cap ? cap : src.n);      // host sizes cap >= the source's max_tracks
+    const int64_t *ids = src.ids; const float4 *box = src.box; const int32_t *cls = src.cls;
 
     if (tid == 0) s_err = 0;
-    for (int i = tid; i < n_old; i += CR_THREADS) old_id[i] = o_id[i];
     for (int i = tid; i < L; i += CR_THREADS) line[i] = a.tb.line[i];
     for (int i = tid; i < NI; i += CR_THREADS) idir[i] = a.tb.dir[i];
     for (int i = tid; i <= G; i += CR_THREADS) goff[i] = a.tb.off[i];
     for (int i = tid; i < a.tb.n_pts; i += CR_THREADS) pts[i] = a.tb.pts[i];
     // an old row survives this frame while frame_id - last <= max_gap, whether or not its id is in the list
-    for (int j = tid; j < n_old; j += CR_THREADS) ret_pre[j] = a.frame_id - o_last[j] <= a.max_gap ? 1 : 0;
+    ledger_stage_old<CR_THREADS>(o_id, n_old, old_id, ret_pre, [&](int j) { return a.frame_id - o_last[j] <= a.max_gap ? 1 : 0; });
 
     int32_t *p_idx = a.p_idx + (size_t)sidx * cap;
     int32_t *oldpos = a.oldpos + (size_t)sidx * cap;
     uint64_t *evmask = a.evmask + (size_t)sidx * cap;
 
-    // ---- 1. the passed tracks, compacted in list order ----
-    int n_pass = 0;
-    for (int base = 0; base < n; base += CR_THREADS) {
-        const int i = base + tid;
-        bool f = false;
-        if (i < n) {
-            int2 c;
-            f = (!tsu || tsu[i] == a.report_tsu) && (!flag || flag[i] == 2) && (!streak || early || streak[i] >= a.o_min_hits) && cr_centroid(box[i], c);
-        }
-        int tot;
-        const int pos = n_pass + block_scan_count<CR_WAVES>(f ? 1 : 0, wsum, tot);
-        if (i < n) ppre[i] = pos;
-        if (f) p_idx[pos] = i;
-        n_pass += tot;
-    }
-    if (tid == 0) ppre[n] = n_pass;
-    // a tracker's list ascends in id unless the swap guard (swapguard.hip) has exchanged two ids in its state: then a row's place among
-    // this frame's rows is counted, not read off its list position
-    __syncthreads();
-    for (int i = tid + 1; i < n; i += CR_THREADS)
-        if (!(ids[i - 1] < ids[i])) s_err = -1;              // (every writer stores the same value)
-    __syncthreads();
-    const bool ascending = s_err != -1;
-    __syncthreads();
-    if (tid == 0 && !ascending) s_err = 0;
-    auto passed_below = [&](int64_t x) {                                       // passed tracks of the list with an id < x
-        if (ascending) return ppre[lower_bound_i64(ids, n, x)];
-        int c = 0;
-        for (int k = 0; k < n; ++k) c += ppre[k + 1] != ppre[k] && ids[k] < x ? 1 : 0;
-        return c;
-    };
-    // each finds its old row; a matched row is no idle row, and one that has expired is not this track's row either
-    for (int t = tid; t < n_pass; t += CR_THREADS) {
-        const int64_t id = ids[p_idx[t]];
-        const int j = lower_bound_i64(old_id, n_old, id);
-        const bool hit = j < n_old && old_id[j] == id;
-        oldpos[t] = hit && ret_pre[j] ? j : -1;
-        if (hit) ret_pre[j] = 0;
-    }
-    __syncthreads();
-    int n_ret = 0;
-    for (int base = 0; base < n_old; base += CR_THREADS) {                    // flags -> exclusive prefix, in place
-        const int j = base + tid;
-        const int f = j < n_old ? ret_pre[j] : 0;
-        int tot;
-        const int pos = block_scan_count<CR_WAVES>(f, wsum, tot);
-        if (j < n_old) ret_pre[j] = f ? n_ret + pos : -(n_ret + pos) - 1;       // retained: rank; dropped: -(rank of next retained) - 1
-        n_ret += tot;
-    }
-    if (tid == 0) ret_pre[n_old] = -n_ret - 1;
-    __syncthreads();
-    auto ranks_below = [&](int j) { const int v = ret_pre[j]; return v >= 0 ? v : -v - 1; };   // retained rows among old[0 .. j)
-    const bool overflow = n_pass + n_ret > cap;                               // keep this frame's rows, drop the idle ones
-    if (overflow && tid == 0) s_err = 1;
+    // ---- 1. the passed tracks, compacted in list order; each finds its old row (an expired one is not this track's row); the
+    //         idle rows are ranked ----
+    const int n_pass = ledger_compact<CR_THREADS>(n, ppre, p_idx, wsum, [&](int i) { int2 c; return selected(src, i) && cr_centroid(box[i], c); });
+    const bool ascending = ledger_list_ascends<CR_THREADS>(ids, n, &s_err);
+    ledger_match<CR_THREADS, true>(ids, p_idx, n_pass, old_id, n_old, ret_pre, oldpos);
+    const int n_ret = ledger_rank<CR_THREADS>(n_old, ret_pre, wsum);
+    const TlMerge mg = ledger_decide(ids, ppre, n, old_id, ret_pre, n_old, n_pass, n_ret, ascending, cap, &s_err);
 
     // ---- 2. (track, item) pairs: P lanes per track, lane `sub` of a group takes line `sub` or gate `sub - L` ----
     int P = 1;
@@ -240,8 +167,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         if (tv) {
             i = p_idx[t]; j = oldpos[t];
             cr_centroid(box[i], c);
-            const int tp = ascending ? t : passed_below(ids[i]);
-            np = overflow ? tp : tp + ranks_below(lower_bound_i64(old_id, n_old, ids[i]));
+            np = tl_member_pos(mg, t, ids[i]);
             if (sub < L) {
                 const int4 ab = line[sub];
                 const int sd = cr_side(ab.x, ab.y, ab.z, ab.w, c.x, c.y);
@@ -289,17 +215,15 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
         }
     }
     // ---- 3. idle rows move to their merged position, unchanged ----
-    if (!overflow)
-        for (int j = tid; j < n_old; j += CR_THREADS) {
-            const int v = ret_pre[j];
-            if (v < 0) continue;
-            const int np = v + passed_below(old_id[j]);
-            n_id[np] = old_id[j];
-            n_last[np] = o_last[j];
-            n_prev[np] = o_prev[j];
-            n_pos[np] = o_pos[j]; n_neg[np] = o_neg[j]; n_in[np] = o_in[j];
-            for (int g = 0; g < G; ++g) { n_entry[(size_t)np * G + g] = o_entry[(size_t)j * G + g]; n_entryf[(size_t)np * G + g] = o_entryf[(size_t)j * G + g]; }
-        }
+    for (int j = tid; j < n_old; j += CR_THREADS) {
+        const int np = tl_idle_pos(mg, j);
+        if (np < 0) continue;
+        n_id[np] = old_id[j];
+        n_last[np] = o_last[j];
+        n_prev[np] = o_prev[j];
+        n_pos[np] = o_pos[j]; n_neg[np] = o_neg[j]; n_in[np] = o_in[j];
+        for (int g = 0; g < G; ++g) { n_entry[(size_t)np * G + g] = o_entry[(size_t)j * G + g]; n_entryf[(size_t)np * G + g] = o_entryf[(size_t)j * G + g]; }
+    }
     __syncthreads();
 
     // ---- 4. events, in list order (the caller's), then item order ----
@@ -347,9 +271,7 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
     }
     if (tid == 0) {
         a.ev_n[sidx] = n_ev;
-        meta[0] = nxt;
-        meta[1] = n_pass + (overflow ? 0 : n_ret);
-        if (s_err) meta[2] = s_err;
+        tl_meta_write(meta, cur, tl_rows(mg), s_err);
     }
 }
 
@@ -450,9 +372,7 @@ int cr_fetch(rtmodt_crossing *z, hipStream_t s, int s0, int cnt, CrEvHost &h) {
 }
 
 int cr_check_sticky(rtmodt_crossing *z, int s, int64_t err) {
-    RT_CHECK(err != 1, RTMODT_E_CAPACITY, "crossing stream %d: ledger full (%d rows): lower max_gap_frames or raise max_tracks", s, z->cap);
-    RT_CHECK(err == 0, RTMODT_E_INVALID, "crossing stream %d: error %lld", s, (long long)err);
-    return RTMODT_OK;
+    return ledger_check_sticky("crossing", s, err, z->cap, "lower max_gap_frames or raise max_tracks");
 }
 
 // copies the events of streams [s0, s0 + cnt) out ([stream][max_events] slots, n_events[stream]); the first failure is reported after every
@@ -479,16 +399,14 @@ int cr_sync_own(rtmodt_crossing *z) {
     return RTMODT_OK;
 }
 
-// one frame on a tracker's device-resident state: `fill` sets the source's own fields of CrossArgs
-template <typename F> int cr_process_view(rtmodt_crossing *z, const TrackViewBase &v, int64_t frame_id, rtmodt_crossing_event *events,
-                                                 int32_t *n_events, F fill) {
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "crossing counter on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the crossing counter (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
-    RT_HIP(hipSetDevice(z->device));
+// one frame on a tracker's device-resident state
+template <typename T> int cr_process_tracker(rtmodt_crossing *z, T *trk, int report_tsu, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
+    RT_CHECK(z && trk && n_events, RTMODT_E_INVALID, "bad argument");
     CrossArgs a = cr_args(z, frame_id);
-    a.t_meta = v.meta;
-    fill(a);
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &a.trk, &v));
+    RT_TRY(ledger_check_view(v, z->device, z->S, z->cap, z->Mc, "crossing counter", "crossing counter"));
+    RT_HIP(hipSetDevice(z->device));
     RT_TRY(cr_launch(z, a, v.n_streams, v.stream));         // the stream the tracker's last update ran on: ordered after it
     CrEvHost h;
     RT_TRY(cr_fetch(z, v.stream, 0, v.n_streams, h));
@@ -579,27 +497,9 @@ int rtmodt_crossing_process(rtmodt_crossing *z, int stream, const int64_t *track
     RT_CHECK(n <= z->Mc, RTMODT_E_CAPACITY, "%d tracks > max_tracks %d", n, z->Mc);
     RT_HIP(hipSetDevice(z->device));
     // the ledger is sorted by id: hand the list over in id order, with the caller's order both ways
-    std::vector<int32_t> perm(n), inv(n);
-    for (int i = 0; i < n; ++i) perm[i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return track_ids[a] < track_ids[b]; });
-    std::vector<int64_t> ids(n); std::vector<float4> box(n); std::vector<int32_t> kc(n);
-    for (int i = 0; i < n; ++i) {
-        const int p = perm[i];
-        inv[p] = i;
-        ids[i] = track_ids[p]; kc[i] = cls[p];
-        box[i] = make_float4(xyxy[4 * p], xyxy[4 * p + 1], xyxy[4 * p + 2], xyxy[4 * p + 3]);
-        RT_CHECK(i == 0 || ids[i] != ids[i - 1], RTMODT_E_INVALID, "track id %lld appears twice", (long long)ids[i]);
-    }
-    const size_t o = (size_t)stream * z->cap;
-    if (n) {
-        RT_HIP(hipMemcpyAsync(z->s_ids + o, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_box + o, box.data(), (size_t)n * 16, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_cls + o, kc.data(), (size_t)n * 4, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_order + o, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_inv + o, inv.data(), (size_t)n * 4, hipMemcpyHostToDevice, z->stream));
-    }
-    RT_HIP(hipMemcpyAsync(z->s_n + stream, &n, 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipStreamSynchronize(z->stream));               // the vectors above are pageable and about to go away
+    const int32_t n32 = n;
+    RT_TRY(ledger_stage_lists(LedgerStaging{z->s_ids, z->s_box, z->s_cls, z->s_order, z->s_inv, z->s_n, z->cap}, stream, 1, track_ids, xyxy, cls, &n32, 0, false,
+                              z->stream));
     CrossArgs a = cr_args(z, frame_id);
     a.stream_base = stream;
     a.s_ids = z->s_ids; a.s_box = z->s_box; a.s_cls = z->s_cls; a.s_order = z->s_order; a.s_inv = z->s_inv; a.s_n = z->s_n; a.s_stride = z->cap;
@@ -611,32 +511,20 @@ int rtmodt_crossing_process(rtmodt_crossing *z, int stream, const int64_t *track
 
 int rtmodt_crossing_process_tracker(rtmodt_crossing *z, rtmodt_tracker *trk, int64_t frame_id, int report_tsu, rtmodt_crossing_event *events,
                                     int32_t *n_events) {
-    RT_CHECK(z && trk && n_events, RTMODT_E_INVALID, "bad argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.t_states = v.states; a.report_tsu = report_tsu; });
+    return cr_process_tracker(z, trk, report_tsu, frame_id, events, n_events);
 }
 
 int rtmodt_crossing_process_deepsort(rtmodt_crossing *z, rtmodt_deepsort *ds, int64_t frame_id, int report_tsu, rtmodt_crossing_event *events,
                                      int32_t *n_events) {
-    RT_CHECK(z && ds && n_events, RTMODT_E_INVALID, "bad argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
-    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.d_states = v.states; a.report_tsu = report_tsu; });
+    return cr_process_tracker(z, ds, report_tsu, frame_id, events, n_events);
 }
 
 int rtmodt_crossing_process_botsort(rtmodt_crossing *z, rtmodt_botsort *bot, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
-    RT_CHECK(z && bot && n_events, RTMODT_E_INVALID, "bad argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
-    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.b_states = v.states; a.report_tsu = 0; });
+    return cr_process_tracker(z, bot, 0, frame_id, events, n_events);
 }
 
 int rtmodt_crossing_process_ocsort(rtmodt_crossing *z, rtmodt_ocsort *oc, int64_t frame_id, rtmodt_crossing_event *events, int32_t *n_events) {
-    RT_CHECK(z && oc && n_events, RTMODT_E_INVALID, "bad argument");
-    OcDeviceView v;
-    RT_TRY(ocsort_device_view(oc, &v));
-    return cr_process_view(z, v, frame_id, events, n_events, [&](CrossArgs &a) { a.o_states = v.states; a.o_min_hits = v.min_hits; a.report_tsu = 0; });
+    return cr_process_tracker(z, oc, 0, frame_id, events, n_events);
 }
 
 int rtmodt_crossing_counts(rtmodt_crossing *z, int stream, int64_t *line_total, int64_t *line_class, int64_t *gate_total, int64_t *gate_class) {

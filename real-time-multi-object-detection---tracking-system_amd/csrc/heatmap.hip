@@ -44,6 +44,7 @@
 namespace rtmodt {
 
 #include "wg_dev.h"
+#include "track_select_dev.h"
 
 constexpr int HM_THREADS = 256, HM_WAVES = HM_THREADS / 64, HM_TW = 64, HM_TH = 16, HM_PARTS = 64;
 constexpr int HM_MAX_POLYS = 32, HM_MAX_POINTS = 2048, HM_MAX_BOXES = 65536, HM_MAX_STREAMS = 1024;
@@ -66,8 +67,7 @@ struct HmGatherArgs {
     HmStampCfg sc;                              // classes: a device pointer
     int h, w, cap;
     HmStamp *out; int32_t *n_out;
-    const TrackerState *t_states; const DsState *d_states; const OcState *o_states; const BotState *b_states;
-    const int64_t *t_meta; int report_tsu, o_min_hits;
+    TrackSrc trk;                               // tracks (track_select_dev.h), or the detections below
     const float4 *det_box; const int32_t *det_cls, *det_n; int det_stride;
 };
 
@@ -86,38 +86,15 @@ struct HmZoneArgs {
     unsigned long long *part;                   // [Z][HM_PARTS]
 };
 
-// ---- device forms: tracks / detections -> stamps (the selection of privacy_gather) ------------------------------------
+// ---- device forms: tracks / detections -> stamps (the selection of track_select_dev.h) ------------------------------------
 __global__ __launch_bounds__(HM_THREADS) void heatmap_gather(HmGatherArgs a) {
     __shared__ int s_wcnt[HM_WAVES];
     const int f = blockIdx.x, tid = threadIdx.x;
-    const float4 *box; const int32_t *cls;
-    const int32_t *tsu = nullptr, *flag = nullptr, *streak = nullptr;
-    bool early = false;
-    int n, want_tsu = a.report_tsu;
-    if (a.det_box) {
-        box = a.det_box + (size_t)f * a.det_stride; cls = a.det_cls + (size_t)f * a.det_stride; n = a.det_n[f];
-    } else {
-        const int64_t *tm = a.t_meta + (size_t)f * 8;
-        const int tc = (int)tm[0] & 1;
-        n = (int)tm[1];
-        if (a.t_states) {                       // ByteTrack: time_since_update == report_tsu
-            const TrackerState *st = a.t_states + f;
-            box = st->box[tc]; cls = st->cls[tc]; tsu = st->tsu[tc];
-        } else if (a.o_states) {                // OC-SORT: the returned tracks
-            const OcState *st = a.o_states + f;
-            box = st->obox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; streak = st->streak[tc];
-            early = tm[5] <= (int64_t)a.o_min_hits;
-            want_tsu = 0;
-        } else if (a.b_states) {                // BoT-SORT: tracked and matched this frame
-            const BotState *st = a.b_states + f;
-            box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-            want_tsu = 0;
-        } else {                                // DeepSORT: confirmed, time_since_update == report_tsu
-            const DsState *st = a.d_states + f;
-            box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-        }
-    }
-    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    TrackSel src;
+    if (a.det_box) src = select_list(nullptr, a.det_box + (size_t)f * a.det_stride, a.det_cls + (size_t)f * a.det_stride, a.det_n[f]);
+    else src = select_tracks(a.trk, f);
+    const float4 *box = src.box; const int32_t *cls = src.cls;
+    const int n = src.n < 0 ? 0 : (src.n > a.cap ? a.cap : src.n);
     HmStamp *out = a.out + (size_t)f * a.cap;
     int total = 0;
     for (int base = 0; base < n; base += HM_THREADS) {
@@ -126,8 +103,7 @@ __global__ __launch_bounds__(HM_THREADS) void heatmap_gather(HmGatherArgs a) {
         HmStamp st{};
         if (i < n) {
             const float4 b = box[i];
-            ok = (!tsu || tsu[i] == want_tsu) && (!flag || flag[i] == 2) && (!streak || early || streak[i] >= a.o_min_hits) &&
-                 finite_bits(b.x) && finite_bits(b.y) && finite_bits(b.z) && finite_bits(b.w) &&
+            ok = selected(src, i) && finite_bits(b.x) && finite_bits(b.y) && finite_bits(b.z) && finite_bits(b.w) &&
                  hm_stamp(a.sc, b.x, b.y, b.z, b.w, cls[i], a.h, a.w, st);
         }
         int tot;
@@ -417,6 +393,14 @@ template <typename F> int hm_accumulate_view(rtmodt_heatmap *p, int src_device, 
     return hm_accumulate(p, q, nullptr, &g);
 }
 
+template <typename T> int hm_accumulate_tracker(rtmodt_heatmap *p, T *trk, int report_tsu) {
+    RT_CHECK(p && trk, RTMODT_E_INVALID, "null argument");
+    TrackSrc src;
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &src, &v));
+    return hm_accumulate_view(p, v.device, v.n_streams, v.max_tracks, v.stream, "the tracker", [&](HmGatherArgs &g) { g.trk = src; });
+}
+
 int hm_check_stream(const rtmodt_heatmap *p, int stream) {
     RT_CHECK(stream >= 0 && stream < p->cfg.n_streams, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, p->cfg.n_streams - 1);
     return RTMODT_OK;
@@ -537,37 +521,10 @@ int rtmodt_heatmap_accumulate(rtmodt_heatmap *p, const float *const *xyxy, const
     return hm_accumulate(p, p->stream, &stamps, nullptr);
 }
 
-int rtmodt_heatmap_accumulate_tracker(rtmodt_heatmap *p, rtmodt_tracker *trk, int report_tsu) {
-    RT_CHECK(p && trk, RTMODT_E_INVALID, "null argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    return hm_accumulate_view(p, v.device, v.n_streams, v.max_tracks, v.stream, "the tracker",
-                              [&](HmGatherArgs &g) { g.t_states = v.states; g.t_meta = v.meta; g.report_tsu = report_tsu; });
-}
-
-int rtmodt_heatmap_accumulate_deepsort(rtmodt_heatmap *p, rtmodt_deepsort *ds, int report_tsu) {
-    RT_CHECK(p && ds, RTMODT_E_INVALID, "null argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
-    return hm_accumulate_view(p, v.device, v.n_streams, v.max_tracks, v.stream, "the tracker",
-                              [&](HmGatherArgs &g) { g.d_states = v.states; g.t_meta = v.meta; g.report_tsu = report_tsu; });
-}
-
-int rtmodt_heatmap_accumulate_ocsort(rtmodt_heatmap *p, rtmodt_ocsort *oc) {
-    RT_CHECK(p && oc, RTMODT_E_INVALID, "null argument");
-    OcDeviceView v;
-    RT_TRY(ocsort_device_view(oc, &v));
-    return hm_accumulate_view(p, v.device, v.n_streams, v.max_tracks, v.stream, "the tracker",
-                              [&](HmGatherArgs &g) { g.o_states = v.states; g.t_meta = v.meta; g.o_min_hits = v.min_hits; });
-}
-
-int rtmodt_heatmap_accumulate_botsort(rtmodt_heatmap *p, rtmodt_botsort *bot) {
-    RT_CHECK(p && bot, RTMODT_E_INVALID, "null argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
-    return hm_accumulate_view(p, v.device, v.n_streams, v.max_tracks, v.stream, "the tracker",
-                              [&](HmGatherArgs &g) { g.b_states = v.states; g.t_meta = v.meta; });
-}
+int rtmodt_heatmap_accumulate_tracker(rtmodt_heatmap *p, rtmodt_tracker *trk, int report_tsu) { return hm_accumulate_tracker(p, trk, report_tsu); }
+int rtmodt_heatmap_accumulate_deepsort(rtmodt_heatmap *p, rtmodt_deepsort *ds, int report_tsu) { return hm_accumulate_tracker(p, ds, report_tsu); }
+int rtmodt_heatmap_accumulate_ocsort(rtmodt_heatmap *p, rtmodt_ocsort *oc) { return hm_accumulate_tracker(p, oc, 0); }
+int rtmodt_heatmap_accumulate_botsort(rtmodt_heatmap *p, rtmodt_botsort *bot) { return hm_accumulate_tracker(p, bot, 0); }
 
 int rtmodt_heatmap_accumulate_detector(rtmodt_heatmap *p, rtmodt_detector *det) {
     RT_CHECK(p && det, RTMODT_E_INVALID, "null argument");

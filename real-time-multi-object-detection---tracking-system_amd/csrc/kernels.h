@@ -347,6 +347,43 @@ int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
 // rows of buffer meta[0] & 1 current; null and dim 0 for a motion-only handle
 int botsort_feature_view(rtmodt_botsort *bot, const int8_t **feat8, int *dim);
 
+// A tracker's device state as the track source of a per-frame consumer: exactly one of the four state pointers is set (none: the
+// consumer reads a list of its own).  select_tracks (track_select_dev.h) turns it into the list and the selection; track_src fills
+// it, and the part of the view all trackers share, from a tracker's handle.  report_tsu takes part for ByteTrack and DeepSORT only,
+// min_hits for OC-SORT only
+struct TrackSrc {
+    const TrackerState *bytetrack; const DsState *deepsort; const OcState *ocsort; const BotState *botsort;
+    const int64_t *meta; int report_tsu, min_hits;
+};
+inline int track_src(rtmodt_tracker *trk, int report_tsu, TrackSrc *src, TrackViewBase *view) {
+    TrackerDeviceView v;
+    RT_TRY(tracker_device_view(trk, &v));
+    *src = TrackSrc{v.states, nullptr, nullptr, nullptr, v.meta, report_tsu, 0};
+    *view = v;
+    return RTMODT_OK;
+}
+inline int track_src(rtmodt_deepsort *ds, int report_tsu, TrackSrc *src, TrackViewBase *view) {
+    DsDeviceView v;
+    RT_TRY(deepsort_device_view(ds, &v));
+    *src = TrackSrc{nullptr, v.states, nullptr, nullptr, v.meta, report_tsu, 0};
+    *view = v;
+    return RTMODT_OK;
+}
+inline int track_src(rtmodt_ocsort *oc, int, TrackSrc *src, TrackViewBase *view) {
+    OcDeviceView v;
+    RT_TRY(ocsort_device_view(oc, &v));
+    *src = TrackSrc{nullptr, nullptr, v.states, nullptr, v.meta, 0, v.min_hits};
+    *view = v;
+    return RTMODT_OK;
+}
+inline int track_src(rtmodt_botsort *bot, int, TrackSrc *src, TrackViewBase *view) {
+    BotDeviceView v;
+    RT_TRY(botsort_device_view(bot, &v));
+    *src = TrackSrc{nullptr, nullptr, nullptr, v.states, v.meta, 0, 0};
+    *view = v;
+    return RTMODT_OK;
+}
+
 // device-resident results of a detector's last enqueue_batch (engine.hip), consumed by the tracker
 struct DetOutputs { const float4 *box; const float *conf; const int32_t *cls; const int32_t *n; int stride, count, device; hipStream_t stream; };
 int detector_outputs(rtmodt_detector *det, DetOutputs *out);

@@ -83,8 +83,7 @@ struct LoArgs {
     // tracks: a staged list per frame of the call, or a tracker's device state (track_select_dev.h)
     int source, list_cap, trk_cap;
     const int64_t *l_ids; const float4 *l_box; const int32_t *l_cls; const int32_t *l_n;
-    const TrackerState *t_states; const DsState *d_states; const OcState *o_states; const BotState *b_states;
-    const int64_t *t_meta; int report_tsu, o_min_hits;
+    TrackSrc trk;
 };
 
 // ---- model: pixels -> cell luma (cell_grid.h) -> the 8-byte cell ---------------------------------------------------------------
@@ -315,10 +314,7 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_step(LoArgs a) {
             const size_t o = (size_t)slot * a.list_cap;
             src = select_list(a.l_ids + o, a.l_box + o, a.l_cls + o, a.l_n[slot]);
             cap = a.list_cap;
-        } else if (a.source == RTMODT_LEFTOBJ_TRACKS_BYTETRACK) src = select_bytetrack(a.t_states + sl.stream, a.t_meta + (size_t)sl.stream * 8, a.report_tsu);
-        else if (a.source == RTMODT_LEFTOBJ_TRACKS_DEEPSORT) src = select_deepsort(a.d_states + sl.stream, a.t_meta + (size_t)sl.stream * 8, a.report_tsu);
-        else if (a.source == RTMODT_LEFTOBJ_TRACKS_OCSORT) src = select_ocsort(a.o_states + sl.stream, a.t_meta + (size_t)sl.stream * 8, a.o_min_hits);
-        else src = select_botsort(a.b_states + sl.stream, a.t_meta + (size_t)sl.stream * 8);
+        } else src = select_tracks(a.trk, sl.stream);
         const int n_t = src.n < 0 ? 0 : (src.n > cap ? cap : src.n);
         for (int i = tid; i < n_t; i += LO_THREADS) {
             if (!selected(src, i)) continue;
@@ -529,11 +525,13 @@ int lo_sync(rtmodt_leftobj *p) {
     return RTMODT_OK;
 }
 
-// the tracker's view: its stream count must be the handle's; the launches are ordered after the tracker's last update
-template <typename V> int lo_take_view(rtmodt_leftobj *p, const V &v, LoArgs &a) {
+// the tracker as the call's track source: its stream count must be the handle's; the launches are ordered after its last update (*after)
+template <typename T> int lo_take_tracker(rtmodt_leftobj *p, void *trk, int report_tsu, LoArgs &a, hipStream_t *after) {
+    TrackViewBase v;
+    RT_TRY(track_src((T *)trk, report_tsu, &a.trk, &v));
     RT_CHECK(v.device == p->device, RTMODT_E_INVALID, "left-object detector on device %d, tracker on device %d", p->device, v.device);
     RT_CHECK(v.n_streams == p->cfg.streams, RTMODT_E_INVALID, "a tracker of %d streams, the left-object detector has %d", v.n_streams, p->cfg.streams);
-    a.t_meta = v.meta; a.trk_cap = v.max_tracks;
+    a.trk_cap = v.max_tracks; *after = v.stream;
     return RTMODT_OK;
 }
 
@@ -653,27 +651,10 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
         }
     } else if (source != RTMODT_LEFTOBJ_TRACKS_NONE) {
         RT_CHECK(tracks->tracker, RTMODT_E_INVALID, "null tracker");
-        if (source == RTMODT_LEFTOBJ_TRACKS_BYTETRACK) {
-            TrackerDeviceView v;
-            RT_TRY(tracker_device_view((rtmodt_tracker *)tracks->tracker, &v));
-            RT_TRY(lo_take_view(p, v, a));
-            a.t_states = v.states; a.report_tsu = tracks->report_tsu; after = v.stream;
-        } else if (source == RTMODT_LEFTOBJ_TRACKS_DEEPSORT) {
-            DsDeviceView v;
-            RT_TRY(deepsort_device_view((rtmodt_deepsort *)tracks->tracker, &v));
-            RT_TRY(lo_take_view(p, v, a));
-            a.d_states = v.states; a.report_tsu = tracks->report_tsu; after = v.stream;
-        } else if (source == RTMODT_LEFTOBJ_TRACKS_OCSORT) {
-            OcDeviceView v;
-            RT_TRY(ocsort_device_view((rtmodt_ocsort *)tracks->tracker, &v));
-            RT_TRY(lo_take_view(p, v, a));
-            a.o_states = v.states; a.o_min_hits = v.min_hits; after = v.stream;
-        } else {
-            BotDeviceView v;
-            RT_TRY(botsort_device_view((rtmodt_botsort *)tracks->tracker, &v));
-            RT_TRY(lo_take_view(p, v, a));
-            a.b_states = v.states; after = v.stream;
-        }
+        if (source == RTMODT_LEFTOBJ_TRACKS_BYTETRACK) RT_TRY(lo_take_tracker<rtmodt_tracker>(p, tracks->tracker, tracks->report_tsu, a, &after));
+        else if (source == RTMODT_LEFTOBJ_TRACKS_DEEPSORT) RT_TRY(lo_take_tracker<rtmodt_deepsort>(p, tracks->tracker, tracks->report_tsu, a, &after));
+        else if (source == RTMODT_LEFTOBJ_TRACKS_OCSORT) RT_TRY(lo_take_tracker<rtmodt_ocsort>(p, tracks->tracker, 0, a, &after));
+        else RT_TRY(lo_take_tracker<rtmodt_botsort>(p, tracks->tracker, 0, a, &after));
     }
     p->timed = false;
     if (n == 0) return RTMODT_OK;

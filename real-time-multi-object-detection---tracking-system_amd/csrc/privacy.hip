@@ -48,6 +48,7 @@
 namespace rtmodt {
 
 #include "wg_dev.h"
+#include "track_select_dev.h"
 
 constexpr int PV_THREADS = 256, PV_WAVES = PV_THREADS / 64, PV_TW = 64, PV_TH = 16;
 constexpr int PV_MAX_POLYS = 32, PV_MAX_POINTS = 2048, PV_MAX_REGIONS = 65536;
@@ -79,8 +80,7 @@ struct GatherArgs {
     PvRegionCfg rc;                             // classes: a device pointer
     int h, w, cap;
     PvRect *out; int32_t *n_out;
-    const TrackerState *t_states; const DsState *d_states; const OcState *o_states; const BotState *b_states;
-    const int64_t *t_meta; int report_tsu, o_min_hits;
+    TrackSrc trk;                               // tracks (track_select_dev.h), or the detections below
     const float4 *det_box; const int32_t *det_cls, *det_n; int det_stride;
 };
 
@@ -341,34 +341,11 @@ __global__ __launch_bounds__(PV_THREADS) void privacy_commit(PaintArgs a) {
 __global__ __launch_bounds__(PV_THREADS) void privacy_gather(GatherArgs a) {
     __shared__ int s_wcnt[PV_WAVES];
     const int f = blockIdx.x, tid = threadIdx.x;
-    const float4 *box; const int32_t *cls;
-    const int32_t *tsu = nullptr, *flag = nullptr, *streak = nullptr;
-    bool early = false;
-    int n, want_tsu = a.report_tsu;
-    if (a.det_box) {
-        box = a.det_box + (size_t)f * a.det_stride; cls = a.det_cls + (size_t)f * a.det_stride; n = a.det_n[f];
-    } else {
-        const int64_t *tm = a.t_meta + (size_t)f * 8;
-        const int tc = (int)tm[0] & 1;
-        n = (int)tm[1];
-        if (a.t_states) {
-            const TrackerState *st = a.t_states + f;
-            box = st->box[tc]; cls = st->cls[tc]; tsu = st->tsu[tc];
-        } else if (a.o_states) {
-            const OcState *st = a.o_states + f;
-            box = st->obox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; streak = st->streak[tc];
-            early = tm[5] <= (int64_t)a.o_min_hits;
-            want_tsu = 0;
-        } else if (a.b_states) {
-            const BotState *st = a.b_states + f;
-            box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-            want_tsu = 0;
-        } else {
-            const DsState *st = a.d_states + f;
-            box = st->dbox[tc]; cls = st->cls[tc]; tsu = st->tsu[tc]; flag = st->flag[tc];
-        }
-    }
-    n = n < 0 ? 0 : (n > a.cap ? a.cap : n);
+    TrackSel src;
+    if (a.det_box) src = select_list(nullptr, a.det_box + (size_t)f * a.det_stride, a.det_cls + (size_t)f * a.det_stride, a.det_n[f]);
+    else src = select_tracks(a.trk, f);
+    const float4 *box = src.box; const int32_t *cls = src.cls;
+    const int n = src.n < 0 ? 0 : (src.n > a.cap ? a.cap : src.n);
     PvRect *out = a.out + (size_t)f * a.cap;
     int total = 0;
     for (int base = 0; base < n; base += PV_THREADS) {
@@ -377,8 +354,7 @@ __global__ __launch_bounds__(PV_THREADS) void privacy_gather(GatherArgs a) {
         PvRect rc{0, 0, -1, -1};
         if (i < n) {
             const float4 b = box[i];
-            ok = (!tsu || tsu[i] == want_tsu) && (!flag || flag[i] == 2) && (!streak || early || streak[i] >= a.o_min_hits) &&
-                 finite_bits(b.x) && finite_bits(b.y) && finite_bits(b.z) && finite_bits(b.w) &&
+            ok = selected(src, i) && finite_bits(b.x) && finite_bits(b.y) && finite_bits(b.z) && finite_bits(b.w) &&
                  pv_region(a.rc, b.x, b.y, b.z, b.w, cls[i], a.h, a.w, rc);
         }
         int tot;
@@ -552,6 +528,14 @@ template <typename F> int pv_apply_view(rtmodt_privacy *p, int src_device, int n
     return pv_execute(p, frames, nullptr, n, h, w, stride_bytes, mem_kind, q, nullptr, &g);
 }
 
+template <typename T> int pv_apply_tracker(rtmodt_privacy *p, T *trk, int report_tsu, uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind) {
+    RT_CHECK(p && trk, RTMODT_E_INVALID, "null argument");
+    TrackSrc src;
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &src, &v));
+    return pv_apply_view(p, v.device, v.n_streams, v.max_tracks, v.stream, frames, h, w, stride_bytes, mem_kind, [&](GatherArgs &g) { g.trk = src; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -670,36 +654,20 @@ int rtmodt_privacy_apply(rtmodt_privacy *p, uint8_t *const *src_frames, uint8_t 
 
 int rtmodt_privacy_apply_tracker(rtmodt_privacy *p, rtmodt_tracker *trk, uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind,
                                  int report_tsu) {
-    RT_CHECK(p && trk, RTMODT_E_INVALID, "null argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    return pv_apply_view(p, v.device, v.n_streams, v.max_tracks, v.stream, frames, h, w, stride_bytes, mem_kind,
-                         [&](GatherArgs &g) { g.t_states = v.states; g.t_meta = v.meta; g.report_tsu = report_tsu; });
+    return pv_apply_tracker(p, trk, report_tsu, frames, h, w, stride_bytes, mem_kind);
 }
 
 int rtmodt_privacy_apply_deepsort(rtmodt_privacy *p, rtmodt_deepsort *ds, uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind,
                                   int report_tsu) {
-    RT_CHECK(p && ds, RTMODT_E_INVALID, "null argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
-    return pv_apply_view(p, v.device, v.n_streams, v.max_tracks, v.stream, frames, h, w, stride_bytes, mem_kind,
-                         [&](GatherArgs &g) { g.d_states = v.states; g.t_meta = v.meta; g.report_tsu = report_tsu; });
+    return pv_apply_tracker(p, ds, report_tsu, frames, h, w, stride_bytes, mem_kind);
 }
 
 int rtmodt_privacy_apply_ocsort(rtmodt_privacy *p, rtmodt_ocsort *oc, uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind) {
-    RT_CHECK(p && oc, RTMODT_E_INVALID, "null argument");
-    OcDeviceView v;
-    RT_TRY(ocsort_device_view(oc, &v));
-    return pv_apply_view(p, v.device, v.n_streams, v.max_tracks, v.stream, frames, h, w, stride_bytes, mem_kind,
-                         [&](GatherArgs &g) { g.o_states = v.states; g.t_meta = v.meta; g.o_min_hits = v.min_hits; });
+    return pv_apply_tracker(p, oc, 0, frames, h, w, stride_bytes, mem_kind);
 }
 
 int rtmodt_privacy_apply_botsort(rtmodt_privacy *p, rtmodt_botsort *bot, uint8_t *const *frames, int h, int w, int stride_bytes, int mem_kind) {
-    RT_CHECK(p && bot, RTMODT_E_INVALID, "null argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
-    return pv_apply_view(p, v.device, v.n_streams, v.max_tracks, v.stream, frames, h, w, stride_bytes, mem_kind,
-                         [&](GatherArgs &g) { g.b_states = v.states; g.t_meta = v.meta; });
+    return pv_apply_tracker(p, bot, 0, frames, h, w, stride_bytes, mem_kind);
 }
 
 int rtmodt_privacy_apply_detector(rtmodt_privacy *p, rtmodt_detector *det, uint8_t *const *frames, int n, int h, int w, int stride_bytes,

@@ -29,6 +29,8 @@
 #include "kernels.h"
 #include "track_layout.h"
 #include "frame_stage.h"
+#define TL_HD __host__ __device__
+#include "track_ledger_host.h"
 
 #define PV_HD __host__ __device__
 #include "snapshot_rule.h"
@@ -37,6 +39,7 @@ namespace rtmodt {
 
 #include "wg_dev.h"
 #include "track_select_dev.h"
+#include "track_ledger_dev.h"
 
 constexpr int SN_THREADS = 256, SN_WAVES = SN_THREADS / 64;
 constexpr int SN_BAND = 8;                  // thumbnail rows per (work item, band)
@@ -73,8 +76,7 @@ struct SnArgs {
     // source A: a staged list [cnt][Mc], sorted by id; order = the caller's index of a sorted entry, inv = its inverse
     const int64_t *s_ids; const float4 *s_box; const float *s_conf; const int32_t *s_cls; const int32_t *s_order, *s_inv; const int32_t *s_n;
     // sources B..E: a tracker's device state (track_select_dev.h)
-    const TrackerState *t_states; const DsState *d_states; const OcState *o_states; const BotState *b_states;
-    const int64_t *t_meta; int report_tsu, o_min_hits;
+    TrackSrc trk;
     // per-stream scratch [n_streams][Mc]
     int32_t *p_idx, *oldpos, *dflags, *upos, *nrank, *freeslot; int64_t *tscore; SnPlan *plan;
     // the resampler's own
@@ -87,16 +89,14 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
     const int sidx = a.stream_base + blockIdx.x, tid = threadIdx.x;
     const int cap = a.cap, Mc = a.Mc;
     int64_t *old_id = (int64_t *)smem;                    // [cap]
-    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] class of an old row, then the idle rows' exclusive prefix
+    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] class of an old row, then the idle rows' rank encoding (track_ledger.h)
     int *ppre = ret_pre + cap + 1;                        // [Mc + 1] exclusive prefix of the list's sampled flags
     int *wsum = ppre + Mc + 1;                            // [SN_WAVES]
     int *s_err = wsum + SN_WAVES;                         // [1]
     uint8_t *used = (uint8_t *)(s_err + 1);               // [cap] one byte per slot
 
     int64_t *meta = a.meta + (size_t)sidx * 4;
-    const int cur = (int)meta[0] & 1, nxt = cur ^ 1;
-    int n_old = (int)meta[1];
-    n_old = n_old < 0 ? 0 : (n_old > cap ? cap : n_old);
+    const int cur = tl_meta_cur(meta), nxt = cur ^ 1, n_old = tl_meta_rows(meta, cap);
     const SnLedger *Lp = a.ledgers + sidx;
     const int64_t *o_id = Lp->id[cur], *o_score = Lp->score[cur], *o_bf = Lp->best_frame[cur], *o_first = Lp->first[cur], *o_last = Lp->last[cur];
     const float4 *o_box = Lp->box[cur]; const float *o_conf = Lp->conf[cur]; const int4 *o_ints = Lp->ints[cur];
@@ -112,18 +112,13 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         src = select_list(a.s_ids + o, a.s_box + o, a.s_cls + o, a.s_n[blockIdx.x]);
         src.conf = a.s_conf ? a.s_conf + o : nullptr;
         order = a.s_order + o; inv = a.s_inv + o;
-    } else if (a.t_states) src = select_bytetrack(a.t_states + sidx, a.t_meta + (size_t)sidx * 8, a.report_tsu);
-    else if (a.d_states) src = select_deepsort(a.d_states + sidx, a.t_meta + (size_t)sidx * 8, a.report_tsu);
-    else if (a.o_states) src = select_ocsort(a.o_states + sidx, a.t_meta + (size_t)sidx * 8, a.o_min_hits);
-    else src = select_botsort(a.b_states + sidx, a.t_meta + (size_t)sidx * 8);
+    } else src = select_tracks(a.trk, sidx);
     const int n = src.n < 0 ? 0 : (src.n > Mc ? Mc : src.n);      // the host refuses a source whose max_tracks exceeds Mc
     const int64_t *ids = src.ids; const float4 *box = src.box; const int32_t *cls = src.cls;
 
     if (tid == 0) *s_err = 0;
-    for (int j = tid; j < n_old; j += SN_THREADS) {
-        old_id[j] = o_id[j];
-        ret_pre[j] = fid - o_last[j] > (int64_t)a.retire_after ? 2 : 1;      // 2: retired by this call; 1: idle unless a sampled track claims it (0)
-    }
+    // 2: retired by this call; 1: idle unless a sampled track claims it (0)
+    ledger_stage_old<SN_THREADS>(o_id, n_old, old_id, ret_pre, [&](int j) { return fid - o_last[j] > (int64_t)a.retire_after ? 2 : 1; });
     __syncthreads();
 
     const size_t so = (size_t)sidx * Mc;
@@ -137,37 +132,15 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
     rtmodt_snapshot_retired *rtd = (rtmodt_snapshot_retired *)(blk + a.off_retired);
 
     // ---- 1. the sampled tracks, compacted in the list's (id) order; their plans ----
-    int n_s = 0;
-    for (int base = 0; base < n; base += SN_THREADS) {
-        const int i = base + tid;
-        bool f = false;
-        if (i < n && selected(src, i)) {
-            const float4 b = box[i];
-            SnPlan P;
-            if (sn_plan(a.c, b.x, b.y, b.z, b.w, cls[i], a.fh, a.fw, P)) { f = true; plan[i] = P; }
-        }
-        int tot;
-        const int pos = n_s + block_scan_count<SN_WAVES>(f ? 1 : 0, wsum, tot);
-        if (i < n) ppre[i] = pos;
-        if (f) p_idx[pos] = i;
-        n_s += tot;
-    }
-    if (tid == 0) ppre[n] = n_s;
-    // a tracker's list ascends in id unless the swap guard has exchanged two ids in its state: then a row's place among this call's
-    // rows is counted, not read off its list position (as speed.hip)
-    __syncthreads();
-    for (int i = tid + 1; i < n; i += SN_THREADS)
-        if (!(ids[i - 1] < ids[i])) *s_err = -1;              // (every writer stores the same value)
-    __syncthreads();
-    const bool ascending = *s_err != -1;
-    __syncthreads();
-    if (tid == 0 && !ascending) *s_err = 0;
-    auto sampled_below = [&](int64_t x) {                                      // sampled tracks of the list with an id < x
-        if (ascending) return ppre[lower_bound_i64(ids, n, x)];
-        int c = 0;
-        for (int k = 0; k < n; ++k) c += ppre[k + 1] != ppre[k] && ids[k] < x ? 1 : 0;
-        return c;
-    };
+    const int n_s = ledger_compact<SN_THREADS>(n, ppre, p_idx, wsum, [&](int i) {
+        if (!selected(src, i)) return false;
+        const float4 b = box[i];
+        SnPlan P;
+        if (!sn_plan(a.c, b.x, b.y, b.z, b.w, cls[i], a.fh, a.fw, P)) return false;
+        plan[i] = P;
+        return true;
+    });
+    const bool ascending = ledger_list_ascends<SN_THREADS>(ids, n, s_err);
 
     // ---- 2. one thread per sampled track: occlusion, score, its old row, the decision ----
     for (int t = tid; t < n_s; t += SN_THREADS) {
@@ -181,8 +154,8 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         const bool cut = plan[i].cut != 0;
         const int64_t score = sn_score(cm, plan[i].area, cut, occl);
         const int64_t id = ids[i];
-        const int j = lower_bound_i64(old_id, n_old, id);
-        const bool live = j < n_old && old_id[j] == id && ret_pre[j] == 1;      // (ids are unique: no other thread touches ret_pre[j])
+        const int j = tl_match(old_id, n_old, id);
+        const bool live = j >= 0 && ret_pre[j] == 1;                            // (ids are unique: no other thread touches ret_pre[j])
         oldpos[t] = live ? j : -1;
         if (live) ret_pre[j] = 0;
         int d = (cut ? SN_F_CUT : 0) | (occl ? SN_F_OCCLUDED : 0);
@@ -201,7 +174,7 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         int tot_i, tot_r;
         const int pos_i = block_scan_count<SN_WAVES>(c == 1 ? 1 : 0, wsum, tot_i);
         const int pos_r = block_scan_count<SN_WAVES>(c == 2 ? 1 : 0, wsum, tot_r);
-        if (j < n_old) ret_pre[j] = c == 1 ? n_idle + pos_i : -(n_idle + pos_i) - 1;      // idle: rank; else: -(rank of the next idle row) - 1
+        if (j < n_old) ret_pre[j] = tl_rank_encode(c == 1, n_idle + pos_i);
         if (c == 2 && n_rtd + pos_r < a.max_retired) {
             rtmodt_snapshot_retired r;
             const float4 b = o_box[j];
@@ -213,7 +186,7 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         }
         n_idle += tot_i; n_rtd += tot_r;
     }
-    if (tid == 0) ret_pre[n_old] = -n_idle - 1;
+    if (tid == 0) ret_pre[n_old] = tl_rank_encode(false, n_idle);
 
     // ---- 4. in the caller's list order: the place of each update in `updated` and the rank of each new row ----
     int n_upd = 0, n_new = 0, n_rew = 0;
@@ -233,8 +206,8 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
     }
     n_rew = n_upd - n_new;
     __syncthreads();
-    auto ranks_below = [&](int j) { const int v = ret_pre[j]; return v >= 0 ? v : -v - 1; };   // idle rows among old[0 .. j)
-    const bool overflow = n_s + n_idle > cap || n_new > cap - n_old;          // keep this call's rows, drop the idle ones
+    const bool overflow = tl_overflow(n_s, n_idle, cap) || n_new > cap - n_old;      // (or: no free slot for a new row)
+    const TlMerge mg{ids, ppre, n, old_id, ret_pre, n_old, n_s, n_idle, ascending, overflow};
     if (overflow && tid == 0) *s_err = 1;
 
     // ---- 5. the slots in use when the call began, then the k-th free slot for the k-th new row ----
@@ -265,8 +238,7 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
     for (int t = tid; t < n_s; t += SN_THREADS) {
         const int i = p_idx[t], j = oldpos[t], d = dflags[t];
         const int64_t id = ids[i];
-        const int tp = ascending ? t : sampled_below(id);
-        const int np = overflow ? tp : tp + ranks_below(lower_bound_i64(old_id, n_old, id));
+        const int np = tl_member_pos(mg, t, id);
         int slot;
         if (j >= 0) {
             int4 v = o_ints[j];
@@ -308,19 +280,17 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         }
     }
     // ---- 7. idle rows move to their merged position; NEW and REWRITTEN are this call's, so they go ----
-    if (!overflow)
-        for (int j = tid; j < n_old; j += SN_THREADS) {
-            const int v = ret_pre[j];
-            if (v < 0) continue;
-            const int np = v + sampled_below(old_id[j]);
-            n_id[np] = old_id[j]; n_score[np] = o_score[j]; n_bf[np] = o_bf[j]; n_first[np] = o_first[j]; n_last[np] = o_last[j];
-            n_box[np] = o_box[j]; n_conf[np] = o_conf[j];
-            int4 w = o_ints[j];
-            w.x = slot_of(j);
-            w.w &= SN_F_CUT | SN_F_OCCLUDED;
-            n_ints[np] = w;
-            used[w.x] = 1;
-        }
+    for (int j = tid; j < n_old; j += SN_THREADS) {
+        const int np = tl_idle_pos(mg, j);
+        if (np < 0) continue;
+        n_id[np] = old_id[j]; n_score[np] = o_score[j]; n_bf[np] = o_bf[j]; n_first[np] = o_first[j]; n_last[np] = o_last[j];
+        n_box[np] = o_box[j]; n_conf[np] = o_conf[j];
+        int4 w = o_ints[j];
+        w.x = slot_of(j);
+        w.w &= SN_F_CUT | SN_F_OCCLUDED;
+        n_ints[np] = w;
+        used[w.x] = 1;
+    }
     __syncthreads();
     uint32_t *bm = a.bitmap + (size_t)sidx * a.words;
     for (int wd = tid; wd < a.words; wd += SN_THREADS) {
@@ -332,9 +302,7 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_decide(SnArgs a) {
         bm[wd] = v;
     }
     if (tid == 0) {
-        meta[0] = nxt;
-        meta[1] = n_s + (overflow ? 0 : n_idle);
-        if (*s_err) meta[2] = *s_err;
+        tl_meta_write(meta, cur, tl_rows(mg), *s_err);
         hdr->n_updated = n_upd; hdr->n_retired = n_rtd; hdr->n_work = n_upd; hdr->err = (int32_t)meta[2]; hdr->n_rewritten = n_rew;
         hdr->n_sampled = n_s; hdr->pad0 = 0; hdr->pad1 = 0;
     }
@@ -611,9 +579,7 @@ int sn_run(rtmodt_snapshot *z, SnArgs &a, int s0, int cnt, const int64_t *frame_
         if (out->retired && nr) memcpy(out->retired + d * z->cfg.max_retired, blk + z->off_retired, sizeof(rtmodt_snapshot_retired) * nr);
         if (out->n_retired) out->n_retired[d] = nr;
         if (out->n_rewritten) out->n_rewritten[d] = h.n_rewritten;
-        if (rc == RTMODT_OK && h.err == 1)
-            rc = fail(RTMODT_E_CAPACITY, "snapshot stream %d: ledger full (%d rows): lower retire_after or raise max_tracks", s, z->cap);
-        if (rc == RTMODT_OK && h.err != 0) rc = fail(RTMODT_E_INVALID, "snapshot stream %d: error %d", s, h.err);
+        if (rc == RTMODT_OK) rc = ledger_check_sticky("snapshot", s, h.err, z->cap, "lower retire_after or raise max_tracks");
         if (rc == RTMODT_OK && h.n_updated > z->cfg.max_updated)
             rc = fail(RTMODT_E_CAPACITY, "snapshot stream %d: %d thumbnails written in one call > max_updated %d (the first ones are delivered)", s,
                       h.n_updated, z->cfg.max_updated);
@@ -678,14 +644,12 @@ int sn_process_lists(rtmodt_snapshot *z, int s0, int cnt, const int64_t *track_i
         const int32_t *tc = cls + (size_t)s * stride;
         int32_t *pm = perm + s * Mc, *iv = inv + s * Mc;
         nn[s] = n[s];
-        for (int i = 0; i < n[s]; ++i) pm[i] = i;
-        std::stable_sort(pm, pm + n[s], [&](int x, int y) { return ti[x] < ti[y]; });
+        const int dup = tl_sort_list(ti, n[s], pm, iv);
+        RT_CHECK(dup < 0, RTMODT_E_INVALID, "stream %d: track id %lld appears twice", s0 + s, (long long)ti[pm[dup]]);
         for (int i = 0; i < n[s]; ++i) {
             const int p = pm[i];
-            iv[p] = i;
             ids[s * Mc + i] = ti[p]; kc[s * Mc + i] = tc[p]; cf[s * Mc + i] = tf ? tf[p] : 1.0f;
             box[s * Mc + i] = make_float4(tb[4 * p], tb[4 * p + 1], tb[4 * p + 2], tb[4 * p + 3]);
-            RT_CHECK(i == 0 || ids[s * Mc + i] != ids[s * Mc + i - 1], RTMODT_E_INVALID, "stream %d: track id %lld appears twice", s0 + s, (long long)ti[p]);
         }
     }
     hipStream_t q = z->stream;
@@ -701,13 +665,15 @@ int sn_process_lists(rtmodt_snapshot *z, int s0, int cnt, const int64_t *track_i
     return sn_run(z, a, s0, cnt, frame_id, q, flat, out);
 }
 
-// one call on a tracker's device-resident state: `fill` sets the source's own fields of SnArgs
-template <typename F> int sn_process_view(rtmodt_snapshot *z, const TrackViewBase &v, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
-                                          const int64_t *frame_id, const rtmodt_snapshot_out *out, F fill) {
+// one call on a tracker's device-resident state
+template <typename T> int sn_process_tracker(rtmodt_snapshot *z, T *trk, int report_tsu, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
+                                             const int64_t *frame_id, const rtmodt_snapshot_out *out) {
+    RT_CHECK(z && trk, RTMODT_E_INVALID, "bad argument");
+    TrackSrc src;
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &src, &v));
     RT_CHECK(frame_id, RTMODT_E_INVALID, "null frame_id");
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "snapshot gallery on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->Mc, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the snapshot gallery (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
+    RT_TRY(ledger_check_view(v, z->device, z->S, z->Mc, z->Mc, "snapshot gallery", "snapshot gallery"));
     RT_TRY(sn_check_frame_args(frames, v.n_streams, fh, fw, stride_bytes, mem_kind));
     RT_TRY(sn_check_ids(z, 0, v.n_streams, frame_id));
     RT_HIP(hipSetDevice(z->device));
@@ -721,8 +687,7 @@ template <typename F> int sn_process_view(rtmodt_snapshot *z, const TrackViewBas
     RT_TRY(sn_cmd_send(z, cb, bytes, q));
     SnArgs a = sn_args(z);
     a.frames = (const SnFrame *)cb->d; a.fh = fh; a.fw = fw; a.fpitch = (int64_t)z->stage.pitch;
-    a.t_meta = v.meta;
-    fill(a);
+    a.trk = src;
     return sn_run(z, a, 0, v.n_streams, frame_id, q, false, out);
 }
 
@@ -837,34 +802,22 @@ int rtmodt_snapshot_process_batch(rtmodt_snapshot *z, const int64_t *track_ids, 
 
 int rtmodt_snapshot_process_tracker(rtmodt_snapshot *z, rtmodt_tracker *trk, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
                                     const int64_t *frame_id, int report_tsu, const rtmodt_snapshot_out *out) {
-    RT_CHECK(z && trk, RTMODT_E_INVALID, "bad argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    return sn_process_view(z, v, frames, fh, fw, stride_bytes, mem_kind, frame_id, out, [&](SnArgs &a) { a.t_states = v.states; a.report_tsu = report_tsu; });
+    return sn_process_tracker(z, trk, report_tsu, frames, fh, fw, stride_bytes, mem_kind, frame_id, out);
 }
 
 int rtmodt_snapshot_process_deepsort(rtmodt_snapshot *z, rtmodt_deepsort *ds, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
                                      const int64_t *frame_id, int report_tsu, const rtmodt_snapshot_out *out) {
-    RT_CHECK(z && ds, RTMODT_E_INVALID, "bad argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
-    return sn_process_view(z, v, frames, fh, fw, stride_bytes, mem_kind, frame_id, out, [&](SnArgs &a) { a.d_states = v.states; a.report_tsu = report_tsu; });
+    return sn_process_tracker(z, ds, report_tsu, frames, fh, fw, stride_bytes, mem_kind, frame_id, out);
 }
 
 int rtmodt_snapshot_process_ocsort(rtmodt_snapshot *z, rtmodt_ocsort *oc, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
                                    const int64_t *frame_id, const rtmodt_snapshot_out *out) {
-    RT_CHECK(z && oc, RTMODT_E_INVALID, "bad argument");
-    OcDeviceView v;
-    RT_TRY(ocsort_device_view(oc, &v));
-    return sn_process_view(z, v, frames, fh, fw, stride_bytes, mem_kind, frame_id, out, [&](SnArgs &a) { a.o_states = v.states; a.o_min_hits = v.min_hits; });
+    return sn_process_tracker(z, oc, 0, frames, fh, fw, stride_bytes, mem_kind, frame_id, out);
 }
 
 int rtmodt_snapshot_process_botsort(rtmodt_snapshot *z, rtmodt_botsort *bot, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
                                     const int64_t *frame_id, const rtmodt_snapshot_out *out) {
-    RT_CHECK(z && bot, RTMODT_E_INVALID, "bad argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
-    return sn_process_view(z, v, frames, fh, fw, stride_bytes, mem_kind, frame_id, out, [&](SnArgs &a) { a.b_states = v.states; });
+    return sn_process_tracker(z, bot, 0, frames, fh, fw, stride_bytes, mem_kind, frame_id, out);
 }
 
 int rtmodt_snapshot_atlas(rtmodt_snapshot *z, int stream, void **dev_ptr, size_t *slot_bytes, int32_t *pitch) {

@@ -3,8 +3,8 @@
 // camera and one plane per stream; ground_plane.h states the per-point rules (anchor, float64 projection in a fixed operation
 // order, integer distance and speed) and include/rtmodt.h the ledger and alarm rules; tests/speed_ref.py restates both and the
 // kernels equal it exactly.  TWO launches per call whatever the tracks do:
-//   speed_update   one 256-thread workgroup per stream.  Per stream a LEDGER, rows sorted by track id, double-buffered, built as
-//                  crossing.hip builds its own: the sampled tracks are compacted by a prefix sum, each finds its old row by binary
+//   speed_update   one 256-thread workgroup per stream.  Per stream a LEDGER, rows sorted by track id, double-buffered, built by
+//                  the steps of track_ledger_dev.h as crossing.hip builds its own: the sampled tracks are compacted by a prefix sum, each finds its old row by binary
 //                  search (old ids staged in LDS), idle rows within max_gap_us are retained and merged by rank (no sort), rows
 //                  beyond it dropped.  One thread owns one sampled track's row: ring, odometer, speed, alarms.  No atomics except the
 //                  integer adds into the histogram; every loop strides over the workgroup, so a list longer than 256 works.
@@ -21,11 +21,14 @@
 
 #define GP_HD __host__ __device__
 #include "ground_plane.h"
+#define TL_HD __host__ __device__
+#include "track_ledger_host.h"
 
 namespace rtmodt {
 
 #include "wg_dev.h"
 #include "track_select_dev.h"
+#include "track_ledger_dev.h"
 
 constexpr int SP_THREADS = 256, SP_WAVES = SP_THREADS / 64;
 constexpr int SP_MAX_WINDOW = 32, SP_MAX_BINS = 256, SP_MAX_CLASSES = 256;
@@ -56,8 +59,7 @@ struct SpArgs {
     // source A: a staged list [n_streams][Mc], sorted by id; order = the caller's index of a sorted entry, inv = its inverse
     const int64_t *s_ids; const float4 *s_box; const int32_t *s_cls; const int32_t *s_order, *s_inv; const int32_t *s_n;
     // sources B..E: a tracker's device state (track_select_dev.h)
-    const TrackerState *t_states; const DsState *d_states; const OcState *o_states; const BotState *b_states;
-    const int64_t *t_meta; int report_tsu, o_min_hits;
+    TrackSrc trk;
     // per-stream scratch [n_streams][Mc]
     int32_t *p_idx, *oldpos, *krow, *evbits, *pair_off; int2 *wxy;
 };
@@ -70,15 +72,13 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
     const int cap = a.cap, Mc = a.Mc, W = a.c.window;
     double *sH = (double *)smem;                          // [10] the stream's plane (9 used; every carve offset a multiple of 16)
     int64_t *old_id = (int64_t *)(sH + 10);               // [cap]
-    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] retained flags, then their exclusive prefix
+    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] retained flags, then their rank encoding (track_ledger.h)
     int *ppre = ret_pre + cap + 1;                        // [Mc + 1] exclusive prefix of the list's sampled flags
     int *wsum = ppre + Mc + 1;                            // [SP_WAVES]
     int &s_err = wsum[SP_WAVES];                          // [1]
 
     int64_t *meta = a.meta + (size_t)sidx * 4;
-    const int cur = (int)meta[0] & 1, nxt = cur ^ 1;
-    int n_old = (int)meta[1];
-    n_old = n_old < 0 ? 0 : (n_old > cap ? cap : n_old);
+    const int cur = tl_meta_cur(meta), nxt = cur ^ 1, n_old = tl_meta_rows(meta, cap);
     const SpLedger *Lp = a.ledgers + sidx;
     const int64_t *o_id = Lp->id[cur], *o_last = Lp->last[cur], *o_odo = Lp->odo[cur], *o_since = Lp->since[cur], *o_rt = Lp->ring_t[cur];
     const int2 *o_rxy = Lp->ring_xy[cur], *o_anchor = Lp->anchor[cur], *o_chord = Lp->chord[cur];
@@ -95,18 +95,14 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
         const size_t o = (size_t)sidx * Mc;
         src = select_list(a.s_ids + o, a.s_box + o, a.s_cls + o, a.s_n[sidx]);
         order = a.s_order + o; inv = a.s_inv + o;
-    } else if (a.t_states) src = select_bytetrack(a.t_states + sidx, a.t_meta + (size_t)sidx * 8, a.report_tsu);
-    else if (a.d_states) src = select_deepsort(a.d_states + sidx, a.t_meta + (size_t)sidx * 8, a.report_tsu);
-    else if (a.o_states) src = select_ocsort(a.o_states + sidx, a.t_meta + (size_t)sidx * 8, a.o_min_hits);
-    else src = select_botsort(a.b_states + sidx, a.t_meta + (size_t)sidx * 8);
+    } else src = select_tracks(a.trk, sidx);
     const int n = src.n < 0 ? 0 : (src.n > Mc ? Mc : src.n);      // the host refuses a source whose max_tracks exceeds Mc
     const int64_t *ids = src.ids; const float4 *box = src.box; const int32_t *cls = src.cls;
 
     if (tid == 0) s_err = 0;
     if (tid < 9) sH[tid] = a.H[(size_t)sidx * 9 + tid];
-    for (int i = tid; i < n_old; i += SP_THREADS) old_id[i] = o_id[i];
     // an old row survives this call while now - last <= max_gap_us, whether or not its id is in the list
-    for (int j = tid; j < n_old; j += SP_THREADS) ret_pre[j] = now - o_last[j] <= a.c.max_gap ? 1 : 0;
+    ledger_stage_old<SP_THREADS>(o_id, n_old, old_id, ret_pre, [&](int j) { return now - o_last[j] <= a.c.max_gap ? 1 : 0; });
     __syncthreads();
 
     int32_t *p_idx = a.p_idx + (size_t)sidx * Mc, *oldpos = a.oldpos + (size_t)sidx * Mc, *krow = a.krow + (size_t)sidx * Mc;
@@ -117,66 +113,24 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
     rtmodt_speed_event *evs = (rtmodt_speed_event *)(blk + a.off_events);
     rtmodt_speed_row *rows = (rtmodt_speed_row *)(blk + a.off_rows);
 
-    // ---- 1. the sampled tracks, compacted in the list's (id) order ----
-    int n_s = 0;
-    for (int base = 0; base < n; base += SP_THREADS) {
-        const int i = base + tid;
-        bool f = false;
-        if (i < n && selected(src, i)) {
-            bool listed = a.c.classes == nullptr;
-            const int k = cls[i];
-            for (int q = 0; q < a.c.n_classes && !listed; ++q) listed = a.c.classes[q] == k;
-            const float4 b = box[i];
-            float u, v;
-            int32_t X, Y;
-            if (listed && gp_anchor(a.c.anchor, b.x, b.y, b.z, b.w, u, v) && gp_project(sH, u, v, X, Y)) {
-                f = true;
-                wxy[i] = make_int2(X, Y);
-            }
-        }
-        int tot;
-        const int pos = n_s + block_scan_count<SP_WAVES>(f ? 1 : 0, wsum, tot);
-        if (i < n) ppre[i] = pos;
-        if (f) p_idx[pos] = i;
-        n_s += tot;
-    }
-    if (tid == 0) ppre[n] = n_s;
-    // a tracker's list ascends in id unless the swap guard has exchanged two ids in its state: then a row's place among this call's
-    // rows is counted, not read off its list position (as crossing.hip)
-    __syncthreads();
-    for (int i = tid + 1; i < n; i += SP_THREADS)
-        if (!(ids[i - 1] < ids[i])) s_err = -1;              // (every writer stores the same value)
-    __syncthreads();
-    const bool ascending = s_err != -1;
-    __syncthreads();
-    if (tid == 0 && !ascending) s_err = 0;
-    auto sampled_below = [&](int64_t x) {                                      // sampled tracks of the list with an id < x
-        if (ascending) return ppre[lower_bound_i64(ids, n, x)];
-        int c = 0;
-        for (int k = 0; k < n; ++k) c += ppre[k + 1] != ppre[k] && ids[k] < x ? 1 : 0;
-        return c;
-    };
-    // each finds its old row; a matched row is no idle row, and one that has expired is not this track's row either
-    for (int t = tid; t < n_s; t += SP_THREADS) {
-        const int64_t id = ids[p_idx[t]];
-        const int j = lower_bound_i64(old_id, n_old, id);
-        const bool hit = j < n_old && old_id[j] == id;
-        oldpos[t] = hit && ret_pre[j] ? j : -1;
-        if (hit) ret_pre[j] = 0;
-    }
-    __syncthreads();
-    int n_ret = 0;
-    for (int base = 0; base < n_old; base += SP_THREADS) {                    // flags -> exclusive prefix, in place
-        const int j = base + tid;
-        const int f = j < n_old ? ret_pre[j] : 0;
-        int tot;
-        const int pos = block_scan_count<SP_WAVES>(f, wsum, tot);
-        if (j < n_old) ret_pre[j] = f ? n_ret + pos : -(n_ret + pos) - 1;       // retained: rank; dropped: -(rank of next retained) - 1
-        n_ret += tot;
-    }
-    if (tid == 0) ret_pre[n_old] = -n_ret - 1;
+    // ---- 1. the sampled tracks, compacted in the list's (id) order; each finds its old row (an expired one is not this track's
+    //         row); the idle rows are ranked ----
+    const int n_s = ledger_compact<SP_THREADS>(n, ppre, p_idx, wsum, [&](int i) {
+        if (!selected(src, i)) return false;
+        bool listed = a.c.classes == nullptr;
+        const int k = cls[i];
+        for (int q = 0; q < a.c.n_classes && !listed; ++q) listed = a.c.classes[q] == k;
+        const float4 b = box[i];
+        float u, v;
+        int32_t X, Y;
+        if (!(listed && gp_anchor(a.c.anchor, b.x, b.y, b.z, b.w, u, v) && gp_project(sH, u, v, X, Y))) return false;
+        wxy[i] = make_int2(X, Y);
+        return true;
+    });
+    const bool ascending = ledger_list_ascends<SP_THREADS>(ids, n, &s_err);
+    ledger_match<SP_THREADS, true>(ids, p_idx, n_s, old_id, n_old, ret_pre, oldpos);
+    const int n_ret = ledger_rank<SP_THREADS>(n_old, ret_pre, wsum);              // (its last barrier: ppre[n] is read below)
     // the row position of each sampled track: the caller's list order (a tracker's list: its own order)
-    __syncthreads();                                                          // (ppre[n] is read below)
     for (int base = 0, run = 0; base < n; base += SP_THREADS) {
         const int p = base + tid;
         int i = 0;
@@ -188,9 +142,7 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
         run += tot;
     }
     __syncthreads();
-    auto ranks_below = [&](int j) { const int v = ret_pre[j]; return v >= 0 ? v : -v - 1; };   // retained rows among old[0 .. j)
-    const bool overflow = n_s + n_ret > cap;                                  // keep this call's rows, drop the idle ones
-    if (overflow && tid == 0) s_err = 1;
+    const TlMerge mg = ledger_decide(ids, ppre, n, old_id, ret_pre, n_old, n_s, n_ret, ascending, cap, &s_err);
 
     // ---- 2. one thread per sampled track: its row ----
     int64_t *hist = a.hist + (size_t)sidx * (a.c.bins > 0 ? a.c.bins : 1);
@@ -198,8 +150,7 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
         const int i = p_idx[t], j = oldpos[t];
         const int64_t id = ids[i];
         const int2 P = wxy[i];
-        const int tp = ascending ? t : sampled_below(id);
-        const int np = overflow ? tp : tp + ranks_below(lower_bound_i64(old_id, n_old, id));
+        const int np = tl_member_pos(mg, t, id);
         int cnt = 0, head = -1, peak = -1, flags = RTMODT_SPEED_F_NEW, run_s = 0, run_w = 0;
         int64_t odo = 0, since = 0;
         int2 anchor = P;
@@ -263,22 +214,20 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
         rows[krow[t]] = r;
     }
     // ---- 3. idle rows move to their merged position, unchanged ----
-    if (!overflow)
-        for (int j = tid; j < n_old; j += SP_THREADS) {
-            const int v = ret_pre[j];
-            if (v < 0) continue;
-            const int np = v + sampled_below(old_id[j]);
-            n_id[np] = old_id[j]; n_last[np] = o_last[j]; n_odo[np] = o_odo[j]; n_since[np] = o_since[j];
-            n_anchor[np] = o_anchor[j]; n_chord[np] = o_chord[j];
-            n_a[np] = o_a[j];
-            int4 b = o_b[j];
-            b.y &= ~RTMODT_SPEED_F_NEW;
-            n_b[np] = b;
-            for (int k = 0; k < W; ++k) {
-                n_rxy[(size_t)k * cap + np] = o_rxy[(size_t)k * cap + j];
-                n_rt[(size_t)k * cap + np] = o_rt[(size_t)k * cap + j];
-            }
+    for (int j = tid; j < n_old; j += SP_THREADS) {
+        const int np = tl_idle_pos(mg, j);
+        if (np < 0) continue;
+        n_id[np] = old_id[j]; n_last[np] = o_last[j]; n_odo[np] = o_odo[j]; n_since[np] = o_since[j];
+        n_anchor[np] = o_anchor[j]; n_chord[np] = o_chord[j];
+        n_a[np] = o_a[j];
+        int4 b = o_b[j];
+        b.y &= ~RTMODT_SPEED_F_NEW;
+        n_b[np] = b;
+        for (int k = 0; k < W; ++k) {
+            n_rxy[(size_t)k * cap + np] = o_rxy[(size_t)k * cap + j];
+            n_rt[(size_t)k * cap + np] = o_rt[(size_t)k * cap + j];
         }
+    }
     __syncthreads();
 
     // ---- 4. events, in list order (the caller's), then kind order ----
@@ -311,9 +260,7 @@ __global__ __launch_bounds__(SP_THREADS) void speed_update(SpArgs a) {
         n_ev += tot;
     }
     if (tid == 0) {
-        meta[0] = nxt;
-        meta[1] = n_s + (overflow ? 0 : n_ret);
-        if (s_err) meta[2] = s_err;
+        tl_meta_write(meta, cur, tl_rows(mg), s_err);
         hdr->n_rows = n_s; hdr->n_events = n_ev; hdr->total_pairs = 0; hdr->err = (int32_t)meta[2];
     }
 }
@@ -439,6 +386,8 @@ SpArgs sp_args(rtmodt_speed *z) {
     return a;
 }
 
+int sp_check_sticky(rtmodt_speed *z, int s, int64_t err) { return ledger_check_sticky("speed", s, err, z->cap, "lower max_gap_us or raise max_tracks"); }
+
 // every stream of [s0, s0 + cnt) has a plane and a timestamp later than its last one
 int sp_check_streams(rtmodt_speed *z, int s0, int cnt, const int64_t *t_us) {
     for (int s = s0; s < s0 + cnt; ++s) {
@@ -492,9 +441,7 @@ int sp_run(rtmodt_speed *z, SpArgs &a, int s0, int cnt, const int64_t *t_us, hip
         if (out->pairs && np) memcpy(out->pairs + d * z->cfg.max_pairs, blk + z->off_pairs, sizeof(rtmodt_speed_pair) * np);
         if (out->n_pairs) out->n_pairs[d] = np;
         if (out->total_pairs) out->total_pairs[d] = h.total_pairs;
-        if (rc == RTMODT_OK && h.err == 1)
-            rc = fail(RTMODT_E_CAPACITY, "speed stream %d: ledger full (%d rows): lower max_gap_us or raise max_tracks", s, z->cap);
-        if (rc == RTMODT_OK && h.err != 0) rc = fail(RTMODT_E_INVALID, "speed stream %d: error %d", s, h.err);
+        if (rc == RTMODT_OK) rc = sp_check_sticky(z, s, h.err);
         if (rc == RTMODT_OK && h.n_events > z->cfg.max_events)
             rc = fail(RTMODT_E_CAPACITY, "speed stream %d: %d events in one call > max_events %d (the first ones are delivered)", s, h.n_events,
                       z->cfg.max_events);
@@ -523,49 +470,23 @@ int sp_process_lists(rtmodt_speed *z, int s0, int cnt, const int64_t *track_ids,
         RT_CHECK(n[s] == 0 || (track_ids && xyxy && cls), RTMODT_E_INVALID, "null tracks");
     }
     RT_HIP(hipSetDevice(z->device));
-    const size_t Mc = z->Mc;
-    std::vector<int32_t> perm(cnt * Mc), inv(cnt * Mc), kc(cnt * Mc);
-    std::vector<int64_t> ids(cnt * Mc);
-    std::vector<float4> box(cnt * Mc);
-    for (int s = 0; s < cnt; ++s) {
-        const int64_t *ti = track_ids + (size_t)s * stride;
-        const float *tb = xyxy + (size_t)s * stride * 4;
-        const int32_t *tc = cls + (size_t)s * stride;
-        int32_t *pm = perm.data() + s * Mc, *iv = inv.data() + s * Mc;
-        for (int i = 0; i < n[s]; ++i) pm[i] = i;
-        std::stable_sort(pm, pm + n[s], [&](int x, int y) { return ti[x] < ti[y]; });
-        for (int i = 0; i < n[s]; ++i) {
-            const int p = pm[i];
-            iv[p] = i;
-            ids[s * Mc + i] = ti[p]; kc[s * Mc + i] = tc[p];
-            box[s * Mc + i] = make_float4(tb[4 * p], tb[4 * p + 1], tb[4 * p + 2], tb[4 * p + 3]);
-            RT_CHECK(i == 0 || ids[s * Mc + i] != ids[s * Mc + i - 1], RTMODT_E_INVALID, "stream %d: track id %lld appears twice", s0 + s, (long long)ti[p]);
-        }
-    }
-    const size_t o = (size_t)s0 * Mc, m = (size_t)cnt * Mc;
-    RT_HIP(hipMemcpyAsync(z->s_ids + o, ids.data(), m * 8, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipMemcpyAsync(z->s_box + o, box.data(), m * 16, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipMemcpyAsync(z->s_cls + o, kc.data(), m * 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipMemcpyAsync(z->s_order + o, perm.data(), m * 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipMemcpyAsync(z->s_inv + o, inv.data(), m * 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipMemcpyAsync(z->s_n + s0, n, (size_t)cnt * 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipStreamSynchronize(z->stream));               // the vectors above are pageable and about to go away
+    RT_TRY(ledger_stage_lists(LedgerStaging{z->s_ids, z->s_box, z->s_cls, z->s_order, z->s_inv, z->s_n, z->Mc}, s0, cnt, track_ids, xyxy, cls, n, stride, true,
+                              z->stream));
     SpArgs a = sp_args(z);
     a.s_ids = z->s_ids; a.s_box = z->s_box; a.s_cls = z->s_cls; a.s_order = z->s_order; a.s_inv = z->s_inv; a.s_n = z->s_n;
     return sp_run(z, a, s0, cnt, t_us, z->stream, flat, out);
 }
 
-// one call on a tracker's device-resident state: `fill` sets the source's own fields of SpArgs
-template <typename F> int sp_process_view(rtmodt_speed *z, const TrackViewBase &v, const int64_t *t_us, const rtmodt_speed_out *out, F fill) {
+// one call on a tracker's device-resident state
+template <typename T> int sp_process_tracker(rtmodt_speed *z, T *trk, int report_tsu, const int64_t *t_us, const rtmodt_speed_out *out) {
+    RT_CHECK(z && trk, RTMODT_E_INVALID, "bad argument");
+    SpArgs a = sp_args(z);
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &a.trk, &v));
     RT_CHECK(t_us, RTMODT_E_INVALID, "null t_us");
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "speed estimator on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->Mc, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the speed estimator (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
+    RT_TRY(ledger_check_view(v, z->device, z->S, z->Mc, z->Mc, "speed estimator", "speed estimator"));
     RT_TRY(sp_check_streams(z, 0, v.n_streams, t_us));
     RT_HIP(hipSetDevice(z->device));
-    SpArgs a = sp_args(z);
-    a.t_meta = v.meta;
-    fill(a);
     return sp_run(z, a, 0, v.n_streams, t_us, v.stream, false, out);      // the stream the tracker's last update ran on: ordered after it
 }
 
@@ -670,31 +591,19 @@ int rtmodt_speed_process_batch(rtmodt_speed *z, const int64_t *track_ids, const 
 }
 
 int rtmodt_speed_process_tracker(rtmodt_speed *z, rtmodt_tracker *trk, const int64_t *t_us, int report_tsu, const rtmodt_speed_out *out) {
-    RT_CHECK(z && trk, RTMODT_E_INVALID, "bad argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    return sp_process_view(z, v, t_us, out, [&](SpArgs &a) { a.t_states = v.states; a.report_tsu = report_tsu; });
+    return sp_process_tracker(z, trk, report_tsu, t_us, out);
 }
 
 int rtmodt_speed_process_deepsort(rtmodt_speed *z, rtmodt_deepsort *ds, const int64_t *t_us, int report_tsu, const rtmodt_speed_out *out) {
-    RT_CHECK(z && ds, RTMODT_E_INVALID, "bad argument");
-    DsDeviceView v;
-    RT_TRY(deepsort_device_view(ds, &v));
-    return sp_process_view(z, v, t_us, out, [&](SpArgs &a) { a.d_states = v.states; a.report_tsu = report_tsu; });
+    return sp_process_tracker(z, ds, report_tsu, t_us, out);
 }
 
 int rtmodt_speed_process_ocsort(rtmodt_speed *z, rtmodt_ocsort *oc, const int64_t *t_us, const rtmodt_speed_out *out) {
-    RT_CHECK(z && oc, RTMODT_E_INVALID, "bad argument");
-    OcDeviceView v;
-    RT_TRY(ocsort_device_view(oc, &v));
-    return sp_process_view(z, v, t_us, out, [&](SpArgs &a) { a.o_states = v.states; a.o_min_hits = v.min_hits; });
+    return sp_process_tracker(z, oc, 0, t_us, out);
 }
 
 int rtmodt_speed_process_botsort(rtmodt_speed *z, rtmodt_botsort *bot, const int64_t *t_us, const rtmodt_speed_out *out) {
-    RT_CHECK(z && bot, RTMODT_E_INVALID, "bad argument");
-    BotDeviceView v;
-    RT_TRY(botsort_device_view(bot, &v));
-    return sp_process_view(z, v, t_us, out, [&](SpArgs &a) { a.b_states = v.states; });
+    return sp_process_tracker(z, bot, 0, t_us, out);
 }
 
 int rtmodt_speed_histogram(rtmodt_speed *z, int stream, int64_t *hist, int reset) {
@@ -714,8 +623,7 @@ int rtmodt_speed_state(rtmodt_speed *z, int stream, int64_t *ids, int64_t *last_
     RT_TRY(sp_sync(z));
     int64_t m[4];
     RT_HIP(hipMemcpy(m, z->d_meta + 4 * stream, sizeof(m), hipMemcpyDeviceToHost));
-    RT_CHECK(m[2] != 1, RTMODT_E_CAPACITY, "speed stream %d: ledger full (%d rows): lower max_gap_us or raise max_tracks", stream, z->cap);
-    RT_CHECK(m[2] == 0, RTMODT_E_INVALID, "speed stream %d: error %lld", stream, (long long)m[2]);
+    RT_TRY(sp_check_sticky(z, stream, m[2]));
     const int cur = (int)m[0] & 1, cnt = (int)m[1];
     RT_CHECK(cnt >= 0 && cnt <= z->cap, RTMODT_E_INVALID, "speed stream %d: corrupt row count", stream);
     const SpLedger &L = z->h_ledgers[stream];

@@ -1,6 +1,6 @@
 // track_select_dev.h -- which tracks of a tracker's device-resident state a per-frame consumer reads, and with which box: one
-// function per source.  The selection is the crossing counter's (crossing.hip: "passed"), which privacy.hip and heatmap.hip repeat;
-// speed.hip takes it from here.  Include inside namespace rtmodt, after kernels.h.
+// function per source, and select_tracks, the one switch over a TrackSrc (kernels.h).  Shared by zones.hip, crossing.hip, speed.hip,
+// snapshot.hip, privacy.hip, heatmap.hip, leftobj.hip and crosscam.hip.  Include inside namespace rtmodt, after kernels.h.
 //   ByteTrack  time_since_update == report_tsu (1 = matched or spawned this frame), the track's box;
 //   DeepSORT   confirmed (flag 2) and time_since_update == report_tsu (0 = matched this frame), the matched detection's box;
 //   OC-SORT    returned: time_since_update == 0 and (hit_streak >= min_hits or frame_count <= min_hits), the last observation;
@@ -45,6 +45,14 @@ __device__ __forceinline__ TrackSel select_botsort(const BotState *st, const int
     TrackSel s;
     s.ids = st->ids[c]; s.box = st->dbox[c]; s.cls = st->cls[c]; s.conf = st->conf[c]; s.tsu = st->tsu[c]; s.flag = st->flag[c]; s.n = (int)tm[1];
     return s;
+}
+// the list of stream `stream` of a tracker source (a consumer with a list of its own asks select_list instead)
+__device__ __forceinline__ TrackSel select_tracks(const TrackSrc &t, int stream) {
+    const int64_t *tm = t.meta + (size_t)stream * 8;
+    if (t.bytetrack) return select_bytetrack(t.bytetrack + stream, tm, t.report_tsu);
+    if (t.deepsort) return select_deepsort(t.deepsort + stream, tm, t.report_tsu);
+    if (t.ocsort) return select_ocsort(t.ocsort + stream, tm, t.min_hits);
+    return select_botsort(t.botsort + stream, tm);
 }
 // is entry i of the list selected?  (a host list selects every entry)
 __device__ __forceinline__ bool selected(const TrackSel &s, int i) {

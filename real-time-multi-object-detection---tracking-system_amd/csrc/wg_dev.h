@@ -1,5 +1,5 @@
 // wg_dev.h -- small device helpers of a wave or a workgroup, shared by zones.hip, crossing.hip, swapguard.hip, ocsort.hip, gmc.hip,
-// crosscam.hip, speed.hip, snapshot.hip, privacy.hip, heatmap.hip, motion.hip, leftobj.hip, health.hip and ccl_dev.h.  Include inside
+// crosscam.hip, speed.hip, snapshot.hip, privacy.hip, heatmap.hip, motion.hip, leftobj.hip, health.hip, ccl_dev.h and track_ledger_dev.h.  Include inside
 // namespace rtmodt.
 #pragma once
 

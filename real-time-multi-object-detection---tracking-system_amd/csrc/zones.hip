@@ -12,7 +12,7 @@
 //      interact through the shared key): integer point-in-polygon (cv::pointPolygonTest's integer
 //      branch restated, oracle/zone_oracle.py), occupancy / dwell / cooldown in double;
 //   3. the new ledger = passed tracks + retained idle rows, merged by rank (prefix sums + binary
-//      searches, no sort); rows idle for more than max_idle frames are dropped -- the reference never
+//      searches, no sort: the steps of track_ledger_dev.h); rows idle for more than max_idle frames are dropped -- the reference never
 //      drops a cooldown entry (a leak); with the device tracker a dead id never returns, so nothing
 //      observable is lost;
 //   4. events leave in (track order, zone order) through a block prefix sum.
@@ -25,9 +25,14 @@
 #include "polygon.h"
 #include "track_layout.h"
 
+#define TL_HD __host__ __device__
+#include "track_ledger_host.h"
+
 namespace rtmodt {
 
 #include "wg_dev.h"
+#include "track_select_dev.h"
+#include "track_ledger_dev.h"
 
 constexpr int ZN_THREADS = 256, ZN_WAVES = ZN_THREADS / 64;
 constexpr int ZN_MAX_ZONES = 32, ZN_MAX_POINTS = 2048;
@@ -53,8 +58,8 @@ struct ZoneArgs {
     double now; int64_t frame_id;
     // source A: staged lists [n_streams][max_tracks], sorted by id, `order` = the caller's index
     const int64_t *s_ids; const float4 *s_box; const int32_t *s_cls; const int32_t *s_order; const int32_t *s_n; int s_stride;
-    // source B: the tracker's device state (s_ids == nullptr); passed tracks are those with tsu == report_tsu
-    const TrackerState *t_states; const int64_t *t_meta; int report_tsu;
+    // source B: the tracker's device state (s_ids == nullptr, track_select_dev.h)
+    TrackSrc trk;
     // per-stream scratch [n_streams][max_tracks]
     int32_t *oldpos; uint32_t *evmask; double *evdwell;    // evdwell [..][Z]
     // events [n_streams][max_events]
@@ -68,13 +73,13 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
     const int sidx = a.stream_base + blockIdx.x, tid = threadIdx.x;
     const int Z = a.zt.Z, cap = a.cap;
     int64_t *old_id = (int64_t *)smem;                    // [cap]
-    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] exclusive prefix of the retained flags
+    int *ret_pre = (int *)(old_id + cap);                 // [cap + 1] retained flags, then their rank encoding (track_ledger.h)
     int2 *pts = (int2 *)(ret_pre + cap + 1 + ((cap + 1) & 1));
     int *wsum = (int *)(pts + a.zt.n_pts);
     __shared__ int s_err;
 
     int64_t *meta = a.meta + (size_t)sidx * 4;
-    const int cur = (int)meta[0], n_old = (int)meta[1], nxt = cur ^ 1;
+    const int cur = tl_meta_cur(meta), n_old = tl_meta_rows(meta, cap);
     const ZoneLedger L = a.ledgers[sidx];
     const int64_t *o_id = cur ? L.id[1] : L.id[0];      int64_t *n_id = cur ? L.id[0] : L.id[1];
     const int64_t *o_seen = cur ? L.seen[1] : L.seen[0]; int64_t *n_seen = cur ? L.seen[0] : L.seen[1];
@@ -83,77 +88,35 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
     const double *o_alert = cur ? L.alert[1] : L.alert[0]; double *n_alert = cur ? L.alert[0] : L.alert[1];
 
     // ---- this frame's list ----
-    const int64_t *ids; const float4 *box; const int32_t *cls; const int32_t *order = nullptr; const int32_t *tsu = nullptr;
-    int n;
+    TrackSel src;
+    const int32_t *order = nullptr;
     if (a.s_ids) {
         const size_t o = (size_t)sidx * a.s_stride;
-        ids = a.s_ids + o; box = a.s_box + o; cls = a.s_cls + o; order = a.s_order + o; n = a.s_n[sidx];
-    } else {
-        const TrackerState st = a.t_states[sidx];
-        const int64_t *tm = a.t_meta + (size_t)sidx * 8;
-        const int tc = (int)tm[0];
-        ids = tc ? st.ids[1] : st.ids[0]; box = tc ? st.box[1] : st.box[0]; cls = tc ? st.cls[1] : st.cls[0]; tsu = tc ? st.tsu[1] : st.tsu[0];
-        n = (int)tm[1];
-    }
-    if (n > cap) n = cap;                                  // host sizes cap >= max_tracks
-
-    if (tid == 0) s_err = 0;
-    for (int i = tid; i < n_old; i += ZN_THREADS) old_id[i] = o_id[i];
-    for (int i = tid; i < a.zt.n_pts; i += ZN_THREADS) pts[i] = a.zt.pts[i];
-    __syncthreads();
-    // a tracker's list ascends in id unless the swap guard (swapguard.hip) has exchanged two ids in its state: then a row's place among
-    // this frame's rows is counted, not read off its list position
-    for (int i = tid + 1; i < n; i += ZN_THREADS)
-        if (!(ids[i - 1] < ids[i])) s_err = -1;              // (every writer stores the same value)
-    __syncthreads();
-    const bool ascending = s_err != -1;
-    __syncthreads();
-    if (tid == 0 && !ascending) s_err = 0;
-    auto listed_below = [&](int64_t x) {                                       // list entries with an id < x
-        if (ascending) return lower_bound_i64(ids, n, x);
-        int c = 0;
-        for (int k = 0; k < n; ++k) c += ids[k] < x ? 1 : 0;
-        return c;
-    };
+        src = select_list(a.s_ids + o, a.s_box + o, a.s_cls + o, a.s_n[sidx]);
+        order = a.s_order + o;
+    } else src = select_tracks(a.trk, sidx);
+    const int n = src.n < 0 ? 0 : (src.n > cap ? cap : src.n);      // host sizes cap >= max_tracks
+    const int64_t *ids = src.ids; const float4 *box = src.box; const int32_t *cls = src.cls;
 
     int32_t *oldpos = a.oldpos + (size_t)sidx * cap;
     uint32_t *evmask = a.evmask + (size_t)sidx * cap;
     double *evdwell = a.evdwell + (size_t)sidx * cap * Z;
 
-    // ---- 1. which old rows are gone, which stay as idle rows ----
-    for (int j = tid; j < n_old; j += ZN_THREADS) ret_pre[j] = 1;             // provisional: retained unless matched / expired
-    __syncthreads();
-    for (int i = tid; i < n; i += ZN_THREADS) {
-        const int64_t id = ids[i];
-        const int j = lower_bound_i64(old_id, n_old, id);
-        const bool hit = j < n_old && old_id[j] == id;
-        oldpos[i] = hit ? j : -1;
-        if (hit) ret_pre[j] = 0;
-    }
-    __syncthreads();
-    for (int j = tid; j < n_old; j += ZN_THREADS)
-        if (ret_pre[j] && (a.max_idle < 0 || a.frame_id - o_seen[j] > a.max_idle)) ret_pre[j] = 0;
-    __syncthreads();
-    int n_ret = 0;
-    for (int base = 0; base < n_old; base += ZN_THREADS) {                    // flags -> exclusive prefix, in place
-        const int j = base + tid;
-        const int f = j < n_old ? ret_pre[j] : 0;
-        int tot;
-        const int pos = block_scan_count<ZN_WAVES>(f, wsum, tot);
-        if (j < n_old) ret_pre[j] = f ? n_ret + pos : -(n_ret + pos) - 1;       // retained: rank; dropped: -(rank of next retained) - 1
-        n_ret += tot;
-    }
-    if (tid == 0) ret_pre[n_old] = -n_ret - 1;
-    __syncthreads();
-    auto ranks_below = [&](int j) { const int v = ret_pre[j]; return v >= 0 ? v : -v - 1; };   // retained rows among old[0 .. j)
-    const bool overflow = n + n_ret > cap;                                    // keep this frame's rows, drop the idle ones
-    if (overflow && tid == 0) s_err = 1;
+    // ---- 1. every list entry is a row and finds its old one; an old row no entry claims stays as an idle row unless it has expired.
+    //         (A claimed row that has expired is still its track's row: step 2 drops what expires with it) ----
+    if (tid == 0) s_err = 0;
+    for (int i = tid; i < a.zt.n_pts; i += ZN_THREADS) pts[i] = a.zt.pts[i];
+    ledger_stage_old<ZN_THREADS>(o_id, n_old, old_id, ret_pre, [&](int j) { return a.max_idle < 0 || a.frame_id - o_seen[j] > a.max_idle ? 0 : 1; });
+    const bool ascending = ledger_list_ascends<ZN_THREADS>(ids, n, &s_err);
+    ledger_match<ZN_THREADS, false>(ids, nullptr, n, old_id, n_old, ret_pre, oldpos);
+    const int n_ret = ledger_rank<ZN_THREADS>(n_old, ret_pre, wsum);
+    const TlMerge mg = ledger_decide(ids, nullptr, n, old_id, ret_pre, n_old, n, n_ret, ascending, cap, &s_err);
 
     // ---- 2. the reference's double loop: tracks (one lane each) x zones (in order) ----
     for (int i = tid; i < n; i += ZN_THREADS) {
         const int j = oldpos[i];
-        const bool active = tsu ? tsu[i] == a.report_tsu : true;
-        const int np = (ascending ? i : listed_below(ids[i])) + (overflow ? 0 : ranks_below(lower_bound_i64(old_id, n_old, ids[i])));
+        const bool active = selected(src, i);
+        const int np = tl_member_pos(mg, i, ids[i]);
         uint32_t mask = j >= 0 ? o_mask[j] : 0u;
         uint32_t ev = 0u;
         double *nf = n_first + (size_t)np * Z, *na = n_alert + (size_t)np * Z;
@@ -191,16 +154,14 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
         evmask[i] = ev;
     }
     // idle rows move to their merged position
-    if (!overflow)
-        for (int j = tid; j < n_old; j += ZN_THREADS) {
-            const int v = ret_pre[j];
-            if (v < 0) continue;
-            const int np = v + listed_below(old_id[j]);
-            n_id[np] = old_id[j];
-            n_seen[np] = o_seen[j];
-            n_mask[np] = 0u;                                                            // idle == not passed == purged occupancy
-            for (int z = 0; z < Z; ++z) { n_first[(size_t)np * Z + z] = 0.0; n_alert[(size_t)np * Z + z] = o_alert[(size_t)j * Z + z]; }
-        }
+    for (int j = tid; j < n_old; j += ZN_THREADS) {
+        const int np = tl_idle_pos(mg, j);
+        if (np < 0) continue;
+        n_id[np] = old_id[j];
+        n_seen[np] = o_seen[j];
+        n_mask[np] = 0u;                                                                // idle == not passed == purged occupancy
+        for (int z = 0; z < Z; ++z) { n_first[(size_t)np * Z + z] = 0.0; n_alert[(size_t)np * Z + z] = o_alert[(size_t)j * Z + z]; }
+    }
     __syncthreads();
 
     // ---- 3. events, in list order then zone order ----
@@ -232,9 +193,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
     if (tid == 0) {
         if (n_ev > a.max_events) s_err = s_err ? s_err : 2;
         a.ev_n[sidx] = n_ev < a.max_events ? n_ev : a.max_events;
-        meta[0] = nxt;
-        meta[1] = n + (overflow ? 0 : n_ret);
-        if (s_err) meta[2] = s_err;
+        tl_meta_write(meta, cur, tl_rows(mg), s_err);
     }
 }
 
@@ -329,10 +288,8 @@ int fetch_events(rtmodt_zones *z, hipStream_t s, EvHost &h) {
 }
 
 int check_err(rtmodt_zones *z, int s, int64_t err) {
-    RT_CHECK(err != 1, RTMODT_E_CAPACITY, "zones stream %d: ledger full (%d rows): lower max_idle_frames or raise max_tracks", s, z->cap);
     RT_CHECK(err != 2, RTMODT_E_CAPACITY, "zones stream %d: more than max_events=%d events in one frame", s, z->max_events);
-    RT_CHECK(err == 0, RTMODT_E_INVALID, "zones stream %d: error %lld", s, (long long)err);
-    return RTMODT_OK;
+    return ledger_check_sticky("zones", s, err, z->cap, "lower max_idle_frames or raise max_tracks");
 }
 
 }  // namespace
@@ -408,25 +365,9 @@ int rtmodt_zones_process(rtmodt_zones *z, int stream, const int64_t *track_ids, 
     RT_CHECK(now == now, RTMODT_E_INVALID, "now is NaN");
     RT_HIP(hipSetDevice(z->device));
     // the ledger is sorted by id: hand the list over in id order, remember the caller's order
-    std::vector<int32_t> perm(n);
-    for (int i = 0; i < n; ++i) perm[i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return track_ids[a] < track_ids[b]; });
-    std::vector<int64_t> ids(n); std::vector<float4> box(n); std::vector<int32_t> kc(n);
-    for (int i = 0; i < n; ++i) {
-        const int p = perm[i];
-        ids[i] = track_ids[p]; kc[i] = cls[p];
-        box[i] = make_float4(xyxy[4 * p], xyxy[4 * p + 1], xyxy[4 * p + 2], xyxy[4 * p + 3]);
-        RT_CHECK(i == 0 || ids[i] != ids[i - 1], RTMODT_E_INVALID, "track id %lld appears twice", (long long)ids[i]);
-    }
-    const size_t o = (size_t)stream * z->cap;
-    if (n) {
-        RT_HIP(hipMemcpyAsync(z->s_ids + o, ids.data(), (size_t)n * 8, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_box + o, box.data(), (size_t)n * 16, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_cls + o, kc.data(), (size_t)n * 4, hipMemcpyHostToDevice, z->stream));
-        RT_HIP(hipMemcpyAsync(z->s_order + o, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, z->stream));
-    }
-    RT_HIP(hipMemcpyAsync(z->s_n + stream, &n, 4, hipMemcpyHostToDevice, z->stream));
-    RT_HIP(hipStreamSynchronize(z->stream));               // the vectors above are pageable and about to go away
+    const int32_t n32 = n;
+    RT_TRY(ledger_stage_lists(LedgerStaging{z->s_ids, z->s_box, z->s_cls, z->s_order, nullptr, z->s_n, z->cap}, stream, 1, track_ids, xyxy, cls, &n32, 0, false,
+                              z->stream));
     ZoneArgs a = make_args(z, now, frame_id);
     a.stream_base = stream;
     a.s_ids = z->s_ids; a.s_box = z->s_box; a.s_cls = z->s_cls; a.s_order = z->s_order; a.s_n = z->s_n; a.s_stride = z->cap;
@@ -454,14 +395,11 @@ int rtmodt_zones_process(rtmodt_zones *z, int stream, const int64_t *track_ids, 
 int rtmodt_zones_process_tracker(rtmodt_zones *z, rtmodt_tracker *trk, double now, int64_t frame_id, int report_tsu, int64_t *ev_track_id,
                                  int32_t *ev_zone, double *ev_dwell, float *ev_xyxy, int32_t *ev_centroid, int32_t *ev_cls, int32_t *n_events) {
     RT_CHECK(z && trk && n_events && now == now, RTMODT_E_INVALID, "bad argument");
-    TrackerDeviceView v;
-    RT_TRY(tracker_device_view(trk, &v));
-    RT_CHECK(v.device == z->device, RTMODT_E_INVALID, "zones on device %d, tracker on device %d", z->device, v.device);
-    RT_CHECK(v.n_streams <= z->S && v.max_tracks <= z->cap, RTMODT_E_INVALID, "tracker (%d streams, %d tracks) larger than the zone engine (%d, %d)",
-             v.n_streams, v.max_tracks, z->S, z->Mc);
-    RT_HIP(hipSetDevice(z->device));
     ZoneArgs a = make_args(z, now, frame_id);
-    a.t_states = v.states; a.t_meta = v.meta; a.report_tsu = report_tsu;
+    TrackViewBase v;
+    RT_TRY(track_src(trk, report_tsu, &a.trk, &v));
+    RT_TRY(ledger_check_view(v, z->device, z->S, z->cap, z->Mc, "zones", "zone engine"));
+    RT_HIP(hipSetDevice(z->device));
     a.max_idle = -1;                                        // a track the tracker dropped never comes back: its row goes too
     RT_TRY(launch(z, a, v.n_streams, v.stream));            // the stream the tracker's last update ran on: ordered after it
     EvHost h;

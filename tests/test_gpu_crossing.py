@@ -8,6 +8,7 @@ import pytest
 
 from oracle import tracker_oracle as T
 import crossing_ref as R
+import ledger_boundary as B
 import deepsort_ref as D
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,36 @@ def test_more_than_one_pass_then_mostly_idle_rows(pkg):
     """max_tracks = 300 with 257, 300, 1 and 300 tracks passed: two passes of the 256-thread loops, then 299 idle rows around one passed."""
     ref, n = run_host(pkg, R.BOUNDARY_LINES, R.BOUNDARY_GATES, R.boundary_calls(), max_tracks=300, max_events=2048, max_gap_frames=10)
     assert n > 300 and len(ref.rows) == 300
+
+
+def test_both_scans_end_at_a_workgroup_pass_then_one_row_too_many(pkg):
+    """ledger_boundary.py: 255, 256 and 257 list entries beside 255, 256 and 257 idle rows (max_tracks = 600), ids that return inside
+    max_gap_frames and after it, a ledger exactly full and then over by one row: every call equals the restatement, the last one is
+    E_CAPACITY with the counts of the overflowing frame complete."""
+    seq = B.calls()
+    B.guards(seq)
+    kw = dict(max_tracks=B.MAX_TRACKS, max_events=4096, max_gap_frames=B.GAP)
+    counter = pkg.events.CrossingCounter(R.BOUNDARY_LINES, R.BOUNDARY_GATES, **kw)
+    ref = R.CrossingRef(R.BOUNDARY_LINES, R.BOUNDARY_GATES, **kw)
+    n_ev = 0
+    for step, ids, idle in seq:
+        rows = [(i, R.box(80 + 12 * ((step + i) % 4), 10 * (i % 300)), i % 90) for i in ids]
+        want = ref.process(rows, step)
+        assert len(ref.rows) - len(ids) == idle, step                                  # the restatement keeps the idle rows the sequence plans
+        if step < B.LAST_STEP:
+            assert not ref.ledger_overflow
+            check(counter, ref, counter.process(tracks_of(rows), step), want, f"step {step}")
+            n_ev += len(want)
+            continue
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            counter.process(tracks_of(rows), step)
+        assert ref.ledger_overflow and e.value.code == pkg._ffi.E_CAPACITY and "ledger full" in str(e.value)
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            counter.snapshot()
+        assert e.value.code == pkg._ffi.E_CAPACITY
+        assert counts_of(counter) == ref.counts()
+    assert n_ev > 300 and len(ref.rows) == 2 * B.MAX_TRACKS + 1
+    counter.close()
 
 
 def test_event_overflow_truncates_events_not_counts(pkg):

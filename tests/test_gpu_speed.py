@@ -6,6 +6,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import ledger_boundary as B
 import speed_ref as R
 import swapguard_ref as SG
 
@@ -196,6 +197,40 @@ def test_300_tracks_and_a_few_hundred_pairs(pkg):
             assert len(ref.rows) == 600
     assert all(100 < t < 1500 for t in totals) and n_ev > 50 and not ref.pairs_truncated and not ref.events_truncated, (totals, n_ev)
     assert len(ref.rows) == 300                                                    # the first 300 have expired
+    est.close()
+
+
+def test_both_scans_end_at_a_workgroup_pass_then_one_row_too_many(pkg):
+    """ledger_boundary.py: 255, 256 and 257 list entries beside 255, 256 and 257 idle rows (max_tracks = 600), ids that return inside
+    max_gap_us and after it, a ledger exactly full and then over by one row: every call equals the restatement, the last one is
+    E_CAPACITY with its own rows complete."""
+    seq = B.calls()
+    B.guards(seq)
+    tick = 100_000
+    kw = dict(window=3, hold=2, limit_mm_s=300, stop_mm_s=40, stop_us=tick, min_step_mm=15, max_events=2048, bins=16, bin_mm_s=50,
+              max_gap_us=B.GAP * tick, max_tracks=B.MAX_TRACKS)
+    est, ref = pkg.events.SpeedEstimator(plane=R.AFFINE_H, **kw), R.SpeedRef(R.AFFINE_H, **kw)
+    n_ev = 0
+    for step, ids, idle in seq:
+        rows = [(i, R.box(20.0 + (i % 40) * 10 + ((step * (i % 5)) % 7), 52.0 + (i // 40 % 30) * 10), i % 3) for i in ids]
+        before = set(ref.rows)
+        want = ref.process(rows, step * tick)
+        if step < B.LAST_STEP:
+            assert not ref.ledger_overflow and len(ref.rows) - len(ids) == idle, step    # the restatement keeps the idle rows the sequence plans
+            est.process(tracks_of(rows), step * tick)
+            check(est, ref, want, f"step {step}")
+            n_ev += len(want[1])
+            continue
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            est.process(tracks_of(rows), step * tick)
+        assert ref.ledger_overflow and len(before) == idle == 2 * B.MAX_TRACKS and not before & set(ids)      # 1200 idle rows + 1: they go
+        assert e.value.code == pkg._ffi.E_CAPACITY and "ledger full" in str(e.value)
+        assert est.last_rows[0] == want[0] and len(want[0]) == 1 and sorted(ref.rows) == ids       # this call's rows are complete all the same
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            est.snapshot()
+        assert e.value.code == pkg._ffi.E_CAPACITY
+        assert est.histogram().tolist() == ref.hist
+    assert n_ev > 50 and not ref.events_truncated
     est.close()
 
 

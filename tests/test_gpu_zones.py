@@ -11,6 +11,7 @@ import pytest
 from oracle import tracker_oracle as T
 from oracle import zone_oracle as Z
 from conftest import GOLDEN
+import ledger_boundary as B
 import zone_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -247,6 +248,36 @@ def test_centroids_truncate_and_round_like_float32(pkg, tmp_path):
     assert model.n_events == 4 * len(tracks)                    # per track and frame: the corner zone and the edge zone
     got = {e.track_id: e.centroid[0] for e in eng.process(ns(tracks), 2, now=1.7e9 + 2.0)}
     assert got == {i + 1: R.CENTROID_CASES[i][1] for i in range(len(tracks))}
+    eng.close()
+
+
+def test_both_scans_end_at_a_workgroup_pass_then_one_row_too_many(pkg, tmp_path):
+    """ledger_boundary.py: 255, 256 and 257 list entries beside 255, 256 and 257 idle rows (max_tracks = 600), ids that return inside
+    max_idle_frames and after it, a ledger exactly full and then over by one row: every call equals the model, the last one is
+    E_CAPACITY and the handle stays in error."""
+    seq = B.calls()
+    B.guards(seq)
+    zones = [{"name": "left", "polygon": [[0, 0], [300, 0], [300, 480], [0, 480]], "dwell_time_sec": 0.0, "cooldown_sec": 2.0},
+             {"name": "band", "polygon": [[0, 100], [640, 100], [640, 300], [0, 300]], "dwell_time_sec": 1.0, "cooldown_sec": 0.0}]
+    eng = pkg.events.ZoneEventEngine(zones, log_path=str(tmp_path / "e.jsonl"), max_tracks=B.MAX_TRACKS, max_events=2048, max_idle_frames=B.GAP)
+    model = R.ZoneLedgerRef(zones, B.MAX_TRACKS, B.GAP)
+    for step, ids, idle in seq:
+        tracks = [(i, np.array([(i * 7 + step * 40) % 620, (i * 13) % 460, (i * 7 + step * 40) % 620 + 20, (i * 13) % 460 + 20], np.float32), i % 5) for i in ids]
+        now = 1.7e9 + step
+        if step < B.LAST_STEP:
+            check_call(eng, model, 0, step, now, tracks, f"step {step}")
+            assert model.history[-1] == (len(ids), idle, len(ids) + idle) and model.overflow is None, step
+            continue
+        model.process(tracks, step, now)
+        assert model.overflow == step and model.rows == 2 * B.MAX_TRACKS + 1
+        for attempt in (tracks, []):                            # the overflowing call, then any other
+            with pytest.raises(pkg._ffi.RtmodtError) as e:
+                eng.process(ns(attempt), step, now=now)
+            assert e.value.code == pkg._ffi.E_CAPACITY
+        with pytest.raises(pkg._ffi.RtmodtError) as e:
+            eng.snapshot()
+        assert e.value.code == pkg._ffi.E_CAPACITY
+    assert model.n_events > 300 and model.returned_live > 100 and model.returned_expired > 0
     eng.close()
 
 
