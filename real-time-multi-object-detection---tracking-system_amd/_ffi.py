@@ -738,6 +738,31 @@ def check(rc: int) -> None:
         raise RtmodtError(rc, lib().rtmodt_last_error().decode(errors="replace"))
 
 
+class Handle:
+    """Base of a class that owns one library handle: ``_h`` and ``_destroy``, the name of the symbol that releases it.  A class that
+    has more to close in a fixed order overrides ``close()`` and calls this one."""
+    _h = None
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def last_ms(symbol: str, h, k: int = 1):
+    """``rtmodt_X_last_ms`` with ``k`` float outputs: the milliseconds as a float, or as a tuple when ``k > 1``."""
+    out = [C.c_float(0) for _ in range(k)]
+    check(getattr(lib(), symbol)(h, *[C.byref(v) for v in out]))
+    return out[0].value if k == 1 else tuple(v.value for v in out)
+
+
 def ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 

@@ -476,8 +476,8 @@ static int launch_botsort_update(const BotArgs &a, int n_streams, hipStream_t s)
 using namespace rtmodt;
 
 struct rtmodt_botsort : TrackHandleBase {
-    hipEvent_t ev[4] = {};                   // describe | distance | update boundaries of the last call
-    bool timed = false, described = false;
+    EventTimer<4> timer;                   // describe | distance | update boundaries of the last call
+    bool described = false;
     rtmodt_botsort_cfg cfg = {};
     int dim = 0;                             // 0: motion only
     char *pool = nullptr;                    // all state arrays but the features (track_layout.h: carve_botsort)
@@ -503,22 +503,22 @@ int botsort_feature_view(rtmodt_botsort *t, const int8_t **feat8, int *dim) {
 
 static int bot_create_impl(rtmodt_botsort *t) {
     RT_TRY(track_open(t));
-    for (auto &e : t->ev) RT_HIP(hipEventCreate(&e));
+    RT_TRY(t->timer.create());
     t->h_states.assign(t->S, BotState{});
     const size_t total = carve_botsort(t->h_states.data(), t->S, t->Mc, nullptr);
     RT_HIP(hipMalloc((void **)&t->pool, total));
-    RT_HIP(hipMemset(t->pool, 0, total));
+    RT_HIP(handle_zero(t->pool, total, t->stream));
     carve_botsort(t->h_states.data(), t->S, t->Mc, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(BotState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(BotState) * t->S, hipMemcpyHostToDevice));
     if (!t->dim) return RTMODT_OK;
     const size_t F = (size_t)t->S * 2 * t->Mc * t->dim, SN = (size_t)t->S * t->Nc;
-    RT_HIP(hipMalloc((void **)&t->d_feat16, F * 2)); RT_HIP(hipMemset(t->d_feat16, 0, F * 2));
-    RT_HIP(hipMalloc((void **)&t->d_feat8, F)); RT_HIP(hipMemset(t->d_feat8, 0, F));
-    RT_HIP(hipMalloc((void **)&t->d_desc, SN * t->dim)); RT_HIP(hipMemset(t->d_desc, 0, SN * t->dim));
+    RT_HIP(hipMalloc((void **)&t->d_feat16, F * 2)); RT_HIP(handle_zero(t->d_feat16, F * 2, t->stream));
+    RT_HIP(hipMalloc((void **)&t->d_feat8, F)); RT_HIP(handle_zero(t->d_feat8, F, t->stream));
+    RT_HIP(hipMalloc((void **)&t->d_desc, SN * t->dim)); RT_HIP(handle_zero(t->d_desc, SN * t->dim, t->stream));
     RT_HIP(hipMalloc((void **)&t->d_counts, SN * APP_DIM * 4));
     RT_HIP(hipMalloc((void **)&t->d_dot, (size_t)t->S * t->Mc * t->Nc * 4));
-    RT_HIP(hipMemset(t->d_dot, 0, (size_t)t->S * t->Mc * t->Nc * 4));
+    RT_HIP(handle_zero(t->d_dot, (size_t)t->S * t->Mc * t->Nc * 4, t->stream));
     return RTMODT_OK;
 }
 
@@ -537,7 +537,7 @@ static BotArgs bot_args(rtmodt_botsort *t, const float *warp, int count) {
 
 // the launches of one call on stream q, detections described by `a`'s det_* fields for streams [0, count)
 static int bot_run(rtmodt_botsort *t, const BotArgs &a, int count, const AppFrames *frames, int fh, int fw, int pitch, hipStream_t q) {
-    RT_HIP(hipEventRecord(t->ev[0], q));
+    RT_TRY(t->timer.record(0, q));
     t->described = frames != nullptr;
     if (frames && t->reid) {
         RT_TRY(reid_run(t->reid, *frames, count, fh, fw, pitch, a.det_box, a.det_n, a.det_stride, std::min(a.det_stride, t->Nc), t->d_desc, t->Nc, q));
@@ -548,7 +548,7 @@ static int bot_run(rtmodt_botsort *t, const BotArgs &a, int count, const AppFram
         d.counts = t->d_counts; d.desc = t->d_desc; d.desc_stride = t->Nc;
         RT_TRY(launch_describe(d, count, q));
     }
-    RT_HIP(hipEventRecord(t->ev[1], q));
+    RT_TRY(t->timer.record(1, q));
     if (t->dim) {
         DotmaxArgs m{};
         m.gallery = t->d_feat8; m.gallery_stream_stride = (size_t)2 * t->Mc * t->dim; m.gallery_cur_stride = (size_t)t->Mc * t->dim;
@@ -557,10 +557,10 @@ static int bot_run(rtmodt_botsort *t, const BotArgs &a, int count, const AppFram
         m.out = t->d_dot; m.out_stream_stride = (size_t)t->Mc * t->Nc; m.out_row_stride = t->Nc;
         RT_TRY(launch_dotmax(m, t->Mc, m.max_dets, count, q));
     }
-    RT_HIP(hipEventRecord(t->ev[2], q));
+    RT_TRY(t->timer.record(2, q));
     RT_TRY(launch_botsort_update(a, count, q));
-    RT_HIP(hipEventRecord(t->ev[3], q));
-    t->timed = true;
+    RT_TRY(t->timer.record(3, q));
+    t->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -592,7 +592,7 @@ int rtmodt_botsort_check_warp(const float *warp, int n_streams) {
 void rtmodt_botsort_destroy(rtmodt_botsort *t) {
     if (!t) return;
     track_close(t, [t] {
-        for (auto &e : t->ev) if (e) hipEventDestroy(e);
+        t->timer.destroy();
         hipFree(t->pool); hipFree(t->d_states); hipFree(t->d_feat16); hipFree(t->d_feat8); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dot);
         t->stage.release();
         reid_close(t->reid);
@@ -629,7 +629,7 @@ int rtmodt_botsort_create(const rtmodt_botsort_cfg *cfg, rtmodt_botsort **out) {
     t->device = cfg->device; t->S = cfg->n_streams; t->Mc = cfg->max_tracks; t->Nc = cfg->max_dets; t->dim = dim;
     int rc = net ? reid_open(e, cfg->device, cfg->n_streams, cfg->max_dets, false, &t->reid) : RTMODT_OK;     // the file is checked before the device is touched
     if (rc == RTMODT_OK) rc = bot_create_impl(t);
-    return track_created(rc, t, rtmodt_botsort_destroy, out);
+    return handle_created(rc, t, rtmodt_botsort_destroy, out);
 }
 
 int rtmodt_botsort_reset(rtmodt_botsort *t, int stream) { return track_reset_meta(t, stream); }
@@ -740,13 +740,10 @@ int rtmodt_botsort_state(rtmodt_botsort *t, int stream, int64_t *ids, int32_t *f
 
 int rtmodt_botsort_last_ms(rtmodt_botsort *t, float *describe_ms, float *distance_ms, float *update_ms) {
     RT_CHECK(t, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(t->timed, RTMODT_E_INVALID, "no update has run yet");
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipEventSynchronize(t->ev[3]));
     float a = 0, b = 0, c = 0;
-    RT_HIP(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
-    RT_HIP(hipEventElapsedTime(&b, t->ev[1], t->ev[2]));
-    RT_HIP(hipEventElapsedTime(&c, t->ev[2], t->ev[3]));
+    RT_TRY(t->timer.elapsed(t->device, 2, 3, &c, "no update has run yet"));      // (the last event first: it waits for the call)
+    RT_TRY(t->timer.elapsed(t->device, 0, 1, &a, "no update has run yet"));
+    RT_TRY(t->timer.elapsed(t->device, 1, 2, &b, "no update has run yet"));
     if (describe_ms) *describe_ms = t->described ? a : 0.f;
     if (distance_ms) *distance_ms = t->dim ? b : 0.f;
     if (update_ms) *update_ms = c;

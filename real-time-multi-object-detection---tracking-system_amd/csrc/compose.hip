@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "frame_stage.h"
+#include "handle_host.h"
 
 #define PV_HD __host__ __device__
 #include "compose_rule.h"
@@ -371,12 +372,10 @@ int cp_resolve_fmt(int i, const rtmodt_compose_out_desc &o, const rtmodt_frame_f
 
 }  // namespace
 
-struct rtmodt_compose {
-    int device = 0;
+struct rtmodt_compose : HandleBase {
     rtmodt_compose_cfg cfg{};
-    bool dev_ready = false, timed = false, has_layout = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool dev_ready = false, has_layout = false;
+    EventTimer<2> timer;
     CpLayout lay;
     CmdBuf cmd;                         // (every run ends with a synchronize: the pinned half is idle when the next one writes it)
     uint8_t *d_stage = nullptr;         // host sources
@@ -388,9 +387,8 @@ namespace {
 int cp_ensure_device(rtmodt_compose *p) {
     RT_HIP(hipSetDevice(p->device));
     if (p->dev_ready) return RTMODT_OK;
-    if (!p->stream) RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    if (!p->ev0) RT_HIP(hipEventCreate(&p->ev0));
-    if (!p->ev1) RT_HIP(hipEventCreate(&p->ev1));
+    if (!p->stream) RT_TRY(handle_open(p));
+    RT_TRY(p->timer.create());           // (makes the events a failed attempt did not)
     p->dev_ready = true;
     return RTMODT_OK;
 }
@@ -493,16 +491,13 @@ void rtmodt_compose_default_cfg(rtmodt_compose_cfg *cfg) {
 
 void rtmodt_compose_destroy(rtmodt_compose *p) {
     if (!p) return;
-    if (p->dev_ready || p->stream) {
-        hipSetDevice(p->device);
-        if (p->stream) hipStreamSynchronize(p->stream);
-        p->lay.release();
-        hipFree(p->d_stage);
-        p->cmd.release();
-        if (p->ev0) hipEventDestroy(p->ev0);
-        if (p->ev1) hipEventDestroy(p->ev1);
-        if (p->stream) hipStreamDestroy(p->stream);
-    }
+    if (p->dev_ready || p->stream)
+        handle_close(p, [&] {
+            p->lay.release();
+            hipFree(p->d_stage);
+            p->cmd.release();
+            p->timer.destroy();
+        });
     delete p;
 }
 
@@ -547,7 +542,7 @@ int rtmodt_compose_set_layout(rtmodt_compose *p, const rtmodt_compose_src_desc *
     p->lay.release();                   // (every run ended with a synchronize: nothing reads the old pool)
     p->lay = std::move(L);
     p->has_layout = true;
-    p->timed = false;
+    p->timer.timed = false;
     return RTMODT_OK;
 }
 
@@ -579,7 +574,7 @@ int rtmodt_compose_set_crop(rtmodt_compose *p, int cell, int x, int y, int w, in
 int rtmodt_compose_run(rtmodt_compose *p, const uint8_t *const *src, const int32_t *src_pitch, int src_mem_kind, uint8_t *const *dst,
                        const rtmodt_frame_format *dst_fmt, int dst_mem_kind) {
     RT_CHECK(p && src, RTMODT_E_INVALID, "null argument");
-    p->timed = false;
+    p->timer.timed = false;
     RT_CHECK(p->has_layout, RTMODT_E_INVALID, "no layout has been set");
     RT_TRY(check_mem_kind(src_mem_kind));
     RT_TRY(check_mem_kind(dst_mem_kind));
@@ -655,10 +650,10 @@ int rtmodt_compose_run(rtmodt_compose *p, const uint8_t *const *src, const int32
     a.tiles = (const CpDevTile *)(L.d_pool + L.o_tiles); a.list = (const uint16_t *)(L.d_pool + L.o_list);
     a.tabs = (const int32_t *)(L.d_pool + L.o_tabs);
     a.src = (const CpRunSrc *)p->cmd.d; a.dst = (const CpRunDst *)(p->cmd.d + ns * sizeof(CpRunSrc));
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     hipLaunchKernelGGL(compose_tiles, dim3((unsigned)L.n_tiles), dim3(CP_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     if (dhost)
         for (int i = 0; i < no; ++i) {
             if (!dst || !dst[i]) continue;
@@ -668,7 +663,7 @@ int rtmodt_compose_run(rtmodt_compose *p, const uint8_t *const *src, const int32
                                         (size_t)planes[i].rowbytes[k], (size_t)planes[i].rows[k], hipMemcpyDeviceToHost, q));
         }
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -683,10 +678,7 @@ int rtmodt_compose_output(rtmodt_compose *p, int i, uint8_t **dev_ptr, size_t *p
 
 int rtmodt_compose_last_ms(rtmodt_compose *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no run has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no run has launched yet");
 }
 
 int rtmodt_compose_plan(const rtmodt_compose_src_desc *sources, int n_sources, const rtmodt_compose_out_desc *outputs, int n_outputs,

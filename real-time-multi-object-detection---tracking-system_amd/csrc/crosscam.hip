@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "handle_host.h"
 #include "track_layout.h"
 #include "lap.h"
 
@@ -550,13 +551,12 @@ __global__ __launch_bounds__(CC_THREADS) void cc_ledger(CcArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_crosscam {
+struct rtmodt_crosscam : HandleBase {
     rtmodt_crosscam_cfg cfg{};
-    int device = 0, cur = 0;
+    int cur = 0;
     long long calls = 0;
-    hipStream_t stream = nullptr, last_stream = nullptr;
-    hipEvent_t ev[2] = {};
-    bool timed = false;
+    hipStream_t last_stream = nullptr;            // the stream of the most recent call (a tracker's, or the own one)
+    EventTimer<2> timer;
     char *pool = nullptr;
     CcArgs a{};                                   // every device pointer; to / tn and lo / ln are set per call from tab / led
     CcTab tab[2]; CcLed led[2];
@@ -626,7 +626,7 @@ int cc_run(rtmodt_crosscam *z, hipStream_t q, bool stage, const rtmodt_crosscam_
     static DynLdsSeen seen_m, seen_l;
     RT_TRY(raise_dynamic_lds((const void *)cc_match, sm_match, seen_m));
     RT_TRY(raise_dynamic_lds((const void *)cc_ledger, sm_led, seen_l));
-    RT_HIP(hipEventRecord(z->ev[0], q));
+    RT_TRY(z->timer.record(0, q));
     RT_HIP(hipMemsetAsync(a.sight, 0, (size_t)I * S * 4, q));
     if (stage) hipLaunchKernelGGL(cc_stage, dim3(S), dim3(CC_THREADS), 0, q, a);
     hipLaunchKernelGGL(cc_retire, dim3(1), dim3(TRK_THREADS), 0, q, a);
@@ -640,8 +640,8 @@ int cc_run(rtmodt_crosscam *z, hipStream_t q, bool stage, const rtmodt_crosscam_
     hipLaunchKernelGGL(cc_update, dim3(cdiv(I, CC_WAVES)), dim3(CC_THREADS), 0, q, a);
     hipLaunchKernelGGL(cc_ledger, dim3(S), dim3(CC_THREADS), sm_led, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(z->ev[1], q));
-    z->timed = true;
+    RT_TRY(z->timer.record(1, q));
+    z->timer.timed = true;
     z->last_stream = q;
     z->calls += 1;
     z->cur ^= 1;
@@ -697,13 +697,11 @@ void rtmodt_crosscam_default_cfg(rtmodt_crosscam_cfg *c) {
 
 void rtmodt_crosscam_destroy(rtmodt_crosscam *z) {
     if (!z) return;
-    hipSetDevice(z->device);
-    if (z->stream) hipStreamSynchronize(z->stream);
-    if (z->last_stream && z->last_stream != z->stream) hipStreamSynchronize(z->last_stream);
-    for (auto &e : z->ev) if (e) hipEventDestroy(e);
-    hipFree(z->pool);
-    hipHostFree(z->h_pin);
-    if (z->stream) hipStreamDestroy(z->stream);
+    handle_close(z, [&] {
+        z->timer.destroy();
+        hipFree(z->pool);
+        hipHostFree(z->h_pin);
+    }, z->last_stream);
     delete z;
 }
 
@@ -716,35 +714,26 @@ int rtmodt_crosscam_create(const rtmodt_crosscam_cfg *cfg, rtmodt_crosscam **out
     z->cfg = c; z->device = c.device;
     const int S = c.n_streams;
     z->tmin.assign((size_t)S * S, 0); z->tmax.assign((size_t)S * S, c.max_age);
+    const int64_t st[2] = {0, 1};
     auto body = [&]() -> int {
         RT_CHECK(cc_match_smem(c.max_identities) <= 150 * 1024, RTMODT_E_INVALID, "crosscam: max_identities %d needs %zu B of LDS", c.max_identities,
                  cc_match_smem(c.max_identities));
-        RT_HIP(hipSetDevice(z->device));
-        RT_HIP(hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking));
-        for (auto &e : z->ev) RT_HIP(hipEventCreate(&e));
+        RT_TRY(handle_open(z));
+        RT_TRY(z->timer.create());
         const size_t total = cc_carve(z, nullptr);
         RT_HIP(hipMalloc((void **)&z->pool, total));
-        RT_HIP(hipMemset(z->pool, 0, total));
+        RT_HIP(handle_zero(z->pool, total, z->stream));
         cc_carve(z, z->pool);
         RT_HIP(hipHostMalloc((void **)&z->h_pin, z->o_bytes, hipHostMallocDefault));
-        const int64_t st[2] = {0, 1};
-        RT_HIP(hipMemcpy(z->a.state, st, sizeof(st), hipMemcpyHostToDevice));
-        RT_HIP(hipMemcpy(z->d_tmin, z->tmin.data(), z->tmin.size() * 4, hipMemcpyHostToDevice));
-        RT_HIP(hipMemcpy(z->d_tmax, z->tmax.data(), z->tmax.size() * 4, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpyAsync(z->a.state, st, sizeof(st), hipMemcpyHostToDevice, z->stream));              // (these three behind the zeroing of the pool)
+        RT_HIP(hipMemcpyAsync(z->d_tmin, z->tmin.data(), z->tmin.size() * 4, hipMemcpyHostToDevice, z->stream));
+        RT_HIP(hipMemcpyAsync(z->d_tmax, z->tmax.data(), z->tmax.size() * 4, hipMemcpyHostToDevice, z->stream));
         CcArgs &a = z->a;
         a.S = S; a.D = c.dim; a.Mc = c.max_tracks; a.I = c.max_identities; a.Q = c.max_queries; a.min_sim = c.min_sim_milli; a.max_age = c.max_age;
         a.bind_age = c.bind_age; a.match_class = c.match_class != 0; a.tmin = z->d_tmin; a.tmax = z->d_tmax;
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_crosscam_destroy(z);
-        last_error() = keep;
-        return rc;
-    }
-    *out = z;
-    return RTMODT_OK;
+    return handle_created(body(), z, rtmodt_crosscam_destroy, out);
 }
 
 int rtmodt_crosscam_set_transit(rtmodt_crosscam *z, int src, int dst, int min_calls, int max_calls) {
@@ -901,7 +890,8 @@ int rtmodt_crosscam_load(rtmodt_crosscam *z, const int64_t *header, const int64_
     }
     const int64_t st[2] = {n64, next};
     RT_HIP(hipMemcpy(z->a.state, st, sizeof(st), hipMemcpyHostToDevice));
-    RT_HIP(hipMemset(z->a.err, 0, S * 4));
+    RT_HIP(handle_zero(z->a.err, S * 4, z->stream));
+    RT_TRY(handle_wait(z->stream));
     z->calls = calls;
     return RTMODT_OK;
 }
@@ -916,17 +906,13 @@ int rtmodt_crosscam_errors(rtmodt_crosscam *z, int32_t *err) {
 int rtmodt_crosscam_clear_errors(rtmodt_crosscam *z) {
     RT_CHECK(z, RTMODT_E_INVALID, "bad argument");
     RT_TRY(cc_sync(z));
-    RT_HIP(hipMemset(z->a.err, 0, (size_t)z->cfg.n_streams * 4));
-    return RTMODT_OK;
+    RT_HIP(handle_zero(z->a.err, (size_t)z->cfg.n_streams * 4, z->stream));
+    return handle_wait(z->stream);
 }
 
 int rtmodt_crosscam_last_ms(rtmodt_crosscam *z, float *ms) {
     RT_CHECK(z && ms, RTMODT_E_INVALID, "bad argument");
-    RT_CHECK(z->timed, RTMODT_E_INVALID, "crosscam: no call yet");
-    RT_HIP(hipSetDevice(z->device));
-    RT_HIP(hipEventSynchronize(z->ev[1]));
-    RT_HIP(hipEventElapsedTime(ms, z->ev[0], z->ev[1]));
-    return RTMODT_OK;
+    return z->timer.elapsed(z->device, 0, 1, ms, "crosscam: no call yet");
 }
 
 int rtmodt_crosscam_similarity(int device, const int8_t *q, int nq, const int8_t *t, int nt, int dim, int32_t *dots, int32_t *sim) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "handle_host.h"
 #include "polygon.h"
 #include "track_layout.h"
 
@@ -282,10 +283,9 @@ __global__ __launch_bounds__(CR_THREADS) void crossing_update(CrossArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_crossing {
-    int device = 0, S = 1, Mc = 0, cap = 0, L = 0, G = 0, C = 0, n_pts = 0, max_events = 0;
+struct rtmodt_crossing : HandleBase {
+    int S = 1, Mc = 0, cap = 0, L = 0, G = 0, C = 0, n_pts = 0, max_events = 0;
     int64_t max_gap = 0;
-    hipStream_t stream = nullptr;
     char *pool = nullptr;                 // every device array below lives in this one allocation
     CrossTable tb{};
     CrossLedger *d_ledgers = nullptr;
@@ -419,11 +419,7 @@ extern "C" {
 
 void rtmodt_crossing_destroy(rtmodt_crossing *z) {
     if (!z) return;
-    hipSetDevice(z->device);
-    if (z->stream) hipStreamSynchronize(z->stream);
-    hipFree(z->pool);
-    hipHostFree(z->h_pin);
-    if (z->stream) hipStreamDestroy(z->stream);
+    handle_close(z, [&] { hipFree(z->pool); hipHostFree(z->h_pin); });
     delete z;
 }
 
@@ -465,29 +461,20 @@ int rtmodt_crossing_create(int device, const rtmodt_line_cfg *lines, int n_lines
     z->n_pts = (int)pts.size(); z->max_events = max_events; z->max_gap = max_gap_frames;
     auto body = [&]() -> int {
         RT_CHECK(cr_smem(z) <= 150 * 1024, RTMODT_E_INVALID, "crossing: capacity %d needs %zu B of LDS", z->cap, cr_smem(z));
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking));
+        RT_TRY(handle_open(z));
         const size_t total = cr_carve(z, nullptr);
         RT_HIP(hipMalloc((void **)&z->pool, total));
-        RT_HIP(hipMemset(z->pool, 0, total));
+        RT_HIP(handle_zero(z->pool, total, z->stream));             // (the copies below go behind it, on the same stream)
         cr_carve(z, z->pool);
         RT_HIP(hipHostMalloc((void **)&z->h_pin, z->ev_bytes + sizeof(int64_t) * 4 * z->S, hipHostMallocDefault));
-        if (!ln.empty()) RT_HIP(hipMemcpy((void *)z->tb.line, ln.data(), ln.size() * sizeof(int4), hipMemcpyHostToDevice));
-        if (!dir.empty()) RT_HIP(hipMemcpy((void *)z->tb.dir, dir.data(), dir.size() * 4, hipMemcpyHostToDevice));
-        if (!pts.empty()) RT_HIP(hipMemcpy((void *)z->tb.pts, pts.data(), pts.size() * sizeof(int2), hipMemcpyHostToDevice));
-        RT_HIP(hipMemcpy((void *)z->tb.off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-        RT_HIP(hipMemcpy(z->d_ledgers, z->h_ledgers.data(), sizeof(CrossLedger) * z->S, hipMemcpyHostToDevice));
+        if (!ln.empty()) RT_HIP(hipMemcpyAsync((void *)z->tb.line, ln.data(), ln.size() * sizeof(int4), hipMemcpyHostToDevice, z->stream));
+        if (!dir.empty()) RT_HIP(hipMemcpyAsync((void *)z->tb.dir, dir.data(), dir.size() * 4, hipMemcpyHostToDevice, z->stream));
+        if (!pts.empty()) RT_HIP(hipMemcpyAsync((void *)z->tb.pts, pts.data(), pts.size() * sizeof(int2), hipMemcpyHostToDevice, z->stream));
+        RT_HIP(hipMemcpyAsync((void *)z->tb.off, off.data(), off.size() * 4, hipMemcpyHostToDevice, z->stream));
+        RT_HIP(hipMemcpyAsync(z->d_ledgers, z->h_ledgers.data(), sizeof(CrossLedger) * z->S, hipMemcpyHostToDevice, z->stream));
         return RTMODT_OK;
     };
-    int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_crossing_destroy(z);
-        last_error() = keep;
-        return rc;
-    }
-    *out = z;
-    return RTMODT_OK;
+    return handle_created(body(), z, rtmodt_crossing_destroy, out);
 }
 
 int rtmodt_crossing_process(rtmodt_crossing *z, int stream, const int64_t *track_ids, const float *xyxy, const int32_t *cls, int n, int64_t frame_id,
@@ -542,8 +529,8 @@ int rtmodt_crossing_counts(rtmodt_crossing *z, int stream, int64_t *line_total, 
 int rtmodt_crossing_reset_counts(rtmodt_crossing *z) {
     RT_CHECK(z, RTMODT_E_INVALID, "null argument");
     RT_TRY(cr_sync_own(z));
-    if (z->counts_stride) RT_HIP(hipMemset(z->d_counts, 0, (size_t)z->S * z->counts_stride * 8));
-    return RTMODT_OK;
+    if (z->counts_stride) RT_HIP(handle_zero(z->d_counts, (size_t)z->S * z->counts_stride * 8, z->stream));
+    return handle_wait(z->stream);
 }
 
 int rtmodt_crossing_state(rtmodt_crossing *z, int stream, int64_t *ids, int64_t *last_frame, int32_t *prev_xy, uint32_t *side_pos, uint32_t *side_neg,

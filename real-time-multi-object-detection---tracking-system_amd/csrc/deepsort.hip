@@ -265,8 +265,8 @@ static int launch_deepsort_update(const DsArgs &a, int n_streams, hipStream_t s)
 using namespace rtmodt;
 
 struct rtmodt_deepsort : TrackHandleBase {
-    hipEvent_t ev[4] = {};                   // describe | distance | update boundaries of the last call
-    bool timed = false, described = false;
+    EventTimer<4> timer;                   // describe | distance | update boundaries of the last call
+    bool described = false;
     int budget = 0, dim = APP_DIM;
     float min_conf = 0.3f; double max_dist = 0.2, max_iou = 0.7; long long thr = 0; int max_age = 70, n_init = 3;
     char *pool = nullptr; int8_t *gallery = nullptr;      // pool: all state arrays (track_layout.h: carve_deepsort)
@@ -293,27 +293,27 @@ int deepsort_gallery_view(rtmodt_deepsort *t, const int8_t **gallery, int *dim, 
 
 static int ds_create_impl(rtmodt_deepsort *t) {
     RT_TRY(track_open(t));
-    for (auto &e : t->ev) RT_HIP(hipEventCreate(&e));
+    RT_TRY(t->timer.create());
     t->h_states.assign(t->S, DsState{});
     const size_t total = carve_deepsort(t->h_states.data(), t->S, t->Mc, nullptr);
     RT_HIP(hipMalloc((void **)&t->pool, total));
-    RT_HIP(hipMemset(t->pool, 0, total));
+    RT_HIP(handle_zero(t->pool, total, t->stream));
     carve_deepsort(t->h_states.data(), t->S, t->Mc, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(DsState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(DsState) * t->S, hipMemcpyHostToDevice));
     RT_HIP(hipMalloc((void **)&t->gallery, ds_gallery_stream_bytes(t) * t->S));
-    RT_HIP(hipMemset(t->gallery, 0, ds_gallery_stream_bytes(t) * t->S));
+    RT_HIP(handle_zero(t->gallery, ds_gallery_stream_bytes(t) * t->S, t->stream));
     const size_t SN = (size_t)t->S * t->Nc;
-    RT_HIP(hipMalloc((void **)&t->d_desc, SN * t->dim)); RT_HIP(hipMemset(t->d_desc, 0, SN * t->dim));
+    RT_HIP(hipMalloc((void **)&t->d_desc, SN * t->dim)); RT_HIP(handle_zero(t->d_desc, SN * t->dim, t->stream));
     RT_HIP(hipMalloc((void **)&t->d_counts, SN * APP_DIM * 4));
     RT_HIP(hipMalloc((void **)&t->d_dotmax, (size_t)t->S * t->Mc * t->Nc * 4));
-    RT_HIP(hipMemset(t->d_dotmax, 0, (size_t)t->S * t->Mc * t->Nc * 4));
+    RT_HIP(handle_zero(t->d_dotmax, (size_t)t->S * t->Mc * t->Nc * 4, t->stream));
     return RTMODT_OK;
 }
 
 // the launches of one call on stream q, detections described by `a`'s det_* fields for streams [0, count)
 static int ds_run(rtmodt_deepsort *t, DsArgs a, int count, const AppFrames *frames, int fh, int fw, int pitch, hipStream_t q) {
-    RT_HIP(hipEventRecord(t->ev[0], q));
+    RT_TRY(t->timer.record(0, q));
     t->described = frames != nullptr;
     if (frames && t->reid) {
         RT_TRY(reid_run(t->reid, *frames, count, fh, fw, pitch, a.det_box, a.det_n, a.det_stride, std::min(a.det_stride, t->Nc), t->d_desc, t->Nc, q));
@@ -324,16 +324,16 @@ static int ds_run(rtmodt_deepsort *t, DsArgs a, int count, const AppFrames *fram
         d.counts = t->d_counts; d.desc = t->d_desc; d.desc_stride = t->Nc;
         RT_TRY(launch_describe(d, count, q));
     }
-    RT_HIP(hipEventRecord(t->ev[1], q));
+    RT_TRY(t->timer.record(1, q));
     DotmaxArgs m{};
     m.gallery = t->gallery; m.gallery_stream_stride = ds_gallery_stream_bytes(t); m.states = t->d_states; m.meta = t->d_meta;
     m.budget = t->budget; m.dim = t->dim; m.dets = t->d_desc; m.det_stride = t->Nc; m.n_dets_dev = a.det_n; m.max_dets = std::min(a.det_stride, t->Nc);
     m.out = t->d_dotmax; m.out_stream_stride = (size_t)t->Mc * t->Nc; m.out_row_stride = t->Nc;
     RT_TRY(launch_dotmax(m, t->Mc, m.max_dets, count, q));
-    RT_HIP(hipEventRecord(t->ev[2], q));
+    RT_TRY(t->timer.record(2, q));
     RT_TRY(launch_deepsort_update(a, count, q));
-    RT_HIP(hipEventRecord(t->ev[3], q));
-    t->timed = true;
+    RT_TRY(t->timer.record(3, q));
+    t->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -364,7 +364,7 @@ extern "C" {
 void rtmodt_deepsort_destroy(rtmodt_deepsort *t) {
     if (!t) return;
     track_close(t, [t] {
-        for (auto &e : t->ev) if (e) hipEventDestroy(e);
+        t->timer.destroy();
         hipFree(t->pool); hipFree(t->gallery); hipFree(t->d_states); hipFree(t->d_desc); hipFree(t->d_counts); hipFree(t->d_dotmax);
         t->stage.release();
         reid_close(t->reid);
@@ -397,13 +397,14 @@ int rtmodt_deepsort_create(const rtmodt_deepsort_cfg *cfg, rtmodt_deepsort **out
     t->thr = (long long)std::floor(cfg->max_dist * 16129.0);
     int rc = net ? reid_open(cfg->embedder, cfg->device, cfg->n_streams, cfg->max_dets, false, &t->reid) : RTMODT_OK;     // the file is checked before the device is touched
     if (rc == RTMODT_OK) rc = ds_create_impl(t);
-    return track_created(rc, t, rtmodt_deepsort_destroy, out);
+    return handle_created(rc, t, rtmodt_deepsort_destroy, out);
 }
 
 int rtmodt_deepsort_reset(rtmodt_deepsort *t, int stream) {
     RT_TRY(track_reset_meta(t, stream));
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->S : stream + 1;
-    for (int s = s0; s < s1; ++s) RT_HIP(hipMemset(t->h_states[s].slot_used, 0, (size_t)t->Mc * 4));
+    for (int s = s0; s < s1; ++s) RT_HIP(handle_zero(t->h_states[s].slot_used, (size_t)t->Mc * 4, t->stream));
+    RT_TRY(handle_wait(t->stream));
     return RTMODT_OK;
 }
 
@@ -498,13 +499,10 @@ int rtmodt_deepsort_state(rtmodt_deepsort *t, int stream, int64_t *ids, int32_t 
 
 int rtmodt_deepsort_last_ms(rtmodt_deepsort *t, float *describe_ms, float *distance_ms, float *update_ms) {
     RT_CHECK(t, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(t->timed, RTMODT_E_INVALID, "no update has run yet");
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipEventSynchronize(t->ev[3]));
     float a = 0, b = 0, c = 0;
-    RT_HIP(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
-    RT_HIP(hipEventElapsedTime(&b, t->ev[1], t->ev[2]));
-    RT_HIP(hipEventElapsedTime(&c, t->ev[2], t->ev[3]));
+    RT_TRY(t->timer.elapsed(t->device, 2, 3, &c, "no update has run yet"));      // (the last event first: it waits for the call)
+    RT_TRY(t->timer.elapsed(t->device, 0, 1, &a, "no update has run yet"));
+    RT_TRY(t->timer.elapsed(t->device, 1, 2, &b, "no update has run yet"));
     if (describe_ms) *describe_ms = t->described ? a : 0.f;
     if (distance_ms) *distance_ms = b;
     if (update_ms) *update_ms = c;

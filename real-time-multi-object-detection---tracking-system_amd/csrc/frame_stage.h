@@ -84,6 +84,22 @@ inline int check_frames(const uint8_t *const *frames, int n, int h, int w, int s
     return check_frame_ptrs(frames, n);
 }
 
+// A gather cannot work in place (lens, stab): no destination range of a call may meet a source range of it.  Sources of sh x sw at
+// src_stride, destinations of dh x dw at dst_stride.
+inline int check_not_in_place(const uint8_t *const *src, int sh, int sw, int src_stride, uint8_t *const *dst, int dh, int dw, int dst_stride, int n) {
+    const size_t sspan = (size_t)(sh - 1) * (size_t)src_stride + (size_t)3 * sw, dspan = (size_t)(dh - 1) * (size_t)dst_stride + (size_t)3 * dw;
+    std::vector<uintptr_t> starts(n);
+    for (int i = 0; i < n; ++i) starts[i] = (uintptr_t)src[i];
+    std::sort(starts.begin(), starts.end());
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t a = (uintptr_t)dst[i], b = a + dspan;
+        // the source with the largest start below b; all spans are equal, so it is the one that reaches furthest
+        const auto it = std::lower_bound(starts.begin(), starts.end(), b);
+        RT_CHECK(it == starts.begin() || *(it - 1) + sspan <= a, RTMODT_E_INVALID, "destination frame %d overlaps a source frame of the call", i);
+    }
+    return RTMODT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- staging
 // Where host frames stand on the device.  Device frames are never staged: the kernels get the caller's pointers and pitch.
 enum FrameLayout {

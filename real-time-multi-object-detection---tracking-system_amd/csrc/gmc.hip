@@ -440,12 +440,12 @@ __global__ __launch_bounds__(GMC_FIT_THREADS) void gmc_fit(GmcArgs a) {
 
 using namespace rtmodt;
 
-struct rtmodt_gmc {
-    int device = 0, S = 1;
+struct rtmodt_gmc : HandleBase {
+    int S = 1;
     rtmodt_gmc_cfg cfg = {};
-    hipStream_t stream = nullptr;
-    hipEvent_t foreign_done = nullptr, own_done = nullptr, ev[2] = {};
-    bool foreign_pending = false, timed = false;
+    hipEvent_t foreign_done = nullptr, own_done = nullptr;
+    EventTimer<2> timer;
+    bool foreign_pending = false;
     int gh = 0, gw = 0;                                      // the geometry the buffers are carved for (0: none yet)
     int W0 = 0, H0 = 0, W1 = 0, H1 = 0, BX = 0, BY = 0, nb = 0;
     size_t l0_bytes = 0, l1_bytes = 0;
@@ -498,9 +498,10 @@ static int gmc_set_geometry(rtmodt_gmc *g, int h, int w) {
     const size_t S = (size_t)g->S, nb = (size_t)g->nb;
     RT_HIP(hipMalloc((void **)&g->d_l0, S * 2 * g->l0_bytes));
     RT_HIP(hipMalloc((void **)&g->d_l1, S * 2 * g->l1_bytes));
-    RT_HIP(hipMalloc((void **)&g->d_blk, S * 6 * nb * 4)); RT_HIP(hipMemset(g->d_blk, 0, S * 6 * nb * 4));
-    RT_HIP(hipMalloc((void **)&g->d_order, S * nb * 4)); RT_HIP(hipMemset(g->d_order, 0, S * nb * 4));
-    RT_HIP(hipMalloc((void **)&g->d_inl, S * 2 * nb)); RT_HIP(hipMemset(g->d_inl, 0, S * 2 * nb));
+    RT_HIP(hipMalloc((void **)&g->d_blk, S * 6 * nb * 4)); RT_HIP(handle_zero(g->d_blk, S * 6 * nb * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_order, S * nb * 4)); RT_HIP(handle_zero(g->d_order, S * nb * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_inl, S * 2 * nb)); RT_HIP(handle_zero(g->d_inl, S * 2 * nb, g->stream));
+    RT_TRY(handle_wait(g->stream));                        // (the estimate that follows may run on a detector's stream)
     g->gh = h; g->gw = w;
     return RTMODT_OK;
 }
@@ -532,7 +533,7 @@ static int gmc_run(rtmodt_gmc *g, const AppFrames &fp, int count, int h, int w, 
     a.mbox = mbox; a.mconf = mconf; a.mn = mn; a.mstride = mstride; a.mmax = GMC_MAX_BOXES;
     a.order = g->d_order; a.nvalid = g->d_nvalid; a.scores = g->d_scores; a.bestk = g->d_bestk; a.inl = g->d_inl; a.sums = g->d_sums; a.model = g->d_model;
     a.warp = g->d_warp; a.status = g->d_status;
-    RT_HIP(hipEventRecord(g->ev[0], q));
+    RT_TRY(g->timer.record(0, q));
     hipLaunchKernelGGL(gmc_luma_l0, dim3(cdiv(a.W0 * a.H0, 256), count), dim3(256), 0, q, a);
     hipLaunchKernelGGL(gmc_l1, dim3(cdiv(a.W1 * a.H1, 256), count), dim3(256), 0, q, a);
     hipLaunchKernelGGL(gmc_coarse_sad, dim3(cdiv(a.H1 - 2 * a.cs, GMC_ROWS), count), dim3(256), 0, q, a);
@@ -540,8 +541,8 @@ static int gmc_run(rtmodt_gmc *g, const AppFrames &fp, int count, int h, int w, 
     hipLaunchKernelGGL(gmc_blocks, dim3(cdiv(a.nb, 4), count), dim3(256), 0, q, a);
     hipLaunchKernelGGL(gmc_fit, dim3(count), dim3(GMC_FIT_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(g->ev[1], q));
-    g->timed = true;
+    RT_TRY(g->timer.record(1, q));
+    g->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -622,32 +623,31 @@ void rtmodt_gmc_destroy(rtmodt_gmc *g) {
     if (!g) return;
     hipSetDevice(g->device);
     if (g->foreign_done) hipEventSynchronize(g->foreign_done);
-    if (g->stream) hipStreamSynchronize(g->stream);
-    if (g->foreign_done) hipEventDestroy(g->foreign_done);
-    if (g->own_done) hipEventDestroy(g->own_done);
-    for (auto &e : g->ev) if (e) hipEventDestroy(e);
-    gmc_free_geometry(g);
-    hipFree(g->d_table); hipFree(g->d_coarse); hipFree(g->d_nvalid); hipFree(g->d_scores); hipFree(g->d_bestk); hipFree(g->d_sums); hipFree(g->d_model);
-    hipFree(g->d_warp); hipFree(g->d_status); hipFree(g->d_mbox); hipFree(g->d_mconf); hipFree(g->d_mn); g->stage.release();
-    hipHostFree(g->h_warp); hipHostFree(g->h_status); hipHostFree(g->h_mn);
-    if (g->stream) hipStreamDestroy(g->stream);
+    handle_close(g, [&] {
+        if (g->foreign_done) hipEventDestroy(g->foreign_done);
+        if (g->own_done) hipEventDestroy(g->own_done);
+        g->timer.destroy();
+        gmc_free_geometry(g);
+        hipFree(g->d_table); hipFree(g->d_coarse); hipFree(g->d_nvalid); hipFree(g->d_scores); hipFree(g->d_bestk); hipFree(g->d_sums); hipFree(g->d_model);
+        hipFree(g->d_warp); hipFree(g->d_status); hipFree(g->d_mbox); hipFree(g->d_mconf); hipFree(g->d_mn); g->stage.release();
+        hipHostFree(g->h_warp); hipHostFree(g->h_status); hipHostFree(g->h_mn);
+    });
     delete g;
 }
 
 static int gmc_create_impl(rtmodt_gmc *g) {
-    RT_HIP(hipSetDevice(g->device));
-    RT_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    RT_TRY(handle_open(g));
     RT_HIP(hipEventCreateWithFlags(&g->foreign_done, hipEventDisableTiming));
     RT_HIP(hipEventCreateWithFlags(&g->own_done, hipEventDisableTiming));
-    for (auto &e : g->ev) RT_HIP(hipEventCreate(&e));
+    RT_TRY(g->timer.create());
     const size_t S = (size_t)g->S, MB = (size_t)std::max(g->cfg.max_boxes, 1);
-    RT_HIP(hipMalloc((void **)&g->d_table, S * GMC_TABLE * 4)); RT_HIP(hipMemset(g->d_table, 0, S * GMC_TABLE * 4));
-    RT_HIP(hipMalloc((void **)&g->d_coarse, S * 8)); RT_HIP(hipMemset(g->d_coarse, 0, S * 8));
-    RT_HIP(hipMalloc((void **)&g->d_nvalid, S * 4)); RT_HIP(hipMemset(g->d_nvalid, 0, S * 4));
-    RT_HIP(hipMalloc((void **)&g->d_scores, S * GMC_MAX_HYP * 4)); RT_HIP(hipMemset(g->d_scores, 0xff, S * GMC_MAX_HYP * 4));
-    RT_HIP(hipMalloc((void **)&g->d_bestk, S * 4)); RT_HIP(hipMemset(g->d_bestk, 0xff, S * 4));
-    RT_HIP(hipMalloc((void **)&g->d_sums, S * 16 * 8)); RT_HIP(hipMemset(g->d_sums, 0, S * 16 * 8));
-    RT_HIP(hipMalloc((void **)&g->d_model, S * 12 * 8)); RT_HIP(hipMemset(g->d_model, 0, S * 12 * 8));
+    RT_HIP(hipMalloc((void **)&g->d_table, S * GMC_TABLE * 4)); RT_HIP(handle_zero(g->d_table, S * GMC_TABLE * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_coarse, S * 8)); RT_HIP(handle_zero(g->d_coarse, S * 8, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_nvalid, S * 4)); RT_HIP(handle_zero(g->d_nvalid, S * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_scores, S * GMC_MAX_HYP * 4)); RT_HIP(handle_fill(g->d_scores, 0xff, S * GMC_MAX_HYP * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_bestk, S * 4)); RT_HIP(handle_fill(g->d_bestk, 0xff, S * 4, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_sums, S * 16 * 8)); RT_HIP(handle_zero(g->d_sums, S * 16 * 8, g->stream));
+    RT_HIP(hipMalloc((void **)&g->d_model, S * 12 * 8)); RT_HIP(handle_zero(g->d_model, S * 12 * 8, g->stream));
     RT_HIP(hipMalloc((void **)&g->d_warp, S * 6 * 4)); RT_HIP(hipMalloc((void **)&g->d_status, S * 4));
     RT_HIP(hipHostMalloc((void **)&g->h_warp, S * 6 * 4, hipHostMallocDefault)); RT_HIP(hipHostMalloc((void **)&g->h_status, S * 4, hipHostMallocDefault));
     RT_HIP(hipHostMalloc((void **)&g->h_mn, S * 4, hipHostMallocDefault));
@@ -659,7 +659,7 @@ static int gmc_create_impl(rtmodt_gmc *g) {
     RT_HIP(hipMemcpy(g->d_warp, g->h_warp, S * 6 * 4, hipMemcpyHostToDevice));
     RT_HIP(hipMemcpy(g->d_status, g->h_status, S * 4, hipMemcpyHostToDevice));
     RT_HIP(hipMalloc((void **)&g->d_mbox, S * MB * 16)); RT_HIP(hipMalloc((void **)&g->d_mconf, S * MB * 4));
-    RT_HIP(hipMalloc((void **)&g->d_mn, S * 4)); RT_HIP(hipMemset(g->d_mn, 0, S * 4));
+    RT_HIP(hipMalloc((void **)&g->d_mn, S * 4)); RT_HIP(handle_zero(g->d_mn, S * 4, g->stream));
     return RTMODT_OK;
 }
 
@@ -679,7 +679,7 @@ int rtmodt_gmc_create(const rtmodt_gmc_cfg *cfg, rtmodt_gmc **out) {
              cfg->max_boxes, GMC_MAX_STREAMS, GMC_MAX_BOXES);
     rtmodt_gmc *g = new rtmodt_gmc();
     g->cfg = *cfg; g->device = cfg->device; g->S = cfg->n_streams;
-    return track_created(gmc_create_impl(g), g, rtmodt_gmc_destroy, out);
+    return handle_created(gmc_create_impl(g), g, rtmodt_gmc_destroy, out);
 }
 
 int rtmodt_gmc_reset(rtmodt_gmc *g, int stream) {
@@ -767,11 +767,7 @@ int rtmodt_gmc_debug(rtmodt_gmc *g, int stream, uint8_t *l0, uint8_t *l1, int32_
 
 int rtmodt_gmc_last_ms(rtmodt_gmc *g, float *estimate_ms) {
     RT_CHECK(g && estimate_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(g->timed, RTMODT_E_INVALID, "no estimate has run yet");
-    RT_HIP(hipSetDevice(g->device));
-    RT_HIP(hipEventSynchronize(g->ev[1]));
-    RT_HIP(hipEventElapsedTime(estimate_ms, g->ev[0], g->ev[1]));
-    return RTMODT_OK;
+    return g->timer.elapsed(g->device, 0, 1, estimate_ms, "no estimate has run yet");
 }
 
 }  // extern "C"

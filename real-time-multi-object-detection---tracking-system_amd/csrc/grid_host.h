@@ -1,12 +1,14 @@
 // grid_host.h -- the host plumbing of the modules that read frames into the luma grid of cell_grid.h (motion.hip, leftobj.hip,
 // health.hip): the grid of a handle and the launch grids over it, the checks of a config's grid and of a call's stream list with
 // their messages, the test for the reader's dword path, and the one launcher of a <SCALE, WIDE> kernel.  Host code only.  What a
-// handle holds on the device differs between the modules and stays with them.
+// handle holds on the device differs between the modules and stays with them; its frame (open, zeroing, create tail, close) is
+// handle_host.h's, like every other handle's.
 #pragma once
 
 #include <vector>
 
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "cell_grid.h"
 
 namespace rtmodt {
@@ -43,11 +45,6 @@ inline int check_grid_cells(int streams, int height, int width, int scale, long 
     RT_CHECK(cells * streams <= max_total_cells, RTMODT_E_CAPACITY, "%lld cells in all (at most %lld)", cells * streams, max_total_cells);
     return RTMODT_OK;
 }
-
-// Zeroes a buffer of a new handle on the handle's own stream q; create synchronizes q once after the last of them.  hipMemset would
-// return before the device has written, on the null stream, which does not order a hipStreamNonBlocking stream: a load_state (a
-// copy on q) directly after create could then be zeroed again behind its back.
-inline hipError_t grid_zero(void *d, size_t bytes, hipStream_t q) { return hipMemsetAsync(d, 0, bytes, q); }
 
 inline int check_stream(int stream, int S) {
     RT_CHECK(stream >= 0 && stream < S, RTMODT_E_INVALID, "stream %d outside 0..%d", stream, S - 1);

@@ -203,13 +203,10 @@ __global__ __launch_bounds__(HL_THREADS) void health_learn(HlArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_health {
-    int device = 0;
+struct rtmodt_health : HandleBase {
     rtmodt_health_cfg cfg{};
     GridGeom g;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     uint16_t *d_r = nullptr;
     uint8_t *d_y = nullptr, *d_g = nullptr;
     HlState *d_state = nullptr;
@@ -277,14 +274,12 @@ void rtmodt_health_default_cfg(rtmodt_health_cfg *cfg) {
 
 void rtmodt_health_destroy(rtmodt_health *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_r); hipFree(p->d_y); hipFree(p->d_g); hipFree(p->d_state); hipFree(p->d_out);
-    hipHostFree(p->h_out);
-    p->cmd.release(); p->stage.release();
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_r); hipFree(p->d_y); hipFree(p->d_g); hipFree(p->d_state); hipFree(p->d_out);
+        hipHostFree(p->h_out);
+        p->cmd.release(); p->stage.release();
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -297,10 +292,8 @@ int rtmodt_health_create(const rtmodt_health_cfg *cfg, rtmodt_health **out) {
     p->g.set(cfg->height, cfg->width, cfg->scale);
     auto body = [&]() -> int {
         const size_t S = (size_t)cfg->streams, all = S * (size_t)p->g.cells;
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_r, all * sizeof(uint16_t)));
         RT_HIP(hipMalloc((void **)&p->d_y, all));
         RT_HIP(hipMalloc((void **)&p->d_g, all));
@@ -308,22 +301,13 @@ int rtmodt_health_create(const rtmodt_health_cfg *cfg, rtmodt_health **out) {
         p->out_bytes = S * (sizeof(HlWork) + sizeof(rtmodt_health_result) + HL_MAX_EVENTS * sizeof(rtmodt_health_event));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, p->out_bytes, hipHostMallocDefault));
-        RT_HIP(grid_zero(p->d_r, all * sizeof(uint16_t), p->stream));
-        RT_HIP(grid_zero(p->d_y, all, p->stream));
-        RT_HIP(grid_zero(p->d_g, all, p->stream));
-        RT_HIP(grid_zero(p->d_state, S * sizeof(HlState), p->stream));
-        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
+        RT_HIP(handle_zero(p->d_r, all * sizeof(uint16_t), p->stream));
+        RT_HIP(handle_zero(p->d_y, all, p->stream));
+        RT_HIP(handle_zero(p->d_g, all, p->stream));
+        RT_HIP(handle_zero(p->d_state, S * sizeof(HlState), p->stream));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_health_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_health_destroy, out);
 }
 
 int rtmodt_health_decide(const rtmodt_health_cfg *cfg, int64_t cells, int64_t frame_id, rtmodt_health_result *row, rtmodt_health_state *state,
@@ -356,7 +340,7 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
     RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     const int S = p->cfg.streams;
     RT_TRY(check_stream_list(frames, streams, n, S));
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
@@ -381,7 +365,7 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
 
     const dim3 block(HL_THREADS);
     const GridGeom &g = p->g;
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, off_res + res_bytes + ev_bytes, q));
     HlArgs m = a;
     m.tiles_x = g.model_tiles_x();
@@ -392,12 +376,12 @@ int rtmodt_health_process(rtmodt_health *p, const uint8_t *const *frames, const 
     hipLaunchKernelGGL(health_decide, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, q, a);
     hipLaunchKernelGGL(health_learn, g.per_cell(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_HIP(hipMemcpyAsync(p->h_out, p->d_out + off_res, res_bytes + ev_bytes, hipMemcpyDeviceToHost, q));       // every result in one copy
     RT_HIP(hipStreamSynchronize(q));
     memcpy(results, p->h_out, res_bytes);
     memcpy(events, p->h_out + res_bytes, ev_bytes);
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -453,10 +437,7 @@ int rtmodt_health_reset(rtmodt_health *p, int stream) {
 
 int rtmodt_health_last_ms(rtmodt_health *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no process call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no process call has launched yet");
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@
 
 #include "kernels.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "polygon.h"
 
 #define PV_HD __host__ __device__
@@ -274,17 +275,14 @@ __global__ __launch_bounds__(HM_THREADS) void heatmap_zone_sums(HmZoneArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_heatmap {
-    int device = 0;
+struct rtmodt_heatmap : HandleBase {
     rtmodt_heatmap_cfg cfg{};
     std::vector<int32_t> classes;       // cfg.classes points here (or is null)
     int32_t *d_classes = nullptr;
     int gw = 0, gh = 0;
     long long cells = 0;                // per stream
     uint64_t calls = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     uint32_t *d_grid = nullptr, *d_maxpart = nullptr;
     unsigned long long *d_part = nullptr, *h_part = nullptr;
     uint8_t *d_lut = nullptr;
@@ -339,7 +337,7 @@ int hm_pack_boxes(const HmStampCfg &sc, const float *xyxy, const int32_t *cls, i
 // Everything after the argument checks of an accumulate call: [gather] + accumulate on stream q, then the call is counted.
 // host_stamps: one list per stream (host form); g: the gather launch (device forms).
 int hm_accumulate(rtmodt_heatmap *p, hipStream_t q, const std::vector<std::vector<HmStamp>> *host_stamps, HmGatherArgs *g) {
-    p->timed = false;
+    p->timer.timed = false;
     RT_HIP(hipSetDevice(p->device));
     const rtmodt_heatmap_cfg &c = p->cfg;
     const int S = c.n_streams;
@@ -368,14 +366,14 @@ int hm_accumulate(rtmodt_heatmap *p, hipStream_t q, const std::vector<std::vecto
         a.stamps = g->out; a.n_dev = g->n_out; a.cap = g->cap;
     }
     const dim3 grid((unsigned)(a.tiles_x * cdiv(p->gh, HM_TH)), S), block(HM_THREADS);
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     if (g) hipLaunchKernelGGL(heatmap_gather, dim3(S), block, 0, q, *g);
     hipLaunchKernelGGL(heatmap_accumulate, grid, block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_HIP(hipStreamSynchronize(q));
     ++p->calls;
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -430,14 +428,12 @@ void rtmodt_heatmap_default_cfg(rtmodt_heatmap_cfg *cfg) {
 
 void rtmodt_heatmap_destroy(rtmodt_heatmap *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_grid); hipFree(p->d_maxpart); hipFree(p->d_part); hipFree(p->d_lut); p->cmd.release(); p->stage.release();
-    hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
-    hipHostFree(p->h_part);
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_grid); hipFree(p->d_maxpart); hipFree(p->d_part); hipFree(p->d_lut); p->cmd.release(); p->stage.release();
+        hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
+        hipHostFree(p->h_part);
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -460,12 +456,10 @@ int rtmodt_heatmap_create(const rtmodt_heatmap_cfg *cfg, rtmodt_heatmap **out) {
         const size_t S = (size_t)p->cfg.n_streams;
         uint8_t lut[768];
         hm_jet(lut);
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_grid, S * p->cells * sizeof(uint32_t)));
-        RT_HIP(hipMemset(p->d_grid, 0, S * p->cells * sizeof(uint32_t)));
+        RT_HIP(handle_zero(p->d_grid, S * p->cells * sizeof(uint32_t), p->stream));
         RT_HIP(hipMalloc((void **)&p->d_maxpart, S * HM_PARTS * sizeof(uint32_t)));
         RT_HIP(hipMalloc((void **)&p->d_part, (size_t)HM_MAX_POLYS * HM_PARTS * sizeof(unsigned long long)));
         RT_HIP(hipHostMalloc((void **)&p->h_part, (size_t)HM_MAX_POLYS * HM_PARTS * sizeof(unsigned long long), hipHostMallocDefault));
@@ -478,15 +472,7 @@ int rtmodt_heatmap_create(const rtmodt_heatmap_cfg *cfg, rtmodt_heatmap **out) {
         }
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_heatmap_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_heatmap_destroy, out);
 }
 
 int rtmodt_heatmap_footprint(const rtmodt_heatmap_cfg *cfg, const float *xyxy, int32_t cls, int32_t *cells_xy, int cap_cells, int32_t *needed) {
@@ -559,7 +545,7 @@ int rtmodt_heatmap_overlay(rtmodt_heatmap *p, uint8_t *const *frames, const int3
         RT_CHECK(frames[i], RTMODT_E_INVALID, "frame %d is null", i);
         if (streams) RT_TRY(hm_check_stream(p, streams[i]));
     }
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
@@ -577,14 +563,14 @@ int rtmodt_heatmap_overlay(rtmodt_heatmap *p, uint8_t *const *frames, const int3
     a.alpha = alpha; a.min_level = min_level; a.scale_max = scale_max;
     a.maxpart = p->d_maxpart; a.lut = p->d_lut;
     const dim3 block(HM_THREADS);
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     if (!scale_max) hipLaunchKernelGGL(heatmap_max, dim3(HM_PARTS, p->cfg.n_streams), block, 0, q, (const uint32_t *)p->d_grid, p->cells, p->d_maxpart);
     hipLaunchKernelGGL(heatmap_overlay, dim3((unsigned)(a.tiles_x * cdiv(h, HM_TH)), n), block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_TRY(p->stage.copy_out(frames, q));
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -648,10 +634,7 @@ int rtmodt_heatmap_reset(rtmodt_heatmap *p, int stream) {
 
 int rtmodt_heatmap_last_ms(rtmodt_heatmap *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no accumulate or overlay call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no accumulate or overlay call has launched yet");
 }
 
 }  // extern "C"

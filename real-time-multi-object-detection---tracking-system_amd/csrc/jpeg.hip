@@ -48,6 +48,7 @@
 
 #include "common.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 
 namespace rtmodt {
 
@@ -517,11 +518,9 @@ static void make_tables(int quality, JpegTables &t) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_jpeg {
-    int device = 0, quality = 95, max_h = 0, max_w = 0, max_batch = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+struct rtmodt_jpeg : HandleBase {
+    int quality = 95, max_h = 0, max_w = 0, max_batch = 0;
+    EventTimer<2> timer;
     JpegTables *d_tab = nullptr;
     int16_t *d_coef = nullptr;
     uint32_t *d_ilen = nullptr, *d_ioff = nullptr, *d_sizes = nullptr, *d_fits = nullptr;
@@ -546,14 +545,12 @@ int rtmodt_jpeg_header(int quality, int h, int w, uint8_t *out, size_t out_bytes
 
 void rtmodt_jpeg_destroy(rtmodt_jpeg *j) {
     if (!j) return;
-    hipSetDevice(j->device);
-    if (j->stream) hipStreamSynchronize(j->stream);
-    hipFree(j->d_tab); hipFree(j->d_coef); hipFree(j->d_ilen); hipFree(j->d_ioff); hipFree(j->d_sizes); hipFree(j->d_fits);
-    hipFree(j->d_ptrs); j->stage.release(); hipFree(j->d_out);
-    hipHostFree(j->h_ptrs); hipHostFree(j->h_sizes);
-    if (j->ev0) hipEventDestroy(j->ev0);
-    if (j->ev1) hipEventDestroy(j->ev1);
-    if (j->stream) hipStreamDestroy(j->stream);
+    handle_close(j, [&] {
+        hipFree(j->d_tab); hipFree(j->d_coef); hipFree(j->d_ilen); hipFree(j->d_ioff); hipFree(j->d_sizes); hipFree(j->d_fits);
+        hipFree(j->d_ptrs); j->stage.release(); hipFree(j->d_out);
+        hipHostFree(j->h_ptrs); hipHostFree(j->h_sizes);
+        j->timer.destroy();
+    });
     delete j;
 }
 
@@ -568,10 +565,8 @@ int rtmodt_jpeg_create(int device, const rtmodt_jpeg_cfg *cfg, rtmodt_jpeg **out
     rtmodt_jpeg *j = new rtmodt_jpeg();
     j->device = device; j->quality = quality; j->max_h = cfg->max_h; j->max_w = cfg->max_w; j->max_batch = cfg->max_batch;
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&j->ev0));
-        RT_HIP(hipEventCreate(&j->ev1));
+        RT_TRY(handle_open(j));
+        RT_TRY(j->timer.create());
         const size_t rows = (size_t)cdiv(j->max_h, 16), mcus = rows * cdiv(j->max_w, 16), nb = (size_t)j->max_batch;
         RT_HIP(hipMalloc((void **)&j->d_tab, sizeof(JpegTables)));
         RT_HIP(hipMalloc((void **)&j->d_coef, nb * mcus * 384 * sizeof(int16_t)));
@@ -587,15 +582,7 @@ int rtmodt_jpeg_create(int device, const rtmodt_jpeg_cfg *cfg, rtmodt_jpeg **out
         RT_HIP(hipMemcpy(j->d_tab, &t, sizeof(t), hipMemcpyHostToDevice));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_jpeg_destroy(j);
-        last_error() = keep;
-        return rc;
-    }
-    *out = j;
-    return RTMODT_OK;
+    return handle_created(body(), j, rtmodt_jpeg_destroy, out);
 }
 
 int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n, int h, int w, int stride_bytes, int mem_kind, uint8_t *out,
@@ -604,7 +591,7 @@ int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n
     RT_TRY(check_frames(frames, n, h, w, stride_bytes, mem_kind, kJpegFrames));
     RT_CHECK(n <= j->max_batch && h <= j->max_h && w <= j->max_w, RTMODT_E_CAPACITY,
              "%d frames of %dx%d: the handle was made for %d frames of %dx%d", n, w, h, j->max_batch, j->max_w, j->max_h);
-    j->timed = false;
+    j->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(j->device));
     const std::vector<uint8_t> hd = make_header(j->quality, h, w);
@@ -632,16 +619,16 @@ int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n
     OffArgs oa{};
     oa.ilen = j->d_ilen; oa.ioff = j->d_ioff; oa.sizes = j->d_sizes; oa.fits = j->d_fits; oa.mcus_y = mcus_y; oa.hdr = (uint32_t)hdr;
     oa.cap = cap;
-    RT_HIP(hipEventRecord(j->ev0, j->stream));
+    RT_TRY(j->timer.record(0, j->stream));
     hipLaunchKernelGGL(jpeg_dct, dim3(cdiv(mcus_x, JP_DCT_MCUS), mcus_y, n), dim3(JP_THREADS), 0, j->stream, da);
     hipLaunchKernelGGL(jpeg_code<false>, dim3(mcus_y, n), dim3(JP_THREADS), 0, j->stream, ca);
     hipLaunchKernelGGL(jpeg_offsets, dim3(n), dim3(JP_THREADS), 0, j->stream, oa);
     hipLaunchKernelGGL(jpeg_code<true>, dim3(mcus_y, n), dim3(JP_THREADS), 0, j->stream, ca);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(j->ev1, j->stream));
+    RT_TRY(j->timer.record(1, j->stream));
     RT_HIP(hipMemcpyAsync(j->h_sizes, j->d_sizes, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, j->stream));
     RT_HIP(hipStreamSynchronize(j->stream));
-    j->timed = true;
+    j->timer.timed = true;
     int first_bad = -1;
     for (int i = 0; i < n; ++i) {
         sizes[i] = j->h_sizes[i];
@@ -660,10 +647,7 @@ int rtmodt_jpeg_encode_batch(rtmodt_jpeg *j, const uint8_t *const *frames, int n
 
 int rtmodt_jpeg_last_ms(rtmodt_jpeg *j, float *kernel_ms) {
     RT_CHECK(j && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(j->timed, RTMODT_E_INVALID, "no encode_batch has run a kernel yet");
-    RT_HIP(hipSetDevice(j->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, j->ev0, j->ev1));
-    return RTMODT_OK;
+    return j->timer.elapsed(j->device, 0, 1, kernel_ms, "no encode_batch has run a kernel yet");
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@
 
 #include "common.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "jpeg_dec_core.h"
 
 namespace rtmodt {
@@ -288,12 +289,10 @@ __global__ __launch_bounds__(256) void jd_pixels(JdArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_jpegdec {
-    int device = 0, max_h = 0, max_w = 0, max_batch = 0, force_lanes = 0;
+struct rtmodt_jpegdec : HandleBase {
+    int max_h = 0, max_w = 0, max_batch = 0, force_lanes = 0;
     size_t max_file = 0, slot = 0;                          // slot: max_file rounded up to 16
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     int last_n = 0;
     uint8_t *h_bytes = nullptr, *d_bytes = nullptr;         // h_*: page-locked
     JdFrame *h_frames = nullptr, *d_frames = nullptr;
@@ -322,14 +321,12 @@ int rtmodt_jpeg_probe(const uint8_t *file, size_t bytes, rtmodt_jpeg_info *info)
 
 void rtmodt_jpegdec_destroy(rtmodt_jpegdec *j) {
     if (!j) return;
-    hipSetDevice(j->device);
-    if (j->stream) hipStreamSynchronize(j->stream);
-    hipFree(j->d_bytes); hipFree(j->d_frames); hipFree(j->d_status); hipFree(j->d_marks); hipFree(j->d_coef); hipFree(j->d_planes);
-    j->stage.release();
-    hipHostFree(j->h_bytes); hipHostFree(j->h_frames); hipHostFree(j->h_status);
-    if (j->ev0) hipEventDestroy(j->ev0);
-    if (j->ev1) hipEventDestroy(j->ev1);
-    if (j->stream) hipStreamDestroy(j->stream);
+    handle_close(j, [&] {
+        hipFree(j->d_bytes); hipFree(j->d_frames); hipFree(j->d_status); hipFree(j->d_marks); hipFree(j->d_coef); hipFree(j->d_planes);
+        j->stage.release();
+        hipHostFree(j->h_bytes); hipHostFree(j->h_frames); hipHostFree(j->h_status);
+        j->timer.destroy();
+    });
     delete j;
 }
 
@@ -347,10 +344,8 @@ int rtmodt_jpegdec_create(int device, const rtmodt_jpegdec_cfg *cfg, rtmodt_jpeg
     auto body = [&]() -> int {
         const size_t nb = (size_t)j->max_batch;
         RT_CHECK(nb * j->slot < (1ull << 32), RTMODT_E_INVALID, "%d files of %zu bytes pass 4 GiB", j->max_batch, j->max_file);
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&j->ev0));
-        RT_HIP(hipEventCreate(&j->ev1));
+        RT_TRY(handle_open(j));
+        RT_TRY(j->timer.create());
         RT_HIP(hipHostMalloc((void **)&j->h_bytes, nb * j->slot, hipHostMallocDefault));
         RT_HIP(hipMalloc((void **)&j->d_bytes, nb * j->slot));
         RT_HIP(hipHostMalloc((void **)&j->h_frames, nb * sizeof(JdFrame), hipHostMallocDefault));
@@ -359,15 +354,7 @@ int rtmodt_jpegdec_create(int device, const rtmodt_jpegdec_cfg *cfg, rtmodt_jpeg
         RT_HIP(hipMalloc((void **)&j->d_status, nb * sizeof(int32_t)));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_jpegdec_destroy(j);
-        last_error() = keep;
-        return rc;
-    }
-    *out = j;
-    return RTMODT_OK;
+    return handle_created(body(), j, rtmodt_jpegdec_destroy, out);
 }
 
 int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, const size_t *sizes, int n, uint8_t *const *frames, int h, int w,
@@ -379,7 +366,7 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
              "%d frames of %dx%d: the handle was made for %d frames of %dx%d", n, w, h, j->max_batch, j->max_w, j->max_h);
     for (int i = 0; i < n; ++i)
         RT_CHECK(sizes[i] <= j->max_file, RTMODT_E_CAPACITY, "file %d has %zu bytes, the handle was made for %zu", i, sizes[i], j->max_file);
-    j->timed = false;
+    j->timer.timed = false;
     j->last_n = 0;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(j->device));
@@ -419,7 +406,7 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
     JdArgs a{};
     a.frames = j->d_frames; a.bytes = j->d_bytes; a.marks = (uint32_t *)j->d_marks; a.status = j->d_status;
     a.coef = (int16_t *)j->d_coef; a.planes = j->d_planes; a.h = h; a.w = w;
-    RT_HIP(hipEventRecord(j->ev0, j->stream));
+    RT_TRY(j->timer.record(0, j->stream));
     hipLaunchKernelGGL(jd_scan, dim3(n), dim3(JD_SCAN_THREADS), 0, j->stream, a);
     // the lanes of a wave run in lockstep through unlike streams: few intervals are spread one per wave, and only a call with more
     // intervals than JD_WAVES waves can take at once packs several (consecutive ones) into a wave
@@ -431,10 +418,10 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
     hipLaunchKernelGGL(jd_idct, dim3(std::max<uint32_t>((max_blocks + JD_IDCT_BLOCKS - 1) / JD_IDCT_BLOCKS, 1), n), dim3(JD_IDCT_THREADS), 0, j->stream, a);
     hipLaunchKernelGGL(jd_pixels, dim3(cdiv(w, 64), cdiv(h, 4), n), dim3(64, 4), 0, j->stream, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(j->ev1, j->stream));
+    RT_TRY(j->timer.record(1, j->stream));
     RT_HIP(hipMemcpyAsync(j->h_status, j->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, j->stream));
     RT_HIP(hipStreamSynchronize(j->stream));
-    j->timed = true;
+    j->timer.timed = true;
     j->last_n = n;
     for (int i = 0; i < n; ++i) {
         status[i] = j->h_status[i];
@@ -446,10 +433,7 @@ int rtmodt_jpegdec_decode_batch(rtmodt_jpegdec *j, const uint8_t *const *files, 
 
 int rtmodt_jpegdec_last_ms(rtmodt_jpegdec *j, float *kernel_ms) {
     RT_CHECK(j && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(j->timed, RTMODT_E_INVALID, "no decode_batch has run a kernel yet");
-    RT_HIP(hipSetDevice(j->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, j->ev0, j->ev1));
-    return RTMODT_OK;
+    return j->timer.elapsed(j->device, 0, 1, kernel_ms, "no decode_batch has run a kernel yet");
 }
 
 int rtmodt_jpegdec_coefficients(rtmodt_jpegdec *j, int frame, int component, int16_t *out, size_t out_elems, int *rows, int *cols) {

@@ -458,13 +458,10 @@ __global__ __launch_bounds__(LO_THREADS) void leftobj_clear(uint64_t *state, lon
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_leftobj {
-    int device = 0;
+struct rtmodt_leftobj : HandleBase {
     rtmodt_leftobj_cfg cfg{};
     GridGeom g;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     uint64_t *d_state = nullptr;
     uint8_t *d_luma = nullptr, *d_mask = nullptr;
     int32_t *d_seen = nullptr, *d_parent = nullptr, *d_meta = nullptr;
@@ -550,15 +547,13 @@ void rtmodt_leftobj_default_cfg(rtmodt_leftobj_cfg *cfg) {
 
 void rtmodt_leftobj_destroy(rtmodt_leftobj *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_state); hipFree(p->d_luma); hipFree(p->d_mask); hipFree(p->d_seen); hipFree(p->d_parent); hipFree(p->d_meta); hipFree(p->d_acc);
-    hipFree(p->d_chunk); hipFree(p->d_ledger); hipFree(p->d_out);
-    hipHostFree(p->h_out);
-    p->cmd.release(); p->stage.release();
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_state); hipFree(p->d_luma); hipFree(p->d_mask); hipFree(p->d_seen); hipFree(p->d_parent); hipFree(p->d_meta); hipFree(p->d_acc);
+        hipFree(p->d_chunk); hipFree(p->d_ledger); hipFree(p->d_out);
+        hipHostFree(p->h_out);
+        p->cmd.release(); p->stage.release();
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -580,10 +575,8 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
     p->out_bytes = p->off_blocks + S * p->block_stride;
     auto body = [&]() -> int {
         const size_t all = S * (size_t)p->g.cells;
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_state, all * sizeof(uint64_t)));
         RT_HIP(hipMalloc((void **)&p->d_luma, all));
         RT_HIP(hipMalloc((void **)&p->d_mask, all));
@@ -595,24 +588,15 @@ int rtmodt_leftobj_create(const rtmodt_leftobj_cfg *cfg, rtmodt_leftobj **out) {
         RT_HIP(hipMalloc((void **)&p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object)));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, S * p->block_stride, hipHostMallocDefault));
-        RT_HIP(grid_zero(p->d_state, all * sizeof(uint64_t), p->stream));
-        RT_HIP(grid_zero(p->d_luma, all, p->stream));
-        RT_HIP(grid_zero(p->d_mask, all, p->stream));
-        RT_HIP(grid_zero(p->d_seen, S * sizeof(int32_t), p->stream));
-        RT_HIP(grid_zero(p->d_meta, S * 4 * sizeof(int32_t), p->stream));
-        RT_HIP(grid_zero(p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object), p->stream));
-        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
+        RT_HIP(handle_zero(p->d_state, all * sizeof(uint64_t), p->stream));
+        RT_HIP(handle_zero(p->d_luma, all, p->stream));
+        RT_HIP(handle_zero(p->d_mask, all, p->stream));
+        RT_HIP(handle_zero(p->d_seen, S * sizeof(int32_t), p->stream));
+        RT_HIP(handle_zero(p->d_meta, S * 4 * sizeof(int32_t), p->stream));
+        RT_HIP(handle_zero(p->d_ledger, S * 2 * MO * sizeof(rtmodt_leftobj_object), p->stream));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_leftobj_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_leftobj_destroy, out);
 }
 
 int rtmodt_leftobj_cell(const rtmodt_leftobj_cfg *cfg, uint32_t yc, int32_t frames_seen, uint64_t *state, int32_t *fg, int32_t *is_static) {
@@ -656,7 +640,7 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
         else if (source == RTMODT_LEFTOBJ_TRACKS_OCSORT) RT_TRY(lo_take_tracker<rtmodt_ocsort>(p, tracks->tracker, 0, a, &after));
         else RT_TRY(lo_take_tracker<rtmodt_botsort>(p, tracks->tracker, 0, a, &after));
     }
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
@@ -708,7 +692,7 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     const dim3 block(LO_THREADS);
     const GridGeom &g = p->g;
     const size_t blocks_bytes = (size_t)n * p->block_stride;
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, p->off_blocks + blocks_bytes, q));
     LoArgs m = a;
     m.tiles_x = g.model_tiles_x();
@@ -724,11 +708,11 @@ int rtmodt_leftobj_process(rtmodt_leftobj *p, const uint8_t *const *frames, cons
     hipLaunchKernelGGL(leftobj_step, dim3(n), block, 0, q, a);
     hipLaunchKernelGGL(leftobj_absorb, g.per_cell(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     const bool any = out && (out->results || out->regions || out->events || out->retired || out->objects);
     if (any) RT_HIP(hipMemcpyAsync(p->h_out, p->d_out + p->off_blocks, blocks_bytes, hipMemcpyDeviceToHost, q));      // everything in one copy
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     if (!any) return RTMODT_OK;
     const size_t MO = (size_t)c.max_objects, MR = (size_t)c.max_regions;
     for (int i = 0; i < n; ++i) {
@@ -853,10 +837,7 @@ int rtmodt_leftobj_reset(rtmodt_leftobj *p, int stream) {
 
 int rtmodt_leftobj_last_ms(rtmodt_leftobj *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no process call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no process call has launched yet");
 }
 
 }  // extern "C"

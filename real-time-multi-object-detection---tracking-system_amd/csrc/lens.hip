@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "lens_model.h"
 
 namespace rtmodt {
@@ -108,14 +109,11 @@ template <bool WIDE> __global__ __launch_bounds__(LN_THREADS) void lens_remap(Ln
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_lens {
-    int device = 0;
+struct rtmodt_lens : HandleBase {
     rtmodt_lens_cfg cfg{};
     int tpitch = 0;
     size_t entries = 0;                 // per stream: out_h * tpitch
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     int2 *d_table = nullptr;
     std::vector<char> has;              // a lens was set
     CmdBuf cmd;                         // (every call ends with a synchronize: the pinned half is idle when the next one writes it)
@@ -175,8 +173,6 @@ void ln_size_host(rtmodt_lens *p) {
     p->qx.resize(n); p->qy.resize(n); p->outside.resize(n);
 }
 
-size_t ln_span(int h, int w, int pitch) { return (size_t)(h - 1) * (size_t)pitch + (size_t)3 * w; }
-
 }  // namespace
 
 extern "C" {
@@ -189,13 +185,11 @@ void rtmodt_lens_default_cfg(rtmodt_lens_cfg *cfg) {
 
 void rtmodt_lens_destroy(rtmodt_lens *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_table);
-    p->cmd.release(); p->sin.release(); p->sout.release();
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_table);
+        p->cmd.release(); p->sin.release(); p->sout.release();
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -210,22 +204,12 @@ int rtmodt_lens_create(const rtmodt_lens_cfg *cfg, rtmodt_lens **out) {
     p->entries = (size_t)cfg->out_h * p->tpitch;
     p->has.assign(cfg->streams, 0);
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_table, (size_t)cfg->streams * p->entries * sizeof(int2)));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_lens_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_lens_destroy, out);
 }
 
 int rtmodt_lens_set_model(rtmodt_lens *p, int stream, const rtmodt_lens_params *params, int32_t *n_outside) {
@@ -271,7 +255,7 @@ int rtmodt_lens_read_map(rtmodt_lens *p, int stream, int32_t *qx, int32_t *qy, u
 int rtmodt_lens_process(rtmodt_lens *p, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride,
                         int dst_mem_kind, const int32_t *streams, int n) {
     RT_CHECK(p && n >= 0 && (n == 0 || (src && dst)), RTMODT_E_INVALID, "null argument");
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     const rtmodt_lens_cfg &c = p->cfg;
     RT_TRY(check_frames(src, n, c.src_h, c.src_w, src_stride, src_mem_kind, kLensFrames));
@@ -281,18 +265,7 @@ int rtmodt_lens_process(rtmodt_lens *p, const uint8_t *const *src, int src_strid
         RT_TRY(ln_check_stream(p, s));
         RT_CHECK(p->has[s], RTMODT_E_INVALID, "stream %d has no lens", s);
     }
-    {   // a gather cannot work in place: no destination range may meet a source range of the call
-        const size_t sspan = ln_span(c.src_h, c.src_w, src_stride), dspan = ln_span(c.out_h, c.out_w, dst_stride);
-        std::vector<uintptr_t> starts(n);
-        for (int i = 0; i < n; ++i) starts[i] = (uintptr_t)src[i];
-        std::sort(starts.begin(), starts.end());
-        for (int i = 0; i < n; ++i) {
-            const uintptr_t a = (uintptr_t)dst[i], b = a + dspan;
-            // the source with the largest start below b; all spans are equal, so it is the one that reaches furthest
-            const auto it = std::lower_bound(starts.begin(), starts.end(), b);
-            RT_CHECK(it == starts.begin() || *(it - 1) + sspan <= a, RTMODT_E_INVALID, "destination frame %d overlaps a source frame of the call", i);
-        }
-    }
+    RT_TRY(check_not_in_place(src, c.src_h, c.src_w, src_stride, dst, c.out_h, c.out_w, dst_stride, n));
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
     RT_TRY(p->sin.place(n, c.src_h, c.src_w, src_stride, src_mem_kind, FRAMES_TIGHT16));
@@ -316,23 +289,20 @@ int rtmodt_lens_process(rtmodt_lens *p, const uint8_t *const *src, int src_strid
     a.tiles_x = cdiv(c.out_w, 64 * LN_RUN);
     a.border = (uint32_t)c.border_bgr[0] | (uint32_t)c.border_bgr[1] << 8 | (uint32_t)c.border_bgr[2] << 16;
     const dim3 grid((unsigned)(a.tiles_x * cdiv(c.out_h, LN_ROWS)), (unsigned)n), block(LN_THREADS);
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     if (wide) hipLaunchKernelGGL(lens_remap<true>, grid, block, 0, q, a);
     else hipLaunchKernelGGL(lens_remap<false>, grid, block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_TRY(p->sout.copy_out(dst, q));
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
 int rtmodt_lens_last_ms(rtmodt_lens *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no process call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no process call has launched yet");
 }
 
 int rtmodt_lens_distort_points(const rtmodt_lens_params *params, const double *xy, int n, double *out_xy, double *residual) {

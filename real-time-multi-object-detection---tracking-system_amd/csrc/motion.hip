@@ -255,14 +255,11 @@ __global__ __launch_bounds__(MO_THREADS) void motion_emit(MoArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_motion {
-    int device = 0;
+struct rtmodt_motion : HandleBase {
     rtmodt_motion_cfg cfg{};
     GridGeom g;
     int bgw = 0, bgh = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     uint32_t *d_model = nullptr, *d_area = nullptr, *d_blocks = nullptr, *d_chunk = nullptr;
     int32_t *d_seen = nullptr, *d_parent = nullptr;
     uint8_t *d_raw = nullptr, *d_mask = nullptr;
@@ -318,15 +315,13 @@ void rtmodt_motion_default_cfg(rtmodt_motion_cfg *cfg) {
 
 void rtmodt_motion_destroy(rtmodt_motion *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_model); hipFree(p->d_area); hipFree(p->d_blocks); hipFree(p->d_chunk); hipFree(p->d_seen); hipFree(p->d_parent);
-    hipFree(p->d_raw); hipFree(p->d_mask); hipFree(p->d_box); hipFree(p->d_out);
-    hipHostFree(p->h_out);
-    p->cmd.release(); p->stage.release();
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_model); hipFree(p->d_area); hipFree(p->d_blocks); hipFree(p->d_chunk); hipFree(p->d_seen); hipFree(p->d_parent);
+        hipFree(p->d_raw); hipFree(p->d_mask); hipFree(p->d_box); hipFree(p->d_out);
+        hipHostFree(p->h_out);
+        p->cmd.release(); p->stage.release();
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -340,10 +335,8 @@ int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out) {
     p->bgw = cdiv(p->g.gw, cfg->block); p->bgh = cdiv(p->g.gh, cfg->block);
     auto body = [&]() -> int {
         const size_t S = (size_t)cfg->streams, all = S * (size_t)p->g.cells, nb = S * (size_t)p->bgw * p->bgh;
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_model, all * sizeof(uint32_t)));
         RT_HIP(hipMalloc((void **)&p->d_raw, all));
         RT_HIP(hipMalloc((void **)&p->d_mask, all));
@@ -356,22 +349,13 @@ int rtmodt_motion_create(const rtmodt_motion_cfg *cfg, rtmodt_motion **out) {
         p->out_bytes = S * (sizeof(MoWork) + sizeof(rtmodt_motion_result) + (size_t)cfg->max_regions * 5 * sizeof(int32_t));
         RT_HIP(hipMalloc((void **)&p->d_out, p->out_bytes));
         RT_HIP(hipHostMalloc((void **)&p->h_out, p->out_bytes, hipHostMallocDefault));
-        RT_HIP(grid_zero(p->d_model, all * sizeof(uint32_t), p->stream));
-        RT_HIP(grid_zero(p->d_mask, all, p->stream));
-        RT_HIP(grid_zero(p->d_blocks, nb * sizeof(uint32_t), p->stream));
-        RT_HIP(grid_zero(p->d_seen, S * sizeof(int32_t), p->stream));
-        RT_HIP(hipStreamSynchronize(p->stream));    // (grid_zero)
+        RT_HIP(handle_zero(p->d_model, all * sizeof(uint32_t), p->stream));
+        RT_HIP(handle_zero(p->d_mask, all, p->stream));
+        RT_HIP(handle_zero(p->d_blocks, nb * sizeof(uint32_t), p->stream));
+        RT_HIP(handle_zero(p->d_seen, S * sizeof(int32_t), p->stream));
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_motion_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_motion_destroy, out);
 }
 
 int rtmodt_motion_cell(const rtmodt_motion_cfg *cfg, uint32_t yc, int32_t frames_seen, uint16_t *bg, uint16_t *dev, int32_t *raw) {
@@ -393,7 +377,7 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
     RT_CHECK(pitch_holds(stride_bytes, w), RTMODT_E_INVALID, "stride %d below 3 x %d", stride_bytes, w);
     const int S = p->cfg.streams;
     RT_TRY(check_stream_list(frames, streams, n, S));
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     hipStream_t q = p->stream;
@@ -420,7 +404,7 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
 
     const dim3 block(MO_THREADS);
     const GridGeom &g = p->g;
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     RT_HIP(hipMemsetAsync(p->d_out, 0, off_res + res_bytes + reg_bytes, q));
     MoArgs m = a;
     m.tiles_x = g.model_tiles_x();
@@ -434,12 +418,12 @@ int rtmodt_motion_process(rtmodt_motion *p, const uint8_t *const *frames, const 
     hipLaunchKernelGGL(motion_finish, dim3(n), block, 0, q, a);
     hipLaunchKernelGGL(motion_emit, g.per_chunk(n), block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_HIP(hipMemcpyAsync(p->h_out, p->d_out + off_res, res_bytes + reg_bytes, hipMemcpyDeviceToHost, q));      // every result in one copy
     RT_HIP(hipStreamSynchronize(q));
     memcpy(results, p->h_out, res_bytes);
     memcpy(regions, p->h_out + res_bytes, reg_bytes);
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -505,10 +489,7 @@ int rtmodt_motion_reset(rtmodt_motion *p, int stream) {
 
 int rtmodt_motion_last_ms(rtmodt_motion *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no process call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no process call has launched yet");
 }
 
 }  // extern "C"

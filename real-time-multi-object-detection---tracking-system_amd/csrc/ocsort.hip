@@ -346,8 +346,7 @@ static int launch_ocsort_update(const OcArgs &a, int n_streams, hipStream_t s) {
 using namespace rtmodt;
 
 struct rtmodt_ocsort : TrackHandleBase {
-    hipEvent_t ev[2] = {};
-    bool timed = false;
+    EventTimer<2> timer;
     rtmodt_ocsort_cfg cfg = {};
     char *pool = nullptr;                    // all state arrays (track_layout.h: carve_ocsort)
     OcState *d_states = nullptr; std::vector<OcState> h_states;
@@ -363,11 +362,11 @@ int ocsort_device_view(rtmodt_ocsort *t, OcDeviceView *out) {
 
 static int oc_create_impl(rtmodt_ocsort *t) {
     RT_TRY(track_open(t));
-    for (auto &e : t->ev) RT_HIP(hipEventCreate(&e));
+    RT_TRY(t->timer.create());
     t->h_states.assign(t->S, OcState{});
     const size_t total = carve_ocsort(t->h_states.data(), t->S, t->Mc, OC_RING, nullptr);
     RT_HIP(hipMalloc((void **)&t->pool, total));
-    RT_HIP(hipMemset(t->pool, 0, total));
+    RT_HIP(handle_zero(t->pool, total, t->stream));
     carve_ocsort(t->h_states.data(), t->S, t->Mc, OC_RING, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(OcState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(OcState) * t->S, hipMemcpyHostToDevice));
@@ -385,10 +384,10 @@ static OcArgs oc_args(rtmodt_ocsort *t) {
 }
 
 static int oc_run(rtmodt_ocsort *t, const OcArgs &a, int count, hipStream_t q) {
-    RT_HIP(hipEventRecord(t->ev[0], q));
+    RT_TRY(t->timer.record(0, q));
     RT_TRY(launch_ocsort_update(a, count, q));
-    RT_HIP(hipEventRecord(t->ev[1], q));
-    t->timed = true;
+    RT_TRY(t->timer.record(1, q));
+    t->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -399,7 +398,7 @@ extern "C" {
 void rtmodt_ocsort_destroy(rtmodt_ocsort *t) {
     if (!t) return;
     track_close(t, [t] {
-        for (auto &e : t->ev) if (e) hipEventDestroy(e);
+        t->timer.destroy();
         hipFree(t->pool); hipFree(t->d_states);
     });
     delete t;
@@ -423,7 +422,7 @@ int rtmodt_ocsort_create(const rtmodt_ocsort_cfg *cfg, rtmodt_ocsort **out) {
     rtmodt_ocsort *t = new rtmodt_ocsort();
     t->cfg = *cfg;
     t->device = cfg->device; t->S = cfg->n_streams; t->Mc = cfg->max_tracks; t->Nc = cfg->max_dets;
-    return track_created(oc_create_impl(t), t, rtmodt_ocsort_destroy, out);
+    return handle_created(oc_create_impl(t), t, rtmodt_ocsort_destroy, out);
 }
 
 int rtmodt_ocsort_reset(rtmodt_ocsort *t, int stream) { return track_reset_meta(t, stream); }
@@ -491,11 +490,8 @@ int rtmodt_ocsort_state(rtmodt_ocsort *t, int stream, int64_t *ids, int32_t *hit
 
 int rtmodt_ocsort_last_ms(rtmodt_ocsort *t, float *update_ms) {
     RT_CHECK(t, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(t->timed, RTMODT_E_INVALID, "no update has run yet");
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipEventSynchronize(t->ev[1]));
     float a = 0;
-    RT_HIP(hipEventElapsedTime(&a, t->ev[0], t->ev[1]));
+    RT_TRY(t->timer.elapsed(t->device, 0, 1, &a, "no update has run yet"));
     if (update_ms) *update_ms = a;
     return RTMODT_OK;
 }

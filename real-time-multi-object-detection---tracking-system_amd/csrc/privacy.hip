@@ -40,6 +40,7 @@
 
 #include "kernels.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "polygon.h"
 
 #define PV_HD __host__ __device__
@@ -372,14 +373,11 @@ __global__ __launch_bounds__(PV_THREADS) void privacy_gather(GatherArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_privacy {
-    int device = 0;
+struct rtmodt_privacy : HandleBase {
     rtmodt_privacy_cfg cfg{};
     std::vector<int32_t> classes;       // cfg.classes points here (or is null)
     int32_t *d_classes = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     char *ppool = nullptr;              // polygon table (device)
     size_t ppool_cap = 0;
     PolyView pv{};
@@ -435,7 +433,7 @@ int pv_check_frames(uint8_t *const *frames, int n, int h, int w, int stride_byte
 // host_rects: one list per frame (host forms); g: the gather launch (device forms).  q: the stream everything is queued on.
 int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int n, int h, int w, int stride_bytes, int mem_kind, hipStream_t q,
                const std::vector<std::vector<PvRect>> *host_rects, GatherArgs *g) {
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     const rtmodt_privacy_cfg &c = p->cfg;
@@ -496,16 +494,16 @@ int pv_execute(rtmodt_privacy *p, uint8_t *const *src, uint8_t *const *dst, int 
     for (int i = 0; i < n; ++i)
         if (!host && dst && dst[i] != src[i]) RT_TRY(copy_bgr_rows(dst[i], stride_bytes, src[i], stride_bytes, h, w, hipMemcpyDeviceToDevice, q));
     const dim3 grid((unsigned)tiles, n), block(PV_THREADS);
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     if (g) hipLaunchKernelGGL(privacy_gather, dim3(n), block, 0, q, *g);
     if (blur) hipLaunchKernelGGL(privacy_blur, grid, block, 0, q, a);
     else hipLaunchKernelGGL(privacy_paint, grid, block, 0, q, a);
     if (scratch) hipLaunchKernelGGL(privacy_commit, grid, block, 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_TRY(p->stage.copy_out(dst ? dst : src, q));
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -516,7 +514,7 @@ template <typename F> int pv_apply_view(rtmodt_privacy *p, int src_device, int n
     RT_CHECK(cap >= 1 && cap <= p->cfg.max_regions, RTMODT_E_CAPACITY, "the source holds up to %d boxes per frame > max_regions %d", cap,
              p->cfg.max_regions);
     RT_TRY(pv_check_frames(frames, n, h, w, stride_bytes, mem_kind));
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(p->device));
     RT_TRY(dev_grow(&p->d_gather, &p->gather_bytes, (size_t)n * cap * sizeof(PvRect)));
@@ -552,13 +550,11 @@ void rtmodt_privacy_default_cfg(rtmodt_privacy_cfg *cfg) {
 
 void rtmodt_privacy_destroy(rtmodt_privacy *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->ppool); p->cmd.release(); p->stage.release(); hipFree(p->d_scratch); hipFree(p->d_mask);
-    hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->ppool); p->cmd.release(); p->stage.release(); hipFree(p->d_scratch); hipFree(p->d_mask);
+        hipFree(p->d_gather); hipFree(p->d_gn); hipFree(p->d_classes);
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -578,25 +574,15 @@ int rtmodt_privacy_create(const rtmodt_privacy_cfg *cfg, rtmodt_privacy **out) {
         p->cfg.n_classes = 0;
     }
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         if (p->cfg.classes) {
             RT_HIP(hipMalloc((void **)&p->d_classes, p->classes.size() * sizeof(int32_t)));
             RT_HIP(hipMemcpy(p->d_classes, p->classes.data(), p->classes.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_privacy_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_privacy_destroy, out);
 }
 
 int rtmodt_privacy_set_polygons(rtmodt_privacy *p, const int32_t *const *polygons_xy, const int32_t *n_points, int n) {
@@ -682,10 +668,7 @@ int rtmodt_privacy_apply_detector(rtmodt_privacy *p, rtmodt_detector *det, uint8
 
 int rtmodt_privacy_last_ms(rtmodt_privacy *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no apply call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no apply call has launched yet");
 }
 
 }  // extern "C"

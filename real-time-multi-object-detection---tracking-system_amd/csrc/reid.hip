@@ -47,6 +47,7 @@
 
 #include "kernels.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 
 namespace rtmodt {
 
@@ -498,12 +499,9 @@ struct BlockW { PwW conv1, pw[4][4], dw[4][4], conv3, down; const float *g_w1, *
 
 using namespace rtmodt;
 
-struct rtmodt_reid {
-    int device = 0, max_frames = 0, max_boxes = 0, n_slots = 0;
-    bool own_stream = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {};
-    bool timed = false;
+struct rtmodt_reid : HandleBase {        // stream: null when a tracker embeds the network and runs it on its own streams
+    int max_frames = 0, max_boxes = 0, n_slots = 0;
+    EventTimer<3> timer;
     uint32_t crc = 0;
     // weights (one arena)
     uint8_t *arena = nullptr;
@@ -604,36 +602,36 @@ static int reid_upload(rtmodt_reid *e, const ReidFile &f) {
 static int reid_alloc(rtmodt_reid *e) {
     const size_t n = (size_t)e->n_slots;
     auto h = [&](f16 **p, size_t elems) -> int { RT_HIP(hipMalloc((void **)p, n * elems * 2)); return RTMODT_OK; };
-    RT_HIP(hipMalloc((void **)&e->valid, n * 4)); RT_HIP(hipMemset(e->valid, 0, n * 4));
+    RT_HIP(hipMalloc((void **)&e->valid, n * 4)); RT_HIP(handle_zero(e->valid, n * 4, e->stream));
     RT_HIP(hipMalloc((void **)&e->crop, n * REID_H * REID_W * 3));
     RT_TRY(h(&e->t_conv1, 8192 * 16)); RT_TRY(h(&e->t_maxpool, 2048 * 16));
     for (int b = 0; b < 6; ++b) RT_TRY(h(&e->t_block[b], (size_t)kBlocks[b].P * kBlocks[b].cout));
     RT_TRY(h(&e->t_trans[0], 512 * 64)); RT_TRY(h(&e->t_trans[1], 128 * 96)); RT_TRY(h(&e->t_conv5, 128 * 128)); RT_TRY(h(&e->pooled, 128));
-    RT_HIP(hipMalloc((void **)&e->feat, n * REID_DIM * 4)); RT_HIP(hipMemset(e->feat, 0, n * REID_DIM * 4));
+    RT_HIP(hipMalloc((void **)&e->feat, n * REID_DIM * 4)); RT_HIP(handle_zero(e->feat, n * REID_DIM * 4, e->stream));
     RT_TRY(h(&e->x1, SCR)); RT_TRY(h(&e->x2, SCR));
     for (int s = 0; s < 4; ++s) RT_TRY(h(&e->tmp[s], SCR));
     for (int l = 0; l < 4; ++l)
         for (int s = l; s < 4; ++s) RT_TRY(h(&e->lvl[l][s], SCR));
     RT_TRY(h(&e->big[0], BIG)); RT_TRY(h(&e->big[1], BIG));
-    RT_HIP(hipMalloc((void **)&e->desc, n * REID_DIM)); RT_HIP(hipMemset(e->desc, 0, n * REID_DIM));
+    RT_HIP(hipMalloc((void **)&e->desc, n * REID_DIM)); RT_HIP(handle_zero(e->desc, n * REID_DIM, e->stream));
     RT_HIP(hipMalloc((void **)&e->d_box, n * 16)); RT_HIP(hipMalloc((void **)&e->d_n, (size_t)e->max_frames * 4));
-    for (auto &v : e->ev) RT_HIP(hipEventCreate(&v));
+    RT_TRY(e->timer.create());
     return RTMODT_OK;
 }
 
 void reid_close(rtmodt_reid *e) {
     if (!e) return;
     hipSetDevice(e->device);
-    if (e->stream) hipStreamSynchronize(e->stream);
-    else hipDeviceSynchronize();
-    for (auto &v : e->ev) if (v) hipEventDestroy(v);
-    hipFree(e->arena); hipFree(e->valid); hipFree(e->crop); hipFree(e->t_conv1); hipFree(e->t_maxpool);
-    for (auto p : e->t_block) hipFree(p);
-    hipFree(e->t_trans[0]); hipFree(e->t_trans[1]); hipFree(e->t_conv5); hipFree(e->pooled); hipFree(e->feat); hipFree(e->x1); hipFree(e->x2);
-    for (auto p : e->tmp) hipFree(p);
-    for (auto &l : e->lvl) for (auto p : l) hipFree(p);
-    hipFree(e->big[0]); hipFree(e->big[1]); hipFree(e->desc); hipFree(e->d_box); hipFree(e->d_n); e->stage.release();
-    if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+    if (!e->stream) hipDeviceSynchronize();
+    handle_close(e, [&] {
+        e->timer.destroy();
+        hipFree(e->arena); hipFree(e->valid); hipFree(e->crop); hipFree(e->t_conv1); hipFree(e->t_maxpool);
+        for (auto p : e->t_block) hipFree(p);
+        hipFree(e->t_trans[0]); hipFree(e->t_trans[1]); hipFree(e->t_conv5); hipFree(e->pooled); hipFree(e->feat); hipFree(e->x1); hipFree(e->x2);
+        for (auto p : e->tmp) hipFree(p);
+        for (auto &l : e->lvl) for (auto p : l) hipFree(p);
+        hipFree(e->big[0]); hipFree(e->big[1]); hipFree(e->desc); hipFree(e->d_box); hipFree(e->d_n); e->stage.release();
+    });
     delete e;
 }
 
@@ -646,23 +644,14 @@ int reid_open(const char *path, int device, int max_frames, int max_boxes, bool 
     RT_TRY(reid_parse(path, &f));                          // everything above and in here: before the device is touched
     rtmodt_reid *e = new rtmodt_reid();
     e->device = device; e->max_frames = max_frames; e->max_boxes = max_boxes; e->n_slots = max_frames * max_boxes; e->crc = f.crc;
-    e->own_stream = own_stream;
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(device));
-        if (own_stream) RT_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+        if (own_stream) RT_TRY(handle_open(e));
+        else RT_HIP(hipSetDevice(device));
         RT_TRY(reid_upload(e, f));
         RT_TRY(reid_alloc(e));
-        return RTMODT_OK;
+        return own_stream ? RTMODT_OK : handle_wait(nullptr);        // (embedded: the zeroing went to the null stream)
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        reid_close(e);
-        last_error() = keep;
-        return rc;
-    }
-    *out = e;
-    return RTMODT_OK;
+    return handle_created(body(), e, reid_close, out);
 }
 
 #define REID_LAUNCH(kernel, grid, block, q, args)              \
@@ -680,12 +669,12 @@ int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, i
     if (launch_mb <= 0) return RTMODT_OK;
     const int mb = launch_mb, smb = e->max_boxes, NS = count * mb;
     e->last_count = count; e->last_mb = mb;
-    RT_HIP(hipEventRecord(e->ev[0], q));
+    RT_TRY(e->timer.record(0, q));
     CropArgs c{};
     c.frames = frames; c.h = h; c.w = w; c.pitch = pitch; c.box = box; c.box_n = box_n; c.box_stride = box_stride; c.launch_mb = mb; c.slot_mb = smb;
     c.crop = e->crop; c.valid = e->valid;
     REID_LAUNCH(reid_crop, dim3(mb, count, REID_H / 32), dim3(256), q, c);
-    RT_HIP(hipEventRecord(e->ev[1], q));
+    RT_TRY(e->timer.record(1, q));
     StemArgs st{e->crop, e->valid, e->table, e->c1_w, e->c1_b, e->t_conv1, mb, smb};
     REID_LAUNCH(reid_conv1, dim3(8192 / 256, NS), dim3(256), q, st);
     auto pool = [&](const f16 *in, f16 *out, int H, int W, int C, int mode) -> int {
@@ -749,8 +738,8 @@ int reid_run(rtmodt_reid *e, const AppFrames &frames, int count, int h, int w, i
         REID_LAUNCH(reid_pw, dim3(cdiv(NS, 64), 1, 1), dim3(256), q, a);
     }
     REID_LAUNCH(reid_quant, dim3(NS), dim3(REID_DIM), q, t);
-    RT_HIP(hipEventRecord(e->ev[2], q));
-    e->timed = true;
+    RT_TRY(e->timer.record(2, q));
+    e->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -831,12 +820,9 @@ int rtmodt_reid_tap(rtmodt_reid *e, const char *name, void *out, size_t out_byte
 
 int rtmodt_reid_last_ms(rtmodt_reid *e, float *crop_ms, float *net_ms) {
     RT_CHECK(e, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(e->timed, RTMODT_E_INVALID, "no embed has run yet");
-    RT_HIP(hipSetDevice(e->device));
-    RT_HIP(hipEventSynchronize(e->ev[2]));
     float a = 0, b = 0;
-    RT_HIP(hipEventElapsedTime(&a, e->ev[0], e->ev[1]));
-    RT_HIP(hipEventElapsedTime(&b, e->ev[1], e->ev[2]));
+    RT_TRY(e->timer.elapsed(e->device, 1, 2, &b, "no embed has run yet"));       // (the last event first: it waits for the call)
+    RT_TRY(e->timer.elapsed(e->device, 0, 1, &a, "no embed has run yet"));
     if (crop_ms) *crop_ms = a;
     if (net_ms) *net_ms = b;
     return RTMODT_OK;

@@ -40,6 +40,7 @@
 #include "common.h"
 #include "font_atlas.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "polygon.h"
 
 namespace rtmodt {
@@ -491,12 +492,9 @@ static bool name_anchor(const int32_t *xy, int n, int &ax, int &ay) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_renderer {
-    int device = 0;
+struct rtmodt_renderer : HandleBase {
     RenderCfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     char *zpool = nullptr;              // zone table (device)
     size_t zpool_cap = 0;
     ZoneView zv{};
@@ -508,14 +506,12 @@ extern "C" {
 
 void rtmodt_renderer_destroy(rtmodt_renderer *r) {
     if (!r) return;
-    hipSetDevice(r->device);
-    if (r->stream) hipStreamSynchronize(r->stream);
-    hipFree(r->zpool);
-    r->cmd.release();
-    r->stage.release();
-    if (r->ev0) hipEventDestroy(r->ev0);
-    if (r->ev1) hipEventDestroy(r->ev1);
-    if (r->stream) hipStreamDestroy(r->stream);
+    handle_close(r, [&] {
+        hipFree(r->zpool);
+        r->cmd.release();
+        r->stage.release();
+        r->timer.destroy();
+    });
     delete r;
 }
 
@@ -527,21 +523,11 @@ int rtmodt_renderer_create(int device, const rtmodt_render_cfg *cfg, rtmodt_rend
     r->device = device;
     r->cfg = c;
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&r->ev0));
-        RT_HIP(hipEventCreate(&r->ev1));
+        RT_TRY(handle_open(r));
+        RT_TRY(r->timer.create());
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_renderer_destroy(r);
-        last_error() = keep;
-        return rc;
-    }
-    *out = r;
-    return RTMODT_OK;
+    return handle_created(body(), r, rtmodt_renderer_destroy, out);
 }
 
 int rtmodt_renderer_set_zones(rtmodt_renderer *r, const int32_t *const *polygons_xy, const int32_t *n_points, const char *const *names, int n_zones) {
@@ -602,7 +588,7 @@ int rtmodt_render_batch(rtmodt_renderer *r, uint8_t *const *frames, int n, int h
     RT_TRY(check_frames(frames, n, h, w, stride_bytes, mem_kind, kPaintFrames));
     Packed P;
     RT_TRY(pack_lists(r->cfg, lists, n, draw_zones, fps, latency_ms, P));
-    r->timed = false;
+    r->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     RT_HIP(hipSetDevice(r->device));
     // host frames: staged tightly on the device (16-byte aligned rows), drawn there, copied back row by row
@@ -622,22 +608,19 @@ int rtmodt_render_batch(rtmodt_renderer *r, uint8_t *const *frames, int n, int h
     a.zv = r->zv;
     const long long tiles = (long long)a.tiles_x * cdiv(h, RD_TH);
     RT_CHECK(tiles <= INT32_MAX, RTMODT_E_INVALID, "frame too large");
-    RT_HIP(hipEventRecord(r->ev0, r->stream));
+    RT_TRY(r->timer.record(0, r->stream));
     hipLaunchKernelGGL(render_tiles, dim3((unsigned)tiles, n), dim3(RD_THREADS), 0, r->stream, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(r->ev1, r->stream));
+    RT_TRY(r->timer.record(1, r->stream));
     RT_TRY(r->stage.copy_out(frames, r->stream));
     RT_HIP(hipStreamSynchronize(r->stream));
-    r->timed = true;
+    r->timer.timed = true;
     return RTMODT_OK;
 }
 
 int rtmodt_renderer_last_ms(rtmodt_renderer *r, float *kernel_ms) {
     RT_CHECK(r && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(r->timed, RTMODT_E_INVALID, "no render_batch has run a kernel yet");
-    RT_HIP(hipSetDevice(r->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, r->ev0, r->ev1));
-    return RTMODT_OK;
+    return r->timer.elapsed(r->device, 0, 1, kernel_ms, "no render_batch has run a kernel yet");
 }
 
 }  // extern "C"

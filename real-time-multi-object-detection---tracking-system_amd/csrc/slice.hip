@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "letterbox_dev.h"
 #include "slice_grid.h"
 
@@ -337,11 +338,10 @@ static SliceMergeArgs merge_args(const rtmodt_slice_cfg &c, const SlicePlan &p, 
 
 }  // namespace rtmodt
 
-struct rtmodt_slicer {
+struct rtmodt_slicer : HandleBase {             // stream: staging copies + slice_gather; idle before the detector is handed the tile pointers
     rtmodt_slice_cfg cfg{};
     int max_det = 0;
     SlicePlan plan;
-    hipStream_t stream = nullptr;            // staging copies + slice_gather; idle before the detector is handed the tile pointers
     FrameStage stage;                        // host frames, repacked to pitch 3 * frame_w; sized for max_frames at create
     uint8_t *d_tiles[2] = {nullptr, nullptr};   // the image batch of the two sliced batches that may be in flight
     int32_t *d_tab = nullptr; ResizeTables tabs{};
@@ -425,25 +425,24 @@ void rtmodt_slicer_destroy(rtmodt_slicer *s) {
     hipSetDevice(s->cfg.device);
     for (auto &o : s->out)
         if (o.done) hipEventSynchronize(o.done);         // a merge may still be queued on a detector's stream
-    if (s->stream) hipStreamSynchronize(s->stream);
-    for (auto &o : s->out) {
-        hipFree(o.box); hipFree(o.conf); hipFree(o.cls); hipFree(o.nm); hipFree(o.n); hipHostFree(o.host);
-        if (o.m0) hipEventDestroy(o.m0);
-        if (o.m1) hipEventDestroy(o.m1);
-        if (o.done) hipEventDestroy(o.done);
-    }
-    if (s->g0) hipEventDestroy(s->g0);
-    if (s->g1) hipEventDestroy(s->g1);
-    s->stage.release(); hipFree(s->d_tiles[0]); hipFree(s->d_tiles[1]); hipFree(s->d_tab); hipFree(s->d_sbox); hipFree(s->d_scls);
-    if (s->stream) hipStreamDestroy(s->stream);
+    handle_close(s, [&] {
+        for (auto &o : s->out) {
+            hipFree(o.box); hipFree(o.conf); hipFree(o.cls); hipFree(o.nm); hipFree(o.n); hipHostFree(o.host);
+            if (o.m0) hipEventDestroy(o.m0);
+            if (o.m1) hipEventDestroy(o.m1);
+            if (o.done) hipEventDestroy(o.done);
+        }
+        if (s->g0) hipEventDestroy(s->g0);
+        if (s->g1) hipEventDestroy(s->g1);
+        s->stage.release(); hipFree(s->d_tiles[0]); hipFree(s->d_tiles[1]); hipFree(s->d_tab); hipFree(s->d_sbox); hipFree(s->d_scls);
+    });
     delete s;
 }
 
 static int slicer_create_impl(rtmodt_slicer *s) {
     const rtmodt_slice_cfg &c = s->cfg;
     const SlicePlan &p = s->plan;
-    RT_HIP(hipSetDevice(c.device));
-    RT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    RT_TRY(handle_open(s));
     RT_HIP(hipEventCreate(&s->g0)); RT_HIP(hipEventCreate(&s->g1));
     RT_TRY(s->stage.reserve((size_t)c.max_frames * c.frame_h * c.frame_w * 3));      // max_frames in the FRAMES_TIGHT layout: every call fits
     const size_t batch_bytes = (size_t)c.max_frames * p.I * p.img_bytes;
@@ -458,7 +457,7 @@ static int slicer_create_impl(rtmodt_slicer *s) {
     for (auto &o : s->out) {
         RT_HIP(hipMalloc((void **)&o.box, FO * 16)); RT_HIP(hipMalloc((void **)&o.conf, FO * 4)); RT_HIP(hipMalloc((void **)&o.cls, FO * 4));
         RT_HIP(hipMalloc((void **)&o.nm, FO * 4)); RT_HIP(hipMalloc((void **)&o.n, (size_t)c.max_frames * 4));
-        RT_HIP(hipMemset(o.n, 0, (size_t)c.max_frames * 4));
+        RT_HIP(handle_zero(o.n, (size_t)c.max_frames * 4, s->stream));
         RT_HIP(hipHostMalloc((void **)&o.host, out_host_bytes(s), hipHostMallocDefault));
         RT_HIP(hipEventCreate(&o.m0)); RT_HIP(hipEventCreate(&o.m1));
         RT_HIP(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
@@ -474,16 +473,8 @@ int rtmodt_slicer_create(const rtmodt_slice_cfg *cfg, int max_det, rtmodt_slicer
     RT_CHECK(cfg->max_frames >= 1 && (long)cfg->max_frames * plan.I <= 64, RTMODT_E_CAPACITY,
              "max_frames %d x %d images per frame: a detector batch holds at most 64 images", cfg->max_frames, plan.I);
     rtmodt_slicer *s = new rtmodt_slicer();
-    s->cfg = *cfg; s->max_det = max_det; s->plan = plan;
-    const int rc = slicer_create_impl(s);
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_slicer_destroy(s);
-        last_error() = keep;
-        return rc;
-    }
-    *out = s;
-    return RTMODT_OK;
+    s->device = cfg->device; s->cfg = *cfg; s->max_det = max_det; s->plan = plan;
+    return handle_created(slicer_create_impl(s), s, rtmodt_slicer_destroy, out);
 }
 
 int rtmodt_slicer_info(rtmodt_slicer *s, int32_t *n_tiles, int32_t *images_per_frame, int32_t *te_w, int32_t *te_h) {

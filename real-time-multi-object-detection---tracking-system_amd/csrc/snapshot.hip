@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "track_layout.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #define TL_HD __host__ __device__
 #include "track_ledger_host.h"
 
@@ -446,13 +447,12 @@ __global__ __launch_bounds__(SN_THREADS) void snapshot_pick(SnPickArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_snapshot {
-    int device = 0, S = 1, Mc = 0, cap = 0, words = 0;
+struct rtmodt_snapshot : HandleBase {
+    int S = 1, Mc = 0, cap = 0, words = 0;
     bool filter = false;                  // a class list was given (the list lives on the device)
     rtmodt_snapshot_cfg cfg{};
-    hipStream_t stream = nullptr, last_stream = nullptr;     // own stream; the stream of the most recent launch
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    hipStream_t last_stream = nullptr;                       // the stream of the most recent launch (its own: HandleBase::stream)
+    EventTimer<2> timer;
     char *pool = nullptr;                 // every device array but the atlas lives in this one allocation
     uint8_t *atlas = nullptr; size_t atlas_stride = 0, slot_bytes = 0; int pitch_t = 0;
     SnLedger *d_ledgers = nullptr;
@@ -554,13 +554,13 @@ int sn_run(rtmodt_snapshot *z, SnArgs &a, int s0, int cnt, const int64_t *frame_
     const size_t smem = sn_smem(z);
     static DynLdsSeen seen;
     RT_TRY(raise_dynamic_lds((const void *)snapshot_decide, smem, seen));
-    RT_HIP(hipEventRecord(z->ev0, q));
+    RT_TRY(z->timer.record(0, q));
     hipLaunchKernelGGL(snapshot_decide, dim3(cnt), dim3(SN_THREADS), smem, q, a);
     RT_HIP(hipGetLastError());
     hipLaunchKernelGGL(snapshot_resample, dim3(SN_GRID_X, cnt), dim3(SN_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(z->ev1, q));
-    z->timed = true;
+    RT_TRY(z->timer.record(1, q));
+    z->timer.timed = true;
     z->last_stream = q;
     for (int s = 0; s < cnt; ++s) { z->last_f[s0 + s] = frame_id[s]; z->has_f[s0 + s] = 1; }
     const bool any = out && (out->updated || out->n_updated || out->retired || out->n_retired || out->n_rewritten);
@@ -721,16 +721,13 @@ void rtmodt_snapshot_default_cfg(rtmodt_snapshot_cfg *cfg) {
 
 void rtmodt_snapshot_destroy(rtmodt_snapshot *z) {
     if (!z) return;
-    hipSetDevice(z->device);
-    if (z->stream) hipStreamSynchronize(z->stream);
-    if (z->last_stream && z->last_stream != z->stream) hipStreamSynchronize(z->last_stream);
-    hipFree(z->pool); hipFree(z->atlas); hipFree(z->d_crop); hipFree(z->d_pick);
-    hipHostFree(z->h_pin);
-    for (int k = 0; k < 2; ++k) { z->cmd[k].release(); if (z->cmd_ev[k]) hipEventDestroy(z->cmd_ev[k]); }
-    z->stage.release();
-    if (z->ev0) hipEventDestroy(z->ev0);
-    if (z->ev1) hipEventDestroy(z->ev1);
-    if (z->stream) hipStreamDestroy(z->stream);
+    handle_close(z, [&] {
+        hipFree(z->pool); hipFree(z->atlas); hipFree(z->d_crop); hipFree(z->d_pick);
+        hipHostFree(z->h_pin);
+        for (int k = 0; k < 2; ++k) { z->cmd[k].release(); if (z->cmd_ev[k]) hipEventDestroy(z->cmd_ev[k]); }
+        z->stage.release();
+        z->timer.destroy();
+    }, z->last_stream);
     delete z;
 }
 
@@ -754,14 +751,12 @@ int rtmodt_snapshot_create(const rtmodt_snapshot_cfg *cfg, int n_streams, int ma
     z->atlas_stride = z->slot_bytes * z->cap;
     auto body = [&]() -> int {
         RT_CHECK(sn_smem(z) <= 150 * 1024, RTMODT_E_INVALID, "snapshot: capacity %d needs %zu B of LDS", z->cap, sn_smem(z));
-        RT_HIP(hipSetDevice(z->device));
-        RT_HIP(hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&z->ev0));
-        RT_HIP(hipEventCreate(&z->ev1));
+        RT_TRY(handle_open(z));
+        RT_TRY(z->timer.create());
         for (int k = 0; k < 2; ++k) RT_HIP(hipEventCreateWithFlags(&z->cmd_ev[k], hipEventDisableTiming));
         const size_t total = sn_carve(z, nullptr), atlas_bytes = z->atlas_stride * z->S;
         RT_HIP(hipMalloc((void **)&z->pool, total));
-        RT_HIP(hipMemset(z->pool, 0, total));
+        RT_HIP(handle_zero(z->pool, total, z->stream));
         sn_carve(z, z->pool);
         if (hipMalloc((void **)&z->atlas, atlas_bytes) != hipSuccess) {
             z->atlas = nullptr;
@@ -769,21 +764,13 @@ int rtmodt_snapshot_create(const rtmodt_snapshot_cfg *cfg, int n_streams, int ma
             return fail(RTMODT_E_HIP, "snapshot: the thumbnail atlas of %d streams x %d slots of %dx%d needs %zu bytes of device memory", z->S, z->cap, c.thumb_w,
                         c.thumb_h, atlas_bytes);
         }
-        RT_HIP(hipMemset(z->atlas, 0, atlas_bytes));
+        RT_HIP(handle_zero(z->atlas, atlas_bytes, z->stream));
         RT_HIP(hipHostMalloc((void **)&z->h_pin, (size_t)z->S * z->block_stride, hipHostMallocDefault));
-        RT_HIP(hipMemcpy(z->d_ledgers, z->h_ledgers.data(), sizeof(SnLedger) * z->S, hipMemcpyHostToDevice));
-        if (!classes.empty()) RT_HIP(hipMemcpy(z->d_classes, classes.data(), classes.size() * 4, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpyAsync(z->d_ledgers, z->h_ledgers.data(), sizeof(SnLedger) * z->S, hipMemcpyHostToDevice, z->stream));      // (behind the zeroing of the pool)
+        if (!classes.empty()) RT_HIP(hipMemcpyAsync(z->d_classes, classes.data(), classes.size() * 4, hipMemcpyHostToDevice, z->stream));
         return RTMODT_OK;
     };
-    int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_snapshot_destroy(z);
-        last_error() = keep;
-        return rc;
-    }
-    *out = z;
-    return RTMODT_OK;
+    return handle_created(body(), z, rtmodt_snapshot_destroy, out);
 }
 
 int rtmodt_snapshot_process(rtmodt_snapshot *z, int stream, const int64_t *track_ids, const float *xyxy, const float *conf, const int32_t *cls, int n,
@@ -873,8 +860,9 @@ int rtmodt_snapshot_state(rtmodt_snapshot *z, int stream, int64_t *ids, int64_t 
 int rtmodt_snapshot_reset(rtmodt_snapshot *z, int stream) {
     RT_CHECK(z && stream >= 0 && stream < z->S, RTMODT_E_INVALID, "bad argument");
     RT_TRY(sn_sync(z));
-    RT_HIP(hipMemset(z->d_meta + 4 * stream, 0, 4 * sizeof(int64_t)));
-    RT_HIP(hipMemset(z->d_bitmap + (size_t)stream * z->words, 0, (size_t)z->words * 4));
+    RT_HIP(handle_zero(z->d_meta + 4 * stream, 4 * sizeof(int64_t), z->stream));
+    RT_HIP(handle_zero(z->d_bitmap + (size_t)stream * z->words, (size_t)z->words * 4, z->stream));
+    RT_TRY(handle_wait(z->stream));
     z->has_f[stream] = 0; z->last_f[stream] = 0;
     return RTMODT_OK;
 }
@@ -937,11 +925,11 @@ int rtmodt_snapshot_crop(rtmodt_snapshot *z, const uint8_t *const *frames, int n
     a.work = (SnWork *)(cb->d + o_work); a.n_work_fixed = z->d_nwork; a.dst_pitch = (int64_t)tight;
     const int bands = (z->cfg.thumb_h + SN_BAND - 1) / SN_BAND;
     const int grid = (int)std::min<long long>((long long)n_work * bands, 4096);
-    RT_HIP(hipEventRecord(z->ev0, q));
+    RT_TRY(z->timer.record(0, q));
     hipLaunchKernelGGL(snapshot_resample, dim3(grid), dim3(SN_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(z->ev1, q));
-    z->timed = true;
+    RT_TRY(z->timer.record(1, q));
+    z->timer.timed = true;
     z->last_stream = q;
     if (host_out)
         for (int i : which) RT_HIP(hipMemcpyAsync(out + (size_t)i * tbytes, z->d_crop + (size_t)i * tbytes, tbytes, hipMemcpyDeviceToHost, q));
@@ -989,13 +977,13 @@ int rtmodt_snapshot_crop_detector(rtmodt_snapshot *z, rtmodt_detector *det, cons
     a.work = p.work; a.n_work_fixed = z->d_nwork; a.dst_pitch = (int64_t)tight;
     const int bands = (z->cfg.thumb_h + SN_BAND - 1) / SN_BAND;
     const int grid = (int)std::min<long long>((long long)m * bands, 4096);
-    RT_HIP(hipEventRecord(z->ev0, q));
+    RT_TRY(z->timer.record(0, q));
     hipLaunchKernelGGL(snapshot_pick, dim3(n), dim3(SN_THREADS), 0, q, p);
     RT_HIP(hipGetLastError());
     hipLaunchKernelGGL(snapshot_resample, dim3(grid), dim3(SN_THREADS), 0, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(z->ev1, q));
-    z->timed = true;
+    RT_TRY(z->timer.record(1, q));
+    z->timer.timed = true;
     z->last_stream = q;
     std::vector<char> res(pbytes - o_index);               // index | sampled | counts lie behind one another: one copy
     RT_HIP(hipMemcpyAsync(res.data(), z->d_pick + o_index, res.size(), hipMemcpyDeviceToHost, q));
@@ -1014,10 +1002,7 @@ int rtmodt_snapshot_crop_detector(rtmodt_snapshot *z, rtmodt_detector *det, cons
 
 int rtmodt_snapshot_last_ms(rtmodt_snapshot *z, float *kernel_ms) {
     RT_CHECK(z && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(z->timed, RTMODT_E_INVALID, "no call has been timed yet");
-    RT_TRY(sn_sync(z));
-    RT_HIP(hipEventElapsedTime(kernel_ms, z->ev0, z->ev1));
-    return RTMODT_OK;
+    return z->timer.elapsed(z->device, 0, 1, kernel_ms, "no call has been timed yet");
 }
 
 }  // extern "C"

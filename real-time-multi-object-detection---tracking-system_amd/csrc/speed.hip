@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "handle_host.h"
 #include "track_layout.h"
 
 #define GP_HD __host__ __device__
@@ -316,11 +317,11 @@ __global__ __launch_bounds__(SP_THREADS) void speed_pairs(SpArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_speed {
-    int device = 0, S = 1, Mc = 0, cap = 0;
+struct rtmodt_speed : HandleBase {
+    int S = 1, Mc = 0, cap = 0;
     bool filter = false;                  // a class list was given (cfg.classes itself is not kept: the list lives on the device)
     rtmodt_speed_cfg cfg{};
-    hipStream_t stream = nullptr, last_stream = nullptr;     // own stream; the stream of the most recent launch
+    hipStream_t last_stream = nullptr;                       // the stream of the most recent launch (its own: HandleBase::stream)
     char *pool = nullptr;                 // every device array below lives in this one allocation
     SpLedger *d_ledgers = nullptr;
     std::vector<SpLedger> h_ledgers;
@@ -496,12 +497,7 @@ extern "C" {
 
 void rtmodt_speed_destroy(rtmodt_speed *z) {
     if (!z) return;
-    hipSetDevice(z->device);
-    if (z->stream) hipStreamSynchronize(z->stream);
-    if (z->last_stream && z->last_stream != z->stream) hipStreamSynchronize(z->last_stream);
-    hipFree(z->pool);
-    hipHostFree(z->h_pin);
-    if (z->stream) hipStreamDestroy(z->stream);
+    handle_close(z, [&] { hipFree(z->pool); hipHostFree(z->h_pin); }, z->last_stream);
     delete z;
 }
 
@@ -533,26 +529,17 @@ int rtmodt_speed_create(int device, const rtmodt_speed_cfg *cfg, int n_streams, 
     z->plane_set.assign(n_streams, 0); z->last_t.assign(n_streams, 0); z->has_t.assign(n_streams, 0);
     auto body = [&]() -> int {
         RT_CHECK(sp_smem(z) <= 150 * 1024, RTMODT_E_INVALID, "speed: capacity %d needs %zu B of LDS", z->cap, sp_smem(z));
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking));
+        RT_TRY(handle_open(z));
         const size_t total = sp_carve(z, nullptr);
         RT_HIP(hipMalloc((void **)&z->pool, total));
-        RT_HIP(hipMemset(z->pool, 0, total));
+        RT_HIP(handle_zero(z->pool, total, z->stream));             // (the copies below go behind it, on the same stream)
         sp_carve(z, z->pool);
         RT_HIP(hipHostMalloc((void **)&z->h_pin, (size_t)z->S * z->block_stride, hipHostMallocDefault));
-        RT_HIP(hipMemcpy(z->d_ledgers, z->h_ledgers.data(), sizeof(SpLedger) * z->S, hipMemcpyHostToDevice));
-        if (!classes.empty()) RT_HIP(hipMemcpy(z->d_classes, classes.data(), classes.size() * 4, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpyAsync(z->d_ledgers, z->h_ledgers.data(), sizeof(SpLedger) * z->S, hipMemcpyHostToDevice, z->stream));
+        if (!classes.empty()) RT_HIP(hipMemcpyAsync(z->d_classes, classes.data(), classes.size() * 4, hipMemcpyHostToDevice, z->stream));
         return RTMODT_OK;
     };
-    int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_speed_destroy(z);
-        last_error() = keep;
-        return rc;
-    }
-    *out = z;
-    return RTMODT_OK;
+    return handle_created(body(), z, rtmodt_speed_destroy, out);
 }
 
 int rtmodt_speed_set_plane(rtmodt_speed *z, int stream, const double H[9]) {
@@ -613,8 +600,8 @@ int rtmodt_speed_histogram(rtmodt_speed *z, int stream, int64_t *hist, int reset
     if (!B) return RTMODT_OK;
     int64_t *d = z->d_hist + (size_t)stream * B;
     if (hist) RT_HIP(hipMemcpy(hist, d, B * 8, hipMemcpyDeviceToHost));
-    if (reset) RT_HIP(hipMemset(d, 0, B * 8));
-    return RTMODT_OK;
+    if (reset) RT_HIP(handle_zero(d, B * 8, z->stream));
+    return handle_wait(z->stream);
 }
 
 int rtmodt_speed_state(rtmodt_speed *z, int stream, int64_t *ids, int64_t *last_t_us, int64_t *odometer_mm, int64_t *stop_since, int32_t *ring_xy,

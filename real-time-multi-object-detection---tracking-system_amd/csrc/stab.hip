@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "kernels.h"
 
 // the rule headers are plain C++; here their functions are compiled for the host and the device alike
@@ -132,13 +133,10 @@ template <bool WIDE> __global__ __launch_bounds__(ST_THREADS) void stab_warp_ker
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_stab {
-    int device = 0;
+struct rtmodt_stab : HandleBase {
     rtmodt_stab_cfg cfg{};
     StabRule rule{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
+    EventTimer<2> timer;
     StDev *d_state = nullptr;
     std::vector<StDev> h_state;         // staging for reset / result
     std::vector<char> seen;
@@ -178,8 +176,6 @@ StDev st_fresh(const StabRule &r) {
     return d;
 }
 
-size_t st_span(int h, int w, int pitch) { return (size_t)(h - 1) * (size_t)pitch + (size_t)3 * w; }
-
 int st_fetch(rtmodt_stab *p, int first, int count) {
     RT_HIP(hipSetDevice(p->device));
     RT_HIP(hipMemcpyAsync(p->h_state.data() + first, p->d_state + first, (size_t)count * sizeof(StDev), hipMemcpyDeviceToHost, p->stream));
@@ -198,7 +194,7 @@ int st_store(rtmodt_stab *p, int first, int count) {
 int st_process(rtmodt_stab *p, rtmodt_gmc *gmc, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride, int dst_mem_kind,
                const int32_t *streams, int n, const float *warps, const uint8_t *valid, const float *mask_xyxy, const float *mask_conf, const int32_t *mask_n) {
     RT_CHECK(p && n >= 0 && (n == 0 || (src && dst)), RTMODT_E_INVALID, "null argument");
-    p->timed = false;
+    p->timer.timed = false;
     if (n == 0) return RTMODT_OK;
     const rtmodt_stab_cfg &c = p->cfg;
     RT_CHECK(n <= c.streams, RTMODT_E_CAPACITY, "%d frames in one call for %d streams", n, c.streams);
@@ -211,18 +207,7 @@ int st_process(rtmodt_stab *p, rtmodt_gmc *gmc, const uint8_t *const *src, int s
         RT_CHECK(!p->seen[s], RTMODT_E_INVALID, "stream %d is named twice in one call", s);
         p->seen[s] = 1;
     }
-    {   // a gather cannot work in place: no destination range may meet a source range of the call
-        const size_t sspan = st_span(c.h, c.w, src_stride), dspan = st_span(c.h, c.w, dst_stride);
-        std::vector<uintptr_t> starts(n);
-        for (int i = 0; i < n; ++i) starts[i] = (uintptr_t)src[i];
-        std::sort(starts.begin(), starts.end());
-        for (int i = 0; i < n; ++i) {
-            const uintptr_t a = (uintptr_t)dst[i], b = a + dspan;
-            // the source with the largest start below b; all spans are equal, so it is the one that reaches furthest
-            const auto it = std::lower_bound(starts.begin(), starts.end(), b);
-            RT_CHECK(it == starts.begin() || *(it - 1) + sspan <= a, RTMODT_E_INVALID, "destination frame %d overlaps a source frame of the call", i);
-        }
-    }
+    RT_TRY(check_not_in_place(src, c.h, c.w, src_stride, dst, c.h, c.w, dst_stride, n));
     if (!gmc && warps)
         for (int i = 0; i < n; ++i)
             RT_CHECK((valid && !valid[i]) || stab_input_ok(warps + 6 * i), RTMODT_E_INVALID, "warp %d is not finite or has |det| < 1e-6", i);
@@ -264,15 +249,15 @@ int st_process(rtmodt_stab *p, rtmodt_gmc *gmc, const uint8_t *const *src, int s
     wa.h = c.h; wa.w = c.w; wa.tiles_x = cdiv(c.w, 64 * ST_RUN);
     wa.border = (uint32_t)c.border_bgr[0] | (uint32_t)c.border_bgr[1] << 8 | (uint32_t)c.border_bgr[2] << 16;
     const dim3 grid((unsigned)(wa.tiles_x * cdiv(c.h, ST_ROWS)), (unsigned)n), block(ST_THREADS);
-    RT_HIP(hipEventRecord(p->ev0, q));
+    RT_TRY(p->timer.record(0, q));
     hipLaunchKernelGGL(stab_step_kernel, dim3(cdiv(n, 64)), dim3(64), 0, q, sa);
     if (wide) hipLaunchKernelGGL(stab_warp_kernel<true>, grid, block, 0, q, wa);
     else hipLaunchKernelGGL(stab_warp_kernel<false>, grid, block, 0, q, wa);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(p->ev1, q));
+    RT_TRY(p->timer.record(1, q));
     RT_TRY(p->sout.copy_out(dst, q));
     RT_HIP(hipStreamSynchronize(q));
-    p->timed = true;
+    p->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -289,13 +274,11 @@ void rtmodt_stab_default_cfg(rtmodt_stab_cfg *cfg) {
 
 void rtmodt_stab_destroy(rtmodt_stab *p) {
     if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    hipFree(p->d_state);
-    p->cmd.release(); p->sin.release(); p->sout.release();
-    if (p->ev0) hipEventDestroy(p->ev0);
-    if (p->ev1) hipEventDestroy(p->ev1);
-    if (p->stream) hipStreamDestroy(p->stream);
+    handle_close(p, [&] {
+        hipFree(p->d_state);
+        p->cmd.release(); p->sin.release(); p->sout.release();
+        p->timer.destroy();
+    });
     delete p;
 }
 
@@ -310,22 +293,12 @@ int rtmodt_stab_create(const rtmodt_stab_cfg *cfg, rtmodt_stab **out) {
     p->rule = r;
     p->h_state.assign(cfg->streams, st_fresh(r));
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(p->device));
-        RT_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        RT_HIP(hipEventCreate(&p->ev0));
-        RT_HIP(hipEventCreate(&p->ev1));
+        RT_TRY(handle_open(p));
+        RT_TRY(p->timer.create());
         RT_HIP(hipMalloc((void **)&p->d_state, (size_t)cfg->streams * sizeof(StDev)));
         return st_store(p, 0, cfg->streams);
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_stab_destroy(p);
-        last_error() = keep;
-        return rc;
-    }
-    *out = p;
-    return RTMODT_OK;
+    return handle_created(body(), p, rtmodt_stab_destroy, out);
 }
 
 int rtmodt_stab_reset(rtmodt_stab *p, int stream) {
@@ -385,10 +358,7 @@ int rtmodt_stab_load_state(rtmodt_stab *p, int stream, const double *j, int32_t 
 
 int rtmodt_stab_last_ms(rtmodt_stab *p, float *kernel_ms) {
     RT_CHECK(p && kernel_ms, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(p->timed, RTMODT_E_INVALID, "no process call has launched yet");
-    RT_HIP(hipSetDevice(p->device));
-    RT_HIP(hipEventElapsedTime(kernel_ms, p->ev0, p->ev1));
-    return RTMODT_OK;
+    return p->timer.elapsed(p->device, 0, 1, kernel_ms, "no process call has launched yet");
 }
 
 int rtmodt_stab_points(const rtmodt_stab_cfg *cfg, const double *j, int to_source, const double *xy, int n, double *out_xy) {

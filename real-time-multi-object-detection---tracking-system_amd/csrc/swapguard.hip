@@ -34,6 +34,7 @@
 
 #include "kernels.h"
 #include "frame_stage.h"
+#include "handle_host.h"
 #include "lap.h"
 #include "track_layout.h"
 
@@ -375,12 +376,10 @@ __global__ __launch_bounds__(SG_THREADS) void swapguard_step(SgArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_swapguard {
+struct rtmodt_swapguard : HandleBase {
     rtmodt_swapguard_cfg cfg{};
-    int device = 0, S = 1, Mc = 0, cap = 0, H = 0, max_events = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_t[4] = {};
-    bool timed = false;
+    int S = 1, Mc = 0, cap = 0, H = 0, max_events = 0;
+    EventTimer<4> timer;
     char *pool = nullptr;                 // every device array below lives in this one allocation
     SgLedger *d_ledgers = nullptr;
     std::vector<SgLedger> h_ledgers;
@@ -444,21 +443,21 @@ int sg_stage(rtmodt_swapguard *g, const uint8_t *const *frames, int count, int f
 // describe + step for streams [s0, s0 + cnt) on stream q; the passed lists are in place
 int sg_run(rtmodt_swapguard *g, SgArgs a, int s0, int cnt, int boxes, const AppFrames &fp, int fh, int fw, int pitch, hipStream_t q) {
     const size_t o = (size_t)s0 * g->Mc;
-    RT_HIP(hipEventRecord(g->ev_t[1], q));
+    RT_TRY(g->timer.record(1, q));
     DescribeArgs d{};
     d.frames = fp; d.h = fh; d.w = fw; d.pitch = pitch;
     d.box = g->g_box + o; d.box_n = g->g_n + s0; d.box_stride = g->Mc; d.max_boxes = boxes;
     d.counts = g->d_counts + o * APP_DIM; d.desc = g->d_desc + o * APP_DIM; d.desc_stride = g->Mc;
     RT_TRY(launch_describe(d, cnt, q));
-    RT_HIP(hipEventRecord(g->ev_t[2], q));
+    RT_TRY(g->timer.record(2, q));
     const size_t smem = sg_smem(g);
     static DynLdsSeen seen;
     RT_TRY(raise_dynamic_lds((const void *)swapguard_step, smem, seen));
     a.stream_base = s0;
     hipLaunchKernelGGL(swapguard_step, dim3(cnt), dim3(SG_THREADS), smem, q, a);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(g->ev_t[3], q));
-    g->timed = true;
+    RT_TRY(g->timer.record(3, q));
+    g->timer.timed = true;
     return RTMODT_OK;
 }
 
@@ -513,12 +512,11 @@ extern "C" {
 
 void rtmodt_swapguard_destroy(rtmodt_swapguard *g) {
     if (!g) return;
-    hipSetDevice(g->device);
-    if (g->stream) hipStreamSynchronize(g->stream);
-    for (auto &e : g->ev_t) if (e) hipEventDestroy(e);
-    hipFree(g->pool); g->stage.release();
-    hipHostFree(g->h_pin);
-    if (g->stream) hipStreamDestroy(g->stream);
+    handle_close(g, [&] {
+        g->timer.destroy();
+        hipFree(g->pool); g->stage.release();
+        hipHostFree(g->h_pin);
+    });
     delete g;
 }
 
@@ -540,26 +538,17 @@ int rtmodt_swapguard_create(const rtmodt_swapguard_cfg *cfg, rtmodt_swapguard **
     for (int i = 0; i < g->Mc; ++i) g->iota[i] = i;
     auto body = [&]() -> int {
         RT_CHECK(sg_smem(g) <= 150 * 1024, RTMODT_E_INVALID, "swap guard: capacity %d needs %zu B of LDS", g->cap, sg_smem(g));
-        RT_HIP(hipSetDevice(g->device));
-        RT_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        for (auto &e : g->ev_t) RT_HIP(hipEventCreate(&e));
+        RT_TRY(handle_open(g));
+        RT_TRY(g->timer.create());
         const size_t total = sg_carve(g, nullptr);
         RT_HIP(hipMalloc((void **)&g->pool, total));
-        RT_HIP(hipMemset(g->pool, 0, total));
+        RT_HIP(handle_zero(g->pool, total, g->stream));
         sg_carve(g, g->pool);
         RT_HIP(hipHostMalloc((void **)&g->h_pin, g->ev_bytes + sizeof(int64_t) * 4 * g->S, hipHostMallocDefault));
-        RT_HIP(hipMemcpy(g->d_ledgers, g->h_ledgers.data(), sizeof(SgLedger) * g->S, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpyAsync(g->d_ledgers, g->h_ledgers.data(), sizeof(SgLedger) * g->S, hipMemcpyHostToDevice, g->stream));      // (behind the zeroing of the pool)
         return RTMODT_OK;
     };
-    const int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_swapguard_destroy(g);
-        last_error() = keep;
-        return rc;
-    }
-    *out = g;
-    return RTMODT_OK;
+    return handle_created(body(), g, rtmodt_swapguard_destroy, out);
 }
 
 int rtmodt_swapguard_process(rtmodt_swapguard *g, int stream, const int64_t *track_ids, const float *xyxy, int n, const uint8_t *frame, int h, int w,
@@ -584,7 +573,7 @@ int rtmodt_swapguard_process(rtmodt_swapguard *g, int stream, const int64_t *tra
     RT_HIP(hipStreamSynchronize(q));                       // `n` and the caller's arrays are pageable
     SgArgs a = sg_args(g, frame_id);
     a.s_ids = g->s_ids;
-    RT_HIP(hipEventRecord(g->ev_t[0], q));                 // (no gather on this path: the interval up to sg_run's first event is empty)
+    RT_TRY(g->timer.record(0, q));                 // (no gather on this path: the interval up to sg_run's first event is empty)
     RT_TRY(sg_run(g, a, stream, 1, n, fp, h, w, stride_bytes, q));
     if (n) RT_HIP(hipMemcpyAsync(ids_out, g->s_ids + o, (size_t)n * 8, hipMemcpyDeviceToHost, q));
     SgEvHost hst;
@@ -603,7 +592,7 @@ int rtmodt_swapguard_process_tracker(rtmodt_swapguard *g, rtmodt_tracker *trk, c
     hipStream_t q = v.stream;                              // the stream the tracker's last update ran on: ordered after it
     AppFrames fp{};
     RT_TRY(sg_stage(g, frames, v.n_streams, h, w, stride_bytes, mem_kind, q, &fp));
-    RT_HIP(hipEventRecord(g->ev_t[0], q));
+    RT_TRY(g->timer.record(0, q));
     SgGatherArgs ga{v.states, v.meta, v.max_tracks, report_tsu, g->Mc, g->g_box, g->g_src, g->g_n, g->d_meta};
     hipLaunchKernelGGL(swapguard_gather, dim3(v.n_streams), dim3(SG_THREADS), 0, q, ga);
     RT_HIP(hipGetLastError());
@@ -670,13 +659,10 @@ int rtmodt_swapguard_counts(rtmodt_swapguard *g, int stream, int64_t *n_reverted
 
 int rtmodt_swapguard_last_ms(rtmodt_swapguard *g, float *describe_ms, float *step_ms) {
     RT_CHECK(g, RTMODT_E_INVALID, "null argument");
-    RT_CHECK(g->timed, RTMODT_E_INVALID, "no call has been timed yet");
-    RT_HIP(hipSetDevice(g->device));
-    RT_HIP(hipEventSynchronize(g->ev_t[3]));
     float gather = 0.f, desc = 0.f, step = 0.f;
-    RT_HIP(hipEventElapsedTime(&gather, g->ev_t[0], g->ev_t[1]));
-    RT_HIP(hipEventElapsedTime(&desc, g->ev_t[1], g->ev_t[2]));
-    RT_HIP(hipEventElapsedTime(&step, g->ev_t[2], g->ev_t[3]));
+    RT_TRY(g->timer.elapsed(g->device, 2, 3, &step, "no call has been timed yet"));      // (the last event first: it waits for the call)
+    RT_TRY(g->timer.elapsed(g->device, 0, 1, &gather, "no call has been timed yet"));
+    RT_TRY(g->timer.elapsed(g->device, 1, 2, &desc, "no call has been timed yet"));
     if (describe_ms) *describe_ms = desc;
     if (step_ms) *step_ms = gather + step;
     return RTMODT_OK;

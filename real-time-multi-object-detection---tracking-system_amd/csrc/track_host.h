@@ -1,15 +1,15 @@
-// track_host.h -- the host skeleton the four tracker handles share (tracker_api.hip: ByteTrack, deepsort.hip, ocsort.hip, botsort.hip): stream
-// and event, the meta rows, the detection staging, and the calls every one of them makes around its own launches.
+// track_host.h -- what the four tracker handles (tracker_api.hip: ByteTrack, deepsort.hip, ocsort.hip, botsort.hip) share on top of
+// handle_host.h: the event that orders them behind a detector, the meta rows, the detection staging, and the calls every one of
+// them makes around its own launches.  A tracker create ends in handle_created like every other.
 #pragma once
 
+#include "handle_host.h"
 #include "kernels.h"
 #include "track_layout.h"
 
 namespace rtmodt {
 
-struct TrackHandleBase {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct TrackHandleBase : HandleBase {
     // An update fed from a detector runs on THAT detector's post-processing stream (ordered behind its NMS, no host hop).
     // The tracker never keeps the foreign stream handle: it records `foreign_done` there, and everything it later does on
     // its own stream (host-fed updates, state read-back, reset, destroy) waits for that event first.
@@ -23,8 +23,7 @@ struct TrackHandleBase {
 static const int64_t track_init_meta[8] = {0, 0, 0, 0, 1, 0, 0, 0};   // cur, n_tracks, err, n_active / n_returned, next_id (tracker.py:55)
 
 inline int track_open(TrackHandleBase *t) {
-    RT_HIP(hipSetDevice(t->device));
-    RT_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    RT_TRY(handle_open(t));
     RT_HIP(hipEventCreateWithFlags(&t->foreign_done, hipEventDisableTiming));
     RT_HIP(hipMalloc((void **)&t->d_meta, sizeof(int64_t) * 8 * t->S));
     RT_HIP(hipHostMalloc((void **)&t->h_meta, sizeof(int64_t) * 8 * t->S, hipHostMallocDefault));
@@ -33,7 +32,7 @@ inline int track_open(TrackHandleBase *t) {
     RT_HIP(hipMemcpy(t->d_meta, t->h_meta, sizeof(int64_t) * 8 * t->S, hipMemcpyHostToDevice));
     const size_t SN = (size_t)t->S * t->Nc;
     RT_HIP(hipMalloc((void **)&t->d_box, SN * 16)); RT_HIP(hipMalloc((void **)&t->d_conf, SN * 4)); RT_HIP(hipMalloc((void **)&t->d_cls, SN * 4));
-    RT_HIP(hipMalloc((void **)&t->d_n, (size_t)t->S * 4)); RT_HIP(hipMemset(t->d_n, 0, (size_t)t->S * 4));
+    RT_HIP(hipMalloc((void **)&t->d_n, (size_t)t->S * 4)); RT_HIP(handle_zero(t->d_n, (size_t)t->S * 4, t->stream));
     return RTMODT_OK;
 }
 
@@ -41,24 +40,12 @@ inline int track_open(TrackHandleBase *t) {
 template <typename F> void track_close(TrackHandleBase *t, F free_own) {
     hipSetDevice(t->device);
     if (t->foreign_done) hipEventSynchronize(t->foreign_done);      // an update may still be queued on a detector's stream
-    if (t->stream) hipStreamSynchronize(t->stream);
-    if (t->foreign_done) hipEventDestroy(t->foreign_done);
-    free_own();
-    hipFree(t->d_meta); hipFree(t->d_box); hipFree(t->d_conf); hipFree(t->d_cls); hipFree(t->d_n);
-    hipHostFree(t->h_meta); hipHostFree(t->h_n);
-    if (t->stream) hipStreamDestroy(t->stream);
-}
-
-// the tail of a create: on failure the handle goes, the error text stays
-template <typename T> int track_created(int rc, T *t, void (*destroy)(T *), T **out) {
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        destroy(t);
-        last_error() = keep;
-        return rc;
-    }
-    *out = t;
-    return RTMODT_OK;
+    handle_close(t, [&] {
+        if (t->foreign_done) hipEventDestroy(t->foreign_done);
+        free_own();
+        hipFree(t->d_meta); hipFree(t->d_box); hipFree(t->d_conf); hipFree(t->d_cls); hipFree(t->d_n);
+        hipHostFree(t->h_meta); hipHostFree(t->h_n);
+    });
 }
 
 // make the tracker's own stream wait for the last update that ran on a detector's stream

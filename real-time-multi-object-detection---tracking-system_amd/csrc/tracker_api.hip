@@ -48,7 +48,7 @@ static int tracker_create_impl(rtmodt_tracker *t) {
     t->h_states.assign(t->S, TrackerState{});
     const size_t total = carve_bytetrack(t->h_states.data(), t->S, t->Mc, nullptr);
     RT_HIP(hipMalloc((void **)&t->pool, total));
-    RT_HIP(hipMemset(t->pool, 0, total));
+    RT_HIP(handle_zero(t->pool, total, t->stream));
     carve_bytetrack(t->h_states.data(), t->S, t->Mc, t->pool);
     RT_HIP(hipMalloc((void **)&t->d_states, sizeof(TrackerState) * t->S));
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(TrackerState) * t->S, hipMemcpyHostToDevice));
@@ -67,7 +67,7 @@ int rtmodt_tracker_create(int device, float track_thresh, int track_buffer, floa
     t->device = device; t->S = n_streams; t->Mc = max_tracks; t->Nc = max_dets;
     t->track_thresh = track_thresh; t->match_thresh = match_thresh; t->track_buffer = track_buffer;
     t->assign_mode = assign_mode; t->cost_limit = 1.0 - (double)match_thresh;
-    return track_created(tracker_create_impl(t), t, rtmodt_tracker_destroy, out);
+    return handle_created(tracker_create_impl(t), t, rtmodt_tracker_destroy, out);
 }
 
 int rtmodt_tracker_set_cost_limit(rtmodt_tracker *t, double cost_limit) {
@@ -223,9 +223,10 @@ int rtmodt_tracker_enable_kalman(rtmodt_tracker *t) {
         RT_CHECK(t->h_meta[8 * s + 1] == 0, RTMODT_E_INVALID, "stream %d already holds tracks: enable the Kalman model before the first update (or after reset)", s);
     const size_t total = carve_bytetrack_kf(t->h_states.data(), t->S, t->Mc, nullptr);
     RT_HIP(hipMalloc((void **)&t->kf_pool, total));
-    RT_HIP(hipMemset(t->kf_pool, 0, total));
+    RT_HIP(handle_zero(t->kf_pool, total, t->stream));
     carve_bytetrack_kf(t->h_states.data(), t->S, t->Mc, t->kf_pool);
     RT_HIP(hipMemcpy(t->d_states, t->h_states.data(), sizeof(TrackerState) * t->S, hipMemcpyHostToDevice));
+    RT_TRY(handle_wait(t->stream));
     t->kalman = true;
     return RTMODT_OK;
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "handle_host.h"
 #include "polygon.h"
 #include "track_layout.h"
 
@@ -204,10 +205,9 @@ __global__ __launch_bounds__(ZN_THREADS) void zones_update(ZoneArgs a) {
 // ======================================================================================
 using namespace rtmodt;
 
-struct rtmodt_zones {
-    int device = 0, S = 1, Mc = 0, cap = 0, Z = 0, n_pts = 0, max_events = 0;
+struct rtmodt_zones : HandleBase {
+    int S = 1, Mc = 0, cap = 0, Z = 0, n_pts = 0, max_events = 0;
     int64_t max_idle = 0;
-    hipStream_t stream = nullptr;
     char *pool = nullptr;                 // every device array below lives in this one allocation
     ZoneTable zt{};
     ZoneLedger *d_ledgers = nullptr;
@@ -298,11 +298,7 @@ extern "C" {
 
 void rtmodt_zones_destroy(rtmodt_zones *z) {
     if (!z) return;
-    hipSetDevice(z->device);
-    if (z->stream) hipStreamSynchronize(z->stream);
-    hipFree(z->pool);
-    hipHostFree(z->h_pin);
-    if (z->stream) hipStreamDestroy(z->stream);
+    handle_close(z, [&] { hipFree(z->pool); hipHostFree(z->h_pin); });
     delete z;
 }
 
@@ -329,32 +325,23 @@ int rtmodt_zones_create(int device, const rtmodt_zone_cfg *zones, int n_zones, i
     z->device = device; z->S = n_streams; z->Mc = max_tracks; z->cap = 2 * max_tracks; z->Z = n_zones; z->n_pts = (int)pts.size();
     z->max_events = max_events; z->max_idle = max_idle_frames;
     auto body = [&]() -> int {
-        RT_HIP(hipSetDevice(device));
-        RT_HIP(hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking));
+        RT_TRY(handle_open(z));
         const size_t total = carve(z, nullptr);
         RT_HIP(hipMalloc((void **)&z->pool, total));
-        RT_HIP(hipMemset(z->pool, 0, total));
+        RT_HIP(handle_zero(z->pool, total, z->stream));             // (the copies below go behind it, on the same stream)
         carve(z, z->pool);
         RT_HIP(hipHostMalloc((void **)&z->h_pin, z->ev_bytes + sizeof(int64_t) * 4 * z->S, hipHostMallocDefault));
-        if (!pts.empty()) RT_HIP(hipMemcpy((void *)z->zt.pts, pts.data(), pts.size() * sizeof(int2), hipMemcpyHostToDevice));
-        RT_HIP(hipMemcpy((void *)z->zt.off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+        if (!pts.empty()) RT_HIP(hipMemcpyAsync((void *)z->zt.pts, pts.data(), pts.size() * sizeof(int2), hipMemcpyHostToDevice, z->stream));
+        RT_HIP(hipMemcpyAsync((void *)z->zt.off, off.data(), off.size() * 4, hipMemcpyHostToDevice, z->stream));
         if (n_zones) {
-            RT_HIP(hipMemcpy((void *)z->zt.dwell, dw.data(), dw.size() * 8, hipMemcpyHostToDevice));
-            RT_HIP(hipMemcpy((void *)z->zt.cooldown, cd.data(), cd.size() * 8, hipMemcpyHostToDevice));
-            RT_HIP(hipMemcpy((void *)z->zt.key, key.data(), key.size() * 4, hipMemcpyHostToDevice));
+            RT_HIP(hipMemcpyAsync((void *)z->zt.dwell, dw.data(), dw.size() * 8, hipMemcpyHostToDevice, z->stream));
+            RT_HIP(hipMemcpyAsync((void *)z->zt.cooldown, cd.data(), cd.size() * 8, hipMemcpyHostToDevice, z->stream));
+            RT_HIP(hipMemcpyAsync((void *)z->zt.key, key.data(), key.size() * 4, hipMemcpyHostToDevice, z->stream));
         }
-        RT_HIP(hipMemcpy(z->d_ledgers, z->h_ledgers.data(), sizeof(ZoneLedger) * z->S, hipMemcpyHostToDevice));
+        RT_HIP(hipMemcpyAsync(z->d_ledgers, z->h_ledgers.data(), sizeof(ZoneLedger) * z->S, hipMemcpyHostToDevice, z->stream));
         return RTMODT_OK;
     };
-    int rc = body();
-    if (rc != RTMODT_OK) {
-        std::string keep = last_error();
-        rtmodt_zones_destroy(z);
-        last_error() = keep;
-        return rc;
-    }
-    *out = z;
-    return RTMODT_OK;
+    return handle_created(body(), z, rtmodt_zones_destroy, out);
 }
 
 int rtmodt_zones_process(rtmodt_zones *z, int stream, const int64_t *track_ids, const float *xyxy, const int32_t *cls, int n, double now,

@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 
 WARMUP, CLEAR, STATIC, SCENE_CHANGE = 0, 1, 2, 3
 STATUS_NAMES = ("warmup", "clear", "static", "scene_change")
@@ -148,7 +149,7 @@ def _region_dict(g) -> dict:
                 attended=g.attended, oid=g.oid, root=g.root)
 
 
-class LeftObjectDetector:
+class LeftObjectDetector(_ffi.Handle):
     """``streams`` models and ledgers for ``height x width`` BGR24 frames.
 
     The model: ``scale`` (1, 2, 4, 8) pixels per cell side; the first ``warmup`` frames only learn (``warm_shift``); afterwards a cell
@@ -182,15 +183,10 @@ class LeftObjectDetector:
         if tracks is not None and tracker is not None:
             raise ValueError("tracks or tracker, not both")
         if tracker is not None:
-            from ..tracking.botsort import _BotSortCore
-            from ..tracking.deepsort import _DeepSortCore
-            from ..tracking.ocsort import _OcSortCore
-            from ..tracking.tracker import _ByteTrackCore
-            core = getattr(tracker, "_core", tracker)
-            for cls, src in ((_ByteTrackCore, TRACKS_BYTETRACK), (_DeepSortCore, TRACKS_DEEPSORT), (_OcSortCore, TRACKS_OCSORT), (_BotSortCore, TRACKS_BOTSORT)):
-                if isinstance(core, cls):
-                    tsu = (1 if getattr(tracker, "report", "matched") == "matched" else 0) if src == TRACKS_BYTETRACK else 0
-                    return _ffi.LeftObjTracks(src, 0, None, None, None, None, core._h, tsu, 0), [tracker]
+            core, suffix, tsu = resolve_tracker(tracker)
+            if suffix is not None:
+                src = {"tracker": TRACKS_BYTETRACK, "deepsort": TRACKS_DEEPSORT, "ocsort": TRACKS_OCSORT, "botsort": TRACKS_BOTSORT}[suffix]
+                return _ffi.LeftObjTracks(src, 0, None, None, None, None, core._h, sum(tsu), 0), [tracker]
             raise TypeError("tracker: the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker (their state is read on the device); "
                             "hand any other tracker's tracks over as lists")
         if tracks is None:
@@ -335,17 +331,6 @@ class LeftObjectDetector:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last ``process`` call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_leftobj_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_leftobj_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_leftobj_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_leftobj_destroy"

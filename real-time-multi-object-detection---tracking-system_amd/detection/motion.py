@@ -65,7 +65,7 @@ class MotionResult:
         return STATUS_NAMES[self.status]
 
 
-class MotionDetector:
+class MotionDetector(_ffi.Handle):
     """``streams`` background models for ``height x width`` BGR24 frames.
 
     ``scale`` (1, 2, 4, 8): pixels per cell side of the luma grid.  ``learn_shift`` (1..8) and ``learn_shift_fg`` (0: never, else
@@ -142,17 +142,6 @@ class MotionDetector:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last ``process`` call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_motion_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_motion_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_motion_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_motion_destroy"

@@ -65,7 +65,7 @@ def slice_merge(cfg: "_ffi.SliceCfg", xyxy, conf, cls, counts, device: int = 0, 
     return (out, ms.value) if want_ms else out
 
 
-class SlicedDetector:
+class SlicedDetector(_ffi.Handle):
     """``Detector`` for frames of one fixed ``frame_size = (width, height)``, run as overlapping tiles plus an overview.
 
     It owns a :class:`Detector` with ``batch = streams * I`` (``I`` images per frame) and ``input_size = tile``; every other
@@ -174,22 +174,14 @@ class SlicedDetector:
 
     def last_ms(self):
         """Device ms (HIP events) of slice_gather of the last enqueue and of slice_merge of the last fetched batch."""
-        a, b = C.c_float(), C.c_float()
-        _ffi.check(_ffi.lib().rtmodt_slicer_last_ms(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return _ffi.last_ms("rtmodt_slicer_last_ms", self._h, 2)
 
     def synchronize(self) -> None:
         self.detector.synchronize()
 
+    _destroy = "rtmodt_slicer_destroy"
+
     def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_slicer_destroy(self._h)        # before the detector: a merge may be queued on its stream
-            self._h = None
+        super().close()                                      # before the detector: a merge may be queued on its stream
         if getattr(self, "detector", None) is not None:
             self.detector.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -29,6 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 
 log = logging.getLogger("rtmodt.events")
 
@@ -76,7 +77,7 @@ def gates_from_zone_configs(zone_configs: Sequence) -> list:
             if z.get("trigger", "intrusion") == "crossing"]
 
 
-class CrossingCounter:
+class CrossingCounter(_ffi.Handle):
     """Counts directional crossings of lines and gates; counts and ledger live on the device, one set per stream."""
 
     def __init__(self, lines: Sequence = (), gates: Sequence = (), *, n_classes: int = 80, device=0, n_streams: int = 1, max_tracks: int = 2048,
@@ -142,24 +143,9 @@ class CrossingCounter:
         this frame); a ``DeepSortTracker`` / ``_DeepSortCore`` its confirmed tracks matched this frame; an ``OcSortTracker`` /
         ``_OcSortCore`` the tracks it returns this frame; a ``BotSortTracker`` / ``_BotSortCore`` its returned tracks matched this
         frame."""
-        from ..tracking.botsort import _BotSortCore
-        from ..tracking.deepsort import _DeepSortCore
-        from ..tracking.ocsort import _OcSortCore
-        from ..tracking.tracker import _ByteTrackCore
-        core = getattr(tracker, "_core", tracker)
+        core, suffix, tsu = resolve_tracker(tracker, "process_tracker", "as a list: process(tracks, frame_id)")
         ev, n = C.cast(self._ev, C.c_void_p), _ffi.ptr(self._n)
-        if isinstance(core, _ByteTrackCore):
-            report = getattr(tracker, "report", "matched")
-            rc = _ffi.lib().rtmodt_crossing_process_tracker(self._h, core._h, int(frame_id), 1 if report == "matched" else 0, ev, n)
-        elif isinstance(core, _DeepSortCore):
-            rc = _ffi.lib().rtmodt_crossing_process_deepsort(self._h, core._h, int(frame_id), 0, ev, n)
-        elif isinstance(core, _OcSortCore):
-            rc = _ffi.lib().rtmodt_crossing_process_ocsort(self._h, core._h, int(frame_id), ev, n)
-        elif isinstance(core, _BotSortCore):
-            rc = _ffi.lib().rtmodt_crossing_process_botsort(self._h, core._h, int(frame_id), ev, n)
-        else:
-            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; hand the tracks of a "
-                            f"{type(tracker).__name__} over as a list: process(tracks, frame_id)")
+        rc = getattr(_ffi.lib(), f"rtmodt_crossing_process_{suffix}")(self._h, core._h, int(frame_id), *tsu, ev, n)
         out = []
         if rc in (_ffi.OK, _ffi.E_CAPACITY):
             for s in range(core.n_streams):
@@ -207,16 +193,7 @@ class CrossingCounter:
                          [[g, int(exy[r, g, 0]), int(exy[r, g, 1]), int(ef[r, g])] for g in range(G) if i >> g & 1]])
         return rows
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_crossing_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_crossing_destroy"
 
     # ------------------------------------------------------------------ internals
     def _emit(self, r, frame_id, stream, class_name) -> CrossingEvent:

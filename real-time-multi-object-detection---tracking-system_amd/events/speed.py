@@ -31,6 +31,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 
 log = logging.getLogger("rtmodt.events")
 
@@ -74,7 +75,7 @@ def percentile_of(hist, bin_mm_s: int, p: float):
     return math.inf
 
 
-class SpeedEstimator:
+class SpeedEstimator(_ffi.Handle):
     """Speed, odometer, alarms, histogram and proximity pairs per stream; ledgers, histograms and planes live on the device."""
 
     def __init__(self, *, mm_per_pixel: Optional[float] = None, plane=None, anchor: str = "foot", window: int = 8, min_samples: int = 2,
@@ -187,25 +188,10 @@ class SpeedEstimator:
     def process_tracker(self, tracker, t_us, class_names=None, *, outputs: bool = True) -> list:
         """All streams of ``tracker`` at once, on its device-resident state; the tracks are those ``CrossingCounter.process_tracker``
         passes for that tracker.  Returns one alarm list per stream."""
-        from ..tracking.botsort import _BotSortCore
-        from ..tracking.deepsort import _DeepSortCore
-        from ..tracking.ocsort import _OcSortCore
-        from ..tracking.tracker import _ByteTrackCore
-        core = getattr(tracker, "_core", tracker)
-        if not isinstance(core, (_ByteTrackCore, _DeepSortCore, _OcSortCore, _BotSortCore)):
-            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; hand the "
-                            f"tracks of a {type(tracker).__name__} over as a list: process(tracks, t_us)")
+        core, suffix, tsu = resolve_tracker(tracker, "process_tracker", "as a list: process(tracks, t_us)")
         t = self._times(t_us, core.n_streams)
         out = C.byref(self._out) if outputs else None
-        L = _ffi.lib()
-        if isinstance(core, _ByteTrackCore):
-            rc = L.rtmodt_speed_process_tracker(self._h, core._h, _ffi.ptr(t), 1 if getattr(tracker, "report", "matched") == "matched" else 0, out)
-        elif isinstance(core, _DeepSortCore):
-            rc = L.rtmodt_speed_process_deepsort(self._h, core._h, _ffi.ptr(t), 0, out)
-        elif isinstance(core, _OcSortCore):
-            rc = L.rtmodt_speed_process_ocsort(self._h, core._h, _ffi.ptr(t), out)
-        else:
-            rc = L.rtmodt_speed_process_botsort(self._h, core._h, _ffi.ptr(t), out)
+        rc = getattr(_ffi.lib(), f"rtmodt_speed_process_{suffix}")(self._h, core._h, _ffi.ptr(t), *tsu, out)
         if not outputs:
             _ffi.check(rc)
             return [[] for _ in range(core.n_streams)]
@@ -252,16 +238,7 @@ class SpeedEstimator:
                          speed, peak, head[r].tolist(), cls, flags, run_s, run_w, int(since[r]) if flags & F_TIMER else None])
         return rows
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_speed_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_speed_destroy"
 
     # ------------------------------------------------------------------ internals
     @staticmethod

@@ -63,7 +63,7 @@ class Zone:
     direction: Optional[str] = None
 
 
-class ZoneEventEngine:
+class ZoneEventEngine(_ffi.Handle):
     """Evaluate tracks against polygon zones and emit events (reference: zone_engine.py:64-157)."""
 
     def __init__(self, zone_configs: list, log_path: str = "logs/events.jsonl", *, device=0, n_streams: int = 1,
@@ -164,16 +164,7 @@ class ZoneEventEngine:
                     cd.append([int(ids[r]), name, float(alert[r, k])])
         return {"occupancy": sorted(occ), "cooldown": sorted(cd)}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_zones_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_zones_destroy"
 
     # ------------------------------------------------------------------ internals
     def _emit(self, zone: Zone, track_id, class_id, class_name, dwell, bbox, centroid, frame_id) -> ZoneEvent:

@@ -124,7 +124,7 @@ def health_decide(counts: dict, cells: int, state: dict, frame_id: int = 0, **cf
     return row.raw, row.learned, [(e.condition, e.kind, e.frame_id) for e in ev[:row.n_events]], new
 
 
-class CameraHealth:
+class CameraHealth(_ffi.Handle):
     """``streams`` camera-health monitors for ``height x width`` BGR24 frames.
 
     ``scale`` (1, 2, 4, 8): pixels per cell side of the luma grid.  A cell is an edge when its coarse gradient reaches
@@ -206,17 +206,6 @@ class CameraHealth:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last ``process`` call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_health_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_health_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_health_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_health_destroy"

@@ -37,7 +37,7 @@ def probe(file) -> _ffi.JpegInfo:
     return info
 
 
-class JpegDecoder:
+class JpegDecoder(_ffi.Handle):
     """Baseline JPEG files -> BGR24 frames on the GPU."""
 
     def __init__(self, *, device=0, max_height: int = 1080, max_width: int = 1920, max_batch: int = 8, max_file_bytes: int = 0) -> None:
@@ -111,20 +111,9 @@ class JpegDecoder:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last batch's kernels (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_jpegdec_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_jpegdec_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_jpegdec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_jpegdec_destroy"
 
     def _open(self) -> None:
         cfg = _ffi.JpegDecCfg(self._max[0], self._max[1], self._max[2], self._max[3])

@@ -132,7 +132,7 @@ def monotonic_r2(dist, r2_max: float = 16.0, step: float = 1e-3) -> float:
     return float(r2[hit[0]]) if hit.size else 0.0
 
 
-class LensCorrector:
+class LensCorrector(_ffi.Handle):
     """``streams`` lenses for BGR24 frames of ``src_size`` -> rectified frames of ``out_size`` (default: the same size).
 
     A pixel that no source pixel reaches, and every tap off the source, reads ``border`` (b, g, r).  A stream has no lens until
@@ -208,20 +208,9 @@ class LensCorrector:
 
     def last_ms(self) -> float:
         """Device time of the last ``process`` call's launch (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_lens_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_lens_last_ms", self._h)
 
     distort_points = staticmethod(distort_points)
     undistort_points = staticmethod(undistort_points)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_lens_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_lens_destroy"

@@ -69,7 +69,7 @@ def map_points(cfg, path, xy, to_source: bool) -> np.ndarray:
     return out
 
 
-class Stabilizer:
+class Stabilizer(_ffi.Handle):
     """``streams`` camera paths for BGR24 frames of ``size``; ``process`` returns the stabilised frames of the same size.
 
     ``leak_shift``: the path decays by ``1 - 2^-leak_shift`` per call, so that slow real drift of the mount (and the drift that
@@ -193,20 +193,12 @@ class Stabilizer:
 
     def last_ms(self) -> float:
         """Device time of the last ``process`` call's two launches (HIP events); the estimator's part is ``gmc.last_ms()``."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_stab_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_stab_last_ms", self._h)
+
+    _destroy = "rtmodt_stab_destroy"
 
     def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_stab_destroy(self._h)
-            self._h = None
+        super().close()
         if getattr(self, "_own_gmc", False) and self.gmc is not None:
             self.gmc.close()
             self.gmc = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

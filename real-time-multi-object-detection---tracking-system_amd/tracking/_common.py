@@ -8,6 +8,31 @@ import numpy as np
 from .. import _ffi
 
 
+def resolve_tracker(tracker, method=None, hint=""):
+    """A tracker front end or core -> ``(core, suffix, tsu)``.  ``suffix`` ends the C symbol that reads that tracker's device-resident
+    state (``rtmodt_<module>_<verb>_<suffix>``: ``tracker`` is ByteTrack) and ``tsu`` is the ``report_tsu`` argument that symbol takes,
+    as a tuple to splice in: ByteTrack passes the tracks ``tracker.report`` names, DeepSORT its confirmed tracks matched this frame,
+    the other two take none.  Anything else raises ``TypeError`` in the words of the caller's ``method`` with its ``hint`` of the list
+    form; without a ``method`` the suffix is ``None`` and the caller refuses it itself."""
+    from .botsort import _BotSortCore
+    from .deepsort import _DeepSortCore
+    from .ocsort import _OcSortCore
+    from .tracker import _ByteTrackCore
+    core = getattr(tracker, "_core", tracker)
+    if isinstance(core, _ByteTrackCore):
+        return core, "tracker", (1 if getattr(tracker, "report", "matched") == "matched" else 0,)
+    if isinstance(core, _DeepSortCore):
+        return core, "deepsort", (0,)
+    if isinstance(core, _OcSortCore):
+        return core, "ocsort", ()
+    if isinstance(core, _BotSortCore):
+        return core, "botsort", ()
+    if method is None:
+        return core, None, ()
+    raise TypeError(f"{method} reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; hand the tracks of a "
+                    f"{type(tracker).__name__} over {hint}")
+
+
 def pad_single_stream(xyxy, confidence, class_id, max_dets: int):
     """One frame's detections as the ``[1, max_dets(, 4)]`` arrays ``update_batch`` takes: ``(bx, cf, cl, n)``."""
     xyxy = np.asarray(xyxy, np.float32).reshape(-1, 4)

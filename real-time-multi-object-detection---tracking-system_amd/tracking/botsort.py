@@ -49,7 +49,7 @@ def check_warp(warp, n_streams: int = 1):
     return warp
 
 
-class _BotSortCore:
+class _BotSortCore(_ffi.Handle):
     """Host face of the device tracker: ``n_streams`` independent states advanced by one call (a fixed number of launches)."""
 
     def __init__(self, track_high_thresh=0.6, track_low_thresh=0.1, new_track_thresh=0.7, track_buffer=30, match_thresh=0.8,
@@ -165,23 +165,12 @@ class _BotSortCore:
 
     def last_ms(self) -> tuple:
         """Device time (ms) of the last update: (descriptors, distance, update)."""
-        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_botsort_last_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return _ffi.last_ms("rtmodt_botsort_last_ms", self._h, 3)
 
     def reset(self, stream: int = -1) -> None:
         _ffi.check(_ffi.lib().rtmodt_botsort_reset(self._h, stream))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_botsort_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_botsort_destroy"
 
 
 class BotSortTracker:

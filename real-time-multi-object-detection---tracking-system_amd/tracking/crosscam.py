@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _ffi
+from ._common import resolve_tracker
 
 NONE, BOUND, LINKED, JOINED, BORN, NO_DESCRIPTOR, DEFERRED, TABLE_FULL, UNBOUND = range(9)
 STATUS_NAMES = ("none", "bound", "linked", "joined", "born", "no_descriptor", "deferred", "table_full", "unbound")
@@ -78,7 +79,7 @@ def similarity(q, t, device=0):
     return dots, sim
 
 
-class CrossCameraLinker:
+class CrossCameraLinker(_ffi.Handle):
     """Site-wide identities over ``n_streams`` cameras; the table and the ledgers live on the device."""
 
     def __init__(self, n_streams: int, dim: int, *, max_tracks: int = 256, max_identities: int = 4096, max_queries: int = 1024,
@@ -150,17 +151,11 @@ class CrossCameraLinker:
         """One call on the device-resident state of a ``BotSortTracker`` (tracked tracks matched this frame, each with its smoothed
         feature) or a ``DeepSortTracker`` (confirmed tracks matched this frame, each with the newest row of its gallery), queued on
         the HIP stream its last update ran on.  The entries come in the tracker's list order; ``global_id`` resolves them."""
-        from .botsort import _BotSortCore
-        from .deepsort import _DeepSortCore
-        core = getattr(tracker, "_core", tracker)
-        out, ne, nr = self._out()
-        if isinstance(core, _BotSortCore):
-            rc = _ffi.lib().rtmodt_crosscam_process_botsort(self._h, core._h, C.byref(out))
-        elif isinstance(core, _DeepSortCore):
-            rc = _ffi.lib().rtmodt_crosscam_process_deepsort(self._h, core._h, C.byref(out))
-        else:
+        core, suffix, _ = resolve_tracker(tracker)
+        if suffix not in ("botsort", "deepsort"):
             raise TypeError(f"{type(tracker).__name__} carries no descriptors on the device; hand its tracks over as lists: process(lists)")
-        _ffi.check(rc)
+        out, ne, nr = self._out()
+        _ffi.check(getattr(_ffi.lib(), f"rtmodt_crosscam_process_{suffix}")(self._h, core._h, C.byref(out)))
         counts = [int(np.count_nonzero(self._status[s])) for s in range(self.n_streams)]
         return self._result(counts, ne, nr)
 
@@ -234,17 +229,6 @@ class CrossCameraLinker:
 
     def last_ms(self) -> float:
         """Device time (ms) of the last call."""
-        v = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_crosscam_last_ms(self._h, C.byref(v)))
-        return float(v.value)
+        return _ffi.last_ms("rtmodt_crosscam_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_crosscam_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_crosscam_destroy"

@@ -38,7 +38,7 @@ def _xyah_to_xyxy(m: np.ndarray) -> np.ndarray:
     return np.stack([x1, y1, x1 + w, y1 + m[:, 3]], 1).astype(np.float32)
 
 
-class _DeepSortCore:
+class _DeepSortCore(_ffi.Handle):
     """Host face of the device tracker: ``n_streams`` independent states advanced by one call (a fixed number of launches)."""
 
     def __init__(self, max_dist=0.2, min_confidence=0.3, max_iou_distance=0.7, max_age=70, n_init=3, nn_budget=100, embedder=BUILTIN_EMBEDDER, *,
@@ -119,23 +119,12 @@ class _DeepSortCore:
 
     def last_ms(self) -> tuple:
         """Device time (ms) of the last update: (descriptors, distance, update)."""
-        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_deepsort_last_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return _ffi.last_ms("rtmodt_deepsort_last_ms", self._h, 3)
 
     def reset(self, stream: int = -1) -> None:
         _ffi.check(_ffi.lib().rtmodt_deepsort_reset(self._h, stream))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_deepsort_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_deepsort_destroy"
 
 
 class DeepSortTracker:

@@ -28,7 +28,7 @@ def default_cfg() -> _ffi.GmcCfg:
     return cfg
 
 
-class CameraMotionEstimator:
+class CameraMotionEstimator(_ffi.Handle):
     """``estimate(frames, detections=None) -> (warp[n, 2, 3], status[n])`` for ``n_streams`` streams at once (a fixed number of
     launches).  The first frame of a stream after construction or :meth:`reset` returns the identity with status ``FIRST``; whenever
     the status is not ``OK`` the warp is exactly the identity.  ``detections``: per stream ``None`` or something with ``xyxy`` and
@@ -124,20 +124,9 @@ class CameraMotionEstimator:
                     inl=inl[:, :n].copy(), sums=sums, model=model)
 
     def last_ms(self) -> float:
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_gmc_last_ms(self._h, C.byref(ms)))
-        return ms.value
+        return _ffi.last_ms("rtmodt_gmc_last_ms", self._h)
 
     def reset(self, stream: int = -1) -> None:
         _ffi.check(_ffi.lib().rtmodt_gmc_reset(self._h, int(stream)))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_gmc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_gmc_destroy"

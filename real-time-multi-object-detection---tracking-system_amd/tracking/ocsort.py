@@ -22,7 +22,7 @@ DEFAULT_MAX_TRACKS = 256
 DEFAULT_MAX_DETS = 1024
 
 
-class _OcSortCore:
+class _OcSortCore(_ffi.Handle):
     """Host face of the device tracker: ``n_streams`` independent states advanced by one call (one launch)."""
 
     def __init__(self, det_thresh=0.6, low_thresh=0.1, max_age=30, min_hits=3, iou_threshold=0.3, delta_t=3, inertia=0.2, use_byte=False, *,
@@ -87,23 +87,12 @@ class _OcSortCore:
 
     def last_ms(self) -> float:
         """Device time (ms) of the last update's launch."""
-        a = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_ocsort_last_ms(self._h, C.byref(a)))
-        return a.value
+        return _ffi.last_ms("rtmodt_ocsort_last_ms", self._h)
 
     def reset(self, stream: int = -1) -> None:
         _ffi.check(_ffi.lib().rtmodt_ocsort_reset(self._h, stream))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_ocsort_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_ocsort_destroy"
 
 
 class OcSortTracker:

@@ -32,7 +32,7 @@ def check_weights_path(path) -> str:
     return path
 
 
-class ReidEmbedder:
+class ReidEmbedder(_ffi.Handle):
     """``embed(frames, boxes, counts) -> (feat, desc)`` for up to ``max_frames`` frames of up to ``max_boxes`` boxes each."""
 
     def __init__(self, weights, device=0, max_boxes: int = 128, max_frames: int = 8) -> None:
@@ -80,17 +80,6 @@ class ReidEmbedder:
 
     def last_ms(self) -> tuple:
         """Device time (ms) of the last embed: (crop, network + quantiser)."""
-        a, b = C.c_float(0), C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_reid_last_ms(self._h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return _ffi.last_ms("rtmodt_reid_last_ms", self._h, 2)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_reid_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_reid_destroy"

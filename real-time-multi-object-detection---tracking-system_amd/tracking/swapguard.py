@@ -50,7 +50,7 @@ class SwapEvent:
     stream: int = 0
 
 
-class IdSwapGuard:
+class IdSwapGuard(_ffi.Handle):
     """Reverts ByteTrack ID swaps by appearance; ledgers live on the device, one per stream."""
 
     def __init__(self, *, history: int = 5, min_history: int = 3, window: int = 3, min_similarity: float = 0.85, min_gain_pm: int = 1,
@@ -145,20 +145,10 @@ class IdSwapGuard:
 
     def last_ms(self) -> dict:
         """Device time of the last call: ``describe`` (the descriptor launches) and ``step`` (gather + decision kernel)."""
-        d, s = C.c_float(0), C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_swapguard_last_ms(self._h, C.byref(d), C.byref(s)))
-        return {"describe": float(d.value), "step": float(s.value)}
+        d, s = _ffi.last_ms("rtmodt_swapguard_last_ms", self._h, 2)
+        return {"describe": d, "step": s}
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_swapguard_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_swapguard_destroy"
 
     @staticmethod
     def _emit(r, stream) -> SwapEvent:

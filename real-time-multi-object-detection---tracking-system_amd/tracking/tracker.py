@@ -38,7 +38,7 @@ class Track:
     trail: list = field(default_factory=list)
 
 
-class _ByteTrackCore:
+class _ByteTrackCore(_ffi.Handle):
     """Host face of the device tracker (reference: tracker.py:43-148).  ``n_streams``
     independent states are advanced by one kernel launch (one workgroup each)."""
 
@@ -143,16 +143,7 @@ class _ByteTrackCore:
     def reset(self, stream: int = -1) -> None:
         _ffi.check(_ffi.lib().rtmodt_tracker_reset(self._h, stream))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_tracker_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_tracker_destroy"
 
 
 class MultiObjectTracker:

@@ -101,7 +101,7 @@ def plan_layout(sources, outputs, cells) -> list:
     return [CellPlan(tuple(out[i].crop), tuple(out[i].inner), KINDS[out[i].kind_x], KINDS[out[i].kind_y]) for i in range(len(cells))]
 
 
-class Compositor:
+class Compositor(_ffi.Handle):
     """A layout on the device and the runs over it.  ``sources``: ``[(h, w)]``; ``outputs``: ``[Output]``; ``cells``: ``[Cell]`` in
     painting order.  The layout is checked and planned by the library when it is set; a rejected one raises and changes nothing."""
 
@@ -286,17 +286,6 @@ class Compositor:
 
     def last_ms(self) -> float:
         """Device time of the last run's launch (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_compose_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_compose_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_compose_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_compose_destroy"

@@ -18,6 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 from .privacy import boxes_of
 
 FOOTPRINTS = {"box": 0, "disc": 1, "foot": 2}
@@ -56,7 +57,7 @@ def footprint_cells(box, cls, height: int, width: int, **cfg_kw) -> np.ndarray:
     return out[:need.value].copy()
 
 
-class Heatmap:
+class Heatmap(_ffi.Handle):
     """One grid of ``ceil(height / cell) x ceil(width / cell)`` ``uint32`` cells per stream.
 
     ``cell``: 1, 2, 4, 8 or 16 pixels.  ``footprint``: ``"box"`` (every cell the box touches), ``"disc"`` (the cells within
@@ -98,24 +99,8 @@ class Heatmap:
     def accumulate_tracker(self, tracker) -> None:
         """One frame of every stream from the tracker's device-resident tracks: those ``PrivacyMask.apply_tracker`` masks.
         Dispatches on the tracker class; the tracker must have as many streams as the heatmap."""
-        from ..tracking.botsort import _BotSortCore
-        from ..tracking.deepsort import _DeepSortCore
-        from ..tracking.ocsort import _OcSortCore
-        from ..tracking.tracker import _ByteTrackCore
-        core = getattr(tracker, "_core", tracker)
-        L = _ffi.lib()
-        if isinstance(core, _ByteTrackCore):
-            rc = L.rtmodt_heatmap_accumulate_tracker(self._h, core._h, 1 if getattr(tracker, "report", "matched") == "matched" else 0)
-        elif isinstance(core, _DeepSortCore):
-            rc = L.rtmodt_heatmap_accumulate_deepsort(self._h, core._h, 0)
-        elif isinstance(core, _OcSortCore):
-            rc = L.rtmodt_heatmap_accumulate_ocsort(self._h, core._h)
-        elif isinstance(core, _BotSortCore):
-            rc = L.rtmodt_heatmap_accumulate_botsort(self._h, core._h)
-        else:
-            raise TypeError(f"accumulate_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT "
-                            f"tracker; hand the tracks of a {type(tracker).__name__} over as lists: accumulate([tracks])")
-        _ffi.check(rc)
+        core, suffix, tsu = resolve_tracker(tracker, "accumulate_tracker", "as lists: accumulate([tracks])")
+        _ffi.check(getattr(_ffi.lib(), f"rtmodt_heatmap_accumulate_{suffix}")(self._h, core._h, *tsu))
 
     def accumulate_detector(self, detector) -> None:
         """One frame of every stream from every detection of ``detector``'s newest batch (frame i -> stream i), read from its
@@ -180,17 +165,6 @@ class Heatmap:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last accumulate or overlay call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_heatmap_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_heatmap_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_heatmap_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_heatmap_destroy"

@@ -35,7 +35,7 @@ def header(quality: int, height: int, width: int) -> bytes:
     return buf.tobytes()
 
 
-class JpegEncoder:
+class JpegEncoder(_ffi.Handle):
     """Baseline JPEG (4:2:0) of BGR24 frames on the GPU."""
 
     def __init__(self, quality: int = 95, *, device=0, max_height: int = 1080, max_width: int = 1920, max_batch: int = 8) -> None:
@@ -88,20 +88,9 @@ class JpegEncoder:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last batch's kernels (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_jpeg_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_jpeg_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_jpeg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_jpeg_destroy"
 
     def _open(self) -> None:
         cfg = _ffi.JpegCfg(self.quality, 0, self._max[0], self._max[1], self._max[2])

@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 
 MODES = {"fill": 0, "pixelate": 1, "blur": 2}
 REGIONS = {"box": 0, "head": 1}
@@ -96,7 +97,7 @@ def boxes_of(tracks):
     return xy, cl
 
 
-class PrivacyMask:
+class PrivacyMask(_ffi.Handle):
     """Masks boxes (whole, or their head rows), optionally of some classes only, and fixed privacy polygons.
 
     ``mode``: ``"fill"`` (``color``, BGR), ``"pixelate"`` (``cell`` 2..64) or ``"blur"`` (``passes`` 1..3 box filters of radius
@@ -160,28 +161,11 @@ class PrivacyMask:
                       offset: int = 0):
         """Masks ``frames`` (one per stream of ``tracker``) in place with the tracker's device-resident tracks: those the
         crossing counter's ``process_tracker`` passes.  Dispatches on the tracker class; returns ``frames``."""
-        from ..tracking.botsort import _BotSortCore
-        from ..tracking.deepsort import _DeepSortCore
-        from ..tracking.ocsort import _OcSortCore
-        from ..tracking.tracker import _ByteTrackCore
-        core = getattr(tracker, "_core", tracker)
-        if not isinstance(core, (_ByteTrackCore, _DeepSortCore, _OcSortCore, _BotSortCore)):
-            raise TypeError(f"apply_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; "
-                            f"hand the tracks of a {type(tracker).__name__} over as a list: apply(frame, tracks)")
+        core, suffix, tsu = resolve_tracker(tracker, "apply_tracker", "as a list: apply(frame, tracks)")
         n = core.n_streams
         ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=height, width=width, stride=stride, offset=offset)
         fp = (C.c_void_p * max(n, 1))(*ptrs)
-        L = _ffi.lib()
-        if isinstance(core, _ByteTrackCore):
-            report = getattr(tracker, "report", "matched")
-            rc = L.rtmodt_privacy_apply_tracker(self._h, core._h, fp, h, w, st, mem, 1 if report == "matched" else 0)
-        elif isinstance(core, _DeepSortCore):
-            rc = L.rtmodt_privacy_apply_deepsort(self._h, core._h, fp, h, w, st, mem, 0)
-        elif isinstance(core, _OcSortCore):
-            rc = L.rtmodt_privacy_apply_ocsort(self._h, core._h, fp, h, w, st, mem)
-        else:
-            rc = L.rtmodt_privacy_apply_botsort(self._h, core._h, fp, h, w, st, mem)
-        _ffi.check(rc)
+        _ffi.check(getattr(_ffi.lib(), f"rtmodt_privacy_apply_{suffix}")(self._h, core._h, fp, h, w, st, mem, *tsu))
         return frames
 
     def apply_detector(self, detector, frames, *, height: Optional[int] = None, width: Optional[int] = None, stride: Optional[int] = None,
@@ -196,17 +180,6 @@ class PrivacyMask:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_privacy_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_privacy_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_privacy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_privacy_destroy"

@@ -38,7 +38,7 @@ def hud_text(fps: float, latency_ms: float) -> str:
     return f"FPS: {fps:.1f} | Latency: {latency_ms:.1f}ms"
 
 
-class FrameRenderer:
+class FrameRenderer(_ffi.Handle):
     """Draw detection + tracking annotations on frames (reference: renderer.py:28-96)."""
 
     def __init__(self, show_boxes: bool = True, show_ids: bool = True, show_trails: bool = True, trail_length: int = 30,
@@ -88,25 +88,14 @@ class FrameRenderer:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last batch's kernel (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_renderer_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_renderer_last_ms", self._h)
 
     def pack(self, tracks_per_frame: Sequence[Sequence], height: int, width: int, zones: bool = False, fps: float = 0.0,
              latency_ms: float = 0.0) -> bytes:
         """The command buffer ``render_batch`` would send for these lists (host only; frame pointers 0)."""
         return pack(self._cfg(), tracks_per_frame, height, width, zones, fps, latency_ms)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_renderer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_renderer_destroy"
 
     # ------------------------------------------------------------------ internals
     def _open(self) -> None:

@@ -19,6 +19,7 @@ from typing import Callable, Iterable, Optional, Sequence
 import numpy as np
 
 from .. import _ffi
+from ..tracking._common import resolve_tracker
 
 F_NEW, F_REWRITTEN, F_CUT, F_OCCLUDED = 1, 2, 4, 8
 
@@ -63,7 +64,7 @@ class _AtlasView(_ffi.DeviceBuffer):
         self.ptr = None
 
 
-class SnapshotGallery:
+class SnapshotGallery(_ffi.Handle):
     """Best-shot thumbnails of ``thumb = (h, w)`` pixels for ``n_streams`` streams of at most ``max_tracks`` tracks each."""
 
     def __init__(self, thumb=(96, 96), *, n_streams: int = 1, max_tracks: int = 256, margin_pm: Optional[int] = None, min_side: Optional[int] = None,
@@ -119,14 +120,7 @@ class SnapshotGallery:
         passes.  ``frames``: one per stream (host arrays or a ``DeviceBuffer``); ``frame_ids``: one per stream, or one for all.
         Dispatches on the tracker class; returns ``(updated, retired)``.  The gallery must hold at least the tracker's streams and
         ``max_tracks`` (a ``MultiObjectTracker`` holds 2048 by default): ``ValueError`` otherwise."""
-        from ..tracking.botsort import _BotSortCore
-        from ..tracking.deepsort import _DeepSortCore
-        from ..tracking.ocsort import _OcSortCore
-        from ..tracking.tracker import _ByteTrackCore
-        core = getattr(tracker, "_core", tracker)
-        if not isinstance(core, (_ByteTrackCore, _DeepSortCore, _OcSortCore, _BotSortCore)):
-            raise TypeError(f"process_tracker reads the device-resident state of the ByteTrack, the DeepSORT, the OC-SORT or the BoT-SORT tracker; "
-                            f"hand the tracks of a {type(tracker).__name__} over as a list: process(tracks, frame, frame_id)")
+        core, suffix, tsu = resolve_tracker(tracker, "process_tracker", "as a list: process(tracks, frame, frame_id)")
         n = core.n_streams
         if n > self.n_streams or core.max_tracks > self.max_tracks:
             raise ValueError(f"the tracker holds {n} stream(s) of up to {core.max_tracks} tracks, this gallery {self.n_streams} of {self.max_tracks}: "
@@ -134,16 +128,7 @@ class SnapshotGallery:
         ptrs, h, w, st, mem, _ = _ffi.batch_frames(frames, n, height=height, width=width, stride=stride, offset=offset, writable=False)
         fp = (C.c_void_p * max(n, 1))(*ptrs)
         fid = np.ascontiguousarray(np.broadcast_to(np.asarray(frame_ids, np.int64), (n,)))
-        L, out = _ffi.lib(), C.byref(self._out)
-        if isinstance(core, _ByteTrackCore):
-            report = getattr(tracker, "report", "matched")
-            rc = L.rtmodt_snapshot_process_tracker(self._h, core._h, fp, h, w, st, mem, _ffi.ptr(fid), 1 if report == "matched" else 0, out)
-        elif isinstance(core, _DeepSortCore):
-            rc = L.rtmodt_snapshot_process_deepsort(self._h, core._h, fp, h, w, st, mem, _ffi.ptr(fid), 0, out)
-        elif isinstance(core, _OcSortCore):
-            rc = L.rtmodt_snapshot_process_ocsort(self._h, core._h, fp, h, w, st, mem, _ffi.ptr(fid), out)
-        else:
-            rc = L.rtmodt_snapshot_process_botsort(self._h, core._h, fp, h, w, st, mem, _ffi.ptr(fid), out)
+        rc = getattr(_ffi.lib(), f"rtmodt_snapshot_process_{suffix}")(self._h, core._h, fp, h, w, st, mem, _ffi.ptr(fid), *tsu, C.byref(self._out))
         return self._collect(rc, list(range(n)), flat=False)
 
     # ---- reading -------------------------------------------------------------------------------------------------------
@@ -225,20 +210,9 @@ class SnapshotGallery:
 
     def last_kernel_ms(self) -> float:
         """Device time of the last call's launches (HIP events)."""
-        ms = C.c_float(0)
-        _ffi.check(_ffi.lib().rtmodt_snapshot_last_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return _ffi.last_ms("rtmodt_snapshot_last_ms", self._h)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _ffi.lib().rtmodt_snapshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "rtmodt_snapshot_destroy"
 
     # ---- internals -----------------------------------------------------------------------------------------------------
     @staticmethod
