@@ -1927,6 +1927,84 @@ int rtmodt_crosscam_last_ms(rtmodt_crosscam *h, float *kernel_ms);
  * [nq][nt] by rule 3; either output may be null.  nq <= 1024, nt <= 4096.  Synchronous. */
 int rtmodt_crosscam_similarity(int device, const int8_t *q, int nq, const int8_t *t, int nt, int dim, int32_t *dots, int32_t *sim);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Appearance index (csrc/index.hip; the per-row rules in csrc/index_rule.h): a device-resident, append-only ring of descriptor
+ * rows with metadata, searched by similarity: "where else, and when, did this one appear?".  Up to 64 queries per call get the
+ * exact, deterministic top-k under filters.  The reference has no counterpart (its Track has no descriptor, its web API answers
+ * with the detections of one image).  PARITY UNPINNED: no published vector index is installed where this runs (and none of them
+ * ranks in integers); tests/index_ref.py restates the rules below and every output equals it.
+ *
+ * A ROW holds dim int8 values, rid (from 1, never reused, below 2^40), key (the caller's: a gid, or stream and track id packed),
+ * stream (0..63), cls, t (the caller's clock), n2 = sum v^2 (computed on the device at add) and a dead flag.  Row rid lives in
+ * slot (rid - 1) % capacity; a newer row overwrites the oldest.  next_rid lives on the device.
+ *   similarity   dot = <q, row> exact in int32; ppm = dot <= 0 ? 0 : min(1000000, 1000000 dot / max(1, isqrt(|q|^2 n2))), floor
+ *                division; ppm / 1000 is rule 3 of the cross-camera linker;
+ *   eligibility  the slot is filled and the row not dead; t0 <= t <= t1; bit `stream` of stream_mask is set; cls < 0 or the row's
+ *                class equals it; key != exclude_key (INT64_MIN: none); ppm >= min_ppm (1..1000000).  A zero row never is;
+ *   rank         ppm << 40 | rid, descending: the best similarity first, the newest row first on a tie.  Ranks are distinct, so
+ *                the top-k is unique.
+ * Not here: approximate indexes (IVF / PQ / HNSW), thumbnails of the hits.  Every entry point waits for what it queued. */
+typedef struct rtmodt_index rtmodt_index;
+#define RTMODT_INDEX_NO_KEY INT64_MIN
+typedef struct rtmodt_index_cfg {
+    int32_t device;
+    int32_t dim;             /* 64..512 in multiples of 64                                                     */
+    int32_t capacity;        /* rows of the ring, 1..2^22                                                      */
+    int32_t max_queries;     /* per search, 1..64                                                              */
+    int32_t max_k;           /* 1..64                                                                          */
+    int32_t max_add;         /* rows per add, 1..65536                                                         */
+    int32_t chunk_rows;      /* rows one workgroup scans: 0 = chosen by the library, else a multiple of 64 that
+                              * cuts capacity into at most 256 chunks                                          */
+} rtmodt_index_cfg;
+typedef struct rtmodt_index_filter {
+    int64_t t0, t1;          /* inclusive                                                                      */
+    uint64_t stream_mask;
+    int64_t exclude_key;     /* RTMODT_INDEX_NO_KEY: none                                                      */
+    int32_t cls;             /* < 0: any                                                                       */
+    int32_t min_ppm;         /* 1..1000000                                                                     */
+} rtmodt_index_filter;
+typedef struct rtmodt_index_hit {
+    int64_t rid, key, t;
+    int32_t stream, cls, ppm, reserved;
+} rtmodt_index_hit;
+void rtmodt_index_default_cfg(rtmodt_index_cfg *cfg);
+/* A parameter outside its range is RTMODT_E_INVALID with nothing allocated. */
+int rtmodt_index_create(const rtmodt_index_cfg *cfg, rtmodt_index **out);
+/* Waits for the handle's queued work, frees everything; null is allowed. */
+void rtmodt_index_destroy(rtmodt_index *h);
+/* Appends n rows [n][dim] from host or device memory (mem_kind: RTMODT_MEM_*) with their host arrays keys / streams / cls / t
+ * [n].  The rows get next_rid .. in list order, their norms are computed on the device; *first_rid (may be null) is the first
+ * one.  n > max_add, or a stream outside 0..63, is RTMODT_E_INVALID with nothing changed.  Two launches. */
+int rtmodt_index_add(rtmodt_index *h, const int8_t *rows, int mem_kind, const int64_t *keys, const int32_t *streams, const int32_t *cls,
+                     const int64_t *t, int n, int64_t *first_rid);
+/* Appends from a cross-camera linker's device-resident table, queued behind the linker's last _process* on the stream that ran
+ * on.  With c the call the linker just made: an identity is appended when max over s of last_seen[s] == c and (c - first_seen)
+ * % every == 0, as a row with key = gid, stream = the lowest s with last_seen[s] == c, its class, its s8 and time t; in gid
+ * order (a workgroup prefix sum, no atomic).  *n_added (may be null) is the count.  A linker of another dim or device, one with
+ * max_identities > max_add, or every < 1 is RTMODT_E_INVALID with nothing changed.  Three launches. */
+int rtmodt_index_add_crosscam(rtmodt_index *h, rtmodt_crosscam *linker, int64_t t, int every, int32_t *n_added);
+/* nq query rows [nq][dim] (host) with one filter each, k hits at most per query: hits [nq][k] in rank order, unused entries
+ * zero, n_hits [nq].  nq > max_queries, k > max_k or a min_ppm outside 1..1000000 is RTMODT_E_INVALID with nothing launched.
+ * Two launches whatever the archive holds (the scan reads rows and metadata once for all queries and writes no product; the
+ * merge picks the k best of the chunks' lists), the outputs in one copy. */
+int rtmodt_index_search(rtmodt_index *h, const int8_t *queries, int nq, const rtmodt_index_filter *filters, int k, rtmodt_index_hit *hits,
+                        int32_t *n_hits);
+/* Every live row whose key is among keys [n <= 4096] becomes dead (it stays in its slot until overwritten and is never a hit
+ * again); *n_marked (may be null) is how many rows that were. */
+int rtmodt_index_forget(rtmodt_index *h, const int64_t *keys, int n, int64_t *n_marked);
+/* The whole archive in slot order (the parity surface of tests/index_ref.py, and what a restart carries over); any array but
+ * header may be null.  header[2] = {next_rid, rows in the ring}; rows [capacity][dim]; rid / key / t (int64), stream / cls / n2 /
+ * dead (int32) [capacity]; an empty slot has rid 0 and zeros everywhere. */
+int rtmodt_index_state(rtmodt_index *h, int64_t *header, int8_t *rows, int64_t *rid, int64_t *key, int64_t *t, int32_t *stream, int32_t *cls,
+                       int32_t *n2, int32_t *dead);
+/* Replaces the archive by one rtmodt_index_state gave (same dim and capacity; n2 is computed again).  A rid that is not the one
+ * its slot holds at next_rid (so also a rid >= next_rid), a stream outside 0..63 or a dead flag other than 0 / 1 is
+ * RTMODT_E_INVALID and changes nothing. */
+int rtmodt_index_load(rtmodt_index *h, int64_t next_rid, const int8_t *rows, const int64_t *rid, const int64_t *key, const int64_t *t,
+                      const int32_t *stream, const int32_t *cls, const int32_t *dead);
+/* Device time (ms, HIP events around the launches) of the last add / add_crosscam and of the last search. */
+int rtmodt_index_last_ms(rtmodt_index *h, float *add_ms, float *search_ms);
+
 /* ---- compositor: video-wall mosaics, sub-streams and zoom insets, BGR24 or 4:2:0 out ---- */
 /* A static LAYOUT (sources, outputs, cells) is set once and kept on the device; one RUN per frame set reads the sources where they
  * lie and writes every output in ONE launch.  csrc/compose_rule.h states every rule (crop, fit, the three kinds of axis, the

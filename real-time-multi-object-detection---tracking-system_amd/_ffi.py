@@ -390,6 +390,19 @@ class CrossCamOut(C.Structure):                      # struct rtmodt_crosscam_ou
                 ("retired", C.c_void_p), ("n_retired", C.POINTER(C.c_int32)), ("counters", C.c_void_p)]
 
 
+class IndexCfg(C.Structure):                         # struct rtmodt_index_cfg
+    _fields_ = [(k, C.c_int32) for k in ("device", "dim", "capacity", "max_queries", "max_k", "max_add", "chunk_rows")]
+
+
+class IndexFilter(C.Structure):                      # struct rtmodt_index_filter
+    _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("stream_mask", C.c_uint64), ("exclude_key", C.c_int64), ("cls", C.c_int32), ("min_ppm", C.c_int32)]
+
+
+class IndexHit(C.Structure):                         # struct rtmodt_index_hit
+    _fields_ = [("rid", C.c_int64), ("key", C.c_int64), ("t", C.c_int64), ("stream", C.c_int32), ("cls", C.c_int32), ("ppm", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class ComposeCfg(C.Structure):                      # struct rtmodt_compose_cfg
     _fields_ = [(k, C.c_int32) for k in ("device", "max_sources", "max_outputs", "max_cells", "max_dim")]
 
@@ -688,6 +701,16 @@ def lib() -> C.CDLL:
         "rtmodt_crosscam_clear_errors": (C.c_int, [vp]),
         "rtmodt_crosscam_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_crosscam_similarity": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+        "rtmodt_index_default_cfg": (None, [C.POINTER(IndexCfg)]),
+        "rtmodt_index_create": (C.c_int, [C.POINTER(IndexCfg), C.POINTER(vp)]),
+        "rtmodt_index_destroy": (None, [vp]),
+        "rtmodt_index_add": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.POINTER(i64)]),
+        "rtmodt_index_add_crosscam": (C.c_int, [vp, vp, i64, C.c_int, C.POINTER(i32)]),
+        "rtmodt_index_search": (C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+        "rtmodt_index_forget": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
+        "rtmodt_index_state": (C.c_int, [vp] * 10),
+        "rtmodt_index_load": (C.c_int, [vp, i64] + [vp] * 7),
+        "rtmodt_index_last_ms": (C.c_int, [vp, C.POINTER(f32), C.POINTER(f32)]),
         "rtmodt_compose_default_cfg": (None, [C.POINTER(ComposeCfg)]),
         "rtmodt_compose_create": (C.c_int, [C.POINTER(ComposeCfg), C.POINTER(vp)]),
         "rtmodt_compose_destroy": (None, [vp]),

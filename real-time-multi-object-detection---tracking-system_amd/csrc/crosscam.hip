@@ -686,6 +686,15 @@ int cc_check_cfg(const rtmodt_crosscam_cfg &c) {
 
 }  // namespace
 
+// the table for the appearance index (kernels.h)
+int rtmodt::crosscam_table_view(rtmodt_crosscam *z, CcTableView *out) {
+    RT_CHECK(z && out, RTMODT_E_INVALID, "bad argument");
+    const CcTab &t = z->tab[z->cur];
+    *out = CcTableView{z->a.state, t.gid, t.first, t.last, t.cls, t.s8, z->cfg.n_streams, z->cfg.dim, z->cfg.max_identities, z->device, z->calls,
+                       z->last_stream ? z->last_stream : z->stream};
+    return RTMODT_OK;
+}
+
 extern "C" {
 
 void rtmodt_crosscam_default_cfg(rtmodt_crosscam_cfg *c) {

@@ -347,6 +347,15 @@ int botsort_device_view(rtmodt_botsort *bot, BotDeviceView *out);
 // rows of buffer meta[0] & 1 current; null and dim 0 for a motion-only handle
 int botsort_feature_view(rtmodt_botsort *bot, const int8_t **feat8, int *dim);
 
+// crosscam.hip, for the appearance index (index.hip): the linker's table as its last call left it, read-only.  n_dev[0] = the
+// identities in it; gid / cls / first_seen [max_identities], last_seen [max_identities][n_streams], s8 [max_identities][dim];
+// calls = the number of the call just made; stream = the HIP stream it ran on
+struct CcTableView {
+    const int64_t *n_dev, *gid, *first_seen, *last_seen; const int32_t *cls; const int8_t *s8;
+    int n_streams, dim, max_identities, device; long long calls; hipStream_t stream;
+};
+int crosscam_table_view(rtmodt_crosscam *cc, CcTableView *out);
+
 // A tracker's device state as the track source of a per-frame consumer: exactly one of the four state pointers is set (none: the
 // consumer reads a list of its own).  select_tracks (track_select_dev.h) turns it into the list and the selection; track_src fills
 // it, and the part of the view all trackers share, from a tracker's handle.  report_tsu takes part for ByteTrack and DeepSORT only,
