@@ -2280,6 +2280,76 @@ int rtmodt_health_last_ms(rtmodt_health *m, float *kernel_ms);
 int rtmodt_health_decide(const rtmodt_health_cfg *cfg, int64_t cells, int64_t frame_id, rtmodt_health_result *row, rtmodt_health_state *state,
                          rtmodt_health_event *events);
 
+/* ---- frame enhancement: low-light and low-contrast frames lifted before every stage that reads pixels ------------------------- */
+/* At night without IR, at dusk, in backlight or in fog the scene occupies twenty or thirty grey levels out of 256; the motion
+ * detector's fixed thresholds and the detector see a flat picture.  This module is contrast-limited adaptive histogram equalisation
+ * (CLAHE) of the luma: per-tile histograms, clipped, integrated into tone curves, interpolated between tile centres -- with the
+ * tone curves held per stream on the device and moved by an integer EMA, because a per-frame CLAHE flickers on video.  The reference
+ * has no counterpart (src/ingestion/rtsp_reader.py hands cap.read()'s frame on): PARITY UNPINNED throughout, against
+ * cv2.createCLAHE too (its tiles are padded by reflection, its interpolation is float), and no default is validated on real footage.
+ * PINNED, exactly, against tests/enhance_ref.py: every output byte, histogram, state value and result field.  csrc/enhance_rule.h
+ * states the rules, csrc/enhance.hip's header the launches; all of it is integer arithmetic.  DELIBERATE LIMITS: luma only, no
+ * denoising, no gamma or white balance, one tile grid per handle, `auto` follows the frame mean without hysteresis. */
+#define RTMODT_ENHANCE_SHIFT 0          /* each channel becomes clamp(c + (Y2 - Y)): chroma untouched                           */
+#define RTMODT_ENHANCE_GAIN 1           /* each channel becomes min(255, (c * Y2 + Y / 2) / Y): hue and saturation kept         */
+#define RTMODT_ENHANCE_MAX_TILES 16
+typedef struct rtmodt_enhance rtmodt_enhance;
+typedef struct rtmodt_enhance_cfg {
+    int32_t streams;            /* 1..1024                                                                                      */
+    int32_t height, width;      /* the frame size, 1..16384 each                                                                */
+    int32_t tiles_y, tiles_x;   /* 1..16 each and no more than the pixels of their axis                                         */
+    int32_t clip_q8;            /* 0..65536: the clip limit in 1 / 256 (OpenCV's clipLimit 2.0 is 512); 0: no clipping          */
+    int32_t strength;           /* 0..256: how much of the equalised luma is taken                                              */
+    int32_t smooth_shift;       /* 0..7: the tone curves move by 1 / 2^smooth_shift per frame; 0 follows the frame at once      */
+    int32_t auto_lo, auto_hi;   /* 0 <= auto_lo <= auto_hi <= 255; auto_hi > auto_lo: full strength at a mean luma of auto_lo
+                                   and below, none at auto_hi and above                                                         */
+    int32_t colour;             /* RTMODT_ENHANCE_SHIFT or RTMODT_ENHANCE_GAIN                                                  */
+    int32_t device;
+} rtmodt_enhance_cfg;
+typedef struct rtmodt_enhance_result {
+    int32_t stream;
+    int32_t frames_seen;        /* after the call                                                                               */
+    uint32_t eff;               /* the strength this frame was enhanced with, 0..256                                            */
+    uint32_t clipped;           /* the pixels above the clip limit, summed over the stream's tiles                              */
+    uint64_t luma_sum;          /* the sum of the frame's luma                                                                  */
+} rtmodt_enhance_result;
+/* Host only: 1 stream, height and width 0 (the caller sets them), 8 x 8 tiles, clip_q8 512, strength 256, smooth_shift 2, auto off
+ * (0, 0), SHIFT, device 0.  No default has been validated on real footage.  PARITY UNPINNED. */
+void rtmodt_enhance_default_cfg(rtmodt_enhance_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range is RTMODT_E_INVALID and the message names it.
+ * Every stream starts with frames_seen 0.  PARITY UNPINNED. */
+int rtmodt_enhance_create(const rtmodt_enhance_cfg *cfg, rtmodt_enhance **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  PARITY UNPINNED. */
+void rtmodt_enhance_destroy(rtmodt_enhance *e);
+/* One frame for each of n distinct streams: src[i] (BGR24, height x width as created, row pitch src_stride >= 3w, host or device
+ * memory by src_mem_kind) is enhanced with the tone curves of streams[i] (streams == NULL: stream i, and n must be the stream
+ * count) into dst[i] (dst_stride, dst_mem_kind; any mix of host and device).  dst[i] may BE src[i] at the same pitch (in place:
+ * the step is pointwise); any other meeting of a destination range with a source range of the call, a frame size other than the
+ * handle's, a stream outside 0..streams - 1 or named twice, a null frame and n above the stream count are RTMODT_E_INVALID with
+ * nothing launched.  Padding bytes of the rows are not touched.  A memset and three launches, whatever the frames show; results
+ * (NULL: none are copied) come back in one copy.  Streams the call does not name keep their state.  Synchronous.  PARITY UNPINNED. */
+int rtmodt_enhance_process(rtmodt_enhance *e, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride,
+                           int dst_mem_kind, const int32_t *streams, int n, int height, int width, rtmodt_enhance_result *results);
+/* One stream's state to host memory: s as uint16[tiles_y][tiles_x][256] (8.8 fixed point) and frames_seen.  PARITY UNPINNED. */
+int rtmodt_enhance_read_state(rtmodt_enhance *e, int stream, uint16_t *s, int32_t *frames_seen);
+/* Replaces one stream's state (n_values must be tiles_y * tiles_x * 256), so that an enhancer survives a restart; another size, a
+ * value above 255 << 8 or frames_seen outside 0..2^30 is RTMODT_E_INVALID and nothing is replaced.  PARITY UNPINNED. */
+int rtmodt_enhance_load_state(rtmodt_enhance *e, int stream, const uint16_t *s, int64_t n_values, int32_t frames_seen);
+/* Forgets one stream's tone curves (its next frame sets them), or every stream's with stream == -1.  PARITY UNPINNED. */
+int rtmodt_enhance_reset(rtmodt_enhance *e, int stream);
+/* The histograms the last process call built for `stream`, uint32[tiles_y][tiles_x][256]; RTMODT_E_INVALID when that call did not
+ * name the stream.  For tests and tuning.  PARITY UNPINNED. */
+int rtmodt_enhance_histograms(rtmodt_enhance *e, int stream, uint32_t *hist);
+/* Device time (ms, HIP events around the memset and the three launches) of the last process call that launched.  PARITY UNPINNED. */
+int rtmodt_enhance_last_ms(rtmodt_enhance *e, float *kernel_ms);
+/* Host only, no device needed: csrc/enhance_rule.h's tone curve of one tile from its histogram hist[256], whose sum must be the
+ * area n (1..2^28), under clip_q8 -> curve[256] and the excess.  The parity surface of the curve rule.  PARITY UNPINNED. */
+int rtmodt_enhance_curve(const uint32_t *hist, int64_t n, int32_t clip_q8, uint32_t *curve, uint32_t *excess);
+/* Host only, no device needed: where each of px pixels (1..16384) sits among `tiles` tiles (1..16, at most px) along one axis
+ * -> k[px] and f[px] (0..256, in 1 / 256 of the way from the centre of tile k to that of tile min(k + 1, tiles - 1)), and
+ * bounds[tiles + 1], the first pixel of every tile and px.  The parity surface of the axis rule.  PARITY UNPINNED. */
+int rtmodt_enhance_axis(int32_t px, int32_t tiles, int32_t *k, int32_t *f, int32_t *bounds);
+
 #ifdef __cplusplus
 }
 #endif

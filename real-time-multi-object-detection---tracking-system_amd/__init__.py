@@ -44,7 +44,9 @@ library being built):
                             decoding into a page-locked ring (reference: src/ingestion/rtsp_reader.py:27-158); ``JpegDecoder`` /
                             ``MjpegCapture``: JPEG / Motion-JPEG files, AVI and multipart streams decoded on the GPU; ``Stabilizer``:
                             frames of a shaking camera steadied on the GPU ahead of every fixed-camera stage; ``CameraHealth``:
-                            covered, re-aimed, defocused, dark, dazzled and frozen cameras told from healthy ones on the GPU
+                            covered, re-aimed, defocused, dark, dazzled and frozen cameras told from healthy ones on the GPU;
+                            ``FrameEnhancer``: low-light and low-contrast frames lifted by temporally smoothed CLAHE on the GPU
+                            ahead of motion detection and the detector
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
                             in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py); ``stitch_tracks`` /
                             ``correct_id_switches``: fragmented tracks merged and their gaps filled on the GPU (the design
@@ -78,6 +80,7 @@ _LAZY = {
     "RTSPReader": ".ingestion.reader",
     "JpegDecoder": ".ingestion.jpeg_decode",
     "MjpegCapture": ".ingestion.mjpeg",
+    "FrameEnhancer": ".ingestion.enhance",
     "FrameRenderer": ".visualization.renderer",
     "PrivacyMask": ".visualization.privacy",
     "Heatmap": ".visualization.heatmap",

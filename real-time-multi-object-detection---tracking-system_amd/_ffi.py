@@ -367,6 +367,15 @@ class HealthState(C.Structure):                     # struct rtmodt_health_state
                 ("run", C.c_int32 * 6), ("off", C.c_int32 * 6)]
 
 
+class EnhanceCfg(C.Structure):                      # struct rtmodt_enhance_cfg
+    _fields_ = [(k, C.c_int32) for k in ("streams", "height", "width", "tiles_y", "tiles_x", "clip_q8", "strength", "smooth_shift", "auto_lo",
+                                         "auto_hi", "colour", "device")]
+
+
+class EnhanceResult(C.Structure):                   # struct rtmodt_enhance_result
+    _fields_ = [("stream", C.c_int32), ("frames_seen", C.c_int32), ("eff", C.c_uint32), ("clipped", C.c_uint32), ("luma_sum", C.c_uint64)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -671,6 +680,17 @@ def lib() -> C.CDLL:
         "rtmodt_health_reset": (C.c_int, [vp, C.c_int]),
         "rtmodt_health_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_health_decide": (C.c_int, [C.POINTER(HealthCfg), i64, i64, C.POINTER(HealthResult), C.POINTER(HealthState), vp]),
+        "rtmodt_enhance_default_cfg": (None, [C.POINTER(EnhanceCfg)]),
+        "rtmodt_enhance_create": (C.c_int, [C.POINTER(EnhanceCfg), C.POINTER(vp)]),
+        "rtmodt_enhance_destroy": (None, [vp]),
+        "rtmodt_enhance_process": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_enhance_read_state": (C.c_int, [vp, C.c_int, vp, C.POINTER(i32)]),
+        "rtmodt_enhance_load_state": (C.c_int, [vp, C.c_int, vp, i64, i32]),
+        "rtmodt_enhance_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_enhance_histograms": (C.c_int, [vp, C.c_int, vp]),
+        "rtmodt_enhance_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_enhance_curve": (C.c_int, [vp, i64, i32, vp, C.POINTER(C.c_uint32)]),
+        "rtmodt_enhance_axis": (C.c_int, [i32, i32, vp, vp, vp]),
         "rtmodt_snapshot_default_cfg": (None, [C.POINTER(SnapshotCfg)]),
         "rtmodt_snapshot_create": (C.c_int, [C.POINTER(SnapshotCfg), C.c_int, C.c_int, C.POINTER(vp)]),
         "rtmodt_snapshot_destroy": (None, [vp]),

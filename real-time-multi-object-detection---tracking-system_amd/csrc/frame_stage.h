@@ -86,15 +86,25 @@ inline int check_frames(const uint8_t *const *frames, int n, int h, int w, int s
 
 // A gather cannot work in place (lens, stab): no destination range of a call may meet a source range of it.  Sources of sh x sw at
 // src_stride, destinations of dh x dw at dst_stride.
-inline int check_not_in_place(const uint8_t *const *src, int sh, int sw, int src_stride, uint8_t *const *dst, int dh, int dw, int dst_stride, int n) {
+//   exact_ok (enhance: a pointwise step): destination i may BE source i -- the same base, size and pitch -- and must then meet no
+//   other source of the call; every other meeting is refused as before.
+inline int check_not_in_place(const uint8_t *const *src, int sh, int sw, int src_stride, uint8_t *const *dst, int dh, int dw, int dst_stride, int n,
+                              bool exact_ok = false) {
     const size_t sspan = (size_t)(sh - 1) * (size_t)src_stride + (size_t)3 * sw, dspan = (size_t)(dh - 1) * (size_t)dst_stride + (size_t)3 * dw;
+    const bool same_shape = sh == dh && sw == dw && src_stride == dst_stride;
     std::vector<uintptr_t> starts(n);
     for (int i = 0; i < n; ++i) starts[i] = (uintptr_t)src[i];
     std::sort(starts.begin(), starts.end());
     for (int i = 0; i < n; ++i) {
         const uintptr_t a = (uintptr_t)dst[i], b = a + dspan;
         // the source with the largest start below b; all spans are equal, so it is the one that reaches furthest
-        const auto it = std::lower_bound(starts.begin(), starts.end(), b);
+        auto it = std::lower_bound(starts.begin(), starts.end(), b);
+        if (exact_ok && same_shape && (uintptr_t)src[i] == a) {
+            // its own source is the one start inside [a, b); what must end before a is the source below it
+            const auto own = std::lower_bound(starts.begin(), starts.end(), a);
+            RT_CHECK(it - own == 1, RTMODT_E_INVALID, "destination frame %d overlaps a source frame of the call other than its own", i);
+            it = own;
+        }
         RT_CHECK(it == starts.begin() || *(it - 1) + sspan <= a, RTMODT_E_INVALID, "destination frame %d overlaps a source frame of the call", i);
     }
     return RTMODT_OK;

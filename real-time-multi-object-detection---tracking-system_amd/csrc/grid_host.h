@@ -2,7 +2,8 @@
 // health.hip): the grid of a handle and the launch grids over it, the checks of a config's grid and of a call's stream list with
 // their messages, the test for the reader's dword path, and the one launcher of a <SCALE, WIDE> kernel.  Host code only.  What a
 // handle holds on the device differs between the modules and stays with them; its frame (open, zeroing, create tail, close) is
-// handle_host.h's, like every other handle's.
+// handle_host.h's, like every other handle's.  enhance.hip, which reads frames through the same reader into histograms and has no
+// grid, takes the checks of a stream and of a call's stream list from here.
 #pragma once
 
 #include <vector>

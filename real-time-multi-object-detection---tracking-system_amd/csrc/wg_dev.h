@@ -1,5 +1,5 @@
 // wg_dev.h -- small device helpers of a wave or a workgroup, shared by zones.hip, crossing.hip, swapguard.hip, ocsort.hip, gmc.hip,
-// crosscam.hip, speed.hip, snapshot.hip, privacy.hip, heatmap.hip, motion.hip, leftobj.hip, health.hip, ccl_dev.h and track_ledger_dev.h.  Include inside
+// crosscam.hip, speed.hip, snapshot.hip, privacy.hip, heatmap.hip, motion.hip, leftobj.hip, health.hip, enhance.hip, ccl_dev.h and track_ledger_dev.h.  Include inside
 // namespace rtmodt.
 #pragma once
 
@@ -19,6 +19,11 @@ __device__ __forceinline__ int lower_bound_i64(const int64_t *a, int n, int64_t 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (unsigned long long)__shfl_xor((long long)v, d);
     return v;
 }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {

@@ -66,7 +66,7 @@ class PinnedFrameRing:
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
         crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
-        left_objects=None, stabilize=None, health=None) -> dict:
+        left_objects=None, stabilize=None, health=None, enhance=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -153,6 +153,12 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     and before ``undistort``: it judges the picture the camera delivered -- covered, re-aimed, defocused, dark, dazzled, frozen -- and
     its events carry the source's frame ids.  It gates nothing: what to do with an alarm is the caller's decision.  The summary then
     carries ``health_alarms``, the RAISED events, and ``health_flags``, the OR of the active masks.  ``None``: the loop, the stage
+    table and the summary are unchanged.
+
+    ``enhance``: a one-stream ``ingestion.FrameEnhancer`` of the frames' size, called inside an ``enhance`` stage directly before
+    ``motion`` and after ``decode``, ``health``, ``undistort`` and ``stabilize`` -- health judges the raw picture and the lens table
+    samples unaltered pixels: a dark or flat frame is replaced by the enhanced one for every later stage and for the recorder.  The
+    summary then carries ``enhance_mean_eff``, the mean effective strength (0..256) over the frames.  ``None``: the loop, the stage
     table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
@@ -185,6 +191,10 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("decode") + 1, "health")
         profiler.STAGE_ORDER = order
+    if enhance is not None and "enhance" not in profiler.STAGE_ORDER:          # likewise, after the four above and directly before motion
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index(next(k for k in ("stabilize", "undistort", "health", "decode") if k in order)) + 1, "enhance")
+        profiler.STAGE_ORDER = order
     if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
@@ -202,6 +212,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     n_stab = [0, 0, 0, 0]                                                      # frames per stabiliser status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     n_health_alarms = health_flags = 0
+    n_enhanced = enhance_eff = 0
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
@@ -223,6 +234,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             frame = stabilize.process([frame])[0]
             n_stab[stabilize.result()[0].status] += 1
             profiler.tock("stabilize")
+        if enhance is not None:
+            profiler.tick("enhance")
+            enhanced = np.empty_like(frame)                                    # (the source may hand out a slot of its ring: it is not written)
+            enhance_eff += enhance.process([frame], out=[enhanced])[0].eff
+            frame = enhanced
+            n_enhanced += 1
+            profiler.tock("enhance")
         skip = False
         if motion is not None:
             profiler.tick("motion")
@@ -361,6 +379,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["stabilize_holds"], out["stabilize_clamped"], out["stabilize_resets"] = n_stab[1], n_stab[2], n_stab[3]
     if health is not None:
         out["health_alarms"], out["health_flags"] = n_health_alarms, health_flags
+    if enhance is not None:
+        out["enhance_mean_eff"] = enhance_eff / max(n_enhanced, 1)
     if motion is not None:
         out["motion_frames"], out["still_frames"], out["scene_changes"] = n_status[2], n_status[1], n_status[3]
     return out
