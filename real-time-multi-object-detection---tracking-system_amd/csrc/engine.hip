@@ -22,6 +22,7 @@
 #include <unistd.h>
 
 #include "kernels.h"
+#include "launch_plan.h"
 
 namespace rtmodt {
 
@@ -114,32 +115,23 @@ static int read_weight_file(const char *path, WeightFile &wf) {
 // ------------------------------------------------------------------ graph description
 struct Tensor { f16 *ptr = nullptr; int H, W, C, pad; size_t per_image; };
 
-enum OpKind { OP_STEM, OP_CONV, OP_POOL, OP_UP, OP_GROUP, OP_BNECK };
-
-struct Op {
-    OpKind kind;
+// kind, `choice` (HOW the launch runs: tiles and form -- launch_plan.h; the tile fields of the launch structs below are filled in from it when
+// the op is launched), what the graph allows (`has_tail`, `front_ok`, `head_final`) and the derived `skip` come from PlanOp
+struct Op : PlanOp {
     std::string name;
-    ConvLaunch conv;                 // OP_CONV
+    ConvLaunch conv;                 // OP_CONV.  conv -> 1x1 pairs (backbone Conv -> C2f.cv1): the producer carries the 1x1 as conv.tail_* (`has_tail`)
     std::vector<ConvLaunch> group;   // OP_GROUP: independent convs issued as one launch
-    int group_tile = TILE_64x64;
-    // OP_BNECK: a Bottleneck either as ONE fused launch (`bneck`) or as its two convs (`group[0]`, `group[1]`
-    // with their own tiles); the autotuner keeps whichever is faster on this device and batch
+    // OP_BNECK: a Bottleneck either as ONE fused launch (`bneck`; with C2f.cv2 as bneck.tail_* where `has_tail`) or as its two convs
+    // (`group[0]`, `group[1]` with their own tiles); the autotuner keeps whichever is faster on this device and batch
     BottleneckLaunch bneck;
-    bool fused = true;
     TensorView v[4];                 // STEM: in,out [, 2.cv1's output when the front end can run fused]; POOL: y,p1,p2,p3; UP: in,out
     const f16 *stem_w = nullptr; const float *stem_b = nullptr;
-    // STEM: the front end as ONE launch (front.hip: stem -> layer 1 -> C2f.cv1 of layer 2; only v[2] is stored).  `front_ok`: the graph allows it;
-    // `front_on`: it runs (the ops of layer 1 and 2.cv1 are then skipped)
-    bool front_ok = false, front_on = false;
+    // STEM: the front end as ONE launch (front.hip: stem -> layer 1 -> C2f.cv1 of layer 2; only v[2] is stored) where `front_ok`
     const f16 *front_w1 = nullptr, *front_w2 = nullptr; const float *front_b1 = nullptr, *front_b2 = nullptr;
     int front_kp1 = 0, front_kp2 = 0, front_c1 = 0, front_c2 = 0;
     int64_t flops = 0;               // per frame
     int B = 1;                       // images this launch covers
     int head_level = -1;             // >= 0: belongs to the Detect branch of that level (independent of the other levels)
-    // conv -> 1x1 pairs (backbone Conv -> C2f.cv1): the producer carries the 1x1 as conv.tail_*; when the tuner finds the
-    // fused launch faster, `tail_on` runs it with `tail_tile` and the 1x1's own op is skipped
-    bool tail_on = false, skip = false;
-    int tail_tile = TILE_TAIL_128x64;
 };
 
 }  // namespace rtmodt
@@ -174,7 +166,7 @@ struct rtmodt_detector {
     bool pipe = false;
     size_t arena_stride = 0;                          // bytes between the two arena copies
     static constexpr int MAX_STAGES = 3;
-    int n_stages = 1;                                 // 2: backbone | neck + Detect; 3: layers 0-6.m.1 | 6.cv2-16 | 18-22
+    int n_stages = 1;                                 // 2: backbone | neck + Detect (cut in front of layer 12); 3: cut in front of 6.cv2 and of layer 18 (build_graph)
     int stage_lo[MAX_STAGES + 1] = {0, 0, 0, 0};      // stage s runs ops [stage_lo[s], stage_lo[s + 1])
     int run_par = 0, last_par = 0;                    // arena copy the launches being issued use / the newest batch used
     std::vector<Op> par_ops[MAX_STAGES];              // d->ops shifted into each arena copy (one copy per stage)
@@ -307,29 +299,16 @@ static int upload(rtmodt_detector *d, const void *src, size_t bytes, void **out)
 // the same launch restricted to images [b0, b0 + nb) of the batch
 static Op sub_batch(const Op &op, int b0, int nb) {
     Op o = op;
-    auto shift = [&](TensorView &v) {
-        if (v.c) v.base += (size_t)b0 * (v.H + 2 * v.pad) * v.padded_w() * v.C;
-    };
-    o.B = nb;
-    if (o.kind == OP_CONV) { shift(o.conv.in); shift(o.conv.out); shift(o.conv.res); shift(o.conv.out2); shift(o.conv.tail_out); shift(o.conv.in_lo); o.conv.B = nb; }
-    else if (o.kind == OP_GROUP || o.kind == OP_BNECK) {
-        for (auto &c : o.group) { shift(c.in); shift(c.out); shift(c.res); c.B = nb; }
-        if (o.kind == OP_BNECK) { shift(o.bneck.in); shift(o.bneck.out); shift(o.bneck.res); shift(o.bneck.tail_in); shift(o.bneck.tail_out); o.bneck.B = nb; }
-    }
-    else for (auto &v : o.v) shift(v);
+    for_each_view(o, [&](TensorView &v) { if (v.c) v.base += (size_t)b0 * (v.H + 2 * v.pad) * v.padded_w() * v.C; });
+    o.B = o.conv.B = o.bneck.B = nb;
+    for (auto &c : o.group) c.B = nb;
     return o;
 }
 
 // the same launch in the other copy of the arena
 static Op shift_arena(const Op &op, size_t bytes) {
     Op o = op;
-    auto shift = [&](TensorView &v) { if (v.c) v.base = (f16 *)((char *)v.base + bytes); };
-    if (o.kind == OP_CONV) { shift(o.conv.in); shift(o.conv.out); shift(o.conv.res); shift(o.conv.out2); shift(o.conv.tail_out); shift(o.conv.in_lo); }
-    else if (o.kind == OP_GROUP || o.kind == OP_BNECK) {
-        for (auto &c : o.group) { shift(c.in); shift(c.out); shift(c.res); }
-        if (o.kind == OP_BNECK) { shift(o.bneck.in); shift(o.bneck.out); shift(o.bneck.res); shift(o.bneck.tail_in); shift(o.bneck.tail_out); }
-    }
-    else for (auto &v : o.v) shift(v);
+    for_each_view(o, [&](TensorView &v) { if (v.c) v.base = (f16 *)((char *)v.base + bytes); });
     return o;
 }
 
@@ -366,6 +345,17 @@ static int pick_tile(int M, int cout) {
 
 // upload a fused conv (one or more records concatenated along cout) in the MFMA layout
 static bool tile_legal(const ConvLaunch *c, int n, int t);
+static bool tail_tile_legal(const ConvLaunch &c, int t) {
+    return tile_is_tail(t) && tile_shape(t).bn == c.cout && !(tile_needs_cin64(t) && (c.cin % 64 != 0 || c.kp % 64 != 0)) && c.cin % 32 == 0;
+}
+static bool tail_legal_for(const Op &op, int t) { return tail_tile_legal(op.conv, t); }
+// the A/B and test hooks that override a launch's form (launch_plan.h: apply_hooks)
+static Hooks read_hooks() {
+    Hooks h;
+    auto get = [](const char *name, int &v) { if (const char *e = rt_opt(name)) v = atoi(e) != 0; };
+    get("BNECK", h.bneck); get("BNECK32", h.bneck32); get("BNECK_TAIL", h.bneck_tail); get("TAIL", h.tail); get("FRONT", h.front);
+    return h;
+}
 static int make_conv(rtmodt_detector *d, WeightFile &wf, const std::vector<std::string> &names, const std::string &op_name,
                      const TensorView &in, const TensorView &out, const TensorView *res, int cout_pad4,
                      std::vector<Op> *dst = nullptr) {
@@ -405,18 +395,19 @@ static int make_conv(rtmodt_detector *d, WeightFile &wf, const std::vector<std::
     c.B = d->B; c.cin = r0.cin; c.cout = cout_eff; c.ks = r0.k; c.stride = r0.stride; c.act = r0.act; c.kp = kp;
     if (const char *e = rt_opt("EPI16")) c.epilogue = atoi(e);      // A/B and test hook
     int M = d->B * out.H * out.W;
-    c.tile = pick_tile(M, cout_eff);
+    int &tile = op.choice.tile;
+    tile = pick_tile(M, cout_eff);
     if (const char *e = rt_opt("TILE_K64")) {            // test hook: a 64-deep tile (incl. the 8-wave ones) wherever it is legal
         const int t = atoi(e);
         if (t >= 0 && t < TILE_COUNT && tile_needs_cin64(t) && !tile_is_rows(t) && !tile_is_tail(t) && c.cin % 64 == 0 && kp % 64 == 0 && !dst &&
             (!tile_is_pt(t) || (((long)d->B * out.H * out.W) % tile_shape(t).bm == 0 && cout_eff % tile_shape(t).bn == 0 && out.coff % 8 == 0 && out.C % 8 == 0)) &&
-            (tile_shape(t).bn <= 128 || cout_eff % tile_shape(t).bn == 0) && (!tile_is_ppt(t) || tile_legal(&c, 1, t))) c.tile = t;
+            (tile_shape(t).bn <= 128 || cout_eff % tile_shape(t).bn == 0) && (!tile_is_ppt(t) || tile_legal(&c, 1, t))) tile = t;
     }
     if (const char *e = rt_opt("TILE_3X3S1")) {          // test hook: force a tap-reuse tile wherever it is legal
         int t = atoi(e);
         if (t >= 0 && t < TILE_COUNT && tile_is_rows(t) && c.ks == 3 && c.stride == 1 && c.in.pad == 1 &&
             c.cin % (tile_needs_cin64(t) ? 64 : 32) == 0 && (!tile_is_pp(t) || tile_legal(&c, 1, t)))
-            c.tile = t;
+            tile = t;
     }
     op.flops = 2LL * out.H * out.W * cout * K;
     (dst ? *dst : d->ops).push_back(op);
@@ -471,13 +462,12 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
                 if (rc != RTMODT_OK) continue;
                 Op op; op.kind = OP_BNECK; op.name = m + " (cv1+cv2)";
                 op.group = {pair[0].conv, pair[1].conv};
+                op.choice.tile = pair[0].choice.tile; op.choice.tile2 = pair[1].choice.tile; op.choice.form = FORM_FUSED;
                 op.flops = pair[0].flops + pair[1].flops;
                 BottleneckLaunch &b = op.bneck;
                 b.in = V(cat, (1 + j) * c, c); b.out = V(cat, (2 + j) * c, c); if (shortcut) b.res = r;
                 b.w1 = pair[0].conv.wt; b.b1 = pair[0].conv.bias; b.w2 = pair[1].conv.wt; b.b2 = pair[1].conv.bias;
                 b.zeros = d->d_zeros; b.B = d->B; b.c = c; b.kp = pair[0].conv.kp;
-                if (const char *e = rt_opt("BNECK")) op.fused = atoi(e) != 0;
-                if (const char *e = rt_opt("BNECK32")) b.persistent32 = atoi(e) != 0;      // A/B and test hook: 0 = bottleneck_fused for the c = 32 C2f too
                 d->ops.push_back(op);
                 continue;
             }
@@ -493,7 +483,7 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
                 cv.conv.out.C % 8 == 0) {
                 bn.bneck.tail_in = V(cat, 0, 2 * c); bn.bneck.tail_out = cv.conv.out; bn.bneck.tail_wt = cv.conv.wt; bn.bneck.tail_bias = cv.conv.bias;
                 bn.bneck.tail_cout = cv.conv.cout; bn.bneck.tail_kp = cv.conv.kp; bn.bneck.tail_act = cv.conv.act;
-                if (const char *e = rt_opt("BNECK_TAIL")) { bn.tail_on = atoi(e) != 0; cv.skip = bn.tail_on && bn.fused; }   // test hook (no autotune)
+                bn.has_tail = true;
             }
         }
     };
@@ -557,9 +547,9 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
     // a conv that also writes the nearest-2x copy cannot run as the tail of the Bottleneck before it
     auto fold_into_last = [&](const TensorView &up) {
         d->ops.back().conv.out2 = up;
-        if (tile_is_pt(d->ops.back().conv.tile) || tile_is_ppt(d->ops.back().conv.tile)) d->ops.back().conv.tile = TILE_K64_128x128_S2_W8;      // (test hook's forced tile: no second destination there)
-        d->ops.back().skip = false;
-        if (d->ops.size() >= 2) { Op &bn = d->ops[d->ops.size() - 2]; if (bn.kind == OP_BNECK) { bn.bneck.tail_wt = nullptr; bn.tail_on = false; } }
+        int &tile = d->ops.back().choice.tile;
+        if (tile_is_pt(tile) || tile_is_ppt(tile)) tile = TILE_K64_128x128_S2_W8;      // (test hook's forced tile: no second destination there)
+        if (d->ops.size() >= 2) { Op &bn = d->ops[d->ops.size() - 2]; if (bn.kind == OP_BNECK) { bn.bneck.tail_wt = nullptr; bn.has_tail = false; } }
     };
     // Upsample + Concat of the neck (layers 10/11 and 13/14), cheapest first: (a) the consumer C2f.cv1 -- a 1x1 -- reads the
     // upsampled channels straight from the half-resolution tensor (no copy exists at all), (b) the producer's epilogue also
@@ -569,7 +559,7 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
         for (auto &op : d->ops)
             if (op.kind == OP_CONV && op.name == cv1 && lo_c % 64 == 0 && op.conv.cin % 64 == 0 && op.conv.kp % 64 == 0 && op.conv.ks == 1) {
                 op.conv.in_lo = lo; op.conv.lo_c = lo_c;
-                if (!tile_reads_lo(op.conv.tile)) op.conv.tile = TILE_K64_128x64_S3_W8;
+                if (!tile_reads_lo(op.choice.tile)) op.choice.tile = TILE_K64_128x64_S3_W8;
                 return true;
             }
         return false;
@@ -606,11 +596,8 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
             if (b.conv.out.coff % 8 != 0 || b.conv.out.C % 8 != 0) continue;
             a.conv.tail_out = b.conv.out; a.conv.tail_wt = b.conv.wt; a.conv.tail_bias = b.conv.bias;
             a.conv.tail_cout = b.conv.cout; a.conv.tail_kp = b.conv.kp; a.conv.tail_act = b.conv.act;
-            a.tail_tile = a.conv.cout == 64 ? TILE_TAIL_128x64 : (a.conv.cin % 64 == 0 ? TILE_TAIL_K64_128x128 : TILE_TAIL_128x64);
-            if (const char *e = rt_opt("TAIL")) {     // test hook (no autotune): force the fused launch on
-                a.tail_on = atoi(e) != 0 && tile_shape(a.tail_tile).bn == a.conv.cout && !(tile_needs_cin64(a.tail_tile) && a.conv.cin % 64 != 0);
-                b.skip = a.tail_on;
-            }
+            a.has_tail = true;
+            a.choice.tail_tile = a.conv.cout == 64 ? TILE_TAIL_128x64 : (a.conv.cin % 64 == 0 ? TILE_TAIL_K64_128x128 : TILE_TAIL_128x64);
         }
     // The front end as one launch (front.hip): stem -> "1" -> "2.cv1", whose two intermediate tensors have no other reader
     if (d->ops.size() >= 3 && !rt_diag("NO_FRONT")) {
@@ -623,11 +610,6 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
             st.v[2] = cv.conv.out;
             st.front_w1 = l1.conv.wt; st.front_b1 = l1.conv.bias; st.front_kp1 = l1.conv.kp; st.front_c1 = l1.conv.cout;
             st.front_w2 = cv.conv.wt; st.front_b2 = cv.conv.bias; st.front_kp2 = cv.conv.kp; st.front_c2 = cv.conv.cout;
-            if (const char *e = rt_opt("FRONT")) {         // test hook (no autotune): force the fused front end on / off
-                st.front_on = atoi(e) != 0;
-                l1.skip = st.front_on;
-                cv.skip = st.front_on || l1.tail_on;       // (with the front end off, a TAIL-hooked layer 1 still computes 2.cv1 itself)
-            }
         }
     }
     // Detect head: the two first 3x3 convs of a level share their input -> one conv, cout = cbox + ccls
@@ -655,10 +637,10 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
     if (const char *e = rt_diag("HEAD_GROUP")) grouping = atoi(e);
     auto add_group = [&](const std::string &name, std::initializer_list<int> idx) {
         Op g; g.kind = OP_GROUP; g.name = name;
-        for (int i : idx) { g.group.push_back(hops[i].conv); g.flops += hops[i].flops; }
+        const int t0 = hops[*idx.begin()].choice.tile;
         bool same = true;
-        for (auto &c : g.group) same = same && c.tile == g.group[0].tile;
-        if (same && tile_is_rows(g.group[0].tile)) g.group_tile = g.group[0].tile;   // RTMODT_TILE_3X3S1 test hook
+        for (int i : idx) { g.group.push_back(hops[i].conv); g.flops += hops[i].flops; same = same && hops[i].choice.tile == t0; }
+        g.choice.tile = same && tile_is_rows(t0) ? t0 : TILE_64x64;                  // (a shared tap-reuse tile: the RTMODT_TILE_3X3S1 test hook)
         d->ops.push_back(g);
     };
     if (grouping == 2) {
@@ -721,26 +703,9 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
     d->arena_stride = align_up(d->arena_bytes, 4096);
     RT_HIP(hipMalloc((void **)&d->arena, d->arena_stride * d->n_stages));
     RT_HIP(hipMemset(d->arena, 0, d->arena_stride * d->n_stages));
-    auto rebase = [&](TensorView &v) { if (v.base || v.c) v.base = (f16 *)(d->arena + (uintptr_t)v.base); };
+    auto rebase = [&](TensorView &v) { if (v.base || v.c) v.base = (f16 *)(d->arena + (uintptr_t)v.base); };      // (a base is still an arena offset here, and 0 is one)
     for (auto &t : d->tensors) t.ptr = (f16 *)(d->arena + (uintptr_t)t.ptr);
-    for (auto &op : d->ops) {
-        if (op.kind == OP_CONV) {
-            rebase(op.conv.in); rebase(op.conv.out);
-            if (op.conv.res.c) rebase(op.conv.res);
-            if (op.conv.out2.c) rebase(op.conv.out2);
-            if (op.conv.tail_out.c) rebase(op.conv.tail_out);
-            if (op.conv.in_lo.c) rebase(op.conv.in_lo);
-        } else if (op.kind == OP_GROUP || op.kind == OP_BNECK) {
-            for (auto &c : op.group) { rebase(c.in); rebase(c.out); if (c.res.c) rebase(c.res); }
-            if (op.kind == OP_BNECK) {
-                rebase(op.bneck.in); rebase(op.bneck.out);
-                if (op.bneck.res.c) rebase(op.bneck.res);
-                if (op.bneck.tail_in.c) { rebase(op.bneck.tail_in); rebase(op.bneck.tail_out); }
-            }
-        } else {
-            for (auto &v : op.v) if (v.c) rebase(v);
-        }
-    }
+    for (auto &op : d->ops) for_each_view(op, rebase);
     for (auto &kv : d->layer_out) rebase(kv.second);
     for (size_t i = 0; i < d->ops.size(); ++i)
         if (d->ops[i].kind == OP_GROUP && d->ops[i].name.rfind("22.stage2", 0) == 0) d->stage2_op = (int)i;
@@ -760,7 +725,7 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
             d->hf.B = d->B; d->hf.nc = d->nc; d->hf.n_anchors = d->n_anchors; d->hf.cbox = cbox_in; d->hf.ccls = ccls_in;
             d->hf.no = d->tensors[d->head_t[0]].C;
             d->head_final = true;
-            d->ops[d->stage2_op].skip = true;
+            d->ops[d->stage2_op].head_final = true;
         }
     }
 
@@ -772,35 +737,40 @@ static int build_graph(rtmodt_detector *d, WeightFile &wf) {
     if (const char *e = rt_opt("CHAIN_JOIN")) d->chain_free_run = atoi(e) == 0;
     chains = std::max(1, std::min(chains, d->B));
     while (d->B % chains) --chains;
+    // the plan as built: the hooks where no tuner follows (autotune_ops applies them itself, behind the cache and the timing), and the skips
+    finish_plan(d->ops, d->cfg.autotune ? Hooks{} : read_hooks(), tail_legal_for, [](const Op &, const TuneRec &) {});
     set_chains(d, chains);
     return RTMODT_OK;
 }
 
-static int run_op_on(const Op &op, hipStream_t s) {
+static ConvLaunch on_tile(const ConvLaunch &c, int tile) {
+    ConvLaunch r = c;
+    r.tile = tile;
+    return r;
+}
+// the op's own launch(es), as its choice says (whether it is skipped is the caller's business: run_op_on)
+static int launch_op(const Op &op, hipStream_t s) {
+    const Choice &ch = op.choice;
     switch (op.kind) {
         case OP_STEM: return launch_stem(op.v[0], op.v[1], op.stem_w, op.stem_b, op.B, op.v[1].c, s);
-        case OP_CONV: {
-            if (op.skip) return RTMODT_OK;  // runs as the tail of the previous launch
-            if (!op.tail_on) return launch_conv(op.conv, s);
-            ConvLaunch c = op.conv;
-            c.tile = op.tail_tile;
-            return launch_conv(c, s);
-        }
-        case OP_GROUP: return op.skip ? RTMODT_OK : launch_conv_group(op.group.data(), (int)op.group.size(), op.group_tile, s);
-        case OP_BNECK:
-            if (op.fused) {
-                if (op.tail_on) return launch_bottleneck(op.bneck, s);       // with C2f.cv2 as its tail
-                BottleneckLaunch b = op.bneck;
-                b.tail_wt = nullptr;
-                return launch_bottleneck(b, s);
+        case OP_CONV: return launch_conv(on_tile(op.conv, carries_tail(op) ? ch.tail_tile : ch.tile), s);
+        case OP_GROUP: return launch_conv_group(op.group.data(), (int)op.group.size(), ch.tile, s);
+        case OP_BNECK: {
+            if (!is_fused(op)) {
+                RT_TRY(launch_conv(on_tile(op.group[0], ch.tile), s));
+                return launch_conv(on_tile(op.group[1], ch.tile2), s);
             }
-            RT_TRY(launch_conv(op.group[0], s));
-            return launch_conv(op.group[1], s);
+            BottleneckLaunch b = op.bneck;
+            if (!carries_tail(op)) b.tail_wt = nullptr;                      // else with C2f.cv2 as its tail
+            b.persistent32 = ch.form == FORM_FUSED_TAIL_P32;
+            return launch_bottleneck(b, s);
+        }
         case OP_POOL: return launch_sppf_pool(op.v[0], op.v[1], op.v[2], op.v[3], op.B, s);
         case OP_UP: return launch_upsample2(op.v[0], op.v[1], op.B, s);
     }
     return RTMODT_OK;
 }
+static int run_op_on(const Op &op, hipStream_t s) { return op.skip ? RTMODT_OK : launch_op(op, s); }      // skipped: another launch carries it (mark_skips)
 // (a failing launch check names the layer it belongs to: "launch_conv: ... [op 8.cv2]")
 static int run_op(rtmodt_detector *d, const Op &op) {
     const int rc = run_op_on(op, d->stream);
@@ -854,7 +824,7 @@ static int front_launch(rtmodt_detector *d, const Op &op, int frame0, bool from_
 static int run_first(rtmodt_detector *d, const std::vector<Op> &ops, int frame0, bool from_bytes, hipStream_t st) {
     const Op &op = ops[0];
     RT_CHECK(op.kind == OP_STEM, RTMODT_E_INVALID, "op 0 is not the stem");
-    if (op.front_on) return front_launch(d, op, frame0, from_bytes, st);
+    if (front_end_on(op)) return front_launch(d, op, frame0, from_bytes, st);
     if (from_bytes) return launch_stem_fused(d->fptrs, frame0, d->last_pitch, d->last_lg, d->in_h, d->in_w, d->lut255, op.v[1], op.stem_w,
                                              op.stem_b, op.B, op.v[1].c, st);
     return run_op_on(op, st);
@@ -880,7 +850,6 @@ static int forward_eager_all(rtmodt_detector *d) {
 // Times every tile configuration of every MFMA conv on the device it will run on (HIP events,
 // best of a few launches) and keeps the fastest: the GEMM shapes of this net are small and
 // skinny, so the best tile depends on how M x N fills 256 CUs, not on a rule.
-// best-of-3 time (ms per launch) of `launch` issued 4 times back to back on the detector's stream
 // best-of-5 time (ms per launch) of `launch` issued 4 times back to back on the detector's stream (with 3 repetitions
 // near-ties between tiles flipped from run to run and the bench moved by +-1 %)
 template <typename F>
@@ -927,9 +896,6 @@ static bool tile_legal(const ConvLaunch *c, int n, int t) {
             if (c[i].out2.base || c[i].in_lo.base || c[i].cout % 8 != 0 || c[i].out.coff % 8 != 0 || c[i].out.C % 8 != 0 ||
                 (c[i].res.base && (c[i].res.coff % 8 != 0 || c[i].res.C % 8 != 0 || tile_shape(t).bn > 128))) return false;
     return true;
-}
-static bool tail_tile_legal(const ConvLaunch &c, int t) {
-    return tile_is_tail(t) && tile_shape(t).bn == c.cout && !(tile_needs_cin64(t) && (c.cin % 64 != 0 || c.kp % 64 != 0)) && c.cin % 32 == 0;
 }
 
 // LDS bytes a workgroup of tile `t` holds (conv.hip's stage rings): two workgroups of DIFFERENT launches share a CU only if
@@ -989,7 +955,6 @@ static std::string tune_key(const rtmodt_detector *d, const Op &op) {
     (void)d;
     return buf;
 }
-struct TuneRec { int t0 = 0, t1 = 0, fused = 0; };
 // first line of a cache file: the tile table it was written for (count + a hash of the tile names in id order); a file
 // written by a build with another table is ignored, so an id can never silently select a different kernel
 static std::string tune_cache_header() {
@@ -1018,136 +983,106 @@ static int autotune_ops(rtmodt_detector *d, std::vector<Op> &ops) {
     const char *cache_path = rt_opt("TUNE_CACHE");
     std::map<std::string, TuneRec> cache;
     if (cache_path) cache = tune_cache_read(cache_path);
-    bool dirty = false;
+    bool dirty = false;                                    // something was timed: the file is rewritten
     for (auto &op : ops) {
         if (op.kind != OP_CONV && op.kind != OP_GROUP && op.kind != OP_BNECK) continue;
-        const std::string key = tune_key(d, op);
-        auto hit = cache.find(key);
-        if (hit != cache.end()) {                          // a hit must pass the same legality checks as a tuning candidate
-            const TuneRec &r = hit->second;
+        Choice &ch = op.choice;
+        auto hit = cache.find(tune_key(d, op));
+        Choice cached = ch;
+        if (hit != cache.end() && decode_choice(op.kind, hit->second, cached)) {      // a hit must pass the same legality checks as a tuning candidate
             bool ok;
-            if (op.kind == OP_CONV) ok = tile_legal(&op.conv, 1, r.t0) && (!op.conv.tail_wt || r.t1 == 0 || !r.fused || tail_tile_legal(op.conv, r.t1));
-            else if (op.kind == OP_GROUP) ok = tile_legal(op.group.data(), (int)op.group.size(), r.t0);
-            else ok = tile_legal(&op.group[0], 1, r.t0) && tile_legal(&op.group[1], 1, r.t1);
-            if (!ok) { cache.erase(hit); hit = cache.end(); }
-        }
-        if (hit != cache.end()) {
-            const TuneRec &r = hit->second;
-            if (op.kind == OP_CONV) { op.conv.tile = r.t0; if (op.conv.tail_wt) { op.tail_tile = r.t1; op.tail_on = r.fused != 0; } }
-            else if (op.kind == OP_GROUP) op.group_tile = r.t0;
-            else { op.group[0].tile = r.t0; op.group[1].tile = r.t1; op.fused = r.fused != 0; op.tail_on = (r.fused == 2 || r.fused == 4) && op.bneck.tail_wt; }
-            continue;
+            if (op.kind == OP_CONV) ok = tile_legal(&op.conv, 1, cached.tile) && (!op.has_tail || cached.form != FORM_WITH_TAIL || tail_tile_legal(op.conv, cached.tail_tile));
+            else if (op.kind == OP_GROUP) ok = tile_legal(op.group.data(), (int)op.group.size(), cached.tile);
+            else ok = tile_legal(&op.group[0], 1, cached.tile) && tile_legal(&op.group[1], 1, cached.tile2);
+            if (ok) { ch = cached; continue; }
         }
         float ms;
-        TuneRec r;
         if (op.kind == OP_CONV) {
-            RT_TRY(tune_conv(d, e0, e1, op.name, &op.conv, 1, op.conv.tile, ms));
-            r.t0 = op.conv.tile;
+            RT_TRY(tune_conv(d, e0, e1, op.name, &op.conv, 1, ch.tile, ms));
         } else if (op.kind == OP_GROUP) {
-            RT_TRY(tune_conv(d, e0, e1, op.name, op.group.data(), (int)op.group.size(), op.group_tile, ms));
-            r.t0 = op.group_tile;
+            RT_TRY(tune_conv(d, e0, e1, op.name, op.group.data(), (int)op.group.size(), ch.tile, ms));
         } else {
             float ms1, ms2, msf;
-            RT_TRY(tune_conv(d, e0, e1, op.group[0].in.c ? op.name + ".cv1" : op.name, &op.group[0], 1, op.group[0].tile, ms1));
-            RT_TRY(tune_conv(d, e0, e1, op.name + ".cv2", &op.group[1], 1, op.group[1].tile, ms2));
+            RT_TRY(tune_conv(d, e0, e1, op.group[0].in.c ? op.name + ".cv1" : op.name, &op.group[0], 1, ch.tile, ms1));
+            RT_TRY(tune_conv(d, e0, e1, op.name + ".cv2", &op.group[1], 1, ch.tile2, ms2));
             BottleneckLaunch plain = op.bneck;
             plain.tail_wt = nullptr;
             RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(plain, d->stream); }, msf));
             if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s fused %8.2f us vs two launches %8.2f us\n", op.name.c_str(), msf * 1e3f, (ms1 + ms2) * 1e3f);
-            op.fused = msf < ms1 + ms2;
-            if (const char *e = rt_opt("BNECK")) op.fused = atoi(e) != 0;      // A/B and test hook
-            r.t0 = op.group[0].tile; r.t1 = op.group[1].tile; r.fused = op.fused;
+            ch.form = msf < ms1 + ms2 ? FORM_FUSED : FORM_TWO_LAUNCHES;
         }
-        cache[key] = r;
+        ch.tail_timed = false;                             // (the tail passes below time it against the tiles just chosen)
         dirty = true;
     }
     // conv -> 1x1 pairs: the fused launch (every legal tail tile) against the two tuned launches
     for (size_t i = 0; i + 1 < ops.size(); ++i) {
         Op &op = ops[i], &nx = ops[i + 1];
-        if (op.kind != OP_CONV || !op.conv.tail_wt) continue;
-        const std::string key = tune_key(d, op);
-        auto hit = cache.find(key);
-        const bool cached = hit != cache.end() && hit->second.t1 != 0;      // t1 == 0 (TILE_128x128) is never a tail tile: "not decided yet"
-        if (!cached) {
-            float ms_a, ms_b, best = 1e30f;
-            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(op.conv, d->stream); }, ms_a));
-            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(nx.conv, d->stream); }, ms_b));
-            for (int t = TILE_TAIL_128x64; t <= TILE_TAIL_K64_128x128; ++t) {
-                if (tile_shape(t).bn != op.conv.cout || (tile_needs_cin64(t) && (op.conv.cin % 64 != 0 || op.conv.kp % 64 != 0)) || op.conv.cin % 32 != 0) continue;
-                ConvLaunch c = op.conv;
-                c.tile = t;
-                float ms;
-                RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(c, d->stream); }, ms));
-                if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s %-16s %8.2f us (+ %s)\n", op.name.c_str(), tile_name(t), ms * 1e3f, nx.name.c_str());
-                if (ms < best) { best = ms; op.tail_tile = t; }
-            }
-            op.tail_on = best < ms_a + ms_b;
-            if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with tail %8.2f us vs two launches %8.2f us\n", op.name.c_str(), best * 1e3f, (ms_a + ms_b) * 1e3f);
-            TuneRec r; r.t0 = op.conv.tile; r.t1 = op.tail_tile; r.fused = op.tail_on;
-            cache[key] = r;
-            dirty = true;
+        Choice &ch = op.choice;
+        if (op.kind != OP_CONV || !op.has_tail || ch.tail_timed) continue;
+        float ms_a, ms_b, best = 1e30f;
+        const ConvLaunch a = on_tile(op.conv, ch.tile), b = on_tile(nx.conv, nx.choice.tile);
+        RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(a, d->stream); }, ms_a));
+        RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(b, d->stream); }, ms_b));
+        for (int t = TILE_TAIL_128x64; t <= TILE_TAIL_K64_128x128; ++t) {
+            if (!tail_tile_legal(op.conv, t)) continue;
+            const ConvLaunch c = on_tile(op.conv, t);
+            float ms;
+            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(c, d->stream); }, ms));
+            if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s %-16s %8.2f us (+ %s)\n", op.name.c_str(), tile_name(t), ms * 1e3f, nx.name.c_str());
+            if (ms < best) { best = ms; ch.tail_tile = t; }
         }
-        if (const char *e = rt_opt("TAIL")) op.tail_on = atoi(e) != 0 && tile_shape(op.tail_tile).bn == op.conv.cout;   // A/B and test hook
-        nx.skip = op.tail_on;
+        if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with tail %8.2f us vs two launches %8.2f us\n", op.name.c_str(), best * 1e3f, (ms_a + ms_b) * 1e3f);
+        ch.form = best < ms_a + ms_b ? FORM_WITH_TAIL : FORM_PLAIN;
+        ch.tail_timed = true;
+        dirty = true;
     }
     // fused Bottleneck + C2f.cv2 as its tail against the fused Bottleneck followed by cv2's own launch
     for (size_t i = 0; i + 1 < ops.size(); ++i) {
         Op &op = ops[i], &nx = ops[i + 1];
-        if (op.kind != OP_BNECK || !op.bneck.tail_wt) continue;
-        const std::string key = tune_key(d, op);
-        auto hit = cache.find(key);
-        const bool decided = hit != cache.end() && hit->second.fused >= 2;      // 2 / 4 = fused with tail, 3 = tail timed and rejected
-        if (decided && hit->second.fused == 4) op.bneck.persistent32 = 0;
-        if (!decided && op.fused) {
-            float ms_plain, ms_cv2, ms_tail;
-            BottleneckLaunch plain = op.bneck;
-            plain.tail_wt = nullptr;
-            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(plain, d->stream); }, ms_plain));
-            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(nx.conv, d->stream); }, ms_cv2));
-            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(op.bneck, d->stream); }, ms_tail));
-            if (op.bneck.c == 32 && !rt_opt("BNECK32") && bottleneck32_tail_supported(op.bneck)) {      // two kernels for this shape: bneck32.hip's persistent form and bottleneck_fused
-                BottleneckLaunch other = op.bneck;
-                other.persistent32 = !op.bneck.persistent32;
-                float ms_other;
-                RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(other, d->stream); }, ms_other));
-                if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with cv2 tail: persistent %8.2f us vs bottleneck_fused %8.2f us\n", op.name.c_str(), (op.bneck.persistent32 ? ms_tail : ms_other) * 1e3f, (op.bneck.persistent32 ? ms_other : ms_tail) * 1e3f);
-                if (ms_other < ms_tail) { op.bneck.persistent32 = other.persistent32; ms_tail = ms_other; }
-            }
-            op.tail_on = ms_tail < ms_plain + ms_cv2;
-            if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with cv2 tail %8.2f us vs fused + cv2 %8.2f us\n", op.name.c_str(), ms_tail * 1e3f, (ms_plain + ms_cv2) * 1e3f);
-            TuneRec r; r.t0 = op.group[0].tile; r.t1 = op.group[1].tile; r.fused = op.tail_on ? (op.bneck.persistent32 ? 2 : 4) : 3;      // 2 / 4: with the tail on bneck32.hip's kernel / on bottleneck_fused
-            cache[key] = r;
-            dirty = true;
+        Choice &ch = op.choice;
+        if (op.kind != OP_BNECK || !op.has_tail || ch.tail_timed || ch.form != FORM_FUSED) continue;
+        float ms_plain, ms_cv2, ms_tail;
+        BottleneckLaunch plain = op.bneck;
+        plain.tail_wt = nullptr;
+        const ConvLaunch cv2 = on_tile(nx.conv, nx.choice.tile);
+        bool p32 = true;                                   // (BottleneckLaunch::persistent32 as op.bneck holds it)
+        RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(plain, d->stream); }, ms_plain));
+        RT_TRY(time_launch(d, e0, e1, [&]() { return launch_conv(cv2, d->stream); }, ms_cv2));
+        RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(op.bneck, d->stream); }, ms_tail));
+        if (op.bneck.c == 32 && bottleneck32_tail_supported(op.bneck)) {      // two kernels for this shape: bneck32.hip's persistent form and bottleneck_fused
+            BottleneckLaunch other = op.bneck;
+            other.persistent32 = 0;
+            float ms_other;
+            RT_TRY(time_launch(d, e0, e1, [&]() { return launch_bottleneck(other, d->stream); }, ms_other));
+            if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with cv2 tail: persistent %8.2f us vs bottleneck_fused %8.2f us\n", op.name.c_str(), ms_tail * 1e3f, ms_other * 1e3f);
+            if (ms_other < ms_tail) { p32 = false; ms_tail = ms_other; }
         }
-        if (const char *e = rt_opt("BNECK_TAIL")) op.tail_on = atoi(e) != 0;      // A/B and test hook
-        op.tail_on = op.tail_on && op.fused;
-        nx.skip = op.tail_on;
+        if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s with cv2 tail %8.2f us vs fused + cv2 %8.2f us\n", op.name.c_str(), ms_tail * 1e3f, (ms_plain + ms_cv2) * 1e3f);
+        ch.form = !(ms_tail < ms_plain + ms_cv2) ? FORM_FUSED : (p32 ? FORM_FUSED_TAIL_P32 : FORM_FUSED_TAIL);
+        ch.tail_timed = true;
+        dirty = true;
     }
     // the fused front end (stem -> layer 1 -> 2.cv1 in one launch) against the launches it replaces, both reading the letterboxed image tensor (what
     // the tuner's eager passes run on; the byte source differs by the same letterbox work on either side)
-    if (ops.size() >= 3 && ops[0].kind == OP_STEM && ops[0].front_ok) {
+    if (ops[0].front_ok) {
         Op &st = ops[0], &l1 = ops[1], &cv = ops[2];
-        const std::string key = "front|" + tune_key(d, l1);
-        auto hit = cache.find(key);
-        if (hit != cache.end()) st.front_on = hit->second.fused != 0;
-        else {
+        auto hit = cache.find("front|" + tune_key(d, l1));
+        if (hit == cache.end() || !decode_choice(OP_STEM, hit->second, st.choice)) {
             float ms_old, ms_new;
-            const bool keep1 = l1.skip, keep2 = cv.skip;
-            l1.skip = false; cv.skip = l1.tail_on;         // (the pair as the tuner just left it)
-            RT_TRY(time_launch(d, e0, e1, [&]() { RT_TRY(launch_stem(st.v[0], st.v[1], st.stem_w, st.stem_b, st.B, st.v[1].c, d->stream)); RT_TRY(run_op_on(l1, d->stream)); return run_op_on(cv, d->stream); }, ms_old));
+            const bool tail = carries_tail(l1);            // (the pair as the tuner just left it)
+            RT_TRY(time_launch(d, e0, e1, [&]() { RT_TRY(launch_stem(st.v[0], st.v[1], st.stem_w, st.stem_b, st.B, st.v[1].c, d->stream)); RT_TRY(launch_op(l1, d->stream)); return tail ? RTMODT_OK : launch_op(cv, d->stream); }, ms_old));
             RT_TRY(time_launch(d, e0, e1, [&]() { return front_launch(d, st, 0, false, d->stream); }, ms_new));
-            l1.skip = keep1; cv.skip = keep2;
-            st.front_on = ms_new < ms_old;
+            st.choice.form = ms_new < ms_old ? FORM_FRONT_END : FORM_PLAIN;
             if (rt_opt("TUNE_LOG")) fprintf(stderr, "[tune] %-28s fused front end %8.2f us vs stem + layer 1 (+ 2.cv1) %8.2f us\n", "0 + 1 + 2.cv1", ms_new * 1e3f, ms_old * 1e3f);
-            TuneRec r; r.fused = st.front_on;
-            cache[key] = r;
             dirty = true;
         }
-        if (const char *e = rt_opt("FRONT")) st.front_on = atoi(e) != 0;      // A/B and test hook
-        if (st.front_on) l1.skip = cv.skip = true;
-        else { l1.skip = false; cv.skip = l1.tail_on; }
     }
     hipEventDestroy(e0); hipEventDestroy(e1);
+    // the records of what the cache and the tuner decided; only then the hooks (which the file therefore never sees) and the skips
+    finish_plan(ops, read_hooks(), tail_legal_for, [&](const Op &op, const TuneRec &r) {
+        if (op.kind == OP_CONV || op.kind == OP_GROUP || op.kind == OP_BNECK) cache[tune_key(d, op)] = r;
+        else if (op.front_ok) cache["front|" + tune_key(d, ops[1])] = r;
+    });
     if (cache_path && dirty) {                            // whole file rewritten through a rename: readers never see half a file
         const std::string tmp = std::string(cache_path) + ".tmp." + std::to_string((long)getpid());
         {
@@ -1163,19 +1098,15 @@ static int autotune_ops(rtmodt_detector *d, std::vector<Op> &ops) {
 static int autotune_tiles(rtmodt_detector *d) {
     RT_TRY(autotune_ops(d, d->ops));
     // the tuner's decisions travel from the op it timed to the copies that run
-    auto adopt = [](Op &dst, const Op &src) {
-        dst.conv.tile = src.conv.tile;
-        dst.group_tile = src.group_tile;
-        dst.fused = src.fused;
-        dst.tail_on = src.tail_on; dst.tail_tile = src.tail_tile; dst.skip = src.skip; dst.front_on = src.front_on; dst.bneck.persistent32 = src.bneck.persistent32;
-        for (size_t g = 0; g < dst.group.size(); ++g) dst.group[g].tile = src.group[g].tile;
+    auto adopt = [](std::vector<Op> &dst, const std::vector<Op> &src) {
+        for (size_t i = 0; i < dst.size(); ++i) dst[i].choice = src[i].choice;
+        mark_skips(dst);
     };
     if (d->n_chains > 1) {
         RT_TRY(autotune_ops(d, d->chain_ops[0]));          // the sub-batch GEMMs have their own best tiles
-        for (int c = 1; c < d->n_chains; ++c)
-            for (size_t i = 0; i < d->ops.size(); ++i) adopt(d->chain_ops[c][i], d->chain_ops[0][i]);
+        for (int c = 1; c < d->n_chains; ++c) adopt(d->chain_ops[c], d->chain_ops[0]);
     } else {
-        for (size_t i = 0; i < d->ops.size(); ++i) adopt(d->chain_ops[0][i], d->ops[i]);
+        adopt(d->chain_ops[0], d->ops);
     }
     // the tuning launches left stale activations; run one clean pass
     RT_TRY(forward_eager_all(d));
@@ -2077,16 +2008,16 @@ int rtmodt_detector_debug_layer(rtmodt_detector *d, const char *name, int img, u
         if (d->newest >= 0) d->cur_dense = d->newest;
         RT_TRY(materialize_heads(d));                      // Detect's last convs live inside head_final
     }
-    if (!ops.empty() && ops[0].kind == OP_STEM && ops[0].front_on && (strcmp(name, "0") == 0 || strcmp(name, "1") == 0))
+    if (!ops.empty() && front_end_on(ops[0]) && (strcmp(name, "0") == 0 || strcmp(name, "1") == 0))
         return fail(RTMODT_E_UNSUPPORTED, "%s lives in LDS only: the front end (stem, layer 1, 2.cv1) runs as one launch", name);
     for (auto &op : ops)                               // a conv whose 1x1 tail runs in the same launch stores only the tail's output
-        if (op.kind == OP_CONV && op.tail_on && !op.skip && op.name == name)
+        if (op.kind == OP_CONV && carries_tail(op) && !op.skip && op.name == name)
             return fail(RTMODT_E_UNSUPPORTED, "%s is consumed in LDS by the 1x1 conv fused into its launch", name);
     for (auto &op : ops)                               // ... and so does a fused Bottleneck whose C2f.cv2 runs as its tail
-        if (op.kind == OP_BNECK && op.fused && op.tail_on && op.name == std::string(name).substr(0, std::string(name).rfind('.')) + " (cv1+cv2)")
+        if (carries_tail(op) && op.kind == OP_BNECK && op.name == std::string(name).substr(0, std::string(name).rfind('.')) + " (cv1+cv2)")
             return fail(RTMODT_E_UNSUPPORTED, "%s is consumed in LDS by the 1x1 conv fused into its launch", name);
     for (auto &op : ops)                               // the first conv of a fused Bottleneck never leaves the CU
-        if (op.kind == OP_BNECK && op.fused && op.name == std::string(name).substr(0, std::string(name).rfind('.')) + " (cv1+cv2)" &&
+        if (is_fused(op) && op.name == std::string(name).substr(0, std::string(name).rfind('.')) + " (cv1+cv2)" &&
             std::string(name).size() > 4 && std::string(name).compare(std::string(name).size() - 4, 4, ".cv1") == 0)
             return fail(RTMODT_E_UNSUPPORTED, "%s is the LDS-resident intermediate of a fused Bottleneck launch", name);
     if (hwc) { hwc[0] = v.H; hwc[1] = v.W; hwc[2] = v.c; }
@@ -2129,22 +2060,22 @@ int rtmodt_detector_profile(rtmodt_detector *d, int iters, int max_entries, cons
     d->prof_names.clear();
     for (auto &op : ops) {
         char buf[160];
-        if (op.kind == OP_CONV && op.skip && ops[0].kind == OP_STEM && ops[0].front_on && (&op == &ops[1] || &op == &ops[2])) {
+        if (op.kind == OP_CONV && op.skip && front_end_on(ops[0]) && (&op == &ops[1] || &op == &ops[2])) {
             snprintf(buf, sizeof(buf), "%s [runs inside the front-end launch]", op.name.c_str());
-        } else if (op.kind == OP_STEM && op.front_on) {
+        } else if (front_end_on(op)) {
             snprintf(buf, sizeof(buf), "%s [front end fused: %sstem + layer 1 + 2.cv1, one launch]", op.name.c_str(), d->last_fused ? "letterbox + " : "");
         } else if (op.kind == OP_CONV && op.skip) {
             snprintf(buf, sizeof(buf), "%s [runs as the tail of the previous launch]", op.name.c_str());
         } else if (op.kind == OP_CONV) {
             snprintf(buf, sizeof(buf), "%s [M=%d N=%d K=%d k%d s%d tile %s]", op.name.c_str(), PB * op.conv.out.H * op.conv.out.W,
-                     op.conv.cout, op.conv.ks * op.conv.ks * op.conv.cin, op.conv.ks, op.conv.stride, tile_name(op.tail_on ? op.tail_tile : op.conv.tile));
+                     op.conv.cout, op.conv.ks * op.conv.ks * op.conv.cin, op.conv.ks, op.conv.stride, tile_name(carries_tail(op) ? op.choice.tail_tile : op.choice.tile));
         } else if (op.kind == OP_BNECK) {
-            if (op.fused) snprintf(buf, sizeof(buf), "%s [fused bottleneck%s, c=%d, %dx%d]", op.name.c_str(), op.tail_on ? " + C2f.cv2 tail" : "", op.bneck.c, op.bneck.in.H, op.bneck.in.W);
-            else snprintf(buf, sizeof(buf), "%s [two launches: %s, %s]", op.name.c_str(), tile_name(op.group[0].tile), tile_name(op.group[1].tile));
+            if (is_fused(op)) snprintf(buf, sizeof(buf), "%s [fused bottleneck%s, c=%d, %dx%d]", op.name.c_str(), carries_tail(op) ? " + C2f.cv2 tail" : "", op.bneck.c, op.bneck.in.H, op.bneck.in.W);
+            else snprintf(buf, sizeof(buf), "%s [two launches: %s, %s]", op.name.c_str(), tile_name(op.choice.tile), tile_name(op.choice.tile2));
         } else if (op.kind == OP_GROUP && op.skip) {
             snprintf(buf, sizeof(buf), "%s [runs inside head_final]", op.name.c_str());
         } else if (op.kind == OP_GROUP) {
-            snprintf(buf, sizeof(buf), "%s [group of %zu, tile %s]", op.name.c_str(), op.group.size(), tile_name(op.group_tile));
+            snprintf(buf, sizeof(buf), "%s [group of %zu, tile %s]", op.name.c_str(), op.group.size(), tile_name(op.choice.tile));
         } else if (op.kind == OP_STEM && d->last_fused) {
             snprintf(buf, sizeof(buf), "%s [letterbox + stem fused]", op.name.c_str());
         } else {

@@ -1613,6 +1613,76 @@ def test_autotune_cache_rejects_foreign_and_illegal_entries(pkg, wdir, monkeypat
         assert float(np.abs(taps[n] - gpu[n]).max()) <= 4e-3 * np.abs(taps[n]).max() + 2e-3, n
     c.close()
     assert len(ref) == 2
+    # (3) a third field no Bottleneck record can hold (launch_plan.h writes 0 .. 4): a miss, tuned again, and the file says so afterwards
+    key = next(l.split()[0] for l in good[1:] if "_(cv1+cv2)|" in l)
+    broken = [f"{l.split()[0]}\t{l.split()[1]} {l.split()[2]} 7" if l.split()[0] == key else l for l in good]
+    cache.write_text("\n".join(broken) + "\n")
+    e, _ = make_detector(pkg, wdir, "n", 320, autotune=True, batch=2)
+    assert len(e.detect_batch(frames)) == 2
+    e.close()
+    after = cache.read_text().splitlines()
+    assert [l for l in after if l.split()[0] != key] == [l for l in good if l.split()[0] != key]      # every other record is a hit and comes back as it was
+    mended = [l.split() for l in after if l.split()[0] == key]
+    assert len(mended) == 1 and int(mended[0][3]) in range(5), mended
+
+
+HOOKS_OVER_A_CACHE = [("BNECK", "0"), ("BNECK32", "0"), ("BNECK_TAIL", "0"), ("TAIL", "0"), ("FRONT", "0"), ("FRONT", "1")]
+
+
+@pytest.fixture(scope="module")
+def tuned_cache(pkg, wdir, tmp_path_factory):
+    """YOLOv8s @ 320, batch 2, tuned once into a cache file of its own: (path, the file's bytes, the tuned detector's launch names, the weights).
+    (s, not n: n's only one-Bottleneck C2f of 32 channels, layer 15, works on 40-pixel rows, which bneck32.hip's 16-wide tiles do not divide.)"""
+    path = str(tmp_path_factory.mktemp("tune") / "tune.txt")
+    old = os.environ.get("RTMODT_TUNE_CACHE")
+    os.environ["RTMODT_TUNE_CACHE"] = path
+    try:
+        det, w = make_detector(pkg, wdir, "s", 320, autotune=True, batch=2)
+        names = [n for n, _, _ in det.profile(1)]
+        det.close()
+    finally:
+        if old is None:
+            del os.environ["RTMODT_TUNE_CACHE"]
+        else:
+            os.environ["RTMODT_TUNE_CACHE"] = old
+    with open(path, "rb") as f:
+        return path, f.read(), names, w
+
+
+@pytest.mark.parametrize("hook,value", HOOKS_OVER_A_CACHE, ids=[f"{h}={v}" for h, v in HOOKS_OVER_A_CACHE])
+def test_hooks_override_a_tune_cache_and_never_reach_it(pkg, wdir, monkeypatch, tuned_cache, hook, value):
+    """A detector created from a tune cache with an A/B hook set: the hook wins over the cached choice (launch_plan.h: apply_hooks runs last), the
+    file keeps its bytes (a hooked choice is never recorded), every launch the hook does not name stays as tuned, and every stored layer passes
+    the layer check.  (Which kernel a Bottleneck's cv2 tail runs on -- BNECK32 -- does not show in the names: same names, same layer check.)"""
+    path, data, tuned, _ = tuned_cache
+    monkeypatch.setenv("RTMODT_TUNE_CACHE", path)
+    monkeypatch.setenv("RTMODT_" + hook, value)
+    det, w = make_detector(pkg, wdir, "s", 320, autotune=True, batch=2)
+    with open(path, "rb") as f:
+        assert f.read() == data, "the hooked create rewrote the cache"
+    prof = [n for n, _, _ in det.profile(1)]
+    print(f"{hook}={value}: {sum(a != b for a, b in zip(prof, tuned))} of {len(prof)} launch names differ from the tuned ones")
+    assert len(prof) == len(tuned)
+    if hook == "BNECK":
+        assert not any("fused bottleneck" in n for n in prof) and sum("two launches" in n for n in prof) == sum("(cv1+cv2)" in n for n in prof) >= 4, prof
+    elif hook == "BNECK32":
+        assert prof == tuned
+    elif hook == "BNECK_TAIL":
+        assert sum("C2f.cv2 tail" in n for n in prof) == 0, [n for n in prof if "bottleneck" in n]
+    elif hook == "TAIL":
+        assert sum("tail:" in n for n in prof) == 0 and not any("runs as the tail of the previous launch" in n and ("2.cv1" in n or "4.cv1" in n) for n in prof), prof[:12]
+    else:
+        assert ("front end fused" in prof[0]) == (value == "1"), prof[:3]
+        assert ("inside the front-end launch" in prof[1] and "inside the front-end launch" in prof[2]) == (value == "1"), prof[:3]
+    c2f = lambda op: op.endswith("(cv1+cv2)") or (op.endswith(".cv2") and ".m." not in op)      # a Bottleneck, or the C2f.cv2 that may ride along
+    may_change = {"BNECK": c2f, "BNECK_TAIL": c2f, "BNECK32": lambda op: False, "TAIL": lambda op: op in ("1", "2.cv1", "3", "4.cv1"),
+                  "FRONT": lambda op: op in ("0", "1", "2.cv1")}[hook]
+    for a, b in zip(prof, tuned):                                    # the launches the hook does not name run as the cache says
+        assert a == b or may_change(a.split(" [")[0]), (a, b)
+    frame = pkg.synth.frames(1, 320, 320, seed=1234)[0]
+    _, _, _, worst = layer_check(pkg, det, w, frame, "s", 320)
+    print(f"{hook}={value}: worst layer {worst}")
+    det.close()
 
 
 @pytest.mark.parametrize("tile,size,batch,up_read,scale", [(T["PT_128x128_S2"], 320, 32, "0", "s"), (T["PT_128x64_S2"], 320, 32, "1", "s"),
