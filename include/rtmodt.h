@@ -2350,6 +2350,136 @@ int rtmodt_enhance_curve(const uint32_t *hist, int64_t n, int32_t clip_q8, uint3
  * bounds[tiles + 1], the first pixel of every tile and px.  The parity surface of the axis rule.  PARITY UNPINNED. */
 int rtmodt_enhance_axis(int32_t px, int32_t tiles, int32_t *k, int32_t *f, int32_t *bounds);
 
+/* ---- colour attributes: the colour names of every track, kept on the device ------------------------------------------------------ */
+/* What colour a track IS, for attribute search ("red top, dark trousers") and the alert record: the reference's Track and alert
+ * carry bbox_xyxy, a class and a frame_id.  Per track and call the module samples the inside of the box on a bounded grid, names
+ * every sample with one of 12 colour names by an all-integer rule, adds the counts of the UPPER and the LOWER part to the track's
+ * row of a per-stream ledger on the device, and answers the dominant and the second name of each part and of the WHOLE with
+ * their shares per mille, for live and for retired tracks.  csrc/colour_rule.h states the per-pixel and per-box rules, the header
+ * of csrc/colour.hip the ledger rules; tests/colour_ref.py restates both and the kernels equal it exactly.  No reference
+ * counterpart.  PARITY UNPINNED: the names agree with no human colour naming study and with no product's by any measurement; every
+ * default is validated on no real footage; there is no white balance, and night or IR frames honestly answer grey everywhere.
+ * Two launches per call for all streams whatever the tracks do.  Every call carries a frame_id per stream, strictly increasing
+ * per stream (else RTMODT_E_INVALID, nothing changes).  Frames are BGR24, h x w at a row pitch of stride_bytes >= 3 w, in host or
+ * device memory, and are only read.  An entry is SAMPLED (takes a row) when its class passes the filter, its coordinates are
+ * finite and x1 >= x0, y1 >= y0 after truncation; its sampled rectangle may still be empty (no samples, no error). */
+#define RTMODT_COLOUR_NAMES 12
+#define RTMODT_COLOUR_UPPER 0
+#define RTMODT_COLOUR_LOWER 1
+#define RTMODT_COLOUR_WHOLE 2
+#define RTMODT_COLOUR_F_NEW 1             /* the row was created by this call */
+#define RTMODT_COLOUR_F_MANY_OCCLUDERS 2  /* more than 8 occluders met the sampled rectangle in the row's last call; the extras were ignored */
+#define RTMODT_COLOUR_F_THIN 4            /* the row's last call took fewer than min_samples samples: its counts were not added */
+typedef struct rtmodt_colour rtmodt_colour;
+typedef struct rtmodt_colour_cfg {
+    /* the name of a pixel (csrc/colour_rule.h, step 1) */
+    int32_t black_max;          /* 0..256: max(b, g, r) below this is black */
+    int32_t chroma_min;         /* 0..256: max - min below this is achromatic */
+    int32_t sat_split;          /* 0..256: sat_hi_pm applies from this max on, sat_lo_pm below */
+    int32_t sat_hi_pm, sat_lo_pm; /* 0..1000: (max - min) * 1000 <= sat * max is achromatic */
+    int32_t y_black, y_white;   /* 0 <= y_black <= y_white <= 256: achromatic luma below y_black is black, from y_white on white, else grey */
+    int32_t hue[8];             /* ascending, 0..1536: the hue bounds red|orange|yellow|green|cyan|blue|purple|pink|red */
+    int32_t pink_mx, red_brown_mx, orange_brown_mx, yellow_brown_mx;   /* 0..256: the max thresholds of the pink and brown cases */
+    /* the sampled rectangle, the grid, the occluders (steps 2..4) */
+    int32_t inset_x_pm;         /* 0..499: the columns lose this many thousandths of the box width on each side */
+    int32_t top_pm, split_pm, bottom_pm;   /* 0 <= top < split < bottom <= 1000: thousandths of the box height */
+    int32_t max_side;           /* 1..256: at most this many samples along each axis */
+    int32_t skip_occluded;      /* 0 / 1: samples inside a nearer box of the list are skipped */
+    /* the ledger (step 5) */
+    int32_t min_samples;        /* 0..65536: a frame's counts are added only with at least this many samples over both parts */
+    int32_t retire_after;       /* >= 0: a row whose track was last sampled more than this many frame ids ago is retired */
+    int32_t device;
+    int32_t n_classes;          /* with `classes`: only these class ids are sampled (at most 256); classes == NULL: all */
+    const int32_t *classes;
+} rtmodt_colour_cfg;
+/* The label of one part: name and second are indices into the name order black, grey, white, red, orange, yellow, green, cyan,
+ * blue, purple, pink, brown (-1: none); shares in thousandths of `samples`, the part's total count. */
+typedef struct rtmodt_colour_label {
+    int32_t name, share_pm, second, second_pm, samples;
+} rtmodt_colour_label;
+/* One row: of `updated` (a member of this call, in list order), of `retired` (ascending track id) or of the ledger (_state, _load).
+ * `track`: index into the caller's list, or into the tracker's list; -1 in retired and ledger rows.  frame_samples: the samples
+ * this call took (0 in retired and ledger rows).  label[UPPER, LOWER, WHOLE] is read off hist; _load ignores it. */
+typedef struct rtmodt_colour_row {
+    int64_t track_id;
+    int64_t first_frame, last_frame;
+    uint32_t hist[2][RTMODT_COLOUR_NAMES];
+    int32_t cls, frames_used, flags, track;
+    int32_t frame_samples, reserved[2];
+    rtmodt_colour_label label[3];
+} rtmodt_colour_row;
+/* What one call hands back; the struct pointer and every member may be null.  With none given nothing crosses to the host and the
+ * call does not wait for the device; otherwise the streams' result blocks come back in one copy.  One-stream calls: updated
+ * [max_tracks], retired [2 max_tracks], counts [1]; all-stream calls: [n_streams][...] and counts [n_streams]. */
+typedef struct rtmodt_colour_out {
+    rtmodt_colour_row *updated;
+    int32_t *n_updated;
+    rtmodt_colour_row *retired;
+    int32_t *n_retired;
+} rtmodt_colour_out;
+/* The plan of one box (the parity surface of csrc/colour_rule.h): rectangles are inclusive x0, y0, x1, y1. */
+typedef struct rtmodt_colour_plan_out {
+    int32_t sampled;            /* 0: the box takes no row, nothing else is written */
+    int32_t raw[4];             /* truncated corners, not clipped */
+    int32_t box[4];             /* raw clipped to the frame (x1 < x0 or y1 < y0: empty) */
+    int32_t rect[4];            /* the sampled rectangle, clipped (empty likewise) */
+    int32_t split_row;          /* rows below it are UPPER */
+    int32_t sx, sy, nx, ny;     /* strides and sample counts (nx = ny = 0: no samples) */
+} rtmodt_colour_plan_out;
+/* black_max 48, chroma_min 20, sat_split 96, sat 180 / 400, y_black 64, y_white 176, hue 64 192 299 725 853 1109 1344 1472,
+ * pink_mx 192, red_brown_mx 96, orange_brown_mx 176, yellow_brown_mx 128, inset_x_pm 200, top / split / bottom 150 / 500 / 900,
+ * max_side 48, skip_occluded 1, min_samples 16, retire_after 30, device 0, every class. */
+void rtmodt_colour_default_cfg(rtmodt_colour_cfg *cfg);
+/* n_streams independent ledgers; max_tracks <= 4096.  A ledger holds 2 x max_tracks rows sorted by track id.  Per call and stream:
+ *   retire   a row with frame_id - last_frame > retire_after leaves the ledger and is reported in `retired` with its final label
+ *            (a track of the same id sampled in this call starts a new row);
+ *   member   a sampled entry keeps or takes its row: last_frame = frame_id, cls = the entry's, flags = this call's; its frame
+ *            counts are added (frames_used gains one) when they hold min_samples samples, and a part past 2^24 is halved.
+ * Occluders are taken in LIST order: ascending track id for a caller's list, the tracker's own order for a tracker.
+ * Capacity, as the snapshot gallery's: the call that needs more than 2 x max_tracks rows returns RTMODT_E_CAPACITY, the idle rows
+ * are dropped and the stream stays in error for good (every later call that asks for output, and _state, returns
+ * RTMODT_E_CAPACITY) until rtmodt_colour_reset.  A call made without outputs cannot report it. */
+int rtmodt_colour_create(const rtmodt_colour_cfg *cfg, int n_streams, int max_tracks, rtmodt_colour **out);
+/* Waits for the handle's queued work, frees everything; null is allowed. */
+void rtmodt_colour_destroy(rtmodt_colour *h);
+/* One stream, a caller-supplied track list (any order, unique ids, at most max_tracks) and its frame. */
+int rtmodt_colour_process(rtmodt_colour *h, int stream, const int64_t *track_ids, const float *xyxy, const int32_t *cls, int n,
+                          const uint8_t *frame, int fh, int fw, int stride_bytes, int mem_kind, int64_t frame_id, const rtmodt_colour_out *out);
+/* Every stream in one call: track_ids / cls [n_streams][stride], xyxy [n_streams][stride][4], n [n_streams], frames [n_streams]
+ * of one geometry, frame_id [n_streams]. */
+int rtmodt_colour_process_batch(rtmodt_colour *h, const int64_t *track_ids, const float *xyxy, const int32_t *cls, const int32_t *n, int stride,
+                                const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind, const int64_t *frame_id,
+                                const rtmodt_colour_out *out);
+/* Every stream of a ByteTrack handle, straight on its device-resident state and on the HIP stream its last update ran on:
+ * exactly the tracks rtmodt_snapshot_process_tracker passes.  frames / frame_id [n_streams of the tracker]. */
+int rtmodt_colour_process_tracker(rtmodt_colour *h, rtmodt_tracker *trk, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
+                                  const int64_t *frame_id, int report_tsu, const rtmodt_colour_out *out);
+/* The same on a DeepSORT handle. */
+int rtmodt_colour_process_deepsort(rtmodt_colour *h, rtmodt_deepsort *ds, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
+                                   const int64_t *frame_id, int report_tsu, const rtmodt_colour_out *out);
+/* The same on an OC-SORT handle. */
+int rtmodt_colour_process_ocsort(rtmodt_colour *h, rtmodt_ocsort *oc, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
+                                 const int64_t *frame_id, const rtmodt_colour_out *out);
+/* The same on a BoT-SORT handle. */
+int rtmodt_colour_process_botsort(rtmodt_colour *h, rtmodt_botsort *bot, const uint8_t *const *frames, int fh, int fw, int stride_bytes, int mem_kind,
+                                  const int64_t *frame_id, const rtmodt_colour_out *out);
+/* The whole ledger of one stream, rows in ascending track id with their labels (the parity surface of tests/colour_ref.py); rows
+ * [2 max_tracks] may be null.  A stream in error fills them all the same and returns RTMODT_E_CAPACITY. */
+int rtmodt_colour_state(rtmodt_colour *h, int stream, rtmodt_colour_row *rows, int32_t *n);
+/* Replaces one stream's ledger by n rows in strictly ascending track id (at most 2 max_tracks, first_frame <= last_frame,
+ * frames_used >= 0; labels are ignored), clears its error, and takes the largest last_frame as the stream's last frame_id: a
+ * handle continues where _state left another.  Anything else is RTMODT_E_INVALID and nothing is replaced. */
+int rtmodt_colour_load(rtmodt_colour *h, int stream, const rtmodt_colour_row *rows, int n);
+/* Empties one stream's ledger, forgets its last frame_id and its error. */
+int rtmodt_colour_reset(rtmodt_colour *h, int stream);
+/* Device time (ms, HIP events around the two launches) of the last _process* call. */
+int rtmodt_colour_last_ms(rtmodt_colour *h, float *kernel_ms);
+/* Host only, no device needed: the name (0..11) of the pixel (b, g, r), each 0..255, under cfg's thresholds; a negative error
+ * code when cfg or a channel is out of range. */
+int rtmodt_colour_name(int b, int g, int r, const rtmodt_colour_cfg *cfg);
+/* Host only, no device needed: the sampled rectangle, the split row and the grid of one box xyxy[4] of any class in an h x w frame. */
+int rtmodt_colour_plan(const rtmodt_colour_cfg *cfg, const float *xyxy, int h, int w, rtmodt_colour_plan_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,8 @@ library being built):
 * ``profiling``          -- ``LatencyProfiler`` (reference: src/profiling/latency_profiler.py:35-143)
 * ``events``             -- ``ZoneEventEngine`` on device-resident tracks (reference: src/events/zone_engine.py:64-157);
                             ``CrossingCounter``: directional line / gate counts (what config/default.yaml:73-77 promises);
-                            ``SpeedEstimator``: track speed, alarms and proximity pairs on a world ground plane
+                            ``SpeedEstimator``: track speed, alarms and proximity pairs on a world ground plane;
+                            ``ColourAttributes``: the colour names of every track's upper and lower part, for attribute search
 * ``pipeline``           -- the reference's per-frame loop (tools/run_pipeline.py:121-158) around the native classes
 * ``visualization``      -- ``FrameRenderer``: boxes, labels, trails, zones and HUD drawn into frames on the GPU
                             (reference: src/visualization/renderer.py:28-96); ``JpegEncoder`` / ``MjpegWriter``: the annotated
@@ -76,6 +77,7 @@ _LAZY = {
     "ZoneEventEngine": ".events.zone_engine",
     "CrossingCounter": ".events.crossing",
     "SpeedEstimator": ".events.speed",
+    "ColourAttributes": ".events.colours",
     "FrameReader": ".ingestion.reader",
     "RTSPReader": ".ingestion.reader",
     "JpegDecoder": ".ingestion.jpeg_decode",

@@ -174,6 +174,33 @@ class SnapshotPlan(C.Structure):                     # struct rtmodt_snapshot_pl
                 ("dw", C.c_int32), ("dh", C.c_int32), ("ox", C.c_int32), ("oy", C.c_int32), ("cut", C.c_int32), ("area", C.c_int32)]
 
 
+class ColourCfg(C.Structure):                        # struct rtmodt_colour_cfg
+    _fields_ = [("black_max", C.c_int32), ("chroma_min", C.c_int32), ("sat_split", C.c_int32), ("sat_hi_pm", C.c_int32), ("sat_lo_pm", C.c_int32),
+                ("y_black", C.c_int32), ("y_white", C.c_int32), ("hue", C.c_int32 * 8), ("pink_mx", C.c_int32), ("red_brown_mx", C.c_int32),
+                ("orange_brown_mx", C.c_int32), ("yellow_brown_mx", C.c_int32), ("inset_x_pm", C.c_int32), ("top_pm", C.c_int32), ("split_pm", C.c_int32),
+                ("bottom_pm", C.c_int32), ("max_side", C.c_int32), ("skip_occluded", C.c_int32), ("min_samples", C.c_int32), ("retire_after", C.c_int32),
+                ("device", C.c_int32), ("n_classes", C.c_int32), ("classes", C.POINTER(C.c_int32))]
+
+
+class ColourLabel(C.Structure):                      # struct rtmodt_colour_label
+    _fields_ = [("name", C.c_int32), ("share_pm", C.c_int32), ("second", C.c_int32), ("second_pm", C.c_int32), ("samples", C.c_int32)]
+
+
+class ColourRow(C.Structure):                        # struct rtmodt_colour_row
+    _fields_ = [("track_id", C.c_int64), ("first_frame", C.c_int64), ("last_frame", C.c_int64), ("hist", (C.c_uint32 * 12) * 2), ("cls", C.c_int32),
+                ("frames_used", C.c_int32), ("flags", C.c_int32), ("track", C.c_int32), ("frame_samples", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("label", ColourLabel * 3)]
+
+
+class ColourOut(C.Structure):                        # struct rtmodt_colour_out
+    _fields_ = [("updated", C.c_void_p), ("n_updated", C.c_void_p), ("retired", C.c_void_p), ("n_retired", C.c_void_p)]
+
+
+class ColourPlan(C.Structure):                       # struct rtmodt_colour_plan_out
+    _fields_ = [("sampled", C.c_int32), ("raw", C.c_int32 * 4), ("box", C.c_int32 * 4), ("rect", C.c_int32 * 4), ("split_row", C.c_int32), ("sx", C.c_int32),
+                ("sy", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32)]
+
+
 class RenderCfg(C.Structure):                        # struct rtmodt_render_cfg
     _fields_ = [("show_boxes", C.c_int32), ("show_ids", C.c_int32), ("show_trails", C.c_int32), ("show_zones", C.c_int32),
                 ("show_fps", C.c_int32), ("trail_length", C.c_int32), ("palette_bgr", C.POINTER(C.c_uint8)), ("n_palette", C.c_int32)]
@@ -708,6 +735,21 @@ def lib() -> C.CDLL:
         "rtmodt_snapshot_crop": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]),
         "rtmodt_snapshot_crop_detector": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp]),
         "rtmodt_snapshot_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_colour_default_cfg": (None, [C.POINTER(ColourCfg)]),
+        "rtmodt_colour_create": (C.c_int, [C.POINTER(ColourCfg), C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtmodt_colour_destroy": (None, [vp]),
+        "rtmodt_colour_process": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, i64, C.POINTER(ColourOut)]),
+        "rtmodt_colour_process_batch": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(ColourOut)]),
+        "rtmodt_colour_process_tracker": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(ColourOut)]),
+        "rtmodt_colour_process_deepsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(ColourOut)]),
+        "rtmodt_colour_process_ocsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(ColourOut)]),
+        "rtmodt_colour_process_botsort": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.POINTER(ColourOut)]),
+        "rtmodt_colour_state": (C.c_int, [vp, C.c_int, vp, C.POINTER(i32)]),
+        "rtmodt_colour_load": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+        "rtmodt_colour_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_colour_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_colour_name": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(ColourCfg)]),
+        "rtmodt_colour_plan": (C.c_int, [C.POINTER(ColourCfg), vp, C.c_int, C.c_int, C.POINTER(ColourPlan)]),
         "rtmodt_crosscam_default_cfg": (None, [C.POINTER(CrossCamCfg)]),
         "rtmodt_crosscam_create": (C.c_int, [C.POINTER(CrossCamCfg), C.POINTER(vp)]),
         "rtmodt_crosscam_destroy": (None, [vp]),

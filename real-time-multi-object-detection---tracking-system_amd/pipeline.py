@@ -66,7 +66,7 @@ class PinnedFrameRing:
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
         crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
-        left_objects=None, stabilize=None, health=None, enhance=None) -> dict:
+        left_objects=None, stabilize=None, health=None, enhance=None, colours=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -159,7 +159,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     ``motion`` and after ``decode``, ``health``, ``undistort`` and ``stabilize`` -- health judges the raw picture and the lens table
     samples unaltered pixels: a dark or flat frame is replaced by the enhanced one for every later stage and for the recorder.  The
     summary then carries ``enhance_mean_eff``, the mean effective strength (0..256) over the frames.  ``None``: the loop, the stage
-    table and the summary are unchanged."""
+    table and the summary are unchanged.
+
+    ``colours``: an ``events.ColourAttributes``, called inside a ``colours`` stage directly before ``left_objects`` (else before
+    ``snapshots``, else ``privacy``, else ``visualization``): after the swap guard, so its ledger follows the corrected ids, and on clean
+    pixels.  Like ``snapshots`` it reads the tracker's device-resident state when the crossings stage would, else the materialised
+    list, and it runs on the held tracks of a motion-gated still frame; for the device-resident form the object must be made with at
+    least the tracker's ``max_tracks``.  The summary then carries ``colours_retired``, the rows of stream 0 that left with their final
+    label.  ``None``: the loop, the stage table and the summary are unchanged."""
     profiler = profiler or LatencyProfiler(gpu_sync=True, warmup_frames=50, log_interval=100)
     detections = tracks = None
     n_events = n_crossings = n_reverted = 0
@@ -203,11 +210,15 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index(next(k for k in ("snapshots", "privacy", "visualization") if k in order)), "left_objects")
         profiler.STAGE_ORDER = order
+    if colours is not None and "colours" not in profiler.STAGE_ORDER:          # likewise, directly before left_objects (else: snapshots, privacy, visualization)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index(next(k for k in ("left_objects", "snapshots", "privacy", "visualization") if k in order)), "colours")
+        profiler.STAGE_ORDER = order
     if compose is not None and "compose" not in profiler.STAGE_ORDER:          # likewise, directly after visualization
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("visualization") + 1, "compose")
         profiler.STAGE_ORDER = order
-    n_speed = n_snap_rewritten = n_snap_retired = n_left_alarms = n_left_retired = 0
+    n_speed = n_snap_rewritten = n_snap_retired = n_left_alarms = n_left_retired = n_colours_retired = 0
     n_status = [0, 0, 0, 0]                                                    # frames per motion status
     n_stab = [0, 0, 0, 0]                                                      # frames per stabiliser status
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
@@ -270,7 +281,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
                             and hasattr(event_engine, "process_tracker"))
         # the crossing counter reads either tracker's state; alone (no event engine, no renderer) it too leaves the list on the device
         crossings_on_device = events_on_device
-        if (crossing_counter is not None or speed is not None or snapshots is not None or left_objects is not None) and event_engine is None and renderer is None and handoff:
+        if (crossing_counter is not None or speed is not None or snapshots is not None or left_objects is not None or colours is not None) and event_engine is None and renderer is None and handoff:
             events_on_device = crossings_on_device = True
         if not skip:
             profiler.tick("tracking")
@@ -308,6 +319,14 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             else:
                 n_speed += len(speed.process(tracks, speed.frame_time_us(fid)))
             profiler.tock("speed")
+        if colours is not None:
+            profiler.tick("colours")
+            if crossings_on_device:
+                _, gone = colours.process_tracker(tracker, [frame], fid)
+            else:
+                _, gone = colours.process(tracks or [], frame, fid)
+            n_colours_retired += len(gone)
+            profiler.tock("colours")
         if left_objects is not None:
             profiler.tick("left_objects")
             if crossings_on_device:
@@ -371,6 +390,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["speed_events"] = n_speed
     if snapshots is not None:
         out["snapshots_rewritten"], out["snapshots_retired"] = n_snap_rewritten, n_snap_retired
+    if colours is not None:
+        out["colours_retired"] = n_colours_retired
     if left_objects is not None:
         out["left_object_alarms"], out["left_objects_retired"] = n_left_alarms, n_left_retired
     if swap_guard is not None:
