@@ -2289,7 +2289,7 @@ int rtmodt_health_decide(const rtmodt_health_cfg *cfg, int64_t cells, int64_t fr
  * cv2.createCLAHE too (its tiles are padded by reflection, its interpolation is float), and no default is validated on real footage.
  * PINNED, exactly, against tests/enhance_ref.py: every output byte, histogram, state value and result field.  csrc/enhance_rule.h
  * states the rules, csrc/enhance.hip's header the launches; all of it is integer arithmetic.  DELIBERATE LIMITS: luma only, no
- * denoising, no gamma or white balance, one tile grid per handle, `auto` follows the frame mean without hysteresis. */
+ * denoising (rtmodt_denoise, run before this), no gamma or white balance, one tile grid per handle, `auto` follows the frame mean without hysteresis. */
 #define RTMODT_ENHANCE_SHIFT 0          /* each channel becomes clamp(c + (Y2 - Y)): chroma untouched                           */
 #define RTMODT_ENHANCE_GAIN 1           /* each channel becomes min(255, (c * Y2 + Y / 2) / Y): hue and saturation kept         */
 #define RTMODT_ENHANCE_MAX_TILES 16
@@ -2349,6 +2349,77 @@ int rtmodt_enhance_curve(const uint32_t *hist, int64_t n, int32_t clip_q8, uint3
  * -> k[px] and f[px] (0..256, in 1 / 256 of the way from the centre of tile k to that of tile min(k + 1, tiles - 1)), and
  * bounds[tiles + 1], the first pixel of every tile and px.  The parity surface of the axis rule.  PARITY UNPINNED. */
 int rtmodt_enhance_axis(int32_t px, int32_t tiles, int32_t *k, int32_t *f, int32_t *bounds);
+
+/* ---- frame noise reduction: motion-adaptive temporal and spatial filtering ("3DNR") before the enhancer ------------------------- */
+/* High-gain sensor noise is on every pixel of every night frame; the enhancer multiplies it, the JPEG encoder spends bytes on it.
+ * Per stream the module keeps acc, a running mean of every channel of every pixel in 8.8 fixed point.  A pixel whose 3 x 3
+ * neighbourhood did not change in the sum of its luma differences (noise cancels in the sum, a real change does not) moves towards
+ * the frame by 1 / 2^temporal_shift; a pixel that changed takes the frame at once, smoothed by a sigma filter over the neighbours
+ * of similar luma; between motion_lo and motion_hi the two blend.  It belongs directly after stabilisation (a temporal filter
+ * needs registered frames) and directly before rtmodt_enhance.  The reference has no counterpart (src/ingestion/rtsp_reader.py
+ * hands cap.read()'s frame on): PARITY UNPINNED throughout, against any camera's 3DNR, cv2.fastNlMeansDenoising and ffmpeg's
+ * hqdn3d too, and no default is validated on real footage.  PINNED, exactly, against tests/denoise_ref.py: every output byte,
+ * state value and result field.  csrc/denoise_rule.h states the rules, csrc/denoise.hip's header the launches; all of it is
+ * integer arithmetic.  DELIBERATE LIMITS: no motion compensation (a PTZ move is motion everywhere: the frame passes), thresholds
+ * do not adapt to the measured noise (it is reported, the choice is the caller's), BGR24 only, and no in-place form. */
+typedef struct rtmodt_denoise rtmodt_denoise;
+typedef struct rtmodt_denoise_cfg {
+    int32_t streams;            /* 1..1024                                                                                      */
+    int32_t height, width;      /* the frame size, 1..16384 each                                                                */
+    int32_t motion_lo, motion_hi; /* 0 <= motion_lo < motion_hi <= 2295, in units of the 3 x 3 luma sum: at and below motion_lo
+                                   a pixel is static, at and above motion_hi it is moving                                       */
+    int32_t temporal_shift;     /* 0..6: a static pixel moves by 1 / 2^temporal_shift per frame; 0: no temporal filtering        */
+    int32_t spatial;            /* 0..256: how much of the sigma filter a moving pixel takes; 0: none                           */
+    int32_t spatial_thr;        /* 0..255: a neighbour counts in the sigma filter when its luma is at most this far from the pixel's */
+    int32_t device;
+} rtmodt_denoise_cfg;
+typedef struct rtmodt_denoise_result {
+    int32_t stream;
+    int32_t frames_seen;        /* after the call                                                                               */
+    uint32_t n_static;          /* the pixels with a == 0                                                                       */
+    uint32_t n_moving;          /* the pixels with a == 256                                                                     */
+    uint64_t absdiff_static;    /* the sum of |Y(x) - Y(prev)| over the static pixels: 256 * absdiff_static / n_static is the
+                                   noise figure to tune the thresholds with                                                     */
+} rtmodt_denoise_result;
+/* Host only: 1 stream, height and width 0 (the caller sets them), motion_lo 18, motion_hi 54, temporal_shift 3, spatial 256,
+ * spatial_thr 6, device 0.  No default has been validated on real footage.  Replaces nothing (rtsp_reader.py).  PARITY UNPINNED. */
+void rtmodt_denoise_default_cfg(rtmodt_denoise_cfg *cfg);
+/* Every parameter is checked before anything is allocated: one outside its range (motion_hi <= motion_lo too) is RTMODT_E_INVALID
+ * and the message names it; more than 2^30 pixels over all streams is RTMODT_E_CAPACITY.  Every stream starts with frames_seen 0.
+ * Replaces nothing (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_create(const rtmodt_denoise_cfg *cfg, rtmodt_denoise **out);
+/* Waits for the handle's own stream, frees its buffers; null is allowed.  Replaces nothing (rtsp_reader.py).  PARITY UNPINNED. */
+void rtmodt_denoise_destroy(rtmodt_denoise *d);
+/* One frame for each of n distinct streams: src[i] (BGR24, height x width as created, row pitch src_stride >= 3w, host or device
+ * memory by src_mem_kind) is filtered with the state of streams[i] (streams == NULL: stream i, and n must be the stream count)
+ * into dst[i] (dst_stride, dst_mem_kind; any mix of host and device).  An output pixel depends on its neighbours' inputs, so
+ * there is NO in-place form: any meeting of a destination range with a source range of the call, dst[i] == src[i] included, a
+ * frame size other than the handle's, a stream outside 0..streams - 1 or named twice, a null frame and n above the stream count
+ * are RTMODT_E_INVALID with nothing launched.  Padding bytes of the rows are not touched.  A memset and two launches, whatever the
+ * frames show; results (NULL: none are copied) come back in one copy.  Streams the call does not name keep their state.
+ * Synchronous.  Replaces the hand-over of cap.read()'s frame (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_process(rtmodt_denoise *d, const uint8_t *const *src, int src_stride, int src_mem_kind, uint8_t *const *dst, int dst_stride,
+                           int dst_mem_kind, const int32_t *streams, int n, int height, int width, rtmodt_denoise_result *results);
+/* One stream's state to host memory: acc as uint16[height][width][3] (8.8 fixed point) and frames_seen.  Replaces nothing
+ * (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_read_state(rtmodt_denoise *d, int stream, uint16_t *acc, int32_t *frames_seen);
+/* Replaces one stream's state (n_values must be height * width * 3), so that a denoiser survives a restart; another size, a value
+ * above 255 << 8 or frames_seen outside 0..2^30 is RTMODT_E_INVALID and nothing is replaced.  Replaces nothing (rtsp_reader.py).
+ * PARITY UNPINNED. */
+int rtmodt_denoise_load_state(rtmodt_denoise *d, int stream, const uint16_t *acc, int64_t n_values, int32_t frames_seen);
+/* Forgets one stream's state (its next frame passes and sets it), or every stream's with stream == -1.  Replaces nothing
+ * (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_reset(rtmodt_denoise *d, int stream);
+/* Device time (ms, HIP events around the memset and the two launches) of the last process call that launched.  Replaces nothing
+ * (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_last_ms(rtmodt_denoise *d, float *kernel_ms);
+/* Host only, no device needed: csrc/denoise_rule.h's rule for one pixel from its two 3 x 3 neighbourhoods, row by row, the
+ * caller having clamped the coordinates: cur[9][3] the frame's BGR bytes and acc[9][3] the state (each at most 255 << 8); bit q
+ * of `inside` says that neighbour q lies inside the frame (bit 4, the centre, must be set).  Only the rule fields of cfg are read
+ * (motion_lo .. spatial_thr).  -> out[3], the centre's new acc_out[3], and (each may be NULL) a and D.  The parity surface of
+ * csrc/denoise_rule.h.  Replaces nothing (rtsp_reader.py).  PARITY UNPINNED. */
+int rtmodt_denoise_pixel(const rtmodt_denoise_cfg *cfg, const uint8_t *cur, const uint16_t *acc, uint32_t inside, int32_t frames_seen, uint8_t *out,
+                         uint16_t *acc_out, int32_t *a, int32_t *d);
 
 /* ---- colour attributes: the colour names of every track, kept on the device ------------------------------------------------------ */
 /* What colour a track IS, for attribute search ("red top, dark trousers") and the alert record: the reference's Track and alert

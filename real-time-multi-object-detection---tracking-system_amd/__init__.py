@@ -47,7 +47,8 @@ library being built):
                             frames of a shaking camera steadied on the GPU ahead of every fixed-camera stage; ``CameraHealth``:
                             covered, re-aimed, defocused, dark, dazzled and frozen cameras told from healthy ones on the GPU;
                             ``FrameEnhancer``: low-light and low-contrast frames lifted by temporally smoothed CLAHE on the GPU
-                            ahead of motion detection and the detector
+                            ahead of motion detection and the detector; ``FrameDenoiser``: sensor noise removed by a
+                            motion-adaptive temporal and spatial filter on the GPU ahead of the enhancer
 * ``evaluation``         -- COCO bbox AP and CLEAR MOT / IDF1 evaluated on the GPU, plus writers of the project's outputs
                             in COCO results / MOTChallenge form (reference: src/evaluation/metrics.py); ``stitch_tracks`` /
                             ``correct_id_switches``: fragmented tracks merged and their gaps filled on the GPU (the design
@@ -83,6 +84,7 @@ _LAZY = {
     "JpegDecoder": ".ingestion.jpeg_decode",
     "MjpegCapture": ".ingestion.mjpeg",
     "FrameEnhancer": ".ingestion.enhance",
+    "FrameDenoiser": ".ingestion.denoise",
     "FrameRenderer": ".visualization.renderer",
     "PrivacyMask": ".visualization.privacy",
     "Heatmap": ".visualization.heatmap",

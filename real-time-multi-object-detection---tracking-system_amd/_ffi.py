@@ -403,6 +403,14 @@ class EnhanceResult(C.Structure):                   # struct rtmodt_enhance_resu
     _fields_ = [("stream", C.c_int32), ("frames_seen", C.c_int32), ("eff", C.c_uint32), ("clipped", C.c_uint32), ("luma_sum", C.c_uint64)]
 
 
+class DenoiseCfg(C.Structure):                      # struct rtmodt_denoise_cfg
+    _fields_ = [(k, C.c_int32) for k in ("streams", "height", "width", "motion_lo", "motion_hi", "temporal_shift", "spatial", "spatial_thr", "device")]
+
+
+class DenoiseResult(C.Structure):                   # struct rtmodt_denoise_result
+    _fields_ = [("stream", C.c_int32), ("frames_seen", C.c_int32), ("n_static", C.c_uint32), ("n_moving", C.c_uint32), ("absdiff_static", C.c_uint64)]
+
+
 class SwapEventRec(C.Structure):                     # struct rtmodt_swap_event
     _fields_ = [("frame_id", C.c_int64), ("id_a", C.c_int64), ("id_b", C.c_int64), ("track_a", C.c_int32), ("track_b", C.c_int32),
                 ("sims", C.c_int32 * 4)]
@@ -718,6 +726,15 @@ def lib() -> C.CDLL:
         "rtmodt_enhance_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
         "rtmodt_enhance_curve": (C.c_int, [vp, i64, i32, vp, C.POINTER(C.c_uint32)]),
         "rtmodt_enhance_axis": (C.c_int, [i32, i32, vp, vp, vp]),
+        "rtmodt_denoise_default_cfg": (None, [C.POINTER(DenoiseCfg)]),
+        "rtmodt_denoise_create": (C.c_int, [C.POINTER(DenoiseCfg), C.POINTER(vp)]),
+        "rtmodt_denoise_destroy": (None, [vp]),
+        "rtmodt_denoise_process": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "rtmodt_denoise_read_state": (C.c_int, [vp, C.c_int, vp, C.POINTER(i32)]),
+        "rtmodt_denoise_load_state": (C.c_int, [vp, C.c_int, vp, i64, i32]),
+        "rtmodt_denoise_reset": (C.c_int, [vp, C.c_int]),
+        "rtmodt_denoise_last_ms": (C.c_int, [vp, C.POINTER(f32)]),
+        "rtmodt_denoise_pixel": (C.c_int, [C.POINTER(DenoiseCfg), vp, vp, C.c_uint32, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
         "rtmodt_snapshot_default_cfg": (None, [C.POINTER(SnapshotCfg)]),
         "rtmodt_snapshot_create": (C.c_int, [C.POINTER(SnapshotCfg), C.c_int, C.c_int, C.POINTER(vp)]),
         "rtmodt_snapshot_destroy": (None, [vp]),

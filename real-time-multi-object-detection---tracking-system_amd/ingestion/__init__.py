@@ -5,5 +5,6 @@ from .lens import LensCorrector, fisheye_map, monotonic_r2  # noqa: F401
 from .stabilizer import Stabilizer  # noqa: F401
 from .health import CameraHealth  # noqa: F401
 from .enhance import FrameEnhancer  # noqa: F401
+from .denoise import FrameDenoiser  # noqa: F401
 
 register_backend("mjpeg", MjpegCapture)          # FrameReader("x.avi", backend="mjpeg"): Motion-JPEG decoded on the GPU

@@ -11,7 +11,7 @@ The work runs in ``csrc/enhance.hip`` (rules in ``csrc/enhance_rule.h``); there 
 ``tests/enhance_ref.py`` restates every rule and the kernels equal it exactly: all of it is integer arithmetic.  Unpinned: parity with
 ``cv2.createCLAHE`` (installed nowhere this runs; its tiles are padded by reflection and its interpolation is float), every default
 (``tiles``, ``clip_limit``, ``smooth_shift``) -- none has been validated on real footage -- and any gain in detector recall.  Deliberate
-limits: luma only; no denoising, gamma or white balance; one tile grid per handle; ``auto`` follows the frame mean without hysteresis.
+limits: luma only; no denoising (``FrameDenoiser`` runs before it), gamma or white balance; one tile grid per handle; ``auto`` follows the frame mean without hysteresis.
 
 Sizes are ``(height, width)`` and tile grids ``(tiles_y, tiles_x)`` throughout.
 """
@@ -100,7 +100,7 @@ class FrameEnhancer(_ffi.Handle):
     0 follows the frame at once (and flickers).  ``auto`` ``(lo, hi)`` with ``hi > lo``: the strength falls linearly from ``strength`` at
     a mean luma of ``lo`` to nothing at ``hi`` -- full strength at night, none by day; ``(0, 0)``: always ``strength``.  ``colour``:
     ``"shift"`` adds the luma change to every channel (chroma untouched), ``"gain"`` scales the channels by it (hue and saturation
-    kept; chroma noise is amplified with the signal).  With an effective strength of 0 the output bytes are the input bytes under both.
+    kept; chroma noise is amplified with the signal -- ``FrameDenoiser`` ahead of it removes it).  With an effective strength of 0 the output bytes are the input bytes under both.
 
     None of the defaults has been validated on real footage."""
 

@@ -66,7 +66,7 @@ class PinnedFrameRing:
 def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, max_frames: int = 200,
         device_stages: bool = True, event_engine=None, device_handoff: bool = True, renderer=None, recorder=None,
         crossing_counter=None, swap_guard=None, privacy=None, heatmap=None, motion=None, speed=None, lens=None, snapshots=None, compose=None,
-        left_objects=None, stabilize=None, health=None, enhance=None, colours=None) -> dict:
+        left_objects=None, stabilize=None, health=None, enhance=None, colours=None, denoise=None) -> dict:
     """Runs ``max_frames`` iterations of the reference loop; returns ``profiler.summary(p50=True)``
     plus the last frame's detections and tracks.
 
@@ -161,6 +161,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     summary then carries ``enhance_mean_eff``, the mean effective strength (0..256) over the frames.  ``None``: the loop, the stage
     table and the summary are unchanged.
 
+    ``denoise``: a one-stream ``ingestion.FrameDenoiser`` of the frames' size, called inside a ``denoise`` stage directly before
+    ``enhance`` -- the enhancer should equalise the clean picture, not the noise -- and, without an enhancer, where ``enhance`` would
+    stand: directly after the last present of ``stabilize``, ``undistort``, ``health`` and ``decode`` (a temporal filter needs
+    registered frames).  The filtered frame goes into a fresh array and replaces the frame for every later stage and for the
+    recorder.  The summary then carries ``denoise_mean_noise_q8``, the mean over the frames of the noise figure
+    (``DenoiseResult.noise_q8``).  ``None``: the loop, the stage table and the summary are unchanged.
+
     ``colours``: an ``events.ColourAttributes``, called inside a ``colours`` stage directly before ``left_objects`` (else before
     ``snapshots``, else ``privacy``, else ``visualization``): after the swap guard, so its ledger follows the corrected ids, and on clean
     pixels.  Like ``snapshots`` it reads the tracker's device-resident state when the crossings stage would, else the materialised
@@ -202,6 +209,11 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index(next(k for k in ("stabilize", "undistort", "health", "decode") if k in order)) + 1, "enhance")
         profiler.STAGE_ORDER = order
+    if denoise is not None and "denoise" not in profiler.STAGE_ORDER:          # likewise, directly before enhance (else: where enhance would stand)
+        order = list(profiler.STAGE_ORDER)
+        order.insert(order.index("enhance") if "enhance" in order else
+                     order.index(next(k for k in ("stabilize", "undistort", "health", "decode") if k in order)) + 1, "denoise")
+        profiler.STAGE_ORDER = order
     if snapshots is not None and "snapshots" not in profiler.STAGE_ORDER:      # likewise, directly before privacy (else: visualization)
         order = list(profiler.STAGE_ORDER)
         order.insert(order.index("privacy" if "privacy" in order else "visualization"), "snapshots")
@@ -224,6 +236,7 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
     still_run = 0                                                              # consecutive frames whose detector pass was skipped
     n_health_alarms = health_flags = 0
     n_enhanced = enhance_eff = 0
+    n_denoised = denoise_noise = 0
     for _ in range(max_frames):
         profiler.tick("decode")
         ok, frame, fid = source.read()
@@ -245,6 +258,13 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
             frame = stabilize.process([frame])[0]
             n_stab[stabilize.result()[0].status] += 1
             profiler.tock("stabilize")
+        if denoise is not None:
+            profiler.tick("denoise")
+            clean = np.empty_like(frame)                                       # (there is no in-place form, and the source's frame is not written)
+            denoise_noise += denoise.process([frame], out=[clean])[0].noise_q8
+            frame = clean
+            n_denoised += 1
+            profiler.tock("denoise")
         if enhance is not None:
             profiler.tick("enhance")
             enhanced = np.empty_like(frame)                                    # (the source may hand out a slot of its ring: it is not written)
@@ -402,6 +422,8 @@ def run(source, detector, tracker, profiler: Optional[LatencyProfiler] = None, m
         out["health_alarms"], out["health_flags"] = n_health_alarms, health_flags
     if enhance is not None:
         out["enhance_mean_eff"] = enhance_eff / max(n_enhanced, 1)
+    if denoise is not None:
+        out["denoise_mean_noise_q8"] = denoise_noise / max(n_denoised, 1)
     if motion is not None:
         out["motion_frames"], out["still_frames"], out["scene_changes"] = n_status[2], n_status[1], n_status[3]
     return out
